@@ -8,9 +8,12 @@ indices; tables drawn U(-sqrt(1/n), sqrt(1/n)) like create_emb.
 
 A step = the hot path over one batch: R = interact_features(x, apply_emb(...))
 -> (B,387), as ONE launch of the fused gather+pool+interaction kernel
-(csrc/evs_fused.hip); the same work through the two-call plugin surface is
-timed beside it ("two_call_path").  Inputs are resident in HBM before the
-timed region.  value = 26 * B * steps / time  (whole job, all ranks).
+(csrc/evs_fused.hip).  Inputs are resident in HBM before the timed region.
+value = 26 * B * steps / time  (whole job, all ranks).  A plain run times
+that alone; --full adds the side lines after it (the same work through the
+two-call plugin surface, "two_call_path", latency, other sizes and
+precisions, the cache tier, the CPU baseline).  --dump-outputs DIR writes
+what the last timed step returned (DIR/R.npy).
 
 N > 1 (one process per GPU, torch.distributed/RCCL): tables are sharded over
 ranks, every rank pools its tables for the FULL global batch (N * B), one
@@ -986,6 +989,23 @@ def cache_tier_section(ev, ln_emb, d, B, dev, steps=200, warmup=60, frac=0.10, a
                         "B=%d, batched snapshot-semantics lookup + interact_features" % (frac * 100, alpha, B)}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs DIR: each array as DIR/<name>.npy, float32, DUMP_LIMIT_BYTES over all of them.  An array above its share
+    is written as a fixed, seeded sample of its rows (sorted row ids, the same for the same shape), so that two builds can be
+    compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            rows = np.sort(np.random.RandomState(seed).choice(a.shape[0], share // (a.nbytes // a.shape[0]), replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -1080,6 +1100,12 @@ def main():
     ap.add_argument("--batch", type=int, default=16384, help="samples per GPU per step")
     ap.add_argument("--dim", type=int, default=36)
     ap.add_argument("--dist", default="uniform", choices=["uniform", "zipf"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every side measurement of the N = 1 path as well (full_side_lines: latency, the other "
+                         "call paths, other batch sizes, widths and precisions, the cache tier, the CPU baseline; --no-cpu-baseline, "
+                         "--no-cache-tier and --no-extras leave parts of it out).  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last timed step returned (R, float32) as DIR/R.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cache-tier", action="store_true", help="skip the configs[2] (EvLFU cache) section")
     ap.add_argument("--no-extras", action="store_true",
@@ -1136,6 +1162,10 @@ def main():
     args = ap.parse_args()
     if args.cpu_baseline_child:
         sys.exit(cpu_baseline_child(args))
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        sys.exit("bench.py: --dump-outputs is available on the N = 1 path only (--gpus 1, no --force-sharded)")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.self_launch or args.dry_launch):
         # called as the driver calls it (`python3 bench.py --gpus N ...`): nothing here has touched the GPU yet (torch is
@@ -1207,7 +1237,7 @@ def main_sharded(args, rank, world, local_rank):
 
 
 def main_single(args, local_rank):
-    """N = 1: the headline launch and its side lines on one GPU"""
+    """N = 1: the headline launch on one GPU; with --full its side lines too (full_side_lines)"""
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     import evstore_dlrm_amd as E
@@ -1218,7 +1248,10 @@ def main_single(args, local_rank):
     ev = make_tables(KAGGLE_LN, d, seed=0, device=dev)
     # >= 64 distinct batches: 64 x 26 x B rows touch far more than the 256 MiB Infinity Cache between two uses of a line
     batches = make_batches(KAGGLE_LN, B, max(1, args.n_batches), seed=1, device=dev, dist=args.dist)
-    xs = [torch.rand((B, d), device=dev) for _ in range(2)]
+    # x from a seeded generator of its own (torch's default CUDA generator starts from a different seed in every process):
+    # the same inputs from run to run, so that --dump-outputs of two builds compare output for output
+    gx = torch.Generator(device=dev).manual_seed(2)
+    xs = [torch.rand((B, d), device=dev, generator=gx) for _ in range(2)]
     Rbuf = [torch.empty((B, d + P), device=dev, dtype=torch.float32) for _ in range(2)]
 
     def step(i):
@@ -1227,10 +1260,6 @@ def main_single(args, local_rank):
         # (any bag structure is allowed; the Criteo collate's arange offsets take the one-index path inside the kernel).
         lS_o, lS_i = batches[i % len(batches)]
         return E.apply_emb_interact(xs[i % 2], lS_o, lS_i, ev, None, out=Rbuf[i % 2])
-
-    def step_general(i):  # the side line: the caller DECLARES one index per bag (not expressible through the reference API):
-        lS_o, lS_i = batches[i % len(batches)]   # lS_o is then not read at all
-        return E.apply_emb_interact(xs[i % 2], lS_o, lS_i, ev, None, out=Rbuf[i % 2], one_index_per_bag=True)
 
     for i in range(args.warmup):
         step(i)
@@ -1265,6 +1294,61 @@ def main_single(args, local_rank):
     # the timed region holds only this kernel, back to back on one stream: events over the region
     # divided by the launches = average launch duration (incl. launch gaps when the host is slower)
     kernel_ms = e0.elapsed_time(e1) / args.steps
+
+    if args.dump_outputs:   # what a caller of the timed path received from its last step
+        dump_outputs(args.dump_outputs, {"R": Rbuf[(args.steps - 1) % 2]})
+
+    lookups = T * B
+    # algorithmic bytes per sample of the fused kernel (SURVEY 8(d), gather read side + interaction
+    # write side; the (B,F,d) intermediate does not exist): per lookup 4d row + 8 index + 8 offset,
+    # per sample 4d for x and 4(d+P) for R
+    # (the declared one-index-per-bag side line does not read the 8-byte offsets: 5 644 B per sample instead of 5 852)
+    bytes_per_sample = T * (4 * d + 8 + 8) + 4 * d + 4 * (d + P)
+    bytes_per_sample_declared = T * (4 * d + 8) + 4 * d + 4 * (d + P)
+    kernel_bytes = B * bytes_per_sample
+    achieved = kernel_bytes / (kernel_ms * 1e-3) / 1e9
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath):
+        try:
+            traffic = json.load(open(tpath)).get("fused_lSo_B%d_d%d_%s" % (B, d, args.dist))
+        except Exception:
+            traffic = None
+    result = {
+        "metric": "inference lookups/sec, Criteo-Kaggle 26-table DLRM (apply_emb + interact_features)",
+        "value": lookups * args.steps / dt, "unit": "lookups/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: Criteo-Kaggle 26 tables (33.76M rows) x d=%d fp32 all in HBM, "
+                               "no cache tier, 1 index/bag (Criteo collate), lS_o GIVEN and checked in the kernel (the drop-in call), %s indices; step = R=interact_features(x, apply_emb(lS_o, lS_i, ...))"
+                               % (d, args.dist),
+                   "batch_per_gpu": B, "global_batch": B, "tables": T, "dim": d, "parallelism": "single"},
+        "settle_s": settle_s,
+        "roofline": {"bound": "hbm",
+                     "kernel": "emb_interact_rf_kernel<2,1,2,4,false,false,false,true>" if (B <= 16384 and d == 36 and os.environ.get("EVS_FUSED_RF", "1") != "0")
+                               else "emb_interact_dot_lds_kernel<32,2,1,2,false,true,false,true,true,true>",
+                     "achieved": achieved,
+                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                     "bytes_per_launch": kernel_bytes, "avg_launch_ms": kernel_ms,
+                     "mfma": mfma_line(B, F, d, kernel_ms)},
+    }
+    if args.full:
+        full_side_lines(args, result, E, ev, dev, batches, xs, Rbuf, step, bytes_per_sample, bytes_per_sample_declared)
+    print(json.dumps(result))
+
+
+def full_side_lines(args, result, E, ev, dev, batches, xs, Rbuf, step, bytes_per_sample, bytes_per_sample_declared):
+    """--full: everything beside the headline -- per-batch latency, the other call paths, two streams, K batches per call,
+    the memory calibration, other batch sizes, widths and precisions, the reference's benchmark shape, the H2D-inclusive
+    loop, the cache tier and the CPU baseline -- measured after the headline's timed region, added to its record"""
+    B, d, T = args.batch, args.dim, len(KAGGLE_LN)
+    F = T + 1
+    P = F * (F - 1) // 2
+    lookups = T * B
+
+    def step_general(i):  # the side line: the caller DECLARES one index per bag (not expressible through the reference API):
+        lS_o, lS_i = batches[i % len(batches)]   # lS_o is then not read at all
+        return E.apply_emb_interact(xs[i % 2], lS_o, lS_i, ev, None, out=Rbuf[i % 2], one_index_per_bag=True)
 
     # ---- per-batch latency (sync per step), outside the throughput region ------------------
     lat = []
@@ -1369,45 +1453,9 @@ def main_single(args, local_rank):
     torch.cuda.synchronize()
     dt2l = time.perf_counter() - t2l
 
-    lookups = T * B
-    # algorithmic bytes per sample of the fused kernel (SURVEY 8(d), gather read side + interaction
-    # write side; the (B,F,d) intermediate does not exist): per lookup 4d row + 8 index + 8 offset,
-    # per sample 4d for x and 4(d+P) for R
-    # (the declared one-index-per-bag side line does not read the 8-byte offsets: 5 644 B per sample instead of 5 852)
-    bytes_per_sample = T * (4 * d + 8 + 8) + 4 * d + 4 * (d + P)
-    bytes_per_sample_declared = T * (4 * d + 8) + 4 * d + 4 * (d + P)
-    kernel_bytes = B * bytes_per_sample
-    achieved = kernel_bytes / (kernel_ms * 1e-3) / 1e9
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            traffic = json.load(open(tpath)).get("fused_lSo_B%d_d%d_%s" % (B, d, args.dist))
-        except Exception:
-            traffic = None
-    result = {
-        "metric": "inference lookups/sec, Criteo-Kaggle 26-table DLRM (apply_emb + interact_features)",
-        "value": lookups * args.steps / dt, "unit": "lookups/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: Criteo-Kaggle 26 tables (33.76M rows) x d=%d fp32 all in HBM, "
-                               "no cache tier, 1 index/bag (Criteo collate), lS_o GIVEN and checked in the kernel (the drop-in call), %s indices; step = R=interact_features(x, apply_emb(lS_o, lS_i, ...))"
-                               % (d, args.dist),
-                   "batch_per_gpu": B, "global_batch": B, "tables": T, "dim": d, "parallelism": "single"},
+    result.update({
         "p50_batch_latency_ms": float(np.percentile(lat, 50)), "p95_batch_latency_ms": float(np.percentile(lat, 95)),
         "p50_batch_latency_polled_ms": float(np.percentile(lat_poll, 50)),   # the host spins on an end event instead of blocking in synchronize()
-        "settle_s": settle_s,
-        "roofline": {"bound": "hbm",
-                     "kernel": "emb_interact_rf_kernel<2,1,2,4,false,false,false,true>" if (B <= 16384 and d == 36 and os.environ.get("EVS_FUSED_RF", "1") != "0")
-                               else "emb_interact_dot_lds_kernel<32,2,1,2,false,true,false,true,true,true>",
-                     "achieved": achieved,
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                     "bytes_per_launch": kernel_bytes, "avg_launch_ms": kernel_ms,
-                     "mfma": mfma_line(B, F, d, kernel_ms),
-                     # (the other half of BASELINE's metric, kept inside an object the driver's parsed record keeps: p50 of one batch
-                     #  launched and waited for -- blocking synchronise / the host spinning on an end event)
-                     "latency": {"p50_batch_latency_ms": float(np.percentile(lat, 50)), "p95_batch_latency_ms": float(np.percentile(lat, 95)),
-                                 "p50_batch_latency_polled_ms": float(np.percentile(lat_poll, 50))}},
         "declared_one_index": {"value": lookups * args.steps / dtg, "unit": "lookups/s",
                                "ms_per_step": dtg / args.steps * 1e3,
                                "frac": B * bytes_per_sample_declared / (dtg / args.steps) / 1e9 / HBM_PEAK_GBPS,
@@ -1430,7 +1478,11 @@ def main_single(args, local_rank):
                           "note": "the same two calls with lazy pooling on (EVS_LAZY_POOLING=1 or apply_emb(..., lazy=True); off by "
                                   "default because the lazy result is a Sequence, not a list): apply_emb launches nothing, "
                                   "interact_features runs the fused kernel"},
-    }
+    })
+    # (the other half of BASELINE's metric, kept inside an object the driver's parsed record keeps: p50 of one batch
+    #  launched and waited for -- blocking synchronise / the host spinning on an end event)
+    result["roofline"]["latency"] = {"p50_batch_latency_ms": float(np.percentile(lat, 50)), "p95_batch_latency_ms": float(np.percentile(lat, 95)),
+                                     "p50_batch_latency_polled_ms": float(np.percentile(lat_poll, 50))}
     # ---- K batches per call: the library's own stream pair (evs_emb_interact_dot_stacked_multi) ----
     if not args.no_extras:
         try:
@@ -1593,7 +1645,6 @@ def main_single(args, local_rank):
                     result["cache_tier"]["mixed_precision_tiers"] = {"error": repr(e)}
     if not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ev, KAGGLE_LN, d, B, args.cpu_seconds)
-    print(json.dumps(result))
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ plain numpy arrays (.npz).  Re-run with:
 
 What is pinned:
   * dlrm_s_pytorch.DLRM_Net.apply_emb / interact_features  (dlrm_s_pytorch.py:407, :483)
+    (`interact_exact`: interact_features on inputs snapped to a grid where fp32 is exact)
   * dlrm_data_pytorch.generate_dist_input_batch            (dlrm_data_pytorch.py:1011)
   * cache_algo/EvLFU_C1.py, LRU.py, LFU.py hit traces       (EvLFU_C1.py:97, LRU.py:38, LFU.py:69)
   * emb_storage/file_read.py + mmap_file_read.py row reads  (file_read.py:27, mmap_file_read.py:32)
@@ -132,6 +133,32 @@ def gen_dlrm_case(D, DP, name, ln_emb, m_spa, B, n_idx, seed, itself=False,
         out["vW_cat"] = np.concatenate([w.numpy() for w in dlrm.v_W_l])
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print("wrote", name, {k: getattr(v, "shape", None) for k, v in out.items()})
+
+
+def gen_interact_exact(D, name):
+    """<name>_interact_exact.npz: the reference's interact_features on the x and pooled rows of <name>.npz snapped to a grid
+    of 2^-e on which every product and every sum of a dot product is exact in fp32 -- the result is then the same whatever
+    order a host's sgemm sums in (the R of the raw data holds the recording host's sgemm rounding)."""
+    import torch
+    g = np.load(os.path.join(HERE, name + ".npz"))
+    x, ly, d = g["x"], g["ly"], int(g["m_spa"])
+    big = max(float(np.abs(x).max()), float(np.abs(ly).max()))
+    e = 0
+    while d * (big * 2.0 ** (e + 1) + 1) ** 2 < 2.0 ** 24:   # d products of integers below 2^e * big + 1: below 2^24
+        e += 1
+    xq = (np.round(x * 2.0 ** e) / 2.0 ** e).astype(np.float32)
+    lyq = (np.round(ly * 2.0 ** e) / 2.0 ** e).astype(np.float32)
+    ln_emb = g["ln_emb"]
+    F = len(ln_emb) + 1
+    itself = bool(g["itself"])
+    n_int = (F * (F + 1)) // 2 if itself else (F * (F - 1)) // 2
+    dlrm = D.DLRM_Net(d, ln_emb, np.array([13, 32, d]), np.array([n_int + d, 16, 1]), arch_interaction_op="dot",
+                      arch_interaction_itself=itself, sigmoid_bot=-1, sigmoid_top=1, ndevices=-1)
+    with torch.no_grad():
+        R = dlrm.interact_features(torch.from_numpy(xq), [torch.from_numpy(v) for v in lyq])
+    np.savez_compressed(os.path.join(HERE, name + "_interact_exact.npz"), x=xq, ly=lyq, R=R.numpy(), grid_exp=np.int64(e),
+                        itself=np.int64(itself))
+    print("wrote", name + "_interact_exact", "grid 2^-%d" % e, R.shape)
 
 
 # --------------------------------------------------------------------------
@@ -673,6 +700,10 @@ def main():
         # the reference's own benchmark shape at a reduced row count (bench/dlrm_s_benchmark.sh:20-45: 8 tables, d = 64,
         # --num-indices-per-lookup=100 --num-indices-per-lookup-fixed=true; rows 1 000 000 -> 600, mb 2 048 -> 40)
         gen_dlrm_case(D, DP, "dlrm_bench_shape", [600] * 8, 64, 40, 100, seed=41, n_idx_fixed=True)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "interact_exact":
+        for name in ("dlrm_ragged_small", "dlrm_kaggle_small", "dlrm_d64"):
+            gen_interact_exact(D, name)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "collate":
         # collate_wrapper_criteo_offset (dlrm_data_pytorch.py:397-410) on a raw batch as CriteoDataset.__getitem__ yields it

@@ -1,12 +1,13 @@
-"""GPU: bench.py keeps its contract -- `python bench.py --gpus 1 --steps K --warmup W` (the flags the round-end driver passes)
-prints ONE JSON record as the LAST line of stdout with the agreed keys, `value` = whole-job lookups per second over exactly
-K timed steps, `roofline` measured live with HIP events, `cpu_baseline` from the oracle port on the host cores; and the N > 1
-code path (one rank, --force-sharded) prints the same record shape."""
+"""GPU: bench.py keeps its contract -- `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON record as the LAST line
+of stdout with the agreed keys, `value` = whole-job lookups per second over exactly K timed steps, `roofline` measured live with
+HIP events; with --full also the side lines and `cpu_baseline` from the oracle port on the host cores; and the N > 1 code path
+(one rank, --force-sharded) prints the same record shape."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _run(extra, timeout=900):
 
 
 def test_bench_line_default_form():
-    j, lines = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"])
+    j, lines = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--full"])
     assert sum(1 for ln in lines if ln.lstrip().startswith("{")) == 1, "one JSON record"
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
@@ -50,6 +51,30 @@ def test_bench_line_default_form():
     ct = j["cache_tier"]
     assert ct["roofline"]["frac"] > 0.2 and abs(ct["hit_rate"] - ct["oracle_hit_rate"]) < 0.01
     assert ct["mixed_precision_tiers"]["roofline"]["bytes_per_launch"] == B * 3226
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is set-up, warm-up, the K timed steps and the record: the headline keys and the roofline of the
+    timed launches, none of the side lines.  --dump-outputs writes what the last timed step returned, the same from run to run."""
+    B, d, P = 16384, 36, 27 * 26 // 2
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        j, lines = _run(["--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(out)], timeout=600)
+        assert sum(1 for ln in lines if ln.lstrip().startswith("{")) == 1, "one JSON record"
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                    "data", "config", "roofline"):
+            assert key in j, key
+        assert j["steps"] == 30 and j["warmup"] == 5 and j["unit"] == "lookups/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert abs(j["value"] - 26 * B / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+        assert j["roofline"]["avg_launch_ms"] <= j["ms_per_step"] * 1.001 and j["roofline"]["bytes_per_launch"] == B * 5852
+        for key in ("cpu_baseline", "cache_tier", "two_call_path", "multi_batch", "large_batch", "p50_batch_latency_ms"):
+            assert key not in j, key
+        assert sorted(os.listdir(out)) == ["R.npy"]
+        R = np.load(out / "R.npy")
+        assert R.dtype == np.float32 and R.shape == (B, d + P) and np.isfinite(R).all()
+        dumps.append(R)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32)), "same arguments, same inputs, same outputs"
 
 
 def test_bench_line_sharded_path_one_rank():

@@ -90,3 +90,28 @@ def test_self_launch_returns_the_failing_ranks_code_quickly():
     assert r.returncode != 0 and "injected failure" in r.stderr
     assert time.time() - t0 < 180
     assert not any(ln.startswith("{") and '"metric"' in ln for ln in r.stdout.splitlines())
+
+
+def test_dump_outputs_and_steps_are_checked_before_any_launch():
+    for extra, msg in ((["--gpus", "2", "--dump-outputs", "out"], "N = 1 path only"), (["--gpus", "1", "--steps", "0"], "--steps")):
+        r = subprocess.run([sys.executable, BENCH] + extra, capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+        assert r.returncode != 0 and msg in r.stderr, (extra, r.stderr[-2000:])
+
+
+def test_dump_outputs_keeps_a_seeded_sample_of_a_large_output(tmp_path):
+    # 96 MB of rows: written as a fixed sample of whole rows within the 64 MB limit, the same sample every time
+    code = ("import sys, torch; out = sys.argv[1]; sys.argv = ['bench.py']; import bench; "
+            "t = torch.arange(24000 * 1000, dtype=torch.float32).reshape(24000, 1000); "
+            "bench.dump_outputs(out, {'A': t, 'b': t[:10, :5]})")
+    for k in range(2):
+        r = subprocess.run([sys.executable, "-c", code, str(tmp_path / ("a%d" % k))], capture_output=True, text=True, timeout=300,
+                           env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+    import numpy as np
+    a0, a1 = np.load(tmp_path / "a0" / "A.npy"), np.load(tmp_path / "a1" / "A.npy")
+    assert np.array_equal(a0, a1) and a0.dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a0" / n) for n in ("A.npy", "b.npy")) <= 64 * 10 ** 6
+    rows = a0[:, 0] / 1000
+    assert a0.shape[1] == 1000 and 0 < len(rows) < 24000 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.round(rows))
+    assert np.array_equal(a0, np.arange(24000 * 1000, dtype=np.float32).reshape(24000, 1000)[rows.astype(np.int64)])
+    assert np.load(tmp_path / "a0" / "b.npy").shape == (10, 5)

@@ -15,7 +15,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 def test_host_engine_is_clean_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "hostcache_asan")
     csrc = os.path.join(ROOT, "ev-store-dlrm_amd", "csrc")
-    cmd = [HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    cmd = [HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), os.path.join(csrc, "evs_hostcache.hip"),
            os.path.join(csrc, "evs_api.hip"), os.path.join(ROOT, "tools", "hostcache_asan.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -31,7 +31,7 @@ def test_file_tier_reader_pool_is_clean_under_tsan(tmp_path):
     persistent reader pool (tools/filetier_tsan.cpp).  (It found the unguarded lazy creation of the pool.)"""
     exe = str(tmp_path / "filetier_tsan")
     csrc = os.path.join(ROOT, "ev-store-dlrm_amd", "csrc")
-    cmd = [HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer",
+    cmd = [HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
            "-I" + os.path.join(ROOT, "include"), os.path.join(csrc, "evs_filetier.hip"), os.path.join(csrc, "evs_api.hip"),
            os.path.join(ROOT, "tools", "filetier_tsan.cpp"), "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -211,15 +211,37 @@ def test_reader_rows(tmp_path):
 
 @pytest.mark.parametrize("name", ["dlrm_ragged_small", "dlrm_kaggle_small", "dlrm_d64"])
 def test_cpu_port_matches_golden(name):
-    """oracle/dlrm_cpu.py (bench.py's cpu_baseline) reproduces the reference's outputs exactly."""
+    """oracle/dlrm_cpu.py (bench.py's cpu_baseline) reproduces the reference's outputs exactly: the pooled rows of the recorded
+    batch bit for bit, and the interaction bit for bit on the same x and pooled rows snapped to a grid on which every product
+    and sum is exact in fp32 (<name>_interact_exact.npz, the reference's interact_features on them).  The R of the raw batch
+    holds the recording host's sgemm rounding, which the BLAS of other CPUs does not reproduce: the port's R of it is held to
+    it bit for bit on the x columns and within the sgemm rounding bound on the interaction columns."""
     import torch
     from oracle import dlrm_cpu
     g = load_golden(name)
     tabs = [torch.from_numpy(t) for t in split_tables(g)]
     lS_o, lS_i = split_indices(g)
     m = dlrm_cpu.CpuHotPath(tabs)
+    with torch.no_grad():
+        ly = m.apply_emb([torch.from_numpy(o) for o in lS_o], [torch.from_numpy(i) for i in lS_i])
+    np.testing.assert_array_equal(np.stack([v.numpy() for v in ly]), g["ly"])
     R = m.step([torch.from_numpy(o) for o in lS_o], [torch.from_numpy(i) for i in lS_i], torch.from_numpy(g["x"]))
-    np.testing.assert_array_equal(R.numpy(), g["R"])
+    d = int(g["m_spa"])
+    assert R.shape == g["R"].shape
+    np.testing.assert_array_equal(R.numpy()[:, :d], g["R"][:, :d])
+    # ... and its interaction columns within the rounding either sgemm may make of the same dot products, in any order of
+    # summation: |fl(sum) - sum| <= d u sum |a_k b_k| for each side, u = 2^-24
+    T = np.concatenate([g["x"][:, None, :], np.transpose(g["ly"], (1, 0, 2))], axis=1).astype(np.float64)
+    A = np.abs(T) @ np.abs(np.transpose(T, (0, 2, 1)))
+    F = T.shape[1]
+    li, lj = np.tril_indices(F, -1)
+    bound = 2 * d * 2.0 ** -24 * A[:, li, lj]
+    assert np.all(np.abs(R.numpy()[:, d:].astype(np.float64) - g["R"][:, d:]) <= bound)
+    e = load_golden(name + "_interact_exact")
+    assert e["R"].shape == g["R"].shape and np.count_nonzero(e["R"][:, d:]) > 0.9 * e["R"][:, d:].size
+    with torch.no_grad():
+        Re = m.interact_features(torch.from_numpy(e["x"]), [torch.from_numpy(v) for v in e["ly"]])
+    np.testing.assert_array_equal(Re.numpy(), e["R"])
 
 
 def _c1c2_decoded_tables():

@@ -8,11 +8,11 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver20.json 2> $OUT/bench_driver20.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver20.json 2> $OUT/bench_driver20.err
 python3 bench.py --force-sharded --steps 300 --warmup 50 > $OUT/bench_force_sharded.json 2> $OUT/bench_force_sharded.err
 python3 bench.py --force-sharded --steps 300 --warmup 50 --sharded-mode graph > $OUT/bench_force_sharded_graph.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 2000 --warmup 500 --no-cpu-baseline --no-extras > $OUT/trace.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --steps 2000 --warmup 500 --no-cpu-baseline --no-extras > $OUT/trace.log 2>&1
 find $OUT/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
 timeout 300 rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum --output-format csv -d $OUT/pmc_rd -- python3 $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --no-cache-tier > $OUT/pmc_rd.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE TCC_EA0_RDREQ_128B_sum --output-format csv -d $OUT/pmc_wr -- python3 $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --no-cache-tier > $OUT/pmc_wr.log 2>&1

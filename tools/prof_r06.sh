@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
 python3 bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/bench_driver20.err | tail -1 > $OUT/bench_driver20.json
+python3 bench.py --gpus 1 --full --steps 20 --warmup 5 2> $OUT/bench_driver20.err | tail -1 > $OUT/bench_driver20.json
 for mode in direct inline p2p; do
   timeout 300 python3 bench.py --gpus 1 --self-launch --force-sharded --force-exchange --exchange-mode $mode --steps 2000 --warmup 200 2>/dev/null | tail -1 > $OUT/bench_force_sharded_exchange_$mode.json
 done
@@ -23,7 +23,7 @@ for i in 1 2; do python3 tools/c2_pair_bench.py 200 2>&1 | grep "tier batched"; 
 python3 tools/c2_pair_bench.py 200 3 2>&1 | grep "tier batched" >> $OUT/c2_pair_bench.log
 cd /tmp && export TMPDIR=/tmp
 # ---- the headline: kernel statistics, HBM traffic
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 2000 --warmup 500 --no-cpu-baseline --no-extras --no-cache-tier > $OUT/trace.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --steps 2000 --warmup 500 --no-cpu-baseline --no-extras --no-cache-tier > $OUT/trace.log 2>&1
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1); grep -E "evs::|Name" $f > $OUT/kernel_stats.csv
 rm -rf $OUT/trace
 timeout 300 rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum --output-format csv -d $OUT/pmc/rd -- python3 $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --no-cache-tier > $OUT/pmc_rd.log 2>&1

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $ROOT
 timeout 1500 python3 -m pytest tests -x -q -m gpu > $OUT/gputest.log 2>&1; echo "pytest rc $?" >> $OUT/gputest.log
 tail -5 $OUT/gputest.log
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver20.json 2> $OUT/bench_driver20.err; echo "bench rc $?"
+timeout 600 python3 bench.py --gpus 1 --full --steps 20 --warmup 5 > $OUT/bench_driver20.json 2> $OUT/bench_driver20.err; echo "bench rc $?"
 tail -c 600 $OUT/bench_driver20.json
 cd /tmp && export TMPDIR=/tmp
 # ---- the pair: kernel statistics and deciles
