@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import _accuracy as acc
 from conftest import load_golden, split_indices, split_tables, split_weights
 
 pytestmark = pytest.mark.gpu
@@ -79,6 +80,9 @@ def test_apply_emb_and_interact_vs_golden_and_oracle(E, orc, name):
     Ro = orc.interact_features(g["x"], list(got), bool(g["itself"]))
     np.testing.assert_allclose(R, Ro, rtol=RTOL, atol=2e-6)
     assert np.array_equal(R[:, :g["x"].shape[1]], g["x"])  # x passthrough is a copy
+    # float64 with the scale-aware bound (tests/_accuracy.py)
+    acc.check(R, acc.reference_from_bags(g["x"], tabs, lS_o, lS_i, bool(g["itself"]), split_weights(g)), name,
+              "interact_features")
 
 
 def test_cfg1_full(E, orc):
@@ -91,6 +95,8 @@ def test_cfg1_full(E, orc):
     np.testing.assert_allclose(got, g["ly"], rtol=RTOL, atol=1e-7)
     R = E.interact_features(_dev(g["x"]), ly).cpu().numpy()
     np.testing.assert_allclose(R, g["R"], rtol=RTOL, atol=2e-6)
+    lS_o, lS_i = split_indices(g)
+    acc.check(R, acc.reference_from_bags(g["x"], tabs, lS_o, lS_i), "dlrm_cfg1", "interact_features")
 
 
 def test_fused_tile_layout(E, orc):
@@ -557,6 +563,12 @@ def test_full_size_kaggle_properties(E):
     li, lj = torch.tril_indices(27, 27, offset=-1, device="cuda")
     ref = torch.cat([x, Z[:, li, lj]], dim=1)
     torch.testing.assert_close(R, ref, rtol=1e-5, atol=1e-5)
+    # float64 with the scale-aware bound over 1 024 sampled rows (every pooled row is the table row: asserted above)
+    rows = acc.sample_rows(B, 1024, seed=5)
+    rt = torch.from_numpy(rows).cuda()
+    feats = [acc.pool64(ev.fp32_view(k)[idx[k, rt]].cpu().numpy())[:2] for k in range(26)]
+    acc.check(R[rt].cpu().numpy(), acc.Reference(x[rt].cpu().numpy(), feats, False), "full size B=4096",
+              "interact_features")
     # the bench configuration itself (B = 16384): fused kernel with the offsets bet, with offsets == NULL, and the
     # two-call path agree bit for bit; a checksum of checksums pins the x passthrough and the row order
     B2 = 16384
@@ -568,6 +580,11 @@ def test_full_size_kaggle_properties(E):
     c = E.interact_features(x2, E.apply_emb(off2b, idx2, ev, lazy=False))
     assert torch.equal(a, b) and torch.equal(a, c)
     assert torch.equal(a[:, :36], x2)
+    rows2 = acc.sample_rows(B2, 1024, seed=6)
+    rt2 = torch.from_numpy(rows2).cuda()
+    feats2 = [acc.pool64(ev.fp32_view(k)[idx2[k, rt2]].cpu().numpy())[:2] for k in range(26)]
+    acc.check(a[rt2].cpu().numpy(), acc.Reference(x2[rt2].cpu().numpy(), feats2, False), "full size B=16384",
+              "apply_emb_interact", rows2)
     # Z[b, pair(k+1, 0)] = <row_k, x>: recompute column 0 of the triangle for three tables from the table rows
     for k in (0, 9, 25):
         f = k + 1
@@ -594,6 +611,8 @@ def test_fused_gather_interact_vs_golden(E, orc, name):
     o, i = [_dev(r) for r in lS_o], [_dev(r) for r in lS_i]
     R = E.apply_emb_interact(x, o, i, ev, w, bool(g["itself"]), check_indices=True)
     np.testing.assert_allclose(R.cpu().numpy(), g["R"], rtol=RTOL, atol=2e-6)
+    acc.check(R.cpu().numpy(), acc.reference_from_bags(g["x"], tabs, lS_o, lS_i, bool(g["itself"]), vW), name,
+              "apply_emb_interact")
     # identical to the two-kernel path bit for bit (same pooled sums, same MFMA chain)
     R2 = E.interact_features(x, E.apply_emb(o, i, ev, w, lazy=False), "dot", bool(g["itself"]))
     assert torch.equal(R, R2)
