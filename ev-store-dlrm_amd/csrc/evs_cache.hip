@@ -1143,52 +1143,193 @@ __device__ __forceinline__ void touch(const CacheArrays &a, Hot &h, int e, int a
     }
 }
 
-__global__ void __launch_bounds__(64) cache_c1c2_kernel(const C1C2Args args) {
+// a probe that starts from a first word already fetched: the first words of two maps (C1's and C2's, or the two alt-key
+// probes) are asked for together and the walks run behind them
+__device__ __forceinline__ int map_find_from(const CacheArrays &a, unsigned long long mask, unsigned long long key,
+                                             unsigned long long i, unsigned long long k) {
+    for (;;) {
+        if (map_key(a, k) == key) return a.packed ? (int)(k >> kMapEntryShift) : ld(&a.slot_entry[i]);
+        if (k == kEmpty) return -1;
+        i = (i + 1) & mask;
+        k = ld(&a.keys[i]);
+    }
+}
+
+// the new entries of BOTH tiers as one list of (source row, arena row) -- C1's first, then C2's -- cut into chunks of `cs`
+// bytes (16, 4, 2 or 1: what both tiers' rows, arenas and tables are aligned to) that all 64 lanes move
+struct FillPlan { int n_ch, n_ch1, n1, cpr1, cpr2; float inv1, inv2; };
+__device__ __forceinline__ void fill_chunk(const FillPlan &p, int idx, int cs, int &j, int &off) {   // (exact for the chunks held in registers)
+    const bool second = idx >= p.n_ch1;
+    const int x = second ? idx - p.n_ch1 : idx;
+    const int jj = __float2int_rz(((float)x + 0.5f) * (second ? p.inv2 : p.inv1));
+    j = (second ? p.n1 : 0) + jj;
+    off = (x - jj * (second ? p.cpr2 : p.cpr1)) * cs;
+}
+__device__ __forceinline__ void fill_chunk_div(const FillPlan &p, int idx, int cs, int &j, int &off) {
+    const bool second = idx >= p.n_ch1;
+    const int x = second ? idx - p.n_ch1 : idx, cpr = second ? p.cpr2 : p.cpr1;
+    const int jj = x / cpr;
+    j = (second ? p.n1 : 0) + jj;
+    off = (x - jj * cpr) * cs;
+}
+template <typename CT, int K>
+__device__ __forceinline__ void fill_load(CT (&reg)[K], const FillPlan &p, int lane, const unsigned char *const *fsrc, const unsigned char *dummy) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int idx = lane + 64 * k;
+        const bool on = idx < p.n_ch;
+        int j, off;
+        fill_chunk(p, on ? idx : 0, (int)sizeof(CT), j, off);
+        const unsigned char *sp = on ? fsrc[j] + off : dummy;   // (a lane with no chunk reads 16 valid, aligned bytes: no load behind a branch)
+        reg[k] = *reinterpret_cast<const CT *>(sp);
+    }
+}
+template <typename CT, int K>
+__device__ __forceinline__ void fill_store(const CT (&reg)[K], const FillPlan &p, int lane, const unsigned char *const *fsrc, unsigned char *const *fdst) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int idx = lane + 64 * k;
+        const bool on = idx < p.n_ch;
+        int j, off;
+        fill_chunk(p, on ? idx : 0, (int)sizeof(CT), j, off);
+        unsigned char *dp = on ? fdst[j] : nullptr;
+        if (dp) *reinterpret_cast<CT *>(dp + off) = reg[k];
+    }
+    for (int idx = lane + 64 * K; idx < p.n_ch; idx += 64) {   // (more than the registers hold: the rest one at a time)
+        int j, off;
+        fill_chunk_div(p, idx, (int)sizeof(CT), j, off);
+        unsigned char *dp = fdst[j];
+        if (dp) *reinterpret_cast<CT *>(dp + off) = *reinterpret_cast<const CT *>(fsrc[j] + off);
+    }
+}
+
+// The tier pair / triple, per launch (SERVE = false: B requests from args.requests, rows to args.out, codes to args.tier_out)
+// or as a resident server (SERVE = true: the single-tier server's mailbox, ServeArgs; the answer line carries the T tier
+// codes).  The policy is lane 0's, in the reference's order (C2 updates, C2 inserts, C1 in table order); what changed against
+// the first form is everything around it: the probes of both tiers leave together, lane 0 visits only the tables that have
+// work (v_readlane with a scalar index, not __shfl), the rows leave as one flat stream and both tiers' new entries are moved
+// by all lanes.
+template <bool SERVE>
+__device__ __forceinline__ void cache_c1c2_body(const C1C2Args &args, const ServeArgs &sv) {
     __shared__ Hot h1, h2;
     __shared__ AprxState s3;
-    __shared__ int s_alt_e[kMaxTables], s_alt_tier[kMaxTables];
     const bool has_c3 = args.c3.st != nullptr;
-    // per key: which tier's row to output (1/2), from its arena entry (>=0) or its backing store (-1);
-    // and the entry to fill afterwards per tier
+    // per key: which tier's row to output (1/2; 3/4: the alt row in C1's / C2's arena), from its arena entry (>=0) or its
+    // backing store (-1); and the entry to fill afterwards per tier
     __shared__ int s_tier[kMaxTables], s_src[kMaxTables], s_fill1[kMaxTables], s_fill2[kMaxTables], s_req[kMaxTables];
+    __shared__ const unsigned char *s_rowp[kMaxTables];   // where table t's row is read from (nullptr: zeros) ...
+    __shared__ int s_codec[kMaxTables];                    // ... and the codec it is in (C1's or C2's: per row, not wave-uniform)
+    __shared__ const unsigned char *s_fsrc[kMaxTables];
+    __shared__ unsigned char *s_fdst[kMaxTables];
+    __shared__ const unsigned char *s_back1[kMaxTables], *s_back2[kMaxTables];
+    __shared__ long long s_brows[kMaxTables];              // rows both tiers' tables have
     const int lane = threadIdx.x;
     const CacheState cs1 = *args.t1.st, cs2 = *args.t2.st;
     const CacheArrays a1 = args.t1.a, a2 = args.t2.a;
     const unsigned long long m1 = cs1.nslot_mask, m2 = cs2.nslot_mask;
-    const int T = cs1.n_tables, d = cs1.dim;
+    const int T = cs1.n_tables, d = cs1.dim, rb1 = cs1.row_bytes, rb2 = cs2.row_bytes;
     hot_load(h1, cs1, args.t1.st, lane);
     hot_load(h2, cs2, args.t2.st, lane);
     if (has_c3 && lane == 0) s3 = *args.c3.st;
-    __syncthreads();
+    for (int k = lane; k < kMaxTables; k += 64) {
+        s_back1[k] = args.t1.backing[k]; s_back2[k] = args.t2.backing[k];
+        const long long r1 = args.t1.backing_rows[k], r2 = args.t2.backing_rows[k];
+        s_brows[k] = r1 < r2 ? r1 : r2;
+    }
+    EVS_WSYNC();
+    static_assert(kMaxTables <= 64, "one lane per table");
+    const unsigned char *const dummy = reinterpret_cast<const unsigned char *>(args.t1.st);   // what a lane with nothing to fetch reads
+    const unsigned long long align_bits = (unsigned long long)(unsigned)(rb1 | rb2) | (unsigned long long)reinterpret_cast<uintptr_t>(a1.arena) |
+                                          (unsigned long long)reinterpret_cast<uintptr_t>(a2.arena) |
+                                          (lane < T ? (unsigned long long)reinterpret_cast<uintptr_t>(s_back1[lane]) | (unsigned long long)reinterpret_cast<uintptr_t>(s_back2[lane]) : 0ull);
+    const int fill_cs = __ballot((align_bits & 15ull) != 0ull) == 0ull ? 16 : __ballot((align_bits & 3ull) != 0ull) == 0ull ? 4 :
+                        __ballot((align_bits & 1ull) != 0ull) == 0ull ? 2 : 1;
+    FillPlan fp;
+    fp.cpr1 = rb1 / fill_cs; fp.cpr2 = rb2 / fill_cs;
+    fp.inv1 = 1.0f / (float)fp.cpr1; fp.inv2 = 1.0f / (float)fp.cpr2;
     long long n_perfect_req = 0, n_hits = 0;
+    unsigned serve_seq = 0;            // SERVE: the last sequence number served
+    long long served = 0;
+    if constexpr (SERVE) {
+        serve_seq = __hip_atomic_load(const_cast<unsigned *>(sv.ans) + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // alive
+    }
 
-    for (long long rq = 0; rq < args.B; rq++) {
-        const int row = lane < T ? args.requests[rq * T + lane] : 0;
+    for (long long rq = 0; SERVE || rq < args.B; rq++) {
+        int row;
+        float *out;
+        if constexpr (SERVE) {
+            // ---- wait for the next request: the line and the control word in one 64-lane load (cache_exact_body's) ----
+            const unsigned want = (serve_seq + 1u) & 0x7fffffffu;
+            const long long t0 = (long long)wall_clock64();
+            unsigned word = 0u;
+            bool leave = false;
+            for (;;) {
+                word = __hip_atomic_load(const_cast<unsigned *>(sv.req) + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if ((__ballot((word & 0x7fffffffu) == want) & 0x80808080ull) == 0x80808080ull) break;
+                const unsigned stop = (unsigned)__builtin_amdgcn_readlane((int)word, 32);
+                if (stop != 0u || (long long)wall_clock64() - t0 > sv.idle_ticks) { leave = true; break; }
+                __builtin_amdgcn_s_sleep(4);
+            }
+            if (leave) break;
+            const int src_lane = lane + lane / 7;   // id of table t: word t + t / 7
+            row = __shfl((int)word, src_lane & 31);
+            const bool by_addr = ((unsigned)rl((int)word, 7) >> 31) != 0u;
+            if (by_addr) {                          // words 0..2: the address of table 0's id and the elements between two tables' ids
+                const unsigned long long pa = ((unsigned long long)(unsigned)rl((int)word, 1) << 32) | (unsigned)rl((int)word, 0);
+                const long long stride = (long long)(unsigned)rl((int)word, 2);
+                const long long *ip = reinterpret_cast<const long long *>((uintptr_t)pa) + (long long)(lane < T ? lane : 0) * stride;
+                row = (int)__hip_atomic_load(ip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            unsigned long long out_a = 0ull;        // where the rows go: an address of the caller's, 0 = this request's ring slot
+            if (by_addr) out_a = ((unsigned long long)(unsigned)rl((int)word, 4) << 32) | (unsigned)rl((int)word, 3);
+            else if (T <= 26) out_a = ((unsigned long long)(unsigned)rl((int)word, 30) << 32) | (unsigned)rl((int)word, 29);
+            if (lane >= T) row = 0;
+            out = out_a ? reinterpret_cast<float *>((uintptr_t)out_a) : sv.ring + (long long)(want % (unsigned)sv.n_slots) * T * d;
+        } else {
+            row = lane < T ? args.requests[rq * T + lane] : 0;
+            out = args.out + rq * (long long)T * d;
+        }
         if (lane < T) s_req[lane] = row;
         const unsigned long long key = ((unsigned long long)(lane + 1) << 32) | (unsigned)row;
-        const bool ok = lane < T && row >= 0 && row < args.t1.backing_rows[lane < T ? lane : 0] &&
-                        row < args.t2.backing_rows[lane < T ? lane : 0];
+        const bool ok = lane < T && row >= 0 && row < s_brows[lane < T ? lane : 0];
         if (has_c3 && lane == 0 && s3.batch_ready) aprx_insert_batch(args.c3, s3);  // a full batch becomes visible here
-        __syncthreads();
-        const int e2 = ok ? map_find(a2, m2, key) : -1;  // evlfu_4.cpp phase_1_find_keys_in_cache
-        const int e1 = ok ? map_find(a1, m1, key) : -1;
+        EVS_WSYNC();
+        // ---- both tiers' probes leave together (evlfu_4.cpp phase_1_find_keys_in_cache; evlfu_8.cpp:513-546): no load behind
+        // `ok ? ... : -1` -- a key that is out of range is in neither map by construction of the request path, a lane past T
+        // probes a key no table has, and what either finds is dropped by the select ----
+        int e1, e2;
+        {
+            const unsigned long long hk = mix64(key);
+            const unsigned long long i2 = hk & m2, i1 = hk & m1;
+            const unsigned long long w2 = ld(&a2.keys[i2]), w1 = ld(&a1.keys[i1]);
+            e2 = map_find_from(a2, m2, key, i2, w2);
+            e1 = map_find_from(a1, m1, key, i1, w1);
+            if (!ok) { e1 = -1; e2 = -1; }
+        }
         const unsigned long long okm = __ballot(ok);
         const unsigned long long hit2 = __ballot(e2 >= 0), hit1 = __ballot(e1 >= 0);
         // alt-key probe for double misses (find_approximate_ev, evlfu_8.cpp:474-490): C1 first, then C2
         int alt_e = -1, alt_tier = 0;
-        if (has_c3 && ok && e1 < 0 && e2 < 0) {
-            const int e3 = aprx_find(args.c3, s3.mask, key);
-            if (e3 >= 0) {
-                const unsigned alt = ld(&args.c3.ealt[e3]);
+        if (has_c3) {
+            const bool need3 = ok && e1 < 0 && e2 < 0;
+            if (__ballot(need3) != 0ull) {   // (wave-uniform: every lane probes, the lanes that need nothing drop what they find)
+                const int e3 = aprx_find(args.c3, s3.mask, key);
+                const unsigned alt = ld(&args.c3.ealt[e3 >= 0 ? e3 : 0]);
                 const unsigned long long akey = ((unsigned long long)(alt % 100u) << 32) | (alt / 100u);
-                int ea = map_find(a1, m1, akey);
-                if (ea >= 0) { alt_tier = 1; alt_e = ea; }
-                else { ea = map_find(a2, m2, akey); if (ea >= 0) { alt_tier = 2; alt_e = ea; } }
-                if (alt_tier) st(&args.c3.eflag[e3], (unsigned char)1);  // set_recency_flag_c3
+                const unsigned long long ha = mix64(akey);
+                const unsigned long long j1 = ha & m1, j2 = ha & m2;
+                const unsigned long long x1 = ld(&a1.keys[j1]), x2 = ld(&a2.keys[j2]);
+                const int ea1 = map_find_from(a1, m1, akey, j1, x1);
+                const int ea2 = map_find_from(a2, m2, akey, j2, x2);
+                if (need3 && e3 >= 0) {
+                    if (ea1 >= 0) { alt_tier = 1; alt_e = ea1; }
+                    else if (ea2 >= 0) { alt_tier = 2; alt_e = ea2; }
+                    if (alt_tier) st(&args.c3.eflag[e3], (unsigned char)1);  // set_recency_flag_c3
+                }
             }
         }
         const unsigned long long hit3 = __ballot(alt_tier != 0);
-        if (lane < T) { s_alt_e[lane] = alt_e; s_alt_tier[lane] = alt_tier; }
         int agg = __popcll(hit2) + __popcll(hit1 & ~hit2) + __popcll(hit3);  // c1_c2_agg_hit (evlfu_8.cpp:513-546)
         const unsigned long long hit1e = hit1 | hit3;        // c1_arr_record_hit is piggybacked for alt hits (:547)
         unsigned long long upd2 = ~hit1 & hit2 & okm;        // C1 miss, C2 hit: C2 serves and updates
@@ -1207,38 +1348,45 @@ __global__ void __launch_bounds__(64) cache_c1c2_kernel(const C1C2Args args) {
             agg = __popcll(hit1);
         }
         if (lane == 0 && has_c3) s3.n_hit += __popcll(hit3);
+        const unsigned char code = (hit1 >> lane) & 1 ? 1 : ((hit2 >> lane) & 1 ? 2 : ((hit3 >> lane) & 1 ? 3 : 0));
         if (lane < T) {
             s_tier[lane] = 0; s_src[lane] = -1; s_fill1[lane] = -1; s_fill2[lane] = -1;
-            args.tier_out[rq * T + lane] = (hit1 >> lane) & 1 ? 1 : ((hit2 >> lane) & 1 ? 2 : ((hit3 >> lane) & 1 ? 3 : 0));
+            if constexpr (!SERVE) args.tier_out[rq * T + lane] = code;
         }
-        __syncthreads();
-        for (int i = 0; i < T; i++) {  // C2 first (phase 2), updates before inserts (evlfu_4.cpp:374-400)
-            const int e2i = __shfl(e2, i);
-            if (lane == 0 && update_c2 && ((upd2 >> i) & 1)) {
-                touch(a2, h2, e2i, agg);
-                s_tier[i] = 2; s_src[i] = e2i;
+        EVS_WSYNC();
+        // ---- the policy, one lane, over the set bits only.  C2 first (phase 2), updates before inserts (evlfu_4.cpp:374-400) ----
+        if (update_c2) {
+            for (unsigned long long mm = upd2; mm; mm &= mm - 1ull) {
+                const int i = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(mm));
+                const int e2i = rl(e2, i);
+                if (lane == 0) {
+                    touch(a2, h2, e2i, agg);
+                    s_tier[i] = 2; s_src[i] = e2i;
+                }
             }
-        }
-        for (int i = 0; i < T; i++) {
-            const unsigned long long ki = __shfl(key, i);
-            if (lane == 0 && update_c2 && ((ins2 >> i) & 1)) {
-                s_fill2[i] = evlfu_set(cs2, a2, h2, m2, ki, agg);
-                if (has_c3) aprx_queue_key(s3, h2.last_evicted);  // evlfu_8.cpp:617-620
-                s_tier[i] = 2; s_src[i] = -1;
+            for (unsigned long long mm = ins2; mm; mm &= mm - 1ull) {
+                const int i = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(mm));
+                const unsigned long long ki = rl64(key, i);
+                if (lane == 0) {
+                    s_fill2[i] = evlfu_set(cs2, a2, h2, m2, ki, agg);
+                    if (has_c3) aprx_queue_key(s3, h2.last_evicted);  // evlfu_8.cpp:617-620
+                    s_tier[i] = 2; s_src[i] = -1;
+                }
             }
+            if (lane == 0 && agg == T) h2.n_perfect = h2.len[T];
         }
-        if (lane == 0 && update_c2 && agg == T) h2.n_perfect = h2.len[T];
-        for (int i = 0; i < T; i++) {  // C1 loop (evlfu_8.cpp:769-785)
-            const int e1i = __shfl(e1, i);
-            const unsigned long long ki = __shfl(key, i);
+        for (unsigned long long mm = hit1 | hit3 | job1; mm; mm &= mm - 1ull) {  // C1 loop (evlfu_8.cpp:769-785)
+            const int i = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(mm));
+            const int e1i = rl(e1, i), alt_ei = rl(alt_e, i), alt_ti = rl(alt_tier, i);
+            const unsigned long long ki = rl64(key, i);
             if (lane == 0) {
                 if ((hit1 >> i) & 1) {
                     s_tier[i] = 1;
                     if (ld(&a1.ekey[e1i]) == ki) { touch(a1, h1, e1i, agg); s_src[i] = e1i; }
                     else s_src[i] = -1;  // evicted earlier in this request
                 } else if ((hit3 >> i) & 1) {
-                    s_tier[i] = 2 + s_alt_tier[i];  // 3: alt row in C1's arena, 4: in C2's arena
-                    s_src[i] = s_alt_e[i];
+                    s_tier[i] = 2 + alt_ti;  // 3: alt row in C1's arena, 4: in C2's arena
+                    s_src[i] = alt_ei;
                 } else if ((job1 >> i) & 1) {
                     s_fill1[i] = evlfu_set(cs1, a1, h1, m1, ki, agg);
                     if (has_c3) aprx_queue_key(s3, h1.last_evicted);  // evlfu_8.cpp:654-658
@@ -1249,55 +1397,130 @@ __global__ void __launch_bounds__(64) cache_c1c2_kernel(const C1C2Args args) {
         if (lane == 0 && agg == T) h1.n_perfect = h1.len[T];
         n_perfect_req += (agg == T);
         n_hits += __popcll((hit1 | hit2 | hit3) & okm);
-        __syncthreads();
+        EVS_WSYNC();
 
-        float *out = args.out + rq * (long long)T * d;
-        for (int i = 0; i < T; i++) {
-            const int tier = s_tier[i], src = s_src[i];
-            const int rrow = s_req[i];
+        // ---- rows: lane t resolves (address, codec) of table t's row ... ----
+        const int f1 = lane < T ? s_fill1[lane] : -1, f2 = lane < T ? s_fill2[lane] : -1;
+        if (lane < T) {
+            const int tier = s_tier[lane], src = s_src[lane];
             const unsigned char *rowp = nullptr;
             int codec = cs1.codec;
-            if (tier == 1) rowp = src >= 0 ? a1.arena + (long long)src * cs1.row_bytes
-                                           : args.t1.backing[i] + (long long)rrow * cs1.row_bytes;
+            if (tier == 1) rowp = src >= 0 ? a1.arena + (long long)src * rb1 : s_back1[lane] + (long long)row * rb1;
             else if (tier == 2) {
                 codec = cs2.codec;
-                rowp = src >= 0 ? a2.arena + (long long)src * cs2.row_bytes
-                                : args.t2.backing[i] + (long long)rrow * cs2.row_bytes;
+                rowp = src >= 0 ? a2.arena + (long long)src * rb2 : s_back2[lane] + (long long)row * rb2;
             } else if (tier == 3) {  // alt-key hit: the ALT row, decoded at the precision of the tier holding it
-                rowp = a1.arena + (long long)src * cs1.row_bytes;
+                rowp = a1.arena + (long long)src * rb1;
             } else if (tier == 4) {
                 codec = cs2.codec;
-                rowp = a2.arena + (long long)src * cs2.row_bytes;
+                rowp = a2.arena + (long long)src * rb2;
             }
-            for (int c = lane; c < d; c += 64) out[i * d + c] = rowp ? decode_elem(rowp, codec, c) : 0.f;
+            s_rowp[lane] = rowp; s_codec[lane] = codec;
         }
-        __syncthreads();
-        for (int i = 0; i < T; i++) {
-            const unsigned long long ki = ((unsigned long long)(i + 1) << 32) | (unsigned)s_req[i];
-            const int f1 = s_fill1[i], f2 = s_fill2[i];
-            if (f1 >= 0 && ld(&a1.ekey[f1]) == ki) {
-                const unsigned char *rowp = args.t1.backing[i] + (long long)s_req[i] * cs1.row_bytes;
-                unsigned char *dst = a1.arena + (long long)f1 * cs1.row_bytes;
-                for (int c = lane; c < cs1.row_bytes; c += 64) dst[c] = rowp[c];
+        // ... and lists the new entries of both tiers, C1's first (a key is inserted into at most one tier)
+        const unsigned long long fm1 = __ballot(f1 >= 0), fm2 = __ballot(f2 >= 0);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        fp.n1 = __popcll(fm1);
+        const int fill_rank = f1 >= 0 ? __popcll(fm1 & below) : fp.n1 + __popcll(fm2 & below);
+        fp.n_ch1 = fp.n1 * fp.cpr1;
+        fp.n_ch = fp.n_ch1 + __popcll(fm2) * fp.cpr2;
+        if (f1 >= 0) { s_fsrc[fill_rank] = s_back1[lane] + (long long)row * rb1; s_fdst[fill_rank] = a1.arena + (long long)f1 * rb1; }
+        else if (f2 >= 0) { s_fsrc[fill_rank] = s_back2[lane] + (long long)row * rb2; s_fdst[fill_rank] = a2.arena + (long long)f2 * rb2; }
+        // (an entry a later key of this request evicted again is not written: its key has changed.  Asked for here, looked at
+        //  behind the out stream)
+        const unsigned long long fkey = ld(f1 >= 0 ? &a1.ekey[f1] : &a2.ekey[f2 >= 0 ? f2 : 0]);
+        EVS_WSYNC();
+        // the new entries' rows are asked for with the rows that go out; their stores stay behind the out stream (an entry that was
+        // evicted and refilled within this request may still be the source of an earlier hit's row)
+        u32x4_t fill_q[2];
+        unsigned fill_w[8];
+        unsigned short fill_h[16];
+        unsigned char fill_b[16];
+        if (fill_cs == 16) fill_load(fill_q, fp, lane, s_fsrc, dummy);
+        else if (fill_cs == 4) fill_load(fill_w, fp, lane, s_fsrc, dummy);
+        else if (fill_cs == 2) fill_load(fill_h, fp, lane, s_fsrc, dummy);
+        else fill_load(fill_b, fp, lane, s_fsrc, dummy);
+        {
+            // one flat stream of T*d elements, sixteen per lane asked for before the first is looked at.  The codec is the ROW's:
+            // every element is fetched as the aligned 32-bit word that holds it (one kind of load whatever the codec; an aligned
+            // word never leaves the page its element is in) and decoded behind the one wait
+            const int n_el = T * d;
+            auto put = [&](int idx, float v) {
+                if constexpr (SERVE) __hip_atomic_store(out + idx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // written through (cache_exact_body)
+                else out[idx] = v;
+            };
+            int ti = lane / d, tc = lane - ti * d;     // (table, column) of this lane's first element; + 64 per step
+            const int step_i = 64 / d, step_c = 64 - step_i * d;
+            const unsigned *wp[16];
+            unsigned meta[16];     // bits 0..5 codec, bit 6 the odd column (u4), bit 7 a row is there, bits 8.. the shift
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const bool in = lane + 64 * k < n_el;
+                const int i_ = in ? ti : T - 1, c_ = in ? tc : d - 1;
+                const unsigned char *rowp = s_rowp[i_];
+                const int codec = s_codec[i_];
+                const unsigned char *p = rowp ? rowp + ((c_ * codec) >> 3) : dummy;
+                const unsigned mis = codec == 32 ? 0u : (unsigned)(reinterpret_cast<uintptr_t>(p) & 3u);   // (fp32 elements are read where they are)
+                wp[k] = reinterpret_cast<const unsigned *>(p - mis);
+                meta[k] = (unsigned)codec | ((unsigned)(c_ & 1) << 6) | ((in && rowp) ? 128u : 0u) | (mis << 11);
+                ti += step_i; tc += step_c;
+                if (tc >= d) { tc -= d; ti++; }
             }
-            if (f2 >= 0 && ld(&a2.ekey[f2]) == ki) {
-                const unsigned char *rowp = args.t2.backing[i] + (long long)s_req[i] * cs2.row_bytes;
-                unsigned char *dst = a2.arena + (long long)f2 * cs2.row_bytes;
-                for (int c = lane; c < cs2.row_bytes; c += 64) dst[c] = rowp[c];
+            unsigned w[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) w[k] = *wp[k];
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const unsigned codec = meta[k] & 63u, v = w[k] >> (meta[k] >> 8);
+                float f;
+                if (codec == 32u) f = __uint_as_float(w[k]);
+                else if (codec == 16u) f = dec_u16(v & 0xffffu);
+                else if (codec == 8u) f = dec_u8(v & 0xffu);
+                else f = kU4Lut[(meta[k] & 64u) ? (v & 15u) : ((v >> 4) & 15u)];
+                if (lane + 64 * k < n_el) put(lane + 64 * k, (meta[k] & 128u) ? f : 0.f);
+            }
+            for (int idx = lane + 1024; idx < n_el; idx += 64) {   // (more than 1 024 elements: the rest one at a time)
+                const int i = idx / d, c = idx - i * d;
+                const unsigned char *rowp = s_rowp[i];
+                put(idx, rowp ? decode_elem(rowp, s_codec[i], c) : 0.f);
             }
         }
+        EVS_WSYNC();
+        if constexpr (SERVE) {
+            // ---- the answer: the T tier codes, then -- behind a wait for the rows (written through) and the codes -- the
+            // sequence number the host polls for; BEFORE both tiers' arena fills, which run while it travels ----
+            served++;
+            serve_seq = (serve_seq + 1u) & 0x7fffffffu;
+            if (lane < T) const_cast<volatile unsigned char *>(reinterpret_cast<volatile unsigned char *>(sv.ans))[lane] = code;
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+            if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 16, serve_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        // ---- every new entry's row, table -> arena ----
+        if ((f1 >= 0 || f2 >= 0) && fkey != key) s_fdst[fill_rank] = nullptr;
+        EVS_WSYNC();
+        if (fill_cs == 16) fill_store(fill_q, fp, lane, s_fsrc, s_fdst);
+        else if (fill_cs == 4) fill_store(fill_w, fp, lane, s_fsrc, s_fdst);
+        else if (fill_cs == 2) fill_store(fill_h, fp, lane, s_fsrc, s_fdst);
+        else fill_store(fill_b, fp, lane, s_fsrc, s_fdst);
         __threadfence_block();   // (as in the one-tier kernel)
-        __syncthreads();
+        EVS_WSYNC();
     }
     hot_store(h1, args.t1.st, lane);
     hot_store(h2, args.t2.st, lane);
     if (has_c3 && lane == 0) *args.c3.st = s3;
     if (lane == 0) {
-        args.t1.st->n_requests = cs1.n_requests + args.B;
+        args.t1.st->n_requests = cs1.n_requests + (SERVE ? served : args.B);
         args.t1.st->n_perfect_hits = cs1.n_perfect_hits + n_perfect_req;
         args.t1.st->n_hits = cs1.n_hits + n_hits;
     }
+    if constexpr (SERVE) {   // the state is back in HBM: only now may the host start another server (or anything else) on it
+        __threadfence_system();
+        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
+__global__ void __launch_bounds__(64) cache_c1c2_kernel(const C1C2Args args) { cache_c1c2_body<false>(args, ServeArgs{}); }
+__global__ void __launch_bounds__(64) cache_c1c2_serve_kernel(const C1C2Args args, const ServeArgs sv) { cache_c1c2_body<true>(args, sv); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -2996,6 +3219,7 @@ __global__ void __launch_bounds__(256) cache_batch_unstage_kernel(const BatchArg
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+struct evs_tier_server;
 struct evs_aprx {
     evs::AprxArrays x{};
     long long nslot = 0, cap = 0;
@@ -3006,6 +3230,7 @@ struct evs_aprx {
     long long nset = 0;
     long long *bstat = nullptr;   // device: [0] members, [1] alt hits served
     int used = 0;                 // 0 fresh, 1 exact machine, 2 batched form
+    evs_tier_server *tsrv = nullptr;   // the tier server this tier belongs to (evs_tiers_serve_*)
 };
 struct evs_cache {
     evs::CacheState host;      // configuration mirror
@@ -3081,7 +3306,28 @@ struct evs_cache {
     hipEvent_t exact_done = nullptr; bool exact_pending = false;
     std::vector<hipEvent_t> slot_done; std::vector<char> slot_busy;
     int inline_mode = -1;          // the update inside the probe launch (evs_fused_rf.hip): -1 not decided (EVS_CACHE_INLINE, default on), 0 / 1
+    evs_tier_server *tsrv = nullptr;   // the tier pair / triple server this cache belongs to (evs_tiers_serve_*)
 };
+// The tier pair / triple as a resident server (cache_c1c2_serve_kernel): the single-tier server's mailbox and ring rules, owned
+// by an object of its own because the state it mutates belongs to two or three handles.  Every entry point that reads or
+// writes a member's exact state goes through serve_pause / aprx_pause, which send this server home first.
+struct evs_tier_server {
+    evs_cache *c1 = nullptr, *c2 = nullptr;
+    evs_aprx *c3 = nullptr;
+    int threshold = 23, n_tables = 0;
+    unsigned *mbox = nullptr, *mbox_dev = nullptr;   // 3 lines of 128 bytes: request, control, answer
+    hipStream_t stream = nullptr;
+    bool serving = false, dead = false;              // dead: a member was destroyed
+    unsigned seq = 0;
+    float *ring = nullptr; int slots = 0;
+    long long idle_ticks = 0;
+    hipEvent_t exact_done = nullptr; bool exact_pending = false;   // (as evs_cache's)
+    std::vector<hipEvent_t> slot_done; std::vector<char> slot_busy;
+};
+static int tiers_pause(evs_tier_server *s);
+static int tiers_launched(evs_tier_server *s, hipStream_t st);
+static void tiers_member_gone(evs_tier_server *s);
+static int aprx_pause(evs_aprx *p) { return (p && p->tsrv) ? tiers_pause(p->tsrv) : EVS_OK; }
 
 // ---- set-associative geometry (host) ----
 namespace {
@@ -3197,6 +3443,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
+    if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
     void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -3414,6 +3661,7 @@ static void serve_launch(evs_cache *c) {
 }
 // behind every exact-path launch: where a server started later has to wait (only caches that have a server pay the record)
 static int exact_launched(evs_cache *c, hipStream_t st) {
+    if (c->tsrv) { const int trc = tiers_launched(c->tsrv, st); if (trc) return trc; }
     if (!c->serve_stream) return EVS_OK;
     if (!c->exact_done) EVS_HIP_CHECK(hipEventCreateWithFlags(&c->exact_done, hipEventDisableTiming));
     EVS_HIP_CHECK(hipEventRecord(c->exact_done, st));
@@ -3423,6 +3671,7 @@ static int exact_launched(evs_cache *c, hipStream_t st) {
 // anything else that reads or writes the exact state first sends the server home (it writes the state back on its way out);
 // the next evs_cache_serve_request starts it again
 static int serve_pause(evs_cache *c) {
+    if (c && c->tsrv) { const int trc = tiers_pause(c->tsrv); if (trc) return trc; }
     if (!c || !c->mbox || !c->serve_stream) return EVS_OK;
     if (hipStreamQuery(c->serve_stream) == hipSuccess) return EVS_OK;   // nothing running
     (void)hipGetLastError();
@@ -3439,6 +3688,7 @@ extern "C" int evs_cache_serve_start(evs_cache *c, int approx_thres, float *ring
     if (!c->has_backing) { set_error("evs_cache_serve_start: call evs_cache_set_backing first"); return EVS_ESTATE; }
     if (c->staged_mask) { set_error("evs_cache_serve_start: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (c->used == 2) { set_error("evs_cache_serve_start: this cache is used through the batched path"); return EVS_ESTATE; }
+    if (c->tsrv) { set_error("evs_cache_serve_start: this cache belongs to a tier server (evs_tiers_serve_start)"); return EVS_ESTATE; }
     EVS_REQUIRE(c->host.n_tables <= 28, "evs_cache_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
     c->used = 1;
     if (!c->mbox) {
@@ -4317,6 +4567,7 @@ extern "C" int evs_cache_lookup_interact_c1c2c3(evs_cache *c1, evs_cache *c2, ev
 extern "C" int64_t evs_aprx_batch_dump(evs_aprx *p, int64_t *triples, int64_t max_triples, int64_t *out4, void *stream) {
     using namespace evs;
     if (!p) { set_error("evs_aprx_batch_dump: NULL tier"); return EVS_EINVAL; }
+    if (aprx_pause(p)) return EVS_EHIP;
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return EVS_EHIP;
     const long long n = p->nset * kSetWays;
     std::vector<unsigned long long> tags(n);
@@ -4699,6 +4950,7 @@ extern "C" int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t 
 // ---- a12: alt-key tier object --------------------------------------------------------------------
 extern "C" int evs_aprx_destroy(evs_aprx *p) {
     if (!p) return EVS_OK;
+    if (p->tsrv) tiers_member_gone(p->tsrv);
     void *ptrs[] = {p->x.st, p->x.keys, p->x.slot_entry, p->x.ekey, p->x.ealt, p->x.eflag, p->x.free_stack, p->x.queue, p->tags, p->bstat};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     delete p;
@@ -4750,6 +5002,7 @@ extern "C" int evs_aprx_create(evs_aprx **out, int64_t capacity, int n_tables) {
 extern "C" int evs_aprx_set_altkeys(evs_aprx *p, const uint32_t *const *alt_tables, const int64_t *n_rows) {
     using namespace evs;
     EVS_REQUIRE(p && alt_tables && n_rows, "evs_aprx_set_altkeys: NULL argument");
+    { const int prc = aprx_pause(p); if (prc) return prc; }
     for (int k = 0; k < p->n_tables; k++) {
         EVS_REQUIRE(alt_tables[k] || n_rows[k] == 0, "evs_aprx_set_altkeys: table %d is NULL", k);
         p->x.alt_tables[k] = alt_tables[k];
@@ -4764,15 +5017,17 @@ extern "C" int evs_aprx_apply_ops(evs_aprx *p, int64_t n, const int32_t *ops, ui
     EVS_REQUIRE(p && (n == 0 || (ops && res)) && n >= 0, "evs_aprx_apply_ops: bad argument");
     if (!p->has_alt) { set_error("evs_aprx_apply_ops: call evs_aprx_set_altkeys first"); return EVS_ESTATE; }
     if (n == 0) return EVS_OK;
+    { const int prc = aprx_pause(p); if (prc) return prc; }
     hipLaunchKernelGGL(aprx_ops_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p->x, (long long)n, ops, res);
     EVS_HIP_CHECK(hipGetLastError());
-    return EVS_OK;
+    return p->tsrv ? tiers_launched(p->tsrv, reinterpret_cast<hipStream_t>(stream)) : EVS_OK;
 }
 
 // the FIFO front to back as (table_1based, row) pairs on the host, stale duplicates included; returns the length
 extern "C" int64_t evs_aprx_dump_queue(evs_aprx *p, int64_t *pairs, int64_t max_pairs, void *stream) {
     using namespace evs;
     if (!p) { set_error("evs_aprx_dump_queue: NULL tier"); return EVS_EINVAL; }
+    if (aprx_pause(p)) return EVS_EHIP;
     AprxState h;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (hipMemcpyAsync(&h, p->x.st, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return EVS_EHIP;
@@ -4791,11 +5046,205 @@ extern "C" int64_t evs_aprx_dump_queue(evs_aprx *p, int64_t *pairs, int64_t max_
 extern "C" int evs_aprx_stats(evs_aprx *p, int64_t *out4, void *stream) {
     using namespace evs;
     EVS_REQUIRE(p && out4, "evs_aprx_stats: NULL argument");
+    { const int prc = aprx_pause(p); if (prc) return prc; }
     AprxState h;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     EVS_HIP_CHECK(hipMemcpyAsync(&h, p->x.st, sizeof h, hipMemcpyDeviceToHost, st));
     EVS_HIP_CHECK(hipStreamSynchronize(st));
     out4[0] = h.count; out4[1] = h.n_hit; out4[2] = h.n_pending; out4[3] = h.error;
+    return EVS_OK;
+}
+
+// ---- the tier pair / triple as a resident server (cache_c1c2_serve_kernel; evs_tiers_serve_*) -----------------------------
+// request_to_c1_c2 / request_to_c1_c2_c3 one request at a time (mixed_precs_caching/cache_manager.cpp:170-229,
+// evlfu_8.cpp:492-667, 669-796) without a launch and a synchronise per request
+static void tiers_args(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int threshold, evs::C1C2Args &args) {
+    using namespace evs;
+    evs_cache *cs[2] = {c1, c2};
+    TierArgs *ts[2] = {&args.t1, &args.t2};
+    for (int t = 0; t < 2; t++) {
+        ts[t]->st = cs[t]->st; ts[t]->a = cs[t]->a;
+        for (int k = 0; k < kMaxTables; k++) { ts[t]->backing[k] = cs[t]->backing[k]; ts[t]->backing_rows[k] = cs[t]->backing_rows[k]; }
+    }
+    if (c3) args.c3 = c3->x; else { args.c3 = AprxArrays{}; args.c3.st = nullptr; }
+    args.requests = nullptr; args.out = nullptr; args.tier_out = nullptr; args.B = 0; args.threshold = threshold;
+}
+static void tiers_launch(evs_tier_server *s) {
+    using namespace evs;
+    C1C2Args args;
+    tiers_args(s->c1, s->c2, s->c3, s->threshold, args);
+    ServeArgs sv;
+    sv.req = s->mbox_dev; sv.ctl = s->mbox_dev + 32; sv.ans = s->mbox_dev + 64;
+    sv.ring = s->ring; sv.n_slots = s->slots; sv.idle_ticks = s->idle_ticks;
+    // a launch-per-call request on the members may still be running on the caller's stream: the server starts behind it
+    if (s->exact_pending) { (void)hipStreamWaitEvent(s->stream, s->exact_done, 0); s->exact_pending = false; }
+    hipLaunchKernelGGL(cache_c1c2_serve_kernel, dim3(1), dim3(64), 0, s->stream, args, sv);
+}
+static int tiers_launched(evs_tier_server *s, hipStream_t st) {
+    if (!s || s->dead || !s->stream) return EVS_OK;
+    if (!s->exact_done) EVS_HIP_CHECK(hipEventCreateWithFlags(&s->exact_done, hipEventDisableTiming));
+    EVS_HIP_CHECK(hipEventRecord(s->exact_done, st));
+    s->exact_pending = true;
+    return EVS_OK;
+}
+// send the server home (it writes h1, h2, s3 and the counters back on its way out); the next request starts it again
+static int tiers_pause(evs_tier_server *s) {
+    if (!s || !s->mbox || !s->stream) return EVS_OK;
+    if (hipStreamQuery(s->stream) == hipSuccess) return EVS_OK;   // nothing running
+    (void)hipGetLastError();
+    volatile unsigned *req = s->mbox;
+    req[32] = 1u;
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    const hipError_t e = hipStreamSynchronize(s->stream);
+    req[32] = 0u;
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    if (e != hipSuccess) { evs::set_error("the tier server's stream failed: %s", hipGetErrorString(e)); return EVS_EHIP; }
+    return EVS_OK;
+}
+static void tiers_detach(evs_tier_server *s) {
+    if (s->c1) s->c1->tsrv = nullptr;
+    if (s->c2) s->c2->tsrv = nullptr;
+    if (s->c3) s->c3->tsrv = nullptr;
+    s->c1 = s->c2 = nullptr; s->c3 = nullptr;
+}
+static void tiers_member_gone(evs_tier_server *s) {
+    (void)tiers_pause(s);
+    tiers_detach(s);
+    s->dead = true; s->serving = false;
+}
+
+extern "C" int evs_tiers_serve_start(evs_tier_server **out, evs_cache *c1, evs_cache *c2, evs_aprx *c3, int high_agghit_threshold,
+                                     float *ring, int n_slots, int64_t idle_us) {
+    using namespace evs;
+    EVS_REQUIRE(out && c1 && c2 && ring && n_slots >= 1 && idle_us >= 1, "evs_tiers_serve_start: bad argument (NULL out / cache / ring, n_slots < 1 or idle_us < 1)");
+    EVS_REQUIRE(c1 != c2, "evs_tiers_serve_start: C1 and C2 are the same cache");
+    EVS_REQUIRE(c1->host.policy == kEvLFU && c2->host.policy == kEvLFU, "evs_tiers_serve_start: both tiers must be EvLFU");
+    EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "evs_tiers_serve_start: the tiers disagree on n_tables/dim");
+    EVS_REQUIRE(c1->host.n_tables <= 28, "evs_tiers_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
+    EVS_REQUIRE(!c3 || c3->n_tables == c1->host.n_tables, "evs_tiers_serve_start: alt-key tier has a different n_tables");
+    if (!c1->has_backing || !c2->has_backing) { set_error("evs_tiers_serve_start: set the backing tables of both tiers first"); return EVS_ESTATE; }
+    if (c1->staged_mask || c2->staged_mask) { set_error("evs_tiers_serve_start: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
+    if (c1->used == 2 || c2->used == 2) { set_error("evs_tiers_serve_start: a tier is used through the batched path"); return EVS_ESTATE; }
+    if (c3 && !c3->has_alt) { set_error("evs_tiers_serve_start: call evs_aprx_set_altkeys first"); return EVS_ESTATE; }
+    if (c3 && c3->used == 2) { set_error("evs_tiers_serve_start: this alt-key tier is used through the batched path"); return EVS_ESTATE; }
+    if (c1->serving || c2->serving) { set_error("evs_tiers_serve_start: a tier runs its own single-tier server (evs_cache_serve_stop first)"); return EVS_ESTATE; }
+    if (c1->tsrv || c2->tsrv || (c3 && c3->tsrv)) { set_error("evs_tiers_serve_start: a tier already belongs to a tier server"); return EVS_ESTATE; }
+    { const int p1 = serve_pause(c1), p2 = serve_pause(c2); if (p1 || p2) return EVS_EHIP; }   // (a stopped single-tier server inside its idle window)
+    evs_tier_server *s = new evs_tier_server();
+    auto fail = [&](int rc) {
+        if (s->stream) (void)hipStreamDestroy(s->stream);
+        if (s->mbox) (void)hipHostFree(s->mbox);
+        delete s;
+        return rc;
+    };
+    if (hipHostMalloc(reinterpret_cast<void **>(&s->mbox), 3 * 128, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: no mailbox"); return fail(EVS_ENOMEM); }
+    memset(s->mbox, 0, 3 * 128);
+    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&s->mbox_dev), s->mbox, 0) != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: the mailbox is not device-accessible"); return fail(EVS_EHIP); }
+    int prio_lo = 0, prio_hi = 0;   // (the highest priority, non-blocking: see evs_cache_serve_start)
+    if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess || hipStreamCreateWithPriority(&s->stream, hipStreamNonBlocking, prio_hi) != hipSuccess) {
+        (void)hipGetLastError(); set_error("evs_tiers_serve_start: no stream"); return fail(EVS_EHIP);
+    }
+    s->c1 = c1; s->c2 = c2; s->c3 = c3; s->threshold = high_agghit_threshold; s->n_tables = c1->host.n_tables;
+    s->ring = ring; s->slots = n_slots; s->idle_ticks = idle_us * 100;   // wall_clock64(): 100 MHz
+    s->slot_done.assign((size_t)n_slots, nullptr); s->slot_busy.assign((size_t)n_slots, 0);
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: hipDeviceSynchronize failed"); return fail(EVS_EHIP); }   // (ring, tables and earlier requests in place)
+    c1->used = c2->used = 1; c1->tsrv = c2->tsrv = s;
+    if (c3) { c3->used = 1; c3->tsrv = s; }
+    s->serving = true;
+    *out = s;
+    return EVS_OK;
+}
+
+static int tiers_request_impl(evs_tier_server *s, const int32_t *rows, const int64_t *ids_dev, int64_t ids_stride, float *out_dev, uint8_t *tier, int *slot_out) {
+    using namespace evs;
+    if (s->dead) { set_error("evs_tiers_serve_request: a member of this tier server was destroyed"); return EVS_ESTATE; }
+    if (!s->serving) { set_error("evs_tiers_serve_request: the server was stopped"); return EVS_ESTATE; }
+    volatile unsigned *req = s->mbox, *ans = s->mbox + 64;
+    const int T = s->n_tables;
+    const unsigned want = (s->seq + 1u) & 0x7fffffffu;
+    const int slot = (int)(want % (unsigned)s->slots);
+    if (!out_dev && s->slot_busy[(size_t)slot]) {   // whoever still READS the slot (evs_tiers_serve_consumed) finishes first
+        EVS_HIP_CHECK(hipEventSynchronize(s->slot_done[(size_t)slot]));
+        s->slot_busy[(size_t)slot] = 0;
+    }
+    s->seq = want;
+    const unsigned long long oa = (unsigned long long)reinterpret_cast<uintptr_t>(out_dev);
+    unsigned guard = want;   // the line is the single-tier server's (serve_request_impl): seven ids and a guard per 32-byte sector
+    if (rows) {
+        for (int t = 0; t < T; t++) req[t + t / 7] = (unsigned)rows[t];
+        if (T <= 26) { req[29] = (unsigned)oa; req[30] = (unsigned)(oa >> 32); }
+    } else {
+        const unsigned long long pa = (unsigned long long)reinterpret_cast<uintptr_t>(ids_dev);
+        req[0] = (unsigned)pa; req[1] = (unsigned)(pa >> 32); req[2] = (unsigned)ids_stride;
+        req[3] = (unsigned)oa; req[4] = (unsigned)(oa >> 32);
+        guard |= 0x80000000u;
+    }
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    req[7] = guard; req[15] = guard; req[23] = guard; req[31] = guard;
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    long long spins = 0;
+    auto fail = [&](int rc) { s->seq = ans[16]; return rc; };   // host and device agree on the number last ANSWERED
+    while (ans[16] != want) {
+        if ((spins & 63) == 0 && ans[17] == 0u) {   // no server (never started, went home idle, or was paused): start one
+            const hipError_t q = hipStreamQuery(s->stream);
+            if (q == hipSuccess) {
+                tiers_launch(s);
+                if (hipGetLastError() != hipSuccess) { set_error("evs_tiers_serve_request: the server could not be started"); return fail(EVS_EHIP); }
+            }
+            else if (q != hipErrorNotReady) { (void)hipGetLastError(); set_error("evs_tiers_serve_request: the server's stream failed"); return fail(EVS_EHIP); }
+            else (void)hipGetLastError();
+        }
+        if (++spins > (1ll << 31)) {
+            (void)tiers_pause(s);
+            set_error("evs_tiers_serve_request: the server did not answer");
+            return fail(EVS_EHIP);
+        }
+        __builtin_ia32_pause();
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const volatile unsigned char *fl = reinterpret_cast<const volatile unsigned char *>(ans);
+    for (int t = 0; t < T; t++) tier[t] = fl[t];
+    *slot_out = out_dev ? -1 : slot;
+    return EVS_OK;
+}
+extern "C" int evs_tiers_serve_request(evs_tier_server *s, const int32_t *rows, uint8_t *tier, int *slot_out) {
+    using namespace evs;
+    EVS_REQUIRE(s && rows && tier && slot_out, "evs_tiers_serve_request: NULL argument");
+    return tiers_request_impl(s, rows, nullptr, 0, nullptr, tier, slot_out);
+}
+extern "C" int evs_tiers_serve_request_to(evs_tier_server *s, const int32_t *rows, const int64_t *ids_dev, int64_t ids_stride, float *out_dev, uint8_t *tier) {
+    using namespace evs;
+    EVS_REQUIRE(s && out_dev && tier && ((rows != nullptr) != (ids_dev != nullptr)) && ids_stride >= 0 && ids_stride < (1ll << 32),
+                "evs_tiers_serve_request_to: bad argument");
+    EVS_REQUIRE(s->n_tables <= 26, "evs_tiers_serve_request_to: at most 26 tables (the line's last two id words carry the address)");
+    int slot = 0;
+    return tiers_request_impl(s, rows, ids_dev, ids_stride, out_dev, tier, &slot);
+}
+extern "C" int evs_tiers_serve_consumed(evs_tier_server *s, int slot, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(s && s->serving && slot >= 0 && slot < s->slots, "evs_tiers_serve_consumed: bad argument");
+    hipEvent_t &e = s->slot_done[(size_t)slot];
+    if (!e) EVS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    EVS_HIP_CHECK(hipEventRecord(e, reinterpret_cast<hipStream_t>(stream)));
+    s->slot_busy[(size_t)slot] = 1;
+    return EVS_OK;
+}
+extern "C" int evs_tiers_serve_stop(evs_tier_server *s) {
+    using namespace evs;
+    EVS_REQUIRE(s, "evs_tiers_serve_stop: NULL server");
+    const int rc = tiers_pause(s);
+    s->serving = false;
+    return rc;
+}
+extern "C" int evs_tiers_serve_destroy(evs_tier_server *s) {
+    if (!s) return EVS_OK;
+    (void)tiers_pause(s);
+    tiers_detach(s);
+    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
+    if (s->mbox) (void)hipHostFree(s->mbox);
+    if (s->exact_done) (void)hipEventDestroy(s->exact_done);
+    for (hipEvent_t e : s->slot_done) if (e) (void)hipEventDestroy(e);
+    delete s;
     return EVS_OK;
 }
 
@@ -4816,19 +5265,14 @@ extern "C" int evs_cache_request_c1c2c3(evs_cache *c1, evs_cache *c2, evs_aprx *
     if (B == 0) return EVS_OK;
     EVS_REQUIRE(B > 0 && rows && out && tier, "evs_cache_request_c1c2c3: NULL argument");
     if (c1->used == 2 || c2->used == 2) { set_error("evs_cache_request_c1c2c3: a tier is used through the batched path"); return EVS_ESTATE; }
-    { const int p1 = serve_pause(c1), p2 = serve_pause(c2); if (p1 || p2) return EVS_EHIP; }
+    { const int p1 = serve_pause(c1), p2 = serve_pause(c2), p3 = aprx_pause(c3); if (p1 || p2 || p3) return EVS_EHIP; }
     c1->used = c2->used = 1;
     C1C2Args args;
-    evs_cache *cs[2] = {c1, c2};
-    TierArgs *ts[2] = {&args.t1, &args.t2};
-    for (int t = 0; t < 2; t++) {
-        ts[t]->st = cs[t]->st; ts[t]->a = cs[t]->a;
-        for (int k = 0; k < kMaxTables; k++) { ts[t]->backing[k] = cs[t]->backing[k]; ts[t]->backing_rows[k] = cs[t]->backing_rows[k]; }
-    }
-    if (c3) args.c3 = c3->x; else { args.c3 = AprxArrays{}; args.c3.st = nullptr; }
-    args.requests = rows; args.out = out; args.tier_out = tier; args.B = B; args.threshold = high_agghit_threshold;
+    tiers_args(c1, c2, c3, high_agghit_threshold, args);
+    args.requests = rows; args.out = out; args.tier_out = tier; args.B = B;
     hipLaunchKernelGGL(cache_c1c2_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), args);
     EVS_HIP_CHECK(hipGetLastError());
     { const int r1 = exact_launched(c1, reinterpret_cast<hipStream_t>(stream)), r2 = exact_launched(c2, reinterpret_cast<hipStream_t>(stream)); if (r1 || r2) return EVS_EHIP; }
+    if (c3 && c3->tsrv) return tiers_launched(c3->tsrv, reinterpret_cast<hipStream_t>(stream));
     return EVS_OK;
 }

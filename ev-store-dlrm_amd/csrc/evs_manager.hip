@@ -16,6 +16,9 @@
 // EVS_BACKING=host).  backing 0 / 1 (EVS_BACKING=hbm / pinned) run the same requests through the GPU tier's exact
 // kernel, one launch + one synchronise per call (~50 us) -- for a deployment that shares ONE cache between this batch-1
 // surface and the batched GPU lookups.  Same results either way (tests/_ev_lookup_child.py runs all three).
+// EVS_MANAGER_SERVE=1 (default off) puts the GPU engine behind a resident server instead: ev_lookup posts the request to the
+// mailbox of evs_cache_serve_request_to (one layer) or evs_tiers_serve_request_to (two / three), the server writes the rows
+// straight into the manager's pinned h_out through its device address -- no launch, no stream synchronise per request.
 #include "evs_common.h"
 
 #include <fcntl.h>
@@ -52,8 +55,18 @@ struct Manager {
     float *d_out = nullptr, *h_out = nullptr;
     unsigned char *d_hit = nullptr, *h_hit = nullptr;
     hipStream_t stream = nullptr;
+    // EVS_MANAGER_SERVE=1: the GPU engine through a resident server
+    bool serve = false;
+    evs_tier_server *tsrv = nullptr;   // two / three layers (one layer: c1's own server)
+    float *serve_ring = nullptr;       // one slot, never handed out: every request names h_out as its destination
 };
 static Manager g_mgr;
+// the manager is never torn down: a process may reach exit with the resident kernel still polling -- send it home first
+static void manager_stop_server() {
+    Manager &m = g_mgr;
+    if (m.tsrv) (void)evs_tiers_serve_stop(m.tsrv);
+    else if (m.serve && m.c1) (void)evs_cache_serve_stop(m.c1);
+}
 static float g_emb_weights_in_1d_floats[kEvTables * kEvDim];  // cache_manager.hpp:51 (library-owned, static)
 
 static const char *precision_dir(int bits) {
@@ -283,6 +296,17 @@ static int ensure_ready() {
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_rows), m.h_rows, 0));
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_out), m.h_out, 0));
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_hit), m.h_hit, 0));
+    if (const char *e = getenv("EVS_MANAGER_SERVE")) {
+        if (e[0] == '1') {
+            constexpr int64_t kIdleUs = 200;
+            EVS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m.serve_ring), kEvTables * kEvDim * 4));
+            rc = m.c2 ? evs_tiers_serve_start(&m.tsrv, m.c1, m.c2, m.c3, 23 /* evlfu_8.hpp:70 */, m.serve_ring, 1, kIdleUs)
+                      : evs_cache_serve_start(m.c1, -1, m.serve_ring, 1, kIdleUs);
+            if (rc) return rc;
+            m.serve = true;
+            atexit(manager_stop_server);
+        }
+    }
     m.ready = true;
     return EVS_OK;
 }
@@ -309,6 +333,12 @@ extern "C" long long evs_manager_aprx_hit() {  // evlfu_8bit->aprx_ev_hit (cache
     if (g_mgr.h3) (void)evs_hostaprx_stats(g_mgr.h3, s4);
     else (void)evs_aprx_stats(g_mgr.c3, s4, g_mgr.stream);
     return s4[1];
+}
+
+extern "C" int evs_manager_engine() {
+    using namespace evs;
+    if (!g_mgr.ready) return 0;
+    return g_mgr.h1 ? 1 : g_mgr.serve ? 3 : 2;
 }
 
 extern "C" int evs_manager_configure(int n_caching_layer, int main_precision, int secondary_precision,
@@ -342,6 +372,16 @@ extern "C" float *ev_lookup(int *arr) {
             printf("%s\n", evs_last_error());
             return nullptr;
         }
+        return g_emb_weights_in_1d_floats;
+    }
+    if (m.serve) {   // the resident server: the ids ride in the request line, the rows land in h_out before the answer does
+        const int src = m.tsrv ? evs_tiers_serve_request_to(m.tsrv, arr, nullptr, 0, m.d_out, m.h_hit)
+                               : evs_cache_serve_request_to(m.c1, arr, nullptr, 0, m.d_out, m.h_hit);
+        if (src != EVS_OK) {
+            printf("%s\n", evs_last_error());
+            return nullptr;
+        }
+        memcpy(g_emb_weights_in_1d_floats, m.h_out, sizeof g_emb_weights_in_1d_floats);
         return g_emb_weights_in_1d_floats;
     }
     memcpy(m.h_rows, arr, kEvTables * sizeof(int));

@@ -455,3 +455,74 @@ def request_c1c2c3(c1, c2, c3, rows, threshold=23, out=None, tier=None):
                                                    out.data_ptr(), tier.data_ptr(), int(threshold),
                                                    torch.cuda.current_stream(c1.device).cuda_stream))
     return tier, out
+
+
+class TierServer:
+    """The tier pair / triple as a resident server (include/evstore_hip.h: evs_tiers_serve_*): request_c1c2 / request_c1c2c3
+    one request at a time without a launch and a synchronise per request.  c1, c2: GpuCache (variant="cpp", backing set),
+    c3: GpuAltKeyTier or None.  Keeps its members alive; any call on a member that reads or writes its exact state
+    (stats, dump, request, ...) sends the server home first and the next request starts it again."""
+
+    def __init__(self, c1, c2, c3=None, threshold=23, n_slots=4, idle_us=200):
+        import numpy as np
+        _warn_hw_queues()
+        self.c1, self.c2, self.c3 = c1, c2, c3
+        self.n_tables, self.dim, self.device = c1.n_tables, c1.dim, c1.device
+        self.ring = torch.empty((n_slots, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
+        self._views = [self.ring[k] for k in range(n_slots)]   # (a tensor index per request is 2 us)
+        self._rows = np.zeros(self.n_tables, np.int32)
+        self._tier = np.zeros(self.n_tables, np.uint8)
+        self._slot = C.c_int(0)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().evs_tiers_serve_start(C.byref(h), c1._h, c2._h, c3._h if c3 is not None else None, int(threshold),
+                                                        self.ring.data_ptr(), int(n_slots), int(idle_us)))
+        self._h = h
+        self._call = (_lib.lib().evs_tiers_serve_request, self._h, self._rows.ctypes.data, self._tier.ctypes.data, C.byref(self._slot))
+
+    def request(self, row_ids):
+        """row_ids: n_tables ints (host) -> (tier codes: a numpy uint8 view valid until the next request; the (T, dim) fp32
+        rows as a DEVICE view of a ring slot, valid until n_slots - 1 more requests are posted -- see consumed())."""
+        self._rows[:] = row_ids
+        fn, h, rp, tp, sp = self._call
+        rc = fn(h, rp, tp, sp)
+        if rc:
+            _lib.check(rc)
+        return self._tier, self._views[self._slot.value]
+
+    def request_to(self, row_ids, out):
+        """the same request with the rows written into `out` (a contiguous (T, dim) fp32 DEVICE tensor, not in use by pending
+        work); row_ids: n_tables ints on the host, or a (T, ...) int64 device tensor whose element 0 of each row is the id.
+        -> tier codes (numpy uint8 view)"""
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.n_tables * self.dim):
+            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (self.n_tables * self.dim))
+        L = _lib.lib()
+        if torch.is_tensor(row_ids) and row_ids.is_cuda:
+            if row_ids.dtype != torch.int64 or row_ids.shape[0] != self.n_tables:
+                raise ValueError("device ids: a (T, ...) int64 tensor")
+            _lib.check(L.evs_tiers_serve_request_to(self._h, None, row_ids.data_ptr(), int(row_ids.stride(0)), out.data_ptr(), self._tier.ctypes.data))
+        else:
+            self._rows[:] = row_ids
+            _lib.check(L.evs_tiers_serve_request_to(self._h, self._rows.ctypes.data, None, 0, out.data_ptr(), self._tier.ctypes.data))
+        return self._tier
+
+    def consumed(self, slot=None, stream=None):
+        """the reads of ring slot `slot` (default: the last request's) have been enqueued on `stream` (default: the current one)"""
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        _lib.check(_lib.lib().evs_tiers_serve_consumed(self._h, int(self._slot.value if slot is None else slot), st.cuda_stream))
+
+    def stop(self):
+        """send the server home for good (the members' state is back in HBM); later requests raise"""
+        if self._h:
+            _lib.check(_lib.lib().evs_tiers_serve_stop(self._h))
+
+    def close(self):
+        if self._h:
+            _lib.lib().evs_tiers_serve_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -556,6 +556,37 @@ EVS_API int64_t evs_aprx_dump_queue(evs_aprx *p, int64_t *pairs, int64_t max_pai
 /* evs_cache_request_c1c2 with the alt-key tier (c3 may be NULL = plain two tiers). */
 EVS_API int evs_cache_request_c1c2c3(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B, const int32_t *rows,
                                      float *out, uint8_t *tier, int high_agghit_threshold, void *stream);
+/* The tier pair / triple as a RESIDENT SERVER: request_to_c1_c2 / request_to_c1_c2_c3 one request at a time, as the
+ * reference's cache manager drives them (mixed_precs_caching/cache_manager.cpp:170-229, evlfu_8.cpp:492-667, 669-796), without the
+ * launch and the synchronise evs_cache_request_c1c2[c3] costs per call.  The same kernel body as that call's (same tier codes,
+ * rows, list order, counters) stays on the device and is fed through the mailbox of evs_cache_serve_*: same request line (7 ids +
+ * a guard per 32-byte sector, ids by value or by address, optional destination address), same ring rule (slot = sequence %
+ * n_slots, valid until n_slots - 1 more requests are POSTED unless evs_tiers_serve_consumed says who still reads it), same
+ * limits (at most 28 tables; _request_to at most 26), one host thread per server, idle time-out idle_us.  tier_host: the T tier
+ * codes of evs_cache_request_c1c2c3 (0 miss, 1 C1, 2 C2, 3 alt-key hit).  c3 may be NULL.
+ * evs_tiers_serve_start (cache_manager.cpp:36-53: the tiers are built once and serve every later request): EVS_EINVAL for NULL
+ * out / c1 / c2 / ring, n_slots < 1, idle_us < 1, c1 == c2, tiers that are not EvLFU or disagree on n_tables / dim, more than
+ * 28 tables; EVS_ESTATE for a tier without backing tables, with staged file tables, used through the batched path, running
+ * its own single-tier server, or already a member of a tier server.  A member cannot start a single-tier server either.
+ * Every call that reads or writes a member's exact state -- evs_cache_stats / _dump / _request / _request_c1c2[c3] / _set_backing /
+ * _set_file_backing / _reset_counters / _destroy, evs_aprx_stats / _apply_ops / _dump_queue / _batch_dump / _set_altkeys /
+ * _destroy -- sends the server home first (it writes the policy state back on its way out); the next request starts it again,
+ * behind any launch-per-call request made on the members in between.  Destroying a member stops the server for good: later
+ * requests return EVS_ESTATE.
+ * evs_tiers_serve_request (evlfu_8.cpp:492-667 / 669-796 for one request): rows in ring slot *slot_out (device).
+ * evs_tiers_serve_request_to (the same; cache_manager.cpp:231-237 hands the rows to the caller's buffer): rows to out_dev,
+ * exactly one of rows_host / ids_dev given, as evs_cache_serve_request_to.
+ * evs_tiers_serve_consumed / _stop / _destroy: as evs_cache_serve_consumed / _stop (cache_manager.cpp has no teardown: the
+ * process exits); _destroy frees the server, not its members. */
+typedef struct evs_tier_server evs_tier_server;
+EVS_API int evs_tiers_serve_start(evs_tier_server **out, evs_cache *c1, evs_cache *c2, evs_aprx *c3 /* may be NULL */,
+                                  int high_agghit_threshold, float *ring, int n_slots, int64_t idle_us);
+EVS_API int evs_tiers_serve_request(evs_tier_server *s, const int32_t *rows_host, uint8_t *tier_host, int *slot_out);
+EVS_API int evs_tiers_serve_request_to(evs_tier_server *s, const int32_t *rows_host, const int64_t *ids_dev,
+                                       int64_t ids_stride, float *out_dev, uint8_t *tier_host);
+EVS_API int evs_tiers_serve_consumed(evs_tier_server *s, int slot, void *stream);
+EVS_API int evs_tiers_serve_stop(evs_tier_server *s);
+EVS_API int evs_tiers_serve_destroy(evs_tier_server *s);
 /* out8 (host): [min_C1, n_perfect, size, n_flush, n_evict, n_requests, n_perfect_hits, n_hits].
  * Synchronises the stream.  Returns EVS_ESTATE if the policy hit an inconsistency. */
 EVS_API int evs_cache_stats(evs_cache *c, int64_t *out8, void *stream);
@@ -632,6 +663,11 @@ EVS_API int evs_manager_set_altkey_dir(const char *dir);  /* n_caching_layer 3: 
 EVS_API long long evs_manager_perfect_hit(void);
 EVS_API long long evs_manager_tier_capacity(int tier);   /* entries of tier 1 | 2 | 3 as configured (0 = absent) */
 EVS_API long long evs_manager_aprx_hit(void);             /* evlfu_8bit->aprx_ev_hit (cache_manager.cpp:279) */
+/* which engine ev_lookup runs on (cache_manager.cpp:170-229 has one, compiled in): 0 not initialised, 1 the host engine,
+ * 2 the GPU engine launched per request, 3 the GPU engine through a resident server (EVS_MANAGER_SERVE=1 with EVS_BACKING=hbm |
+ * pinned: evs_cache_serve_request_to for one layer, evs_tiers_serve_request_to for two / three; the server is stopped at exit).
+ * Reads the manager's fields only: callable without a GPU. */
+EVS_API int evs_manager_engine(void);
 EVS_API float *ev_lookup(int *arr);                      /* cache_manager.cpp:231 */
 EVS_API float *get_ev_values(int *arr);                  /* cache_manager.cpp:257 */
 EVS_API void print_perfect_hit(void);                    /* cache_manager.cpp:262 */

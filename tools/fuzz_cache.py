@@ -6,7 +6,9 @@
   batched3     lookup_batch_c1c2c3 (alt-key tier as a key set): tier codes, rows, C3 membership / flags / size
   batched      lookup_batch with random capacities / batch sizes (incl. caches smaller than one batch): snapshot hit
                flags, exact rows, no duplicate keys, size <= capacity, histogram consistent
-usage: python tools/fuzz_cache.py [seconds] [seed]"""
+  tier server  the pair / triple through gpu_cache.TierServer against the HOST engine (evs_hostcache_request_c1c2c3): at most
+               1 200 requests per case, the first mismatch ends the run -- a leg of its own: [seconds] [seed] tiers
+usage: python tools/fuzz_cache.py [seconds] [seed] [tiers]"""
 import os
 import sys
 import time
@@ -194,6 +196,73 @@ def c1c2c3_case(rs, case):
     assert np.array_equal(np.concatenate(outs).view(np.uint32), np.stack(want_o).view(np.uint32)), tag + ": rows"
     assert np.array_equal(c1.dump(), o.c1.dump()) and np.array_equal(c2.dump(), o.c2.dump()), tag + ": final lists"
     assert c3.stats() == o.c3_state(), tag + ": alt-key tier counters"
+    return tag
+
+
+def tiers_serve_case(rs, case):
+    """The tier pair / triple through the resident server (gpu_cache.TierServer) against the HOST engine
+    (evs_hostcache_request_c1c2c3): the three ways a request is posted, a launch-per-call request, a stats call and an idle
+    gap in between.  At most 1 200 requests; the first mismatch ends the run."""
+    from evstore_dlrm_amd import host_cache as H
+    T, d = 26, 36
+    n = int(rs.choice([80, 400]))
+    ws = [rs.uniform(-1, 1, size=(n, d)).astype(np.float32) for _ in range(T)]
+    raw8 = [orc.encode_table(w, 8) for w in ws]
+    raw4 = [orc.encode_table(w, 4) for w in ws]
+    with_c3 = bool(rs.rand() < 0.5)
+    alt = [(rs.randint(0, n, size=n) * 100 + rs.randint(1, T + 1, size=n)).astype(np.uint32) for _ in range(T)]
+    cap1, cap2, cap3 = int(rs.choice([30, 150, 600])), int(rs.choice([30, 300, 1200])), int(rs.choice([50, 51, 120, 400]))
+    thr = int(rs.choice([23, 23, 12, 26]))
+    n_req = int(rs.choice([60, 500, 1200]))
+    tag = "tier server case %d: n=%d caps=%d/%d/%d c3=%d thr=%d n_req=%d" % (case, n, cap1, cap2, cap3, with_c3, thr, n_req)
+    reqs = _stream(rs, [n] * T, n_req)
+    h1 = H.HostCache("evlfu", cap1, T, d, 8, "cpp").set_backing(raw8)
+    h2 = H.HostCache("evlfu", cap2, T, d, 4, "cpp").set_backing(raw4)
+    h3 = H.HostAltKeyTier(cap3, alt) if with_c3 else None
+    want_t, want_o = H.request_c1c2c3(h1, h2, h3, reqs, thr) if with_c3 else H.request_c1c2(h1, h2, reqs, thr)
+    c1 = E.GpuCache("evlfu", cap1, T, d, 8, "cpp")
+    c2 = E.GpuCache("evlfu", cap2, T, d, 4, "cpp")
+    c1.set_backing([torch.from_numpy(r).cuda() for r in raw8])
+    c2.set_backing([torch.from_numpy(r).cuda() for r in raw4])
+    c3 = gpu_cache.GpuAltKeyTier(cap3, [torch.from_numpy(a.view(np.int32)).cuda() for a in alt]) if with_c3 else None
+    srv = gpu_cache.TierServer(c1, c2, c3, threshold=thr, n_slots=int(rs.choice([1, 2, 5])), idle_us=int(rs.choice([30, 300])))
+    r = torch.from_numpy(reqs).cuda()
+    try:
+        for i, rq in enumerate(reqs):
+            way = int(rs.randint(0, 7))
+            if way == 1:
+                rows = torch.full((T, d), -7.0, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                t = srv.request_to(rq, rows)
+            elif way == 2:
+                ids = torch.from_numpy(np.stack([rq.astype(np.int64), np.full(T, -1, np.int64)], 1)).cuda()
+                rows = torch.full((T, d), -7.0, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                t = srv.request_to(ids, rows)
+            elif way == 3:     # launched the old way (sends the server home first)
+                t, rows = gpu_cache.request_c1c2c3(c1, c2, c3, r[i:i + 1].contiguous(), threshold=thr)
+                t, rows = t.cpu().numpy()[0], rows[0]
+            else:
+                if way == 4:
+                    c1.stats()
+                elif way == 5:
+                    time.sleep(0.001)
+                t, rows = srv.request(rq)
+            same = np.array_equal(np.asarray(t), want_t[i]) and np.array_equal(rows.reshape(T, d).cpu().numpy().view(np.uint32), want_o[i].view(np.uint32))
+            if not same and with_c3 and c3.stats()["error"] == 1:
+                # the alt-key tier's FIFO ring is full: the GPU engine (and the oracle) latch error 1 and stop inserting, the host
+                # engine doubles its ring (DESIGN 3.4, round 4) -- from here on the two engines differ by specification
+                return tag + " (ended at request %d: the alt-key ring latched error 1)" % i
+            assert np.array_equal(np.asarray(t), want_t[i]), tag + ": tier codes, request %d way %d" % (i, way)
+            assert same, tag + ": rows, request %d way %d" % (i, way)
+        srv.stop()
+    finally:
+        srv.close()
+    if with_c3 and c3.stats()["error"] == 1:
+        return tag + " (the alt-key ring latched error 1 by the end: final state not compared)"
+    assert np.array_equal(c1.dump(), h1.dump()) and np.array_equal(c2.dump(), h2.dump()), tag + ": final lists"
+    if with_c3:
+        assert c3.stats() == h3.stats(), tag + ": alt-key tier counters"
     return tag
 
 
@@ -435,18 +504,19 @@ def batched3_case(rs, case):
 def main():
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    only_tiers = len(sys.argv) > 3 and sys.argv[3] == "tiers"   # the tier-server leg alone (the mixed run keeps the case sequence of its seeds)
     rs = np.random.RandomState(seed)
     t0 = time.time()
-    n = [0, 0, 0, 0, 0, 0]
+    n = [0, 0, 0, 0, 0, 0, 0]
     last = ""
     while time.time() - t0 < seconds:
-        which = int(rs.choice([0, 0, 1, 2, 2, 3, 4, 5]))
+        which = 6 if only_tiers else int(rs.choice([0, 0, 1, 2, 2, 3, 4, 5]))
         if os.environ.get("EVS_FUZZ_VERBOSE"):
             print("-> case %d kind %d" % (sum(n), which), flush=True)
-        last = (exact_case, c1c2_case, batched_case, batched2_case, c1c2c3_case, batched3_case)[which](rs, sum(n))
+        last = (exact_case, c1c2_case, batched_case, batched2_case, c1c2c3_case, batched3_case, tiers_serve_case)[which](rs, sum(n))
         n[which] += 1
-    print("cache fuzz ok: %d exact, %d two-tier, %d batched, %d batched two-tier, %d three-tier, %d batched three-tier cases in %.0f s (seed %d); last %s" % (
-        n[0], n[1], n[2], n[3], n[4], n[5], time.time() - t0, seed, last))
+    print("cache fuzz ok: %d exact, %d two-tier, %d batched, %d batched two-tier, %d three-tier, %d batched three-tier, %d tier-server cases in %.0f s (seed %d); last %s" % (
+        n[0], n[1], n[2], n[3], n[4], n[5], n[6], time.time() - t0, seed, last))
 
 
 if __name__ == "__main__":
