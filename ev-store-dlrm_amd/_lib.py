@@ -169,6 +169,10 @@ _PROTOS = {
     "evs_hostaprx_stats": (_int, [_vp, _i64p]),
     "evs_hostaprx_apply_ops": (_int, [_vp, _i64, _vp, _vp]),
     "evs_hostaprx_dump_queue": (_i64, [_vp, _i64p, _i64]),
+    "evs_table_update_rows": (_int, [_int, _int, _int, _pp, _i64p, _i64, _vp, _vp, _i64, _vp]),
+    "evs_cache_update_rows": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "evs_cache_refresh_rows": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "evs_hostcache_refresh_rows": (_int, [_vp, _i64, _vp, _vp]),
 }
 
 

@@ -19,3 +19,9 @@ def request_to_ev_lfu(group_row_ids, use_gpu=False, approx_emb_thres=-1, ev_dim=
 
 def stats():
     return _m.stats()
+
+
+def update_rows(keys, values):
+    """online row update (no reference counterpart): (table index 0-based, row) -> new fp32 vector into the tables and into
+    the cache's copies, whichever engine is bound (_common._ModuleCache.update_rows)"""
+    return _m.update_rows(keys, values)

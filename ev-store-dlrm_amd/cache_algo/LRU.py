@@ -10,3 +10,9 @@ def init(capacity, device="cuda", engine="auto"):
 
 def request_to_lru(group_row_ids, use_gpu=False):
     return _m.request(group_row_ids, use_gpu)
+
+
+def update_rows(keys, values):
+    """online row update (no reference counterpart): (table index 0-based, row) -> new fp32 vector into the tables and into
+    the cache's copies, whichever engine is bound (_common._ModuleCache.update_rows)"""
+    return _m.update_rows(keys, values)

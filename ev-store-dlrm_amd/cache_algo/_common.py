@@ -85,6 +85,35 @@ class _ModuleCache:
             self._bind()
         return self.cache.stats()
 
+    # ---- online row updates ----------------------------------------------------------------------------------------------
+    def update_rows(self, keys, values):
+        """a delta of (table index 0-based, row) -> new fp32 vector into the tables AND the cache's copies, whichever engine
+        is bound (gpu: GpuCache.update_rows; host: the fp32 backing arrays are written, then HostCache.refresh_rows).
+        A key out of range is skipped and reported (gpu: the sticky flag of evs_check_index_errors; host: EvsError
+        EVS_EINDEX after the keys in range have been applied).  Waits for the stream (the keys are de-duplicated).
+        -> the number of delta keys that were resident (host engine) / None (GPU engine)"""
+        if not getattr(self, "_bound", False):
+            self._bind()
+        if self.engine == "gpu":
+            return self.cache.update_rows(keys, values)
+        if self.cache.codec != 32:
+            raise NotImplementedError("update_rows on the host engine over %d-bit tables: there is no host-side encoder; write the "
+                                      "encoded rows into HostCache.backing_tables() yourself and call refresh_rows(keys)" % self.cache.codec)
+        keys = np.asarray(keys.cpu() if torch.is_tensor(keys) else keys).astype(np.int64).reshape(-1, 2)
+        values = np.asarray(values.cpu() if torch.is_tensor(values) else values, dtype=np.float32).reshape(-1, self.dim)
+        if len(keys) != len(values):
+            raise ValueError("%d keys but %d value rows" % (len(keys), len(values)))
+        views = []
+        for w in self.cache.backing_tables():
+            views.append(w.reshape(-1).view(np.float32).reshape(-1, self.dim))
+        for (t, r), v in zip(keys, values):   # in order: the last of duplicate keys wins
+            if not (0 <= t < self.n_tables and 0 <= r < len(views[t])):
+                continue                      # skipped here, reported by refresh_rows below
+            if not views[t].flags.writeable:
+                raise ValueError("table %d is a read-only mapping: write the file, then refresh_rows" % t)
+            views[t][r] = v
+        return self.cache.refresh_rows(keys)
+
     # ---- requests -----------------------------------------------------------------------------------------------------
     def _run(self, group_row_ids, approx_thres, want_device_rows):
         """-> (hit flags as a list of bool, rows as a (T, d) float32 tensor on the host, or on the device when the GPU

@@ -23,6 +23,7 @@
 //   * cache_probe_gather_kernel (batched, snapshot semantics) -- see the section below.
 #include "evs_common.h"
 #include "evs_hash.h"
+#include "evs_update.h"
 #include <type_traits>
 
 #include <mutex>
@@ -4945,6 +4946,89 @@ extern "C" int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t 
         n++;
     }
     return n;
+}
+
+// ---- online row updates (evs_update.h): the table row and every cached copy of it, in stream order ----------------------------
+// The look-up of the update / refresh kernels: where (if anywhere) this cache keeps a copy of key (t, row).  Read-only -- the
+// exact map (map_find: entry e owns arena row e), the batched hash (probe_ro on the packed words: the entry rides in the word)
+// or the set records (the way word names the arena row, its select bit the live copy of a two-copy arena; a tier of a pair
+// looks at its own ways of the shared record).  A fresh cache holds nothing.
+namespace evs {
+struct CacheLookup {
+    static constexpr bool kHas = true;
+    unsigned char *arena;
+    int mode;   // 0 nothing resident, 1 exact map, 2 batched hash, 3 set records
+    CacheArrays a; unsigned long long nslot_mask;
+    const unsigned long long *slots; unsigned long long bmask;
+    SaGeom sa; SaUniverse sau;
+    __device__ __forceinline__ unsigned row_base(int i) const { return sau.row_base[i & 31]; }
+    __device__ __forceinline__ long long find(int t, unsigned row, const unsigned *s_base) const {
+        const unsigned long long key = ((unsigned long long)(t + 1) << 32) | row;
+        if (mode == 1) return map_find(a, nslot_mask, key);
+        if (mode == 2) {
+            unsigned long long end_slot;
+            const int e = probe_ro(slots, bmask, key, end_slot);
+            return e >= 0 ? e : -1;
+        }
+        if (mode == 3) {
+            unsigned es, tag1, w;
+            sa_split(sa, sa_perm(sau, s_base[t & 31] + row), es, tag1);
+            SaLine l;
+            int way;
+            if (sa.ways == 8u) { sa_load<8>(sa, es, l); way = sa_find<8>(sa, l, tag1, w); }
+            else { sa_load<0>(sa, es, l); way = sa_find<0>(sa, l, tag1, w); }
+            return way >= 0 ? (long long)sa_entry(sa, es, (unsigned)way, w) : -1;
+        }
+        return -1;
+    }
+};
+}  // namespace evs
+
+static int cache_rows_impl(evs_cache *c, int64_t n, const int32_t *keys, const float *values, int64_t values_stride,
+                           int64_t *n_resident, void *stream, bool refresh, const char *who) {
+    using namespace evs;
+    { const int cc = upd_check_common(who, n, keys); if (cc) return cc < 0 ? cc : EVS_OK; }
+    EVS_REQUIRE(c && (refresh || values), "%s: NULL argument", who);
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys) % 8 == 0, "%s: keys must be 8-byte aligned", who);
+    EVS_REQUIRE(refresh || values_stride >= c->host.dim, "%s: values_stride %lld is below dim = %d", who, (long long)values_stride, c->host.dim);
+    if (!c->has_backing) { set_error("%s: call evs_cache_set_backing first", who); return EVS_ESTATE; }
+    if (!refresh && c->ft) { set_error("%s: the tables of a file-backed cache are read-only mappings (write the files, then evs_cache_refresh_rows)", who); return EVS_ESTATE; }
+    if (refresh && c->staged_mask) { set_error("%s: a file-backed tier with staged tables has no device-visible rows to refresh from", who); return EVS_ESTATE; }
+    // a resident server holds the policy state in its registers and reads rows inside a running launch, where another
+    // kernel's stores need not be visible (per-XCD L2s): it goes home first, the next request starts it again
+    { const int prc = serve_pause(c); if (prc) return prc; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    RowUpdateArgs<CacheLookup> a{};
+    for (int k = 0; k < kMaxTables; k++) { a.tables[k] = const_cast<unsigned char *>(c->backing[k]); a.n_rows[k] = k < c->host.n_tables ? c->backing_rows[k] : 0; }
+    a.keys = keys; a.values = values; a.values_stride = values_stride; a.n = n;
+    a.n_tables = c->host.n_tables; a.d = c->host.dim; a.row_bytes = c->host.row_bytes;
+    a.values_aligned = (values && reinterpret_cast<uintptr_t>(values) % 16 == 0 && values_stride % 4 == 0) ? 1 : 0;
+    a.n_resident = reinterpret_cast<unsigned long long *>(n_resident);
+    a.lk.arena = c->a.arena;
+    a.lk.a = c->a; a.lk.nslot_mask = c->host.nslot_mask;
+    a.lk.slots = c->bslots; a.lk.bmask = (unsigned long long)(c->bnslot - 1);
+    a.lk.sa = c->sa; a.lk.sau = c->sau;
+    a.lk.mode = c->used == 1 ? 1 : c->used == 2 ? ((c->batch_policy == 2 && c->sa.tags) ? 3 : (c->bslots ? 2 : 0)) : 0;
+    a.err = index_error_flag();
+    if (!a.err) return EVS_EHIP;
+    // an exact-path launch may be pending on ANOTHER stream, with a server start waiting for its event: this launch goes
+    // behind that event and re-records it, so the server start keeps waiting for both
+    if (c->exact_pending && c->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->exact_done, 0));
+    if (c->tsrv && c->tsrv->exact_pending && c->tsrv->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->tsrv->exact_done, 0));
+    if (n_resident) EVS_HIP_CHECK(hipMemsetAsync(n_resident, 0, sizeof(int64_t), st));
+    if (refresh) launch_row_refresh(a, st);
+    else launch_row_update(c->host.codec, a, st);
+    EVS_HIP_CHECK(hipGetLastError());
+    return exact_launched(c, st);
+}
+
+extern "C" int evs_cache_update_rows(evs_cache *c, int64_t n, const int32_t *keys, const float *values, int64_t values_stride,
+                                     int64_t *n_resident, void *stream) {
+    return cache_rows_impl(c, n, keys, values, values_stride, n_resident, stream, false, "evs_cache_update_rows");
+}
+
+extern "C" int evs_cache_refresh_rows(evs_cache *c, int64_t n, const int32_t *keys, int64_t *n_resident, void *stream) {
+    return cache_rows_impl(c, n, keys, nullptr, 0, n_resident, stream, true, "evs_cache_refresh_rows");
 }
 
 // ---- a12: alt-key tier object --------------------------------------------------------------------

@@ -8,44 +8,9 @@
 // the fp32 input to fp64 and do the same IEEE arithmetic (the library is built with -ffp-contract=off).
 // Codes are stored like numpy's astype(uint8/uint16): modulo 2^8 / 2^16.
 #include "evs_common.h"
+#include "evs_encode.h"   // enc_u8 / enc_u16 / enc_u4 (shared with the row-update kernels)
 
 namespace evs {
-
-__device__ __forceinline__ long long enc_u8(double x) { return (long long)rint(((x + 1.0) / 2.0) * 254.0); }
-
-__device__ __forceinline__ long long enc_u16(double value) {
-    if (value < -0.65) {
-        long long leftover = (long long)(-100.0 * (0.65 + value));
-        if (leftover % 2 == 0) leftover += 1;
-        return 65000 + leftover;
-    } else if (value > 0.65) {
-        long long leftover = (long long)(100.0 * (value - 0.65));
-        if (leftover % 2 == 1) leftover -= 1;
-        return 65000 + leftover;
-    }
-    return (long long)((value + 0.65) / 1.3 * 65000.0);
-}
-
-__device__ __forceinline__ int enc_u4(double v) {
-    if (v == 0.0) return 7;
-    if (v > 0.0) {
-        if (v >= 0.8) return 0;
-        if (v >= 0.6) return 1;
-        if (v >= 0.4) return 2;
-        if (v >= 0.25) return 3;
-        if (v >= 0.015) return 4;
-        if (v >= 0.00025) return 5;
-        return 6;
-    }
-    if (v >= -0.00025) return 8;
-    if (v < -1.0) return 15;
-    if (v < -0.8) return 14;
-    if (v < -0.6) return 13;
-    if (v < -0.4) return 12;
-    if (v < -0.25) return 11;
-    if (v < -0.015) return 10;
-    return 9;
-}
 
 template <int CODEC>
 __global__ void __launch_bounds__(256) encode_table_kernel(const float *__restrict__ src, unsigned char *__restrict__ dst,

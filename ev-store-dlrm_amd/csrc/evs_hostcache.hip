@@ -658,6 +658,30 @@ extern "C" int evs_hostcache_request_c1c2c3(evs_hostcache *c1, evs_hostcache *c2
     return EVS_OK;
 }
 
+// Online row updates on the host engine: the caller has written its host tables; the arena row of every resident key of the
+// delta is re-copied from its backing row.  The policy state (map, lists, counters) is only read.
+extern "C" int evs_hostcache_refresh_rows(evs_hostcache *c, int64_t n, const int32_t *keys_host, int64_t *n_resident_host) {
+    using namespace evs;
+    EVS_REQUIRE(n >= 0, "evs_hostcache_refresh_rows: n = %lld", (long long)n);
+    if (n_resident_host && n == 0) *n_resident_host = 0;
+    if (n == 0) return EVS_OK;
+    EVS_REQUIRE(c && keys_host, "evs_hostcache_refresh_rows: NULL argument");
+    if (!c->t.bound) { set_error("evs_hostcache_refresh_rows: no backing tables (evs_hostcache_set_backing)"); return EVS_ESTATE; }
+    host::Tier &t = c->t;
+    int64_t resident = 0, bad = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t k = keys_host[2 * i], row = keys_host[2 * i + 1];
+        if (k < 0 || k >= t.T || row < 0 || row >= t.n_rows[k]) { bad++; continue; }   // skipped, reported below
+        const int32_t e = t.map.find(host::make_key(k, row));
+        if (e < 0) continue;
+        memcpy(t.row_of(e), t.backing_row(k, row), (size_t)t.row_bytes);
+        resident++;
+    }
+    if (n_resident_host) *n_resident_host = resident;
+    if (bad) { set_error("evs_hostcache_refresh_rows: %lld keys out of range (skipped)", (long long)bad); return EVS_EINDEX; }
+    return EVS_OK;
+}
+
 extern "C" int evs_hostcache_stats(evs_hostcache *c, int64_t *out8) {
     using namespace evs;
     EVS_REQUIRE(c && out8, "evs_hostcache_stats: NULL argument");

@@ -111,11 +111,15 @@ if not (hasattr(torch._C, "_storage_Use_Count") and hasattr(torch._C, "DisableTo
 
 class _Deferred:
     """state behind one deferred apply_emb result"""
-    __slots__ = ("lS_o", "lS_i", "ev", "buf", "done", "vers", "one", "consumed")
+    __slots__ = ("lS_o", "lS_i", "ev", "buf", "done", "vers", "one", "consumed", "gen")
+
+    def stale(self):
+        """the indices / offsets were written in place since the call (the result can no longer be computed)"""
+        # (inference tensors keep no version counter: nothing to compare, and in-place writes to them are the caller's to order)
+        return any(v is not None and t._version != v for t, v in self.vers)
 
     def _check(self):
         for t, v in self.vers:
-            # (inference tensors keep no version counter: nothing to compare, and in-place writes to them are the caller's to order)
             if v is not None and t._version != v:
                 raise RuntimeError("apply_emb's indices / offsets were modified in place before its (deferred) result was first used; "
                                    "consume the result first, or call apply_emb(..., lazy=False)")
@@ -212,7 +216,7 @@ class _PoolEntry:
     def __init__(self, T, B, d, device):
         self.buf = buf = torch.empty((T, B, d), dtype=torch.float32, device=device)
         self.st = st = _Deferred()
-        st.buf, st.done, st.consumed = buf, True, True
+        st.buf, st.done, st.consumed, st.gen = buf, True, True, 0
         self.rows = []
         for v in buf.unbind(0):
             r = v.as_subclass(_DeferredRow)
@@ -273,6 +277,11 @@ def _deferred_result_locked(lS_o, lS_i, ev, one_index_per_bag, B):
     st.lS_o, st.lS_i, st.ev, st.done, st.one, st.consumed = lS_o, lS_i, ev, False, bool(one_index_per_bag), False
     ts = ([lS_o] if torch.is_tensor(lS_o) else list(lS_o)) + ([lS_i] if torch.is_tensor(lS_i) else list(lS_i))
     st.vers = [(t, _version_of(t)) for t in ts]
+    # what a later write to the tables has to compute first (EVTables.update_rows -> materialize_pending): this hand-out, kept
+    # with the tables themselves -- pooled or not -- until it is computed, recycled, or nobody can look at it any more
+    st.gen += 1
+    ev._pending = [(e, g) for e, g in getattr(ev, "_pending", []) if e.st.gen == g and not e.st.done and not e.free()]
+    ev._pending.append((ent, st.gen))
     ly = ent.hand_out()
     ly._evs_meta = (buf.data_ptr(), B * d, d, B, d, T)
     ly._evs_defer = st
@@ -381,6 +390,7 @@ class EVTables:
         self._n_rows_c = (C.c_int64 * T)(*self.n_rows)
         self._ptrs = ptrs
         self._xt = None
+        self._pending = []   # deferred apply_emb results of these tables not computed yet: (pool entry, its hand-out number)
 
     def ext_tables(self):
         """this model's tables as the C++ extension holds them (None without the extension)"""
@@ -443,6 +453,79 @@ class EVTables:
     def fp32_view(self, k):
         assert self.codec == 32
         return self.raw[k].view(torch.float32).reshape(self.n_rows[k], self.d)
+
+
+    def update_rows(self, keys, values, assume_distinct=False):
+        """Online row update (include/evstore_hip.h: evs_table_update_rows): keys (n, 2) = (table index 0-based, row), values
+        (n, d) fp32 -- device tensors or anything torch.as_tensor takes.  Every value row is encoded in these tables' codec
+        (bit-exact with encode()) and stored at its row, in stream order on the current stream.  Duplicate keys: the LAST
+        one wins -- the de-duplication (a torch.unique) and host inputs (a copy) make the call WAIT for the stream;
+        assume_distinct=True with device tensors skips both: the call then only enqueues (distinct keys are then the caller's
+        word: with duplicates any of the duplicated values may stay).  A key out of range is skipped and reported by evs_check_index_errors.  Deferred apply_emb results of
+        these tables that somebody still holds and nobody has touched yet are computed first, so they keep the rows of their own
+        call (materialize_pending says which results that covers; LazyPooled ones are not).
+        A cache in front of the tables keeps its own copies: update through GpuCache.update_rows instead (or call its
+        refresh_rows afterwards); an InteractServer over these tables is stop()ped around an update."""
+        materialize_pending(self)
+        keys, values = delta_tensors(keys, values, self.device, self.d, assume_distinct)
+        n = int(keys.shape[0])
+        if n == 0:
+            return self
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().evs_table_update_rows(self.codec, self.d, len(self.raw), self._tables_c, self._n_rows_c, n,
+                                                        keys.data_ptr(), values.data_ptr(), int(values.stride(0)), _stream_ptr(self.device)))
+        return self
+
+
+def materialize_pending(ev):
+    """Compute the deferred apply_emb results of the EVTables `ev` that somebody can still look at and that have not been
+    computed yet: a write to the tables must not change what an earlier call returns.  Skipped: results nobody can observe
+    any more (the list died and no row or view of it escaped -- what a serving loop leaves behind after the fused
+    interact_features consumed the result), and results whose indices / offsets were since rewritten in place (they cannot be
+    computed; their first use raises, as it would have without the update).  NOT covered: LazyPooled results
+    (apply_emb(..., lazy=True) / EVS_LAZY_POOLING=1) -- materialize() those before an update."""
+    with _defer_lock:
+        pending, ev._pending = getattr(ev, "_pending", []), []
+        for e, gen in pending:
+            st = e.st
+            if st.gen != gen or st.done or st.ev is not ev or e.free() or st.stale():
+                continue
+            st.materialize()
+
+
+def dedup_last(keys, values=None):
+    """keys (n, 2) integer tensor, values (n, ...) or None -> the delta with every key once, the LAST occurrence kept, in
+    the order of those occurrences (the kernels want distinct keys: two lanes groups writing one row is a race)"""
+    n = int(keys.shape[0])
+    if n > 1:
+        k64 = (keys[:, 0].to(torch.int64) << 32) | (keys[:, 1].to(torch.int64) & 0xffffffff)
+        uniq, inv = torch.unique(k64, return_inverse=True)
+        if int(uniq.numel()) != n:
+            last = torch.full((int(uniq.numel()),), -1, dtype=torch.int64, device=keys.device)
+            last.scatter_reduce_(0, inv, torch.arange(n, dtype=torch.int64, device=keys.device), "amax", include_self=True)
+            last = torch.sort(last).values
+            keys = keys[last]
+            values = None if values is None else values[last]
+    return keys, values
+
+
+def delta_tensors(keys, values, device, d, assume_distinct=False):
+    """the (keys, values) of a row update as the kernels take them: (n, 2) int32 and (n, d) fp32 contiguous on `device`,
+    keys distinct (dedup_last -- a torch.unique, which waits for the stream -- unless the caller vouches for that:
+    assume_distinct); values None: keys only (a refresh)"""
+    keys = torch.as_tensor(keys)
+    if keys.numel() == 0:
+        keys = keys.reshape(0, 2)
+    if keys.dim() != 2 or keys.shape[1] != 2 or keys.dtype.is_floating_point:
+        raise ValueError("keys must be an (n, 2) integer array of (table index, row)")
+    keys = keys.to(device=device, dtype=torch.int32)
+    if values is not None:
+        values = torch.as_tensor(values, dtype=torch.float32).to(device).reshape(-1, d)
+        if values.shape[0] != keys.shape[0]:
+            raise ValueError("%d keys but %d value rows" % (keys.shape[0], values.shape[0]))
+    if not assume_distinct:
+        keys, values = dedup_last(keys, values)
+    return keys.contiguous(), None if values is None else values.contiguous()
 
 
 def _as_evtables(emb_l):
@@ -664,7 +747,8 @@ class InteractServer:
     Opt-in, and with rules (the header spells them out): fp32 tables, d in {16, 32, 36, 64}, T <= 27, stacked (T, B) int64
     lS_o / lS_i on the device; the inputs of a batch are COMPLETE when it is posted (synchronise the producer's stream first);
     R may be read by anything started after wait() returned; while the grid is resident it holds the compute units, so other
-    launches run when it has left (idle_us, or stop())."""
+    launches run when it has left (idle_us, or stop()).  The dispatcher reads the tables from a resident launch, where an
+    update's stores need not be visible: stop() it around EVTables.update_rows (the next post starts it again)."""
 
     def __init__(self, emb_l, arch_interaction_itself=False, n_blocks=0, idle_us=200):
         ev = _as_evtables(emb_l)

@@ -139,6 +139,7 @@ class GpuCache:
         rb = self.dim * self.codec // 8
         n_rows = [int(t.numel() * t.element_size() // rb) for t in raws]
         self._backing = raws  # keep alive
+        self._backing_ev = tables if hasattr(tables, "raw") else None   # (update_rows: deferred apply_emb results of these tables)
         ptrs = (C.c_void_p * self.n_tables)(*[_dev_ptr(t) for t in raws])   # pinned host tables: their device-side address
         rows = (C.c_int64 * self.n_tables)(*n_rows)
         _lib.check(_lib.lib().evs_cache_set_backing(self._h, ptrs, rows))
@@ -148,6 +149,7 @@ class GpuCache:
         host's reader pool; batched lookups only when any table is staged)."""
         assert tier.n_tables == self.n_tables and tier.row_bytes == self.dim * self.codec // 8
         self._backing = tier  # keep alive
+        self._backing_ev = None
         _lib.check(_lib.lib().evs_cache_set_file_backing(self._h, tier._h))
 
     def staged_rows(self):
@@ -290,6 +292,41 @@ class GpuCache:
         out = np.zeros((max(n, 1), 3), np.int64)
         _lib.lib().evs_cache_batch_dump(self._h, out.ctypes.data, n, st)
         return out[:n]
+
+    # ---- online row updates (include/evstore_hip.h: evs_cache_update_rows / evs_cache_refresh_rows) ----
+    def _rows_call(self, keys, values, count, assume_distinct=False):
+        from . import dlrm_ops
+        if getattr(self, "_backing_ev", None) is not None:
+            dlrm_ops.materialize_pending(self._backing_ev)   # deferred apply_emb results keep the rows of their own call
+        keys, values = dlrm_ops.delta_tensors(keys, values, self.device, self.dim, assume_distinct)
+        n = int(keys.shape[0])
+        cnt = torch.zeros((1,), dtype=torch.int64, device=self.device) if count else None
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            if values is None:
+                _lib.check(_lib.lib().evs_cache_refresh_rows(self._h, n, keys.data_ptr(), cnt.data_ptr() if count else None, st))
+            else:
+                _lib.check(_lib.lib().evs_cache_update_rows(self._h, n, keys.data_ptr(), values.data_ptr(), int(values.stride(0)) if n else self.dim,
+                                                            cnt.data_ptr() if count else None, st))
+        return int(cnt.item()) if count else None
+
+    def update_rows(self, keys, values, count=False, assume_distinct=False):
+        """A delta of (table index 0-based, row) -> new fp32 vector, in ONE launch on the current stream: every vector is
+        encoded in this tier's codec, stored at its row of the BACKING table and into the arena row of every key that is
+        resident -- a lookup issued on this stream afterwards serves the new rows from either place.  Residency, priorities,
+        lists and counters do not move.  keys (n, 2), values (n, dim): device tensors or anything torch.as_tensor takes;
+        duplicate keys: the last one wins.  A resident server (serve_start / TierServer) is sent home first and started again
+        by the next request.  A tier pair / triple: one call per cache, each over its own backing in its own codec.
+        count=True: returns how many keys were resident WHEN THE CALL RAN (an EvLFU flush the last batch's close asked for
+        runs with the next batched call, not here).  The de-duplication of the keys, host inputs and count=True make the
+        call wait for the stream; assume_distinct=True with device tensors and count=False only enqueues (the keys are then
+        distinct on the caller's word).  EvsError(EVS_ESTATE) over a FileTier."""
+        return self._rows_call(keys, values, count, assume_distinct)
+
+    def refresh_rows(self, keys, count=False, assume_distinct=False):
+        """The arena row of every resident key of `keys` re-copied from its backing row: for callers that wrote the table
+        themselves (pinned host tables written by the host, the files under a FileTier's registered tables)."""
+        return self._rows_call(keys, None, count, assume_distinct)
 
     def stats(self):
         s = (C.c_int64 * 8)()

@@ -73,6 +73,20 @@ class HostCache:
         _lib.check(_lib.lib().evs_hostcache_request(self._h, B, rows.ctypes.data, out.ctypes.data, hit.ctypes.data, int(approx_thres)))
         return hit, out
 
+    def backing_tables(self):
+        """the arrays the engine actually reads, one per table (set_backing may have copied a non-contiguous input): an
+        online row update writes THESE, then calls refresh_rows"""
+        return self._backing
+
+    def refresh_rows(self, keys):
+        """keys: (n, 2) integers of (table index 0-based, row) whose rows the caller has just overwritten in
+        backing_tables(): the arena copy of every resident one is re-copied from its table (duplicates are harmless; the
+        policy state does not move).  -> the number of resident keys."""
+        keys = _np(keys, np.int32).reshape(-1, 2)
+        cnt = C.c_int64(0)
+        _lib.check(_lib.lib().evs_hostcache_refresh_rows(self._h, keys.shape[0], keys.ctypes.data, C.byref(cnt)))
+        return int(cnt.value)
+
     def stats(self):
         s = (C.c_int64 * 8)()
         _lib.check(_lib.lib().evs_hostcache_stats(self._h, s))

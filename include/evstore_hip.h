@@ -636,6 +636,54 @@ EVS_API int evs_hostaprx_apply_ops(evs_hostaprx *p, int64_t n, const int32_t *op
 EVS_API int64_t evs_hostaprx_dump_queue(evs_hostaprx *p, int64_t *pairs, int64_t max_pairs);
 
 /* ---------------------------------------------------------------------------
+ * Online row updates: a model refresh while the store serves (no reference counterpart -- the reference's tables are files
+ * written offline, script/reduce_precision.py + script/convert_ev_to_binary.py, and its tiers are filled from them).
+ * A delta of (table, row) -> new fp32 vector is encoded in the table's codec (bit-exact with evs_encode_table for the same
+ * values), stored at its row in the table AND into every cached copy of that row, in stream order, so that "served rows are
+ * exactly the table rows" (evs_cache_set_batch_policy, above) keeps holding for resident keys.
+ *   keys    device (n, 2) int32, 8-byte aligned: keys[i] = (table index 0-based, row) -- "table = position", as in the
+ *           request arrays.  The keys of ONE call must be distinct: with duplicates the table and a cached copy may keep
+ *           different ones of the duplicated values.
+ *   values  device fp32, row i at values + i * values_stride, values_stride >= d (16-byte aligned with a stride % 4 == 0:
+ *           vector loads).
+ *   n == 0 is success; arguments are checked before the device is touched (EVS_EINVAL); a key out of range is skipped and
+ *   raises the sticky flag evs_check_index_errors reports.
+ * evs_table_update_rows   tables without a cache in front: tables / n_rows are HOST arrays of n_tables (<= 64) device-
+ *                         accessible table addresses / row counts, rows of d elements in `codec` (32 / 16 / 8 / 4).
+ * evs_cache_update_rows   ONE launch: encode in the cache's codec, store the row into c's backing table, look the key up in c
+ *                         and store the same bytes into the arena row when it is resident.  n_resident (device int64, may be
+ *                         NULL) receives the number of keys that were resident WHEN THE CALL RAN: an EvLFU flush that the last
+ *                         batch's close has asked for runs with the next batched call (or evs_cache_batch_stats / _dump), not
+ *                         here, and may retire keys this call counted -- their arena rows were written all the same.
+ * evs_cache_refresh_rows  the same look-up; the arena row is re-copied from the backing row -- for callers who wrote the table
+ *                         themselves, and for tables the kernels can read but must not write (registered file mappings,
+ *                         host tables written by the host).
+ * Every form of the tier is served: the exact engines (EvLFU / LRU / LFU: entry e owns arena row e), the batched policies 0
+ * and 1 (the packed hash words), the set-associative policy 2 (one tier with 8 or 16 ways and its two-copy arena -- the live
+ * copy is the one the way word's select bit names --, or a tier's view of a shared C1 + C2 record).  A tier pair or triple is
+ * updated by one call per cache, each in its own codec on its own backing; the alt-key tier stores no rows and needs
+ * nothing.  A fresh cache only has its table written and stays fresh.  Backing in HBM or in pinned device-visible host memory.
+ * EVS_ESTATE: a cache without backing; evs_cache_update_rows on a file-backed cache (read-only mappings);
+ * evs_cache_refresh_rows on a file tier with staged tables (no device-visible rows).
+ * THE POLICY STATE DOES NOT MOVE: no way word, hash word, priority, list link, stamp or counter changes; evs_cache_dump /
+ * _batch_dump / _stats / _batch_stats return the same before and after.  An update never changes residency.
+ * ORDERING: stream-ordered like the lookups -- a lookup on the same stream after the call sees the new rows; concurrent lookups
+ * on other streams are the caller's to order.  A resident server (evs_cache_serve_*, evs_tiers_serve_*) is sent home first, as
+ * evs_cache_stats does, and the next request starts it again BEHIND the update launch: per-XCD L2s are not coherent inside a
+ * running launch, so a resident kernel cannot be relied on to see the new bytes; a kernel boundary can.  (The dispatcher of
+ * evs_emb_interact_serve_* reads its tables from a resident launch too: serve_stop it around an update.)
+ * evs_hostcache_refresh_rows: the host engine's form of evs_cache_refresh_rows -- the caller writes its host tables, then
+ * refreshes; keys_host (n, 2) int32 and n_resident_host (may be NULL) are HOST memory; keys out of range are skipped and the
+ * call then returns EVS_EINDEX (the host engine has no sticky flag).
+ * ------------------------------------------------------------------------- */
+EVS_API int evs_table_update_rows(int codec, int d, int n_tables, void *const *tables, const int64_t *n_rows, int64_t n,
+                                  const int32_t *keys, const float *values, int64_t values_stride, void *stream);
+EVS_API int evs_cache_update_rows(evs_cache *c, int64_t n, const int32_t *keys, const float *values, int64_t values_stride,
+                                  int64_t *n_resident, void *stream);
+EVS_API int evs_cache_refresh_rows(evs_cache *c, int64_t n, const int32_t *keys, int64_t *n_resident, void *stream);
+EVS_API int evs_hostcache_refresh_rows(evs_hostcache *c, int64_t n, const int32_t *keys_host, int64_t *n_resident_host);
+
+/* ---------------------------------------------------------------------------
  * a14: the reference's cache-manager C ABI (mixed_precs_caching/cache_manager.cpp), bound by
  * cache_algo/cpp_socket_client.py:69-83 through ctypes.  Same names, same signatures.
  *   ev_lookup: reads 26 int32 row ids (0-based; table = position), returns a pointer to the
