@@ -1,6 +1,9 @@
 // Library-wide state of libevstore_hip.so: error strings, the sticky index-error flag.
 #include "evs_common.h"
 
+#include <stdlib.h>
+#include <string.h>
+
 #include <mutex>
 
 namespace evs {
@@ -12,6 +15,41 @@ void set_error(const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
+}
+
+// the record of switches read: a handful of names, each noted once (the call sites are static-cached or per object)
+static std::mutex g_env_mu;
+static struct { const char *name; bool set; } g_env_seen[128];
+static int g_env_n = 0;
+
+const char *env_switch(const char *name) {
+    const char *e = getenv(name);
+    std::lock_guard<std::mutex> lk(g_env_mu);
+    for (int i = 0; i < g_env_n; i++)
+        if (strcmp(g_env_seen[i].name, name) == 0) return e;
+    const int cap = (int)(sizeof g_env_seen / sizeof g_env_seen[0]);
+    if (g_env_n < cap) {
+        g_env_seen[g_env_n].name = name;   // callers pass string literals
+        g_env_seen[g_env_n].set = e != nullptr;
+        g_env_n++;
+    } else {
+        static bool warned = false;
+        if (!warned) fprintf(stderr, "libevstore_hip: the record of switches read is full (%d names); %s and later names are not recorded\n", cap, name);
+        warned = true;
+    }
+    return e;
+}
+
+long long env_switch_range(const char *name, long long dflt, long long lo, long long hi) {
+    const char *e = env_switch(name);
+    if (!e) return dflt;
+    char *end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    if (end == e || v < lo || v > hi) {
+        fprintf(stderr, "libevstore_hip: %s=%s is outside [%lld, %lld]; using the default %lld\n", name, e, lo, hi, dflt);
+        return dflt;
+    }
+    return v;
 }
 
 int *index_error_flag() {
@@ -111,6 +149,19 @@ int *optimistic_slot(int *id_out) {
 
 extern "C" int evs_abi_version(void) { return EVS_ABI_VERSION; }
 extern "C" const char *evs_last_error(void) { return evs::g_err; }
+
+extern "C" int evs_env_switches_seen(char *buf, int n) {
+    std::lock_guard<std::mutex> lk(evs::g_env_mu);
+    int len = 0;
+    if (buf && n > 0) buf[0] = 0;
+    for (int i = 0; i < evs::g_env_n; i++) {
+        char line[96];
+        const int k = snprintf(line, sizeof line, "%s=%d\n", evs::g_env_seen[i].name, evs::g_env_seen[i].set ? 1 : 0);
+        if (buf && len + k < n) memcpy(buf + len, line, (size_t)k + 1);
+        len += k;
+    }
+    return len;
+}
 
 extern "C" void *evs_host_device_pointer(void *host_ptr) {
     void *dev = nullptr;

@@ -3366,7 +3366,7 @@ bool sa_make_geom(evs::SaGeom &g, unsigned nset, unsigned ways, unsigned w_off, 
 }
 unsigned sa_single_ways() {
     static int w = -1;
-    if (w < 0) { const char *e = getenv("EVS_SA_WAYS"); w = (e && atoi(e) == 16) ? 16 : (int)kSaSingleWays; }
+    if (w < 0) { const char *e = evs::env_switch("EVS_SA_WAYS"); w = (e && atoi(e) == 16) ? 16 : (int)kSaSingleWays; }
     return (unsigned)w;
 }
 // can this cache take the set-associative form on its own (universe below 2^32 keys, tags that fit the word)
@@ -3376,7 +3376,7 @@ bool sa_single_feasible(const evs_cache *c, evs::SaUniverse *u_out = nullptr, ev
     if (!c->has_backing || c->host.cap < (long long)ways) return false;
     if (!sa_make_universe(c->backing_rows, nullptr, c->host.n_tables, u)) return false;
     // a tier alone keeps two arena rows per way (evs_hash.h: the two-copy arena; EVS_SA_DUAL=0: one, developer A/B)
-    static const unsigned dual_on = (getenv("EVS_SA_DUAL") && getenv("EVS_SA_DUAL")[0] == '0') ? 0u : 1u;
+    static const unsigned dual_on = (evs::env_switch("EVS_SA_DUAL") && evs::env_switch("EVS_SA_DUAL")[0] == '0') ? 0u : 1u;
     if (!sa_make_geom(g, (unsigned)(c->host.cap / ways), ways, 0, ways, u, 0, dual_on)) return false;
     if (u_out) *u_out = u;
     if (g_out) *g_out = g;
@@ -3388,7 +3388,7 @@ bool sa_single_feasible(const evs_cache *c, evs::SaUniverse *u_out = nullptr, ev
 // min(cap2 / nset, 16) ways in one.  false: no such geometry (a tier would get fewer than 4 ways) -- each tier then keeps
 // records of its own (two line requests per key)
 bool sa_pair_geometry(const evs_cache *c1, const evs_cache *c2, evs::SaUniverse &u, evs::SaGeom &g1, evs::SaGeom &g2) {
-    static const bool on = !(getenv("EVS_SA_PAIR") && getenv("EVS_SA_PAIR")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_SA_PAIR") && evs::env_switch("EVS_SA_PAIR")[0] == '0');
     if (!on || !c1->has_backing || !c2->has_backing || c1->host.n_tables != c2->host.n_tables) return false;
     const long long cap1 = c1->host.cap, cap2 = c2->host.cap;
     long long nset = std::max<long long>(std::max<long long>(cap1 / 8, (cap2 + 15) / 16), 1);
@@ -3404,7 +3404,7 @@ bool sa_pair_geometry(const evs_cache *c1, const evs_cache *c2, evs::SaUniverse 
 int sa_alloc(evs_cache *c, evs_cache *partner, hipStream_t st) {   // the set records of c (shared with partner), zeroed on st
     auto *m = new evs_cache::SaShared();
     m->bytes = (size_t)c->sa.nset * c->sa.line_words * 4;
-    static const long long pad_mb = getenv("EVS_SA_PAD_MB") ? atoll(getenv("EVS_SA_PAD_MB")) : 0;   // developer A/B: allocation size vs page size
+    static const long long pad_mb = evs::env_switch("EVS_SA_PAD_MB") ? atoll(evs::env_switch("EVS_SA_PAD_MB")) : 0;   // developer A/B: allocation size vs page size
     const size_t alloc = std::max<size_t>(m->bytes, (size_t)pad_mb << 20);
     if (hipMalloc(&m->tags, alloc) != hipSuccess) { (void)hipGetLastError(); delete m; return EVS_ENOMEM; }
     if (hipMemsetAsync(m->tags, 0, m->bytes, st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m->tags); delete m; return EVS_EHIP; }
@@ -3506,7 +3506,7 @@ extern "C" int evs_cache_create(evs_cache **out, int policy, int64_t capacity, i
     // slot hints: deletions leave tombstones, and how often they have to be swept / the table rebuilt (~170 us at 3.4 M
     // entries) is a matter of tombstones per slot -- 16 us per batch amortised at load 0.4, a third of that here.
     c->bnslot = (nslot * 2 <= (1ll << 24)) ? nslot * 2 : nslot;
-    if (const char *e = getenv("EVS_CACHE_HASH_SCALE")) { if (e[0] == '1') c->bnslot = nslot; }   // developer A/B: the denser table
+    if (const char *e = evs::env_switch("EVS_CACHE_HASH_SCALE")) { if (e[0] == '1') c->bnslot = nslot; }   // developer A/B: the denser table
     h.nslot_mask = (unsigned long long)(nslot - 1);
     h.min_c1 = 0; h.n_perfect = 0;
     h.max_perfect = (int)(capacity * perfect_item_cap);          // EvLFU_C1.py:30
@@ -4123,8 +4123,8 @@ static void batch_close(evs_cache *c, evs::BatchArgs a, hipStream_t st) {
 // threads per miss list (EVS_CACHE_LIST_WAVES overrides: developer A/B)
 static unsigned sampled_list_threads(const evs::BatchArgs &a) {
     static int w = -1;
-    if (w < 0) { const char *e = getenv("EVS_CACHE_LIST_WAVES"); w = e ? atoi(e) : 0; }
-    if (w >= 1 && w <= 4) return 64u * (unsigned)w;
+    if (w < 0) w = (int)evs::env_switch_range("EVS_CACHE_LIST_WAVES", 0, 1, 4);   // (0: unset, the rule below)
+    if (w >= 1) return 64u * (unsigned)w;
     return a.list_cap > 8 * a.T ? 128u : 64u;
 }
 // the sampled update, compiled per row size (row_bytes = PIECES pieces of 16 / 8 / 4 / 2 bytes, at most 16 of them)
@@ -4175,7 +4175,7 @@ static void launch_sa_update(const evs::BatchArgs &a, hipStream_t st) {
 // ... and of a set-associative pair
 static bool launch_sa_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs &a2, hipStream_t st) {
     using namespace evs;
-    static const bool on = !(getenv("EVS_CACHE_PAIR") && getenv("EVS_CACHE_PAIR")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_CACHE_PAIR") && evs::env_switch("EVS_CACHE_PAIR")[0] == '0');
     if (!on || a1.g1 != a2.g1 || sampled_list_threads(a1) != sampled_list_threads(a2)) return false;
     const dim3 grid((unsigned)(2 * a1.g1)), block(sampled_list_threads(a1));
     if (a1.row_bytes == 36 && a2.row_bytes == 18)
@@ -4193,7 +4193,7 @@ static bool launch_sa_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs
 // both tiers' list updates as one launch (the pairs of row sizes a u8 C1 + u4 C2 make); false: no merged kernel for the pair
 static bool launch_sampled_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs &a2, hipStream_t st) {
     using namespace evs;
-    static const bool on = !(getenv("EVS_CACHE_PAIR") && getenv("EVS_CACHE_PAIR")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_CACHE_PAIR") && evs::env_switch("EVS_CACHE_PAIR")[0] == '0');
     if (!on || !a1.miss_rec || !a2.miss_rec || a1.g1 != a2.g1 || sampled_list_threads(a1) != sampled_list_threads(a2)) return false;
     const dim3 grid((unsigned)(2 * a1.g1)), block(sampled_list_threads(a1));
     if (a1.row_bytes == 36 && a2.row_bytes == 18)
@@ -4212,7 +4212,7 @@ static bool launch_sampled_update_pair(const evs::BatchArgs &a1, const evs::Batc
 // and file-backed miss tiers, the two- / three-tier lookups).
 static int resolved_batch_policy(evs_cache *c, bool single_tier) {
     if (c->batch_policy < 0) {
-        const char *e = getenv("EVS_CACHE_POLICY");
+        const char *e = evs::env_switch("EVS_CACHE_POLICY");
         const bool sa_ok = single_tier && !c->host_backing && !c->ft && sa_single_feasible(c);
         if (e && e[0] == 'p') c->batch_policy = 0;
         else if (e && e[0] == 's' && e[1] == 'a') c->batch_policy = 1;
@@ -4345,17 +4345,17 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         sampled_flush_if_wanted(c, st);
         a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
         a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
-        static const bool fold_on = !(getenv("EVS_CACHE_FOLD") && getenv("EVS_CACHE_FOLD")[0] == '0');
+        static const bool fold_on = !(evs::env_switch("EVS_CACHE_FOLD") && evs::env_switch("EVS_CACHE_FOLD")[0] == '0');
         bool small_tabs = true;   // (tile entries carry a row id in 30 bits)
         for (int k = 0; k < T; k++) small_tabs = small_tabs && c->backing_rows[k] < (1ll << 30);
         // a reduced-precision tier (the reference's one-layer 16 / 8 / 4-bit builds): the probe folded into ITS consumer too
-        static const bool foldq_on = !(getenv("EVS_CACHE_FOLDQ") && getenv("EVS_CACHE_FOLDQ")[0] == '0');
+        static const bool foldq_on = !(evs::env_switch("EVS_CACHE_FOLDQ") && evs::env_switch("EVS_CACHE_FOLDQ")[0] == '0');
         const bool foldq = fold_on && foldq_on && c->host.codec != 32 && R && !out && c->sa.ways == 8 && c->sa.sub_shift == 0 && small_tabs &&
                            (cap << c->sa.dual) < (1ll << 30) && fused_probe_codec_supported(B, T, c->host.dim, c->host.codec);
         const bool fold = (fold_on && a.row_ids && R && !out && c->sa.ways == 8 && (cap << c->sa.dual) < (1ll << 30)) || foldq;   // (the folded probes are compiled for 8-way sets; tile entries carry an arena row in 30 bits)
         // the update inside the probe launch too: fp32 rows, the folded fp32 launch, a two-copy arena (EVS_CACHE_INLINE=0: every
         // batch updated by a launch of its own behind it -- the round-4 chain, strict snapshot flags)
-        if (c->inline_mode < 0) c->inline_mode = (getenv("EVS_CACHE_INLINE") && getenv("EVS_CACHE_INLINE")[0] == '0') ? 0 : 1;
+        if (c->inline_mode < 0) c->inline_mode = (evs::env_switch("EVS_CACHE_INLINE") && evs::env_switch("EVS_CACHE_INLINE")[0] == '0') ? 0 : 1;
         // (a reduced-precision tier takes the same form in its own consumer: evs_fused_rfq.hip, PROBE)
         // (a way stamped by the RUNNING batch is hidden from this launch's probers; the stamp is the batch number modulo
         //  2^stamp_bits, so an entry last touched exactly k * 2^stamp_bits batches ago is hidden too -- a miss served from its
@@ -4376,8 +4376,6 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
                 pa.miss_rec = nullptr; pa.list_cnt = nullptr;
                 pa.pend_stamp = (unsigned)a.stamp & c->sa.stamp_mask;
                 pa.arena_w = c->a.arena; pa.row_bytes = c->host.row_bytes; pa.part2 = a.part2;
-                static const int xf = getenv("EVS_X_INL") ? atoi(getenv("EVS_X_INL")) : 0;
-                pa.xflags = xf;
             }
             const int rc = fused_probe_interact(B, T, c->host.dim, x, x_stride, pa, c->a.arena,
                                                 reinterpret_cast<const void *const *>(c->backing), c->backing_rows, itself, R, st, c->host.codec);
@@ -4409,7 +4407,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
         }
         if (c->fork_mode < 0) {
-            const char *e = getenv("EVS_CACHE_FORK");
+            const char *e = evs::env_switch("EVS_CACHE_FORK");
             c->fork_mode = (e && e[0] == '1') ? 1 : 0;
         }
         // EVS_CACHE_FORK=1: the update runs on a side stream UNDER the consumer.  What makes that legal: with the hits of
@@ -4430,7 +4428,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         }
         // the probe inside the consumer: one launch instead of two when the consumer is the rows-in-registers kernel
         // (EVS_CACHE_FOLD=0: the two-launch form)
-        static const bool fold_on = !(getenv("EVS_CACHE_FOLD") && getenv("EVS_CACHE_FOLD")[0] == '0');
+        static const bool fold_on = !(evs::env_switch("EVS_CACHE_FOLD") && evs::env_switch("EVS_CACHE_FOLD")[0] == '0');
         const bool fold = fold_on && a.row_ids && a.miss_rec && !fork && R && !out;
         if (fold) {
             ProbeArgs pa;
@@ -4471,7 +4469,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     }
     hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
     if (c->fork_mode < 0) {
-        const char *e = getenv("EVS_CACHE_FORK");
+        const char *e = evs::env_switch("EVS_CACHE_FORK");
         c->fork_mode = (e && e[0] == '1') ? 1 : 0;
     }
     // Fork / join inside the batch (EVS_CACHE_FORK=1, off by default): K2, K3 and K4 only touch the hash, the
@@ -4613,7 +4611,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         if (file2) {
             if (free1) c1->batch_policy = 0;
             if (free2) c2->batch_policy = 0;
-        } else if (free1 && free2 && !(getenv("EVS_CACHE_POLICY"))) c1->batch_policy = c2->batch_policy = sa_ok ? 2 : 1;
+        } else if (free1 && free2 && !(evs::env_switch("EVS_CACHE_POLICY"))) c1->batch_policy = c2->batch_policy = sa_ok ? 2 : 1;
         else if (free1 != free2) {
             evs_cache *set = free1 ? c2 : c1, *unset = free1 ? c1 : c2;
             unset->batch_policy = (set->batch_policy == 2 && !sa_ok) ? 1 : set->batch_policy;
@@ -4694,7 +4692,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         return EVS_ESTATE;
     }
     constexpr unsigned kRouteWords = 1u << 20;
-    static const bool route_on_env = !(getenv("EVS_CACHE_ROUTEFILTER") && getenv("EVS_CACHE_ROUTEFILTER")[0] == '0');
+    static const bool route_on_env = !(evs::env_switch("EVS_CACHE_ROUTEFILTER") && evs::env_switch("EVS_CACHE_ROUTEFILTER")[0] == '0');
     const bool route_on = route_on_env || sa2;   // (the set-associative update has no cross-tier hash look-up to fall back on)
     if (sampled2 && route_on && !c1->route_filter) {
         EVS_HIP_CHECK(hipMalloc(&c1->route_filter, kRouteWords * 4));
@@ -4707,7 +4705,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
             if (!host2) a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;   // (host tiers: set above, with the hit stamps)
             a.tomb_parity = sa2 ? -1 : (a.stamp & 1);
             sampled_flush_if_wanted(c, st);
-            static const bool c3_inline_on = !(getenv("EVS_CACHE_C3INLINE") && getenv("EVS_CACHE_C3INLINE")[0] == '0');
+            static const bool c3_inline_on = !(evs::env_switch("EVS_CACHE_C3INLINE") && evs::env_switch("EVS_CACHE_C3INLINE")[0] == '0');
             if (c3 && (c3_inline_on || sa2)) {   // the evicting thread inserts its victim into the alt-key set itself
                 a.c3_tags = c3->tags; a.c3_nset = c3->nset; a.c3_stat = c3->bstat;
             } else
@@ -4733,7 +4731,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         // the probe lists each tier's misses per block (as K1 does for one tier); with the alt-key tier attached a list
         // kernel block stages its victims in LDS: lists of at most kListVictMax records
         const long long lc = (B + 8 * (long long)a1.g1 - 1) / (8 * (long long)a1.g1) * 8 * T;
-        static const bool list_on = !(getenv("EVS_CACHE_LIST2") && getenv("EVS_CACHE_LIST2")[0] == '0');
+        static const bool list_on = !(evs::env_switch("EVS_CACHE_LIST2") && evs::env_switch("EVS_CACHE_LIST2")[0] == '0');
         if (sa2 || (list_on && !host2 && a1.g1 == a2.g1 && (!c3 || lc <= kListVictMax))) {   // (host tiers: the patch kernel reads the per-position records)
             a1.miss_rec = c1->miss_rec; a1.list_cnt = c1->list_cnt; a1.list_cap = (int)lc;
             a2.miss_rec = c2->miss_rec; a2.list_cnt = c2->list_cnt; a2.list_cap = (int)lc;
@@ -4745,7 +4743,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         tt.route_filter = c1->route_filter; tt.route_mask = kRouteWords - 1; tt.route_stamp = (unsigned)a1.stamp;
         a2.route_filter = c1->route_filter; a2.route_mask = kRouteWords - 1; a2.route_stamp = (unsigned)a1.stamp;
     }
-    static const bool fold2_on = !(getenv("EVS_CACHE_FOLD2") && getenv("EVS_CACHE_FOLD2")[0] == '0');
+    static const bool fold2_on = !(evs::env_switch("EVS_CACHE_FOLD2") && evs::env_switch("EVS_CACHE_FOLD2")[0] == '0');
     const bool fold2 = fold2_on && sampled2 && !host2 && a1.miss_rec && R && !out && B <= 65536 && T <= 32 &&
                        (!sa2 || (c1->sa.ways == 8 && c2->sa.ways == 8 && (c1->host.cap << c1->sa.dual) < (1ll << 30) && (c2->host.cap << c2->sa.dual) < (1ll << 30))) &&   // (the folded probe is compiled for 8-way sets)
                        mixed84_supported(T, c1->host.dim, c1->host.codec, c2->host.codec);
@@ -4855,7 +4853,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         // Once a close that ran after C1's last flush has reported it full -- nothing but a flush takes entries away -- the
         // counters are folded every kCloseEvery-th batch as in the single-tier path (5 us per batch become 0.6); while C1
         // fills, every batch.  (EVS_CACHE_LAZY2=0: every batch.)
-        static const bool lazy2_on = !(getenv("EVS_CACHE_LAZY2") && getenv("EVS_CACHE_LAZY2")[0] == '0');
+        static const bool lazy2_on = !(evs::env_switch("EVS_CACHE_LAZY2") && evs::env_switch("EVS_CACHE_LAZY2")[0] == '0');
         volatile int *rep1 = reinterpret_cast<volatile int *>(c1->host_tomb);
         // (set-associative tiers: the routing reads the key's own set, not the entry count -- lazy from the first batch)
         const bool c1_known_full = sa2 || (lazy2_on && rep1 && rep1[3] == 1 && (long long)rep1[2] >= c1->last_flush_call && c1->last_flush_call < c1->batch_calls);

@@ -186,7 +186,7 @@ extern "C" int evs_filetier_open(evs_filetier **out, int n_tables, const char *c
     // (tools/file_tier_bench.py, ~57 k new rows per batch, per-batch time): 4 threads 627 us, 8 515, 12 495, 16 476, 24 478,
     // 32 482, 64 561 (waking them costs more than they return) -- against 936 us for 16 threads spawned per fetch without prefetch
     ft->n_threads = hc >= 16 ? 16 : (hc >= 2 ? (int)hc : 2);
-    if (const char *e = getenv("EVS_FILETIER_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 256) ft->n_threads = v; }
+    if (const char *e = evs::env_switch("EVS_FILETIER_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 256) ft->n_threads = v; }
     *out = ft;
     return EVS_OK;
 }

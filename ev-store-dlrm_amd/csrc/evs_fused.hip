@@ -1125,13 +1125,13 @@ __global__ void __launch_bounds__(256) offsets_arange_kernel(const FusedArgs arg
 
 static bool optimistic_enabled() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_OPTIMISTIC"); v = e ? atoi(e) : 1; }
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_OPTIMISTIC"); v = e ? atoi(e) : 1; }
     return v != 0;
 }
 
 static bool use_lds_rows() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_LDS"); v = e ? atoi(e) : 1; }
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_LDS"); v = e ? atoi(e) : 1; }
     return v != 0;
 }
 
@@ -1154,19 +1154,19 @@ static void launch_persistent(const FusedArgs &a, hipStream_t st) {
 // batch is large enough to keep every block busy that way)
 static int tile_mode() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_TILE"); v = e ? atoi(e) : 1; }
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_TILE"); v = e ? atoi(e) : 1; }
     return v;
 }
 static int64_t tile_min_batch() {
     static int64_t v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_TILE_MIN_B"); v = e ? atoll(e) : 2048; }   // (below: one chunk per block at most, nothing to win)
+    if (v < 0) v = env_switch_range("EVS_FUSED_TILE_MIN_B", 2048, 0, 1ll << 40);   // (below: one chunk per block at most, nothing to win)
     return v;
 }
 // reduced precision, offsets given, whole batches: from this batch size on the rows-in-registers kernel checks the offsets
 // itself (evs_fused_rfq.hip, CHECK)
 static int64_t rfq_check_min_batch() {
     static int64_t v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RFQ_CHECK_MIN_B"); v = e ? atoll(e) : 256; }
+    if (v < 0) v = env_switch_range("EVS_FUSED_RFQ_CHECK_MIN_B", 256, 0, 1ll << 40);
     return v;
 }
 static bool tile_eligible(const FusedArgs &a, int codec) {
@@ -1183,7 +1183,7 @@ static void launch_tile(FusedArgs a, hipStream_t st) {
     const int64_t cap = (int64_t)kNumCu * per_cu;
     int64_t per = (a.B + cap - 1) / cap;
     static int align = 0;
-    if (!align) { const char *e = getenv("EVS_FUSED_TILE_ALIGN"); align = e ? atoi(e) : 4; if (align < 1) align = 1; }
+    if (!align) { const char *e = evs::env_switch("EVS_FUSED_TILE_ALIGN"); align = e ? atoi(e) : 4; if (align < 1) align = 1; }
     per = (per + align - 1) / align * align;
     a.tile_per = (int)per;
     const int64_t blocks = (a.B + per - 1) / per;
@@ -1257,7 +1257,7 @@ static void launch_nt(const FusedArgs &a, hipStream_t st) {
                 // every feature is dense -- the rows-in-registers kernel takes dense features as rows addressed by the sample
                 // number (it does so for x and for the sharded step's received vectors), with no index round trip at all.
                 // Needs 16-byte aligned rows (EVS_INTERACT_RF=0: the LDS-DMA loop).
-                static const bool dense_rf = !(getenv("EVS_INTERACT_RF") && getenv("EVS_INTERACT_RF")[0] == '0');
+                static const bool dense_rf = !(evs::env_switch("EVS_INTERACT_RF") && evs::env_switch("EVS_INTERACT_RF")[0] == '0');
                 bool ok = dense_rf && tile_eligible(a, CODEC);
                 for (int f = 0; f < a.F && ok; f++)
                     ok = (reinterpret_cast<uintptr_t>(a.src[f]) & 15) == 0 && ((a.stride[f] * 4) & 15) == 0;
@@ -1490,7 +1490,7 @@ extern "C" int evs_emb_interact_dot(int64_t B, int F, int d, int codec, const ev
     // the rows-in-registers kernel then computes every feature's index / offsets address itself and asks for them before it
     // reads its feature table out of the kernel arguments (FusedArgs::stk)
     a.stk = 0;
-    static const bool stk_on = !(getenv("EVS_FUSED_STK") && getenv("EVS_FUSED_STK")[0] == '0');   // developer A/B
+    static const bool stk_on = !(evs::env_switch("EVS_FUSED_STK") && evs::env_switch("EVS_FUSED_STK")[0] == '0');   // developer A/B
     if (stk_on && indirect && !weighted && codec == 32 && F >= 2 && !feats[0].indices && (a.bag1 == 1 || a.bag1 == 3)) {
         bool yes = feats[1].indices != nullptr;
         const int64_t si = F > 2 && feats[2].indices ? feats[2].indices - feats[1].indices : 0;
@@ -1568,7 +1568,7 @@ extern "C" int evs_emb_interact_dot_stacked_multi(int K, int64_t B, int T, int d
     for (int k = 0; k < K; k++)
         EVS_REQUIRE(x[k] && indices_base[k] && R[k] && (!offsets_base || offsets_base[k]), "evs_emb_interact_dot_stacked_multi: batch %d has a NULL pointer", k);
     const int F = T + 1;
-    static const bool one_launch = !(getenv("EVS_FUSED_MULTI") && getenv("EVS_FUSED_MULTI")[0] == '0');
+    static const bool one_launch = !(evs::env_switch("EVS_FUSED_MULTI") && evs::env_switch("EVS_FUSED_MULTI")[0] == '0');
     // the one-launch form: fp32 tables, whole batches (nnz == B: what makes lS_o checkable per block), aligned operands
     bool fast = one_launch && K > 1 && codec == 32 && T >= 1 && nnz_per_table == B && B < (1ll << 31) && rf_multi_supported(B, F, d) &&
                 x_stride % 4 == 0 && x_stride >= 0 && x_stride < (1ll << 31) && optimistic_enabled();

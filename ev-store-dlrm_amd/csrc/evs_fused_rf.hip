@@ -712,7 +712,7 @@ __device__ __forceinline__ void rf_body(const FusedArgs &args, const FusedArgs *
         if (ins) {
 #pragma unroll
             for (int h = 0; h < 2; h++)
-                if (pok[h] && pe[h] < 0 && !(pa.xflags & 2)) uwait[h] = sa_claim_issue(pa.sa, pa.pend_stamp, phint[h], ptag[h], agg, lw[h], upk[h], uprev[h], s_udelta);
+                if (pok[h] && pe[h] < 0) uwait[h] = sa_claim_issue(pa.sa, pa.pend_stamp, phint[h], ptag[h], agg, lw[h], upk[h], uprev[h], s_udelta);
         }
         EVS_PT(10);          // (the claims are ranked and sent)
 #pragma unroll
@@ -804,7 +804,7 @@ __device__ __forceinline__ void rf_body(const FusedArgs &args, const FusedArgs *
     fill_stage();
     fill_flush();
     EVS_PT(6);               // (the row requests are out)
-    const bool ins_blk = PROBE && args.probe.arena_w != nullptr && !(args.probe.xflags & 1);   // block-uniform: missed keys' rows go into the cache arena on the way
+    const bool ins_blk = PROBE && args.probe.arena_w != nullptr;   // block-uniform: missed keys' rows go into the cache arena on the way
 #pragma unroll
     for (int u = 0; u < D; u++) {
         const int64_t b = blk_first + wave_in_block + 4 * (int64_t)u;   // wave-uniform
@@ -956,39 +956,65 @@ __global__ void __launch_bounds__(256, (MLP ? 3 : (CQ >= 4 ? 2 : EVS_RF_LB))) em
 
 static int rf_mode() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RF"); v = e ? atoi(e) : 1; }   // developer switch: 0 = the LDS-DMA loop
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_RF"); v = e ? atoi(e) : 1; }   // developer switch: 0 = the LDS-DMA loop
     return v;
 }
 
 // developer switch: bytes of dynamic LDS added to every block, i.e. fewer blocks per CU (27 KB static: 4 per CU; +20 KB: 3;
 // +40 KB: 2) -- does a launch whose blocks arrive in two waves overlap its own fill and drain?
+// Checked on the host, once per kernel: static + dynamic LDS beyond the device's limit per block would fail the launch and leave
+// R unwritten, so such a value is refused here (one warning line, no padding) and never reaches the launch.
+static long long rf_pad_lds_env() {
+    static const long long v = env_switch_range("EVS_FUSED_RF_PADLDS", 0, 0, 1ll << 30);
+    return v;
+}
+template <auto K>
 static unsigned rf_pad_lds() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RF_PADLDS"); v = e ? atoi(e) : 0; }
-    return (unsigned)v;
+    if (rf_pad_lds_env() == 0) return 0u;
+    static const unsigned v = [] {
+        hipFuncAttributes fa;
+        int dev = 0, limit = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+            hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(K)) != hipSuccess) {
+            (void)hipGetLastError();
+            fprintf(stderr, "libevstore_hip: EVS_FUSED_RF_PADLDS ignored: the LDS limit of the device could not be read\n");
+            return 0u;
+        }
+        if (rf_pad_lds_env() + (long long)fa.sharedSizeBytes > (long long)limit) {
+            fprintf(stderr, "libevstore_hip: EVS_FUSED_RF_PADLDS=%lld ignored: with %zu bytes of static LDS it exceeds the %d bytes a block may use\n",
+                    rf_pad_lds_env(), (size_t)fa.sharedSizeBytes, limit);
+            return 0u;
+        }
+        return (unsigned)rf_pad_lds_env();
+    }();
+    return v;
 }
 // developer switch: samples per block (16: one generation of co-resident blocks at B = 16 384; 8 / 4: the grid arrives in two / four
 // generations whose heads and bodies can overlap -- the per-block timeline of tools/probe_stage_probe.py asked for the experiment.
 // Measured on the plain launch, B = 16 384: 19.2 us at 16, 28.8 at 8, 48.7 at 4 -- but a wave still issues four samples' worth of
 // requests (the missing ones against the zero page; the body does not build at a depth of 2), so this prices a block's fixed cost,
 // not two generations as such: EVS_FUSED_RF_PADLDS -- the same blocks, fewer per CU -- is the fair form of that question.
-// Plain launches only: the cache tier's per-block buffers are sized for 16.)
+// Plain and CHECK launches only (launch_rf, launch_rf_check pass it): the cache tier's per-block buffers (PROBE), and the IDS / MLP
+// forms, are sized for 16 samples per block and always get 16.)
 static int rf_tile_per() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RF_TILE"); v = e ? atoi(e) : 16; if (v != 4 && v != 8 && v != 12) v = 16; }
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_RF_TILE"); v = e ? atoi(e) : 16; if (v != 4 && v != 8 && v != 12) v = 16; }
     return v;
 }
 template <auto K>
-static void launch_rf_grid(FusedArgs a, hipStream_t st) {
-    a.tile_per = rf_tile_per();   // (default 16) one 16-sample chunk per block: 4 samples per wave, all requested at once
-    hipLaunchKernelGGL(K, dim3((unsigned)((a.B + a.tile_per - 1) / a.tile_per)), dim3(256), rf_pad_lds(), st, a);
+static void launch_rf_grid(FusedArgs a, hipStream_t st, int tile_per = 16) {
+    a.tile_per = tile_per;   // (default 16) one 16-sample chunk per block: 4 samples per wave, all requested at once
+    hipLaunchKernelGGL(K, dim3((unsigned)((a.B + a.tile_per - 1) / a.tile_per)), dim3(256), rf_pad_lds<K>(), st, a);
 }
 
 // the batch sizes this form is for: every block resident at once (4 blocks of 256 threads per CU at 128 VGPRs)
-static int64_t rf_max_batch() {
-    static int64_t v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RF_MAX_B"); v = e ? atoll(e) : 16ll * kNumCu * EVS_RF_LB; }
+// (-1 from the read: unset, or a value that was refused -- both mean the default behaviour)
+static int64_t rf_max_batch_env() {
+    static const int64_t v = env_switch_range("EVS_FUSED_RF_MAX_B", -1, 0, 1ll << 40);
     return v;
+}
+static int64_t rf_max_batch() {
+    return rf_max_batch_env() >= 0 ? rf_max_batch_env() : 16ll * kNumCu * EVS_RF_LB;
 }
 
 bool launch_rf_mlp(const FusedArgs &a, hipStream_t st) {
@@ -1049,27 +1075,27 @@ bool launch_rf_probe(const FusedArgs &a, hipStream_t st) {
 // per sample, 135 VGPRs (three blocks per CU).  Same box, B = 16 384: one index per bag declared 30.4 -> 25.6 us (0.59 -> 0.70 of
 // peak), lS_o given 33.2 -> 27.5 us; B = 65 536: 91.5 -> 89.5 us.
 static bool rf_d64() {
-    static const bool on = !(getenv("EVS_FUSED_RF_D64") && getenv("EVS_FUSED_RF_D64")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_FUSED_RF_D64") && evs::env_switch("EVS_FUSED_RF_D64")[0] == '0');
     return on;
 }
 
 bool launch_rf_check(const FusedArgs &a, hipStream_t st) {
-    static const bool on = !(getenv("EVS_FUSED_RF_CHECK") && getenv("EVS_FUSED_RF_CHECK")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_FUSED_RF_CHECK") && evs::env_switch("EVS_FUSED_RF_CHECK")[0] == '0');
     if (!on || !rf_mode() || a.F > kTileMaxF || a.bag1 != 3 || a.B > rf_max_batch()) return false;
     const bool nt2 = a.F > 16;
     switch (a.d) {
     case 16:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<1, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<1, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<1, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<1, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per());
         return true;
     case 32:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<2, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per());
         return true;
     case 36:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 1, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 1, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 1, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<2, 1, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per());
         return true;
     case 64:
         if (!rf_d64()) return false;
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<4, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<4, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<4, 0, 2, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<4, 0, 1, EVS_RF_DEPTH, false, false, false, true>>(a, st, rf_tile_per());
         return true;
     default:
         return false;
@@ -1115,9 +1141,10 @@ bool launch_rf_multi(const FusedArgs &a, hipStream_t st) {
 // the round-3 head the one-chunk blocks beat the LDS-DMA loop there too (same box, d = 36: B = 32 768 36.2 -> 32.4 us,
 // 65 536 62.1 -> 60.0, 131 072 120.0 -> 114.6, 262 144 235 -> 227; d = 16 at 65 536: 42.0 -> 38.5; d = 32 loses, 48.6 ->
 // 50.6, and keeps the loop).  The checked / probing / row-id forms stay at one generation (no gain measured for the
-// checked form: 65.6 vs 65.7 us at 65 536).  EVS_FUSED_RF_MAX_B, when set, bounds every form.
+// checked form: 65.6 vs 65.7 us at 65 536).  EVS_FUSED_RF_MAX_B, when set to a valid value, bounds every form.
 static int64_t rf_max_batch_plain(int d) {
-    if (getenv("EVS_FUSED_RF_MAX_B") || d == 32) return rf_max_batch();
+    const bool bounded = rf_max_batch_env() >= 0;   // (a refused value does not bound: it falls back to the unset behaviour)
+    if (bounded || d == 32) return rf_max_batch();
     if (d == 64) return 1ll << 22;
     return 1ll << 22;
 }
@@ -1127,17 +1154,17 @@ bool launch_rf(const FusedArgs &a, hipStream_t st) {
     const bool nt2 = a.F > 16;
     switch (a.d) {
     case 16:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<1, 0, 2, EVS_RF_DEPTH>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<1, 0, 1, EVS_RF_DEPTH>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<1, 0, 2, EVS_RF_DEPTH>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<1, 0, 1, EVS_RF_DEPTH>>(a, st, rf_tile_per());
         return true;
     case 32:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 0, 2, EVS_RF_DEPTH>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 0, 1, EVS_RF_DEPTH>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 0, 2, EVS_RF_DEPTH>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<2, 0, 1, EVS_RF_DEPTH>>(a, st, rf_tile_per());
         return true;
     case 36:
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 1, 2, EVS_RF_DEPTH>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 1, 1, EVS_RF_DEPTH>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 1, 2, EVS_RF_DEPTH>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<2, 1, 1, EVS_RF_DEPTH>>(a, st, rf_tile_per());
         return true;
     case 64:   // 28 VGPRs per sample in flight (135 in all: three blocks per CU); EVS_FUSED_RF_D64=0: the LDS-DMA loop
         if (!rf_d64()) return false;
-        if (nt2) launch_rf_grid<emb_interact_rf_kernel<4, 0, 2, EVS_RF_DEPTH>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<4, 0, 1, EVS_RF_DEPTH>>(a, st);
+        if (nt2) launch_rf_grid<emb_interact_rf_kernel<4, 0, 2, EVS_RF_DEPTH>>(a, st, rf_tile_per()); else launch_rf_grid<emb_interact_rf_kernel<4, 0, 1, EVS_RF_DEPTH>>(a, st, rf_tile_per());
         return true;
     default:   // (d = 128 was built the same way -- CQ = 8, 14 loads per sample, 248 VGPRs, one or two blocks per CU -- and lost to the
                //  LDS-DMA loop: 57.5 vs 52.5 us at B = 16 384, 220 vs 182 us at 65 536; removed)
@@ -1559,7 +1586,7 @@ extern "C" int evs_emb_interact_serve_start(evs_rf_server **out, int T, int d, c
     if (hipMemset(s->st_dev, 0, sizeof(SrvState)) != hipSuccess) return fail(EVS_EHIP);
     {   // The host-published front end where the host can address device memory (EVS_SERVE_PUBLISH=leader keeps the leader's
         // mailbox: developer A/B, and what parts without a large BAR run)
-        const char *how = getenv("EVS_SERVE_PUBLISH");
+        const char *how = evs::env_switch("EVS_SERVE_PUBLISH");
         int dev_id = 0, large_bar = 0;
         if (!(how && !strcmp(how, "leader")) && s->n_blocks <= 4096 && hipGetDevice(&dev_id) == hipSuccess &&
             hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev_id) == hipSuccess && large_bar) {

@@ -863,12 +863,12 @@ __global__ void __launch_bounds__(256, rfq_min_blocks(CODEC, PROBE)) emb_interac
 
 static int rfq_mode() {
     static int v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RFQ"); v = e ? atoi(e) : 1; }   // developer switch: 0 = the LDS-DMA loop
+    if (v < 0) { const char *e = evs::env_switch("EVS_FUSED_RFQ"); v = e ? atoi(e) : 1; }   // developer switch: 0 = the LDS-DMA loop
     return v;
 }
 static int64_t rfq_max_batch() {
     static int64_t v = -1;
-    if (v < 0) { const char *e = getenv("EVS_FUSED_RFQ_MAX_B"); v = e ? atoll(e) : (1ll << 40); }
+    if (v < 0) v = env_switch_range("EVS_FUSED_RFQ_MAX_B", 1ll << 40, 0, 1ll << 40);
     return v;
 }
 

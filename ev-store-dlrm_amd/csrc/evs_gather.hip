@@ -289,6 +289,12 @@ __global__ void __launch_bounds__(256) embedding_bag_sum_scalar_kernel(const Gat
     if (bad) atomicOr(args.err, 1);
 }
 
+// developer A/B: blocks per CU of the grid-stride gather (read once for every instantiation of launch_vec: one warning line)
+static int gather_blocks_per_cu() {
+    static const int v = (int)env_switch_range("EVS_GATHER_BLOCKS_PER_CU", 8, 1, 64);
+    return v;
+}
+
 template <int CODEC, int LPR_T, int UNROLL>
 static void launch_vec(const GatherArgs &a, int lpr, hipStream_t stream, bool bag1) {
     GatherArgs args = a;
@@ -297,8 +303,7 @@ static void launch_vec(const GatherArgs &a, int lpr, hipStream_t stream, bool ba
     args.chunks_per_table = (a.B + bags_per_item - 1) / bags_per_item;
     const int64_t n_items = (int64_t)a.T * args.chunks_per_table;
     int64_t blocks = (n_items + 3) / 4;
-    static const int cap_per_cu = getenv("EVS_GATHER_BLOCKS_PER_CU") ? atoi(getenv("EVS_GATHER_BLOCKS_PER_CU")) : 8;   // (developer A/B)
-    const int64_t cap = (int64_t)kNumCu * cap_per_cu;  // 8 blocks of 256 threads per CU
+    const int64_t cap = (int64_t)kNumCu * gather_blocks_per_cu();  // 8 blocks of 256 threads per CU
     if (blocks > cap) blocks = cap;
     blocks = round_up((int)blocks, kNumXcd);
     if (bag1)
@@ -696,13 +701,13 @@ __global__ void __launch_bounds__(256) bag_sum_flat_kernel(const GatherArgs args
 }
 
 static bool launch_bag_sum_flat(const GatherArgs &a, bool vec_ok, hipStream_t stream) {
-    static const bool on = !(getenv("EVS_GATHER_FLAT") && getenv("EVS_GATHER_FLAT")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_GATHER_FLAT") && evs::env_switch("EVS_GATHER_FLAT")[0] == '0');
     if (!on || !vec_ok || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64)) return false;
     int64_t nnz = 0;
     for (int k = 0; k < a.T; k++) { if (a.row_w[k] || !a.offsets[k]) return false; nnz += a.nnz[k]; }
     // very long bags: a tile holds the rows of one or two bags and as few (bag, piece) threads do all the adding -- beyond an
     // average of 128 indices the grid-stride kernel's lane group per bag takes over (at ~38: 218 us here, 229 there)
-    static const int max_avg = getenv("EVS_GATHER_FLAT_MAXAVG") ? atoi(getenv("EVS_GATHER_FLAT_MAXAVG")) : 128;
+    static const int max_avg = evs::env_switch("EVS_GATHER_FLAT_MAXAVG") ? atoi(evs::env_switch("EVS_GATHER_FLAT_MAXAVG")) : 128;
     if (nnz > (int64_t)max_avg * a.B * (int64_t)a.T) return false;
     const bool sel = nnz > 16 * a.B * (int64_t)a.T;
     const int64_t chunks = (a.B + 63) / 64;
@@ -806,7 +811,7 @@ __global__ void __launch_bounds__(256) bag_sum_long_kernel(const GatherArgs args
 }
 
 static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t stream) {
-    static const bool on = !(getenv("EVS_GATHER_LONG") && getenv("EVS_GATHER_LONG")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_GATHER_LONG") && evs::env_switch("EVS_GATHER_LONG")[0] == '0');
     if (!on || !vec_ok || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64 || a.d == 128) || !zero_page()) return false;
     int64_t nnz = 0;
     for (int k = 0; k < a.T; k++) {
@@ -815,7 +820,7 @@ static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t st
     }
     // from an average of 2 indices per bag on (measured, ragged 1..10-index bags at B = 16 384: 62 vs 75 us for the tile kernel; 9 per bag: 29 vs 48;
     // fixed 100 per bag: 72 vs 500) -- below that the batch is mostly one-index bags and the tile kernel keeps every lane busy
-    static const int min_avg = getenv("EVS_GATHER_LONG_MINAVG") ? atoi(getenv("EVS_GATHER_LONG_MINAVG")) : 2;
+    static const int min_avg = evs::env_switch("EVS_GATHER_LONG_MINAVG") ? atoi(evs::env_switch("EVS_GATHER_LONG_MINAVG")) : 2;
     if (nnz < (int64_t)min_avg * a.B * (int64_t)a.T) return false;
     const int lpr = a.d / 4, G = 64 / lpr;
     const int64_t items = (int64_t)a.T * ((a.B + G - 1) / G);
@@ -836,7 +841,7 @@ static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t st
 // is there a rows-in-registers gather for the launch, and launch it
 template <int CODEC>
 static bool launch_gather_rows(const GatherArgs &a, bool vec_ok, hipStream_t stream, bool bag1) {
-    static const bool on = !(getenv("EVS_GATHER_RF") && getenv("EVS_GATHER_RF")[0] == '0');
+    static const bool on = !(evs::env_switch("EVS_GATHER_RF") && evs::env_switch("EVS_GATHER_RF")[0] == '0');
     const void *zp = CODEC == 32 ? zero_page() : zero_code_page(CODEC);
     if (!on || !vec_ok || a.T > 32 || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64) || !zp) return false;
     for (int k = 0; k < a.T; k++) {

@@ -329,7 +329,6 @@ struct ProbeArgs {
     unsigned pend_stamp = kSaNoStamp;
     unsigned char *arena_w = nullptr; int row_bytes = 0;
     int *part2 = nullptr;                 // replica rows of the inserts' totals (as the update kernels write them)
-    int xflags = 0;                       // developer A/B (timing only): 1 = no arena stores, 2 = no claims
 };
 
 // One missed key into its set (the per-record step of cache_batch_sa_list_kernel restated for callers that hold the source

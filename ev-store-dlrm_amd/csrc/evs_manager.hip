@@ -163,14 +163,14 @@ static int ensure_ready() {
     if (m.ready) return EVS_OK;
     if (m.root.empty()) {
         const char *e;
-        if ((e = getenv("EVS_N_CACHING_LAYER"))) m.n_layer = atoi(e);
-        if ((e = getenv("EVS_MAIN_PRECISION"))) m.main_prec = atoi(e);
-        if ((e = getenv("EVS_SECONDARY_PRECISION"))) m.secondary_prec = atoi(e);
-        if ((e = getenv("EVS_TOTAL_SIZE"))) m.total_size = atoll(e);
-        if ((e = getenv("EVS_SIZE_PROPORTION"))) m.proportion = e;
-        if ((e = getenv("EVS_BACKING"))) m.backing_kind = strcmp(e, "pinned") == 0 ? 1 : strcmp(e, "hbm") == 0 ? 0 : strcmp(e, "host") == 0 ? 2 : -1;
-        if ((e = getenv("EVS_EV_TABLE_ROOT"))) m.root = e;
-        if ((e = getenv("EVS_ALTKEY_DIR"))) m.altkey_dir = e;
+        if ((e = evs::env_switch("EVS_N_CACHING_LAYER"))) m.n_layer = atoi(e);
+        if ((e = evs::env_switch("EVS_MAIN_PRECISION"))) m.main_prec = atoi(e);
+        if ((e = evs::env_switch("EVS_SECONDARY_PRECISION"))) m.secondary_prec = atoi(e);
+        if ((e = evs::env_switch("EVS_TOTAL_SIZE"))) m.total_size = atoll(e);
+        if ((e = evs::env_switch("EVS_SIZE_PROPORTION"))) m.proportion = e;
+        if ((e = evs::env_switch("EVS_BACKING"))) m.backing_kind = strcmp(e, "pinned") == 0 ? 1 : strcmp(e, "hbm") == 0 ? 0 : strcmp(e, "host") == 0 ? 2 : -1;
+        if ((e = evs::env_switch("EVS_EV_TABLE_ROOT"))) m.root = e;
+        if ((e = evs::env_switch("EVS_ALTKEY_DIR"))) m.altkey_dir = e;
         if (m.root.empty()) {
             set_error("cache manager is not configured: call evs_manager_configure() or set EVS_EV_TABLE_ROOT");
             return EVS_ESTATE;
@@ -296,7 +296,7 @@ static int ensure_ready() {
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_rows), m.h_rows, 0));
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_out), m.h_out, 0));
     EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&m.d_hit), m.h_hit, 0));
-    if (const char *e = getenv("EVS_MANAGER_SERVE")) {
+    if (const char *e = evs::env_switch("EVS_MANAGER_SERVE")) {
         if (e[0] == '1') {
             constexpr int64_t kIdleUs = 200;
             EVS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m.serve_ring), kEvTables * kEvDim * 4));

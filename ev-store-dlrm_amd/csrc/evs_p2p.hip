@@ -101,7 +101,7 @@ extern "C" int evs_p2p_sync(int n_sig, uint32_t *const *sig, uint32_t sig_value,
     a.sig_value = sig_value; a.wait_value = wait_value; a.n_sig = n_sig; a.n_wait = n_wait;
     a.err = index_error_flag();
     if (!a.err) return EVS_EHIP;
-    static const long long spins = getenv("EVS_P2P_SPINS") ? atoll(getenv("EVS_P2P_SPINS")) : 4000000ll;   // x ~0.5 us per look
+    static const long long spins = evs::env_switch("EVS_P2P_SPINS") ? atoll(evs::env_switch("EVS_P2P_SPINS")) : 4000000ll;   // x ~0.5 us per look
     a.spins = spins;
     hipLaunchKernelGGL(p2p_sync_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
     EVS_HIP_CHECK(hipGetLastError());

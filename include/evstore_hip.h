@@ -46,6 +46,10 @@ extern "C" {
 
 EVS_API int evs_abi_version(void);
 EVS_API const char *evs_last_error(void);
+/* The EVS_* environment switches this process has read so far (every switch is read once, at its dispatch site): one
+ * "NAME=1\n" (the variable was set) or "NAME=0\n" (unset: the default) line per name, in first-read order, written to
+ * buf (n bytes, always NUL-terminated when n > 0).  Returns the length of the whole text, which may exceed n - 1. */
+EVS_API int evs_env_switches_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)
