@@ -24,6 +24,7 @@
 #include "evs_common.h"
 #include "evs_hash.h"
 #include "evs_update.h"
+#include "evs_cache_policy.h"
 #include <type_traits>
 
 #include <mutex>
@@ -1659,6 +1660,7 @@ __device__ __forceinline__ int block_reserve_n(int *counter, int n, int *s_tot /
 // no better: a thread walking 277 rows is 277 dependent round trips.)
 constexpr int kPartCols = 40;   // 0..32 priority-histogram deltas, 36 recycled tombstones, 37 dropped, 38 hits, 39 perfect requests
 constexpr int kReplicas = 32;
+static_assert(kPartCols == kPolPartCols && kReplicas == kPolReplicas, "evs_cache_policy.hip adds into the same replica rows");
 constexpr int kProbeGridMax = 8192;   // one request pair per wave up to B = 65 536, then the blocks loop
 
 // K1: one 32-lane half-wave per request (T <= 32): probe, agg_hit by ballot, priority bump, miss record,
@@ -3233,6 +3235,7 @@ struct evs_aprx {
     int used = 0;                 // 0 fresh, 1 exact machine, 2 batched form
     evs_tier_server *tsrv = nullptr;   // the tier server this tier belongs to (evs_tiers_serve_*)
 };
+static const char *policy_name(int policy) { return policy == evs::kEvLFU ? "evlfu" : policy == evs::kLRU ? "lru" : "lfu"; }
 struct evs_cache {
     evs::CacheState host;      // configuration mirror
     evs::CacheState *st = nullptr;
@@ -3372,7 +3375,7 @@ unsigned sa_single_ways() {
 // can this cache take the set-associative form on its own (universe below 2^32 keys, tags that fit the word)
 bool sa_single_feasible(const evs_cache *c, evs::SaUniverse *u_out = nullptr, evs::SaGeom *g_out = nullptr) {
     evs::SaUniverse u; evs::SaGeom g;
-    const unsigned ways = sa_single_ways();
+    const unsigned ways = c->host.policy == evs::kEvLFU ? sa_single_ways() : kSaSingleWays;   // (the LRU / LFU kernels are compiled for 8-way sets)
     if (!c->has_backing || c->host.cap < (long long)ways) return false;
     if (!sa_make_universe(c->backing_rows, nullptr, c->host.n_tables, u)) return false;
     // a tier alone keeps two arena rows per way (evs_hash.h: the two-copy arena; EVS_SA_DUAL=0: one, developer A/B)
@@ -3564,6 +3567,8 @@ extern "C" int evs_cache_create(evs_cache **out, int policy, int64_t capacity, i
 extern "C" int evs_cache_set_inline_update(evs_cache *c, int on) {
     using namespace evs;
     EVS_REQUIRE(c && (on == 0 || on == 1), "evs_cache_set_inline_update: bad argument");
+    EVS_REQUIRE(on == 0 || c->host.policy == kEvLFU, "evs_cache_set_inline_update: the one-launch form is EvLFU's; an %s cache runs probe, consumer and insert as launches of their own",
+                policy_name(c->host.policy));
     c->inline_mode = on;
     return EVS_OK;
 }
@@ -3618,6 +3623,8 @@ extern "C" int64_t evs_cache_staged_rows(evs_cache *c) { return c ? c->n_staged_
 extern "C" int evs_cache_set_batch_policy(evs_cache *c, int policy) {
     using namespace evs;
     EVS_REQUIRE(c && policy >= 0 && policy <= 2, "evs_cache_set_batch_policy: bad argument");
+    EVS_REQUIRE(policy == 2 || c->host.policy == kEvLFU, "evs_cache_set_batch_policy: the batched path of an %s cache is set-associative (policy 2) only; %d was asked for",
+                policy_name(c->host.policy), policy);
     EVS_REQUIRE(policy != 2 || c->host.cap >= (long long)kSaSingleWays, "evs_cache_set_batch_policy: the set-associative policy needs a capacity of at least %d entries", (int)kSaSingleWays);
     if (c->used == 2) { set_error("evs_cache_set_batch_policy: the batched path is already in use"); return EVS_ESTATE; }
     c->batch_policy = policy;
@@ -3914,9 +3921,20 @@ static int resolved_batch_policy(evs_cache *c, bool single_tier = true);
 static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream_t st, evs::BatchArgs &a, const char *who) {
     using namespace evs;
     EVS_REQUIRE(c, "%s: NULL cache", who);
-    EVS_REQUIRE(c->host.policy == kEvLFU, "%s: EvLFU only", who);
     EVS_REQUIRE(c->host.n_tables <= 32, "%s: at most 32 tables", who);
     if (!c->has_backing) { set_error("%s: call evs_cache_set_backing first", who); return EVS_ESTATE; }
+    if (c->host.policy != kEvLFU) {   // LRU / LFU: the set-associative form or nothing (evs_cache_policy.hip), refused before anything is allocated
+        const char *pn = policy_name(c->host.policy);
+        if (c->host_backing || c->ft) {
+            set_error("%s: the batched path of an %s cache reads its tables in place from HBM (no host-memory / file-backed tables)", who, pn);
+            return EVS_ESTATE;
+        }
+        EVS_REQUIRE(c->host.cap >= (long long)kSaSingleWays, "%s: the batched path of an %s cache needs a capacity of at least %d entries (one set), not %lld",
+                    who, pn, (int)kSaSingleWays, (long long)c->host.cap);
+        unsigned long long universe = 0;
+        for (int k = 0; k < c->host.n_tables; k++) universe += (unsigned long long)std::max<long long>(c->backing_rows[k], 0);
+        EVS_REQUIRE(universe < (1ull << 32), "%s: the batched path of an %s cache needs fewer than 2^32 rows over all tables, not %llu", who, pn, universe);
+    }
     if (c->used == 1) { set_error("%s: this cache is used through the exact path", who); return EVS_ESTATE; }
     EVS_REQUIRE(c->host.cap <= kMaxBatchedCap, "%s: capacity above %lld entries needs wider hash words", who, kMaxBatchedCap);
     EVS_REQUIRE(B > 0 && B < (1ll << 31) / 32 && rows, "%s: bad argument", who);
@@ -4211,6 +4229,7 @@ static bool launch_sampled_update_pair(const evs::BatchArgs &a1, const evs::Batc
 // tables the kernels read in place (HBM), at least one full set -- and the sampled update everywhere else (host-memory
 // and file-backed miss tiers, the two- / three-tier lookups).
 static int resolved_batch_policy(evs_cache *c, bool single_tier) {
+    if (c->batch_policy < 0 && c->host.policy != evs::kEvLFU) c->batch_policy = 2;   // LRU / LFU: set-associative (batch_prepare refuses what that form cannot take)
     if (c->batch_policy < 0) {
         const char *e = evs::env_switch("EVS_CACHE_POLICY");
         const bool sa_ok = single_tier && !c->host_backing && !c->ft && sa_single_feasible(c);
@@ -4250,6 +4269,7 @@ static void sampled_close_pending2(evs_cache *c1, int rebuild1, evs_cache *c2, i
 static void sampled_flush_if_wanted(evs_cache *c, hipStream_t st) {
     using namespace evs;
     if ((c->batch_policy != 1 && c->batch_policy != 2) || !c->host_tomb || !c->bs) return;
+    if (c->host.policy != evs::kEvLFU) return;   // (LRU / LFU have no flush: n_flush stays 0)
     volatile int *flags = reinterpret_cast<volatile int *>(c->host_tomb);
     if (!flags[1]) return;
     flags[1] = 0;
@@ -4341,6 +4361,29 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         // Set-associative policy (evs_hash.h): probe (one line per key) -> consumers -> ONE update kernel (one line, one
         // CAS and the row per new key) -> counters folded every kCloseEvery-th batch.  No hash, no tombstones, no sweeps.
         if (host_tier || c->ft) { set_error("evs_cache_lookup_batch: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)"); return EVS_ESTATE; }
+        if (c->host.policy != kEvLFU) {
+            // LRU / LFU (evs_cache_policy.hip): probe + touch -> consumers -> insert, always as launches of their own; batch
+            // number n = 1, 2, ... rides in the way words modulo 2^S
+            PolicyArgs pa;
+            pa.sa = c->sa; pa.sau = c->sau;
+            pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+            pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+            if ((cap << c->sa.dual) >= (1ll << 30)) a.row_ids = nullptr;   // (a row id carries the arena entry in 30 bits)
+            pa.requests = rows; pa.hit = hit; pa.row_ptrs = c->row_ptrs; pa.row_ids = a.row_ids;
+            pa.miss_rec = c->miss_rec; pa.list_cnt = c->list_cnt;
+            pa.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+            pa.part1 = a.part1; pa.part2 = a.part2;
+            for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = c->backing_rows[k]; }
+            pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
+            a.list_cap = pa.list_cap;
+            policy_probe_launch(pa, a.g1, st);
+            const int rc = consumers(); if (rc) return rc;
+            policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
+            c->pending_batches++; c->pending_requests += B;
+            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+            EVS_HIP_CHECK(hipGetLastError());
+            return EVS_OK;
+        }
         a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;
         sampled_flush_if_wanted(c, st);
         a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
@@ -4589,6 +4632,9 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     using namespace evs;
     if (B == 0) return EVS_OK;
     EVS_REQUIRE(c1 && c2 && tier, "evs_cache_lookup_batch_c1c2: NULL argument");
+    EVS_REQUIRE(c1->host.policy == kEvLFU && c2->host.policy == kEvLFU,
+                "evs_cache_lookup_batch_c1c2: the tier pair / triple is EvLFU's (C1 %s, C2 %s); an lru / lfu cache serves the batched path as a single tier",
+                policy_name(c1->host.policy), policy_name(c2->host.policy));
     if (R) EVS_REQUIRE((c1->host.dim == 16 || c1->host.dim == 32 || c1->host.dim == 36) && c1->host.n_tables + 1 <= EVS_MAX_FEATURES,
                        "evs_cache_lookup_interact_c1c2: d must be 16, 32 or 36 and T <= 31");
     EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim,
@@ -4928,7 +4974,13 @@ extern "C" int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t 
                 const unsigned word = tags[(size_t)(es >> g.sub_shift) * g.line_words + g.w_off + (es & ((1u << g.sub_shift) - 1u)) * g.ways + w];
                 if (!word) continue;
                 const unsigned long long key = sa_key_of_host(c->sau, g, es, word);
-                if (n < max_triples && triples) { triples[3 * n] = (int64_t)(word >> evs::kSaPrioShift); triples[3 * n + 1] = (int64_t)(key >> 32); triples[3 * n + 2] = (int64_t)(key & 0xffffffffull); }
+                // (LRU: the way's age in batches, 0 = touched by the latest batch; LFU: its counter; EvLFU: its priority)
+                int64_t score = (int64_t)(word >> evs::kSaPrioShift);
+                if (c->host.policy == evs::kLRU) {
+                    const evs::PolLayout lay = evs::pol_layout(g, 0);
+                    score = (int64_t)evs::pol_age(lay, (unsigned)((unsigned long long)c->stamp_counter & evs::pol_stamp_mask(lay)), word);
+                }
+                if (n < max_triples && triples) { triples[3 * n] = score; triples[3 * n + 1] = (int64_t)(key >> 32); triples[3 * n + 2] = (int64_t)(key & 0xffffffffull); }
                 n++;
             }
         return n;

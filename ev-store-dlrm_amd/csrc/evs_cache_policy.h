@@ -1,0 +1,71 @@
+// Batched LRU and LFU on the set-associative tier (batch policy 2 of an LRU / LFU cache): the way-word layout above the tag,
+// the arguments of the two kernels (evs_cache_policy.hip) and their launchers.  The rule the kernels implement is written
+// down in include/evstore_hip.h (evs_cache_set_batch_policy, "the batched rule"); the set geometry, the key permutation, the
+// tag field and the copy-select bit are evs_hash.h's, so sa_lookup, the dump and the row updates read such a tier unchanged.
+#pragma once
+#include "evs_hash.h"
+
+namespace evs {
+
+// The bits of a way word above the tag.  evs_hash.h splits them into a low field [25 - dual : tag_bits] (EvLFU: the stamp of
+// the batch that filled the way) and a high field [31 : 26] (EvLFU: the priority); bit 25 of a two-copy arena is `sel`.
+//   LFU: high field = the saturating counter (6 bits, 1..63), low field = `last`, the batch that touched the way last:
+//        S = 26 - dual - tag_bits stamp bits;
+//   LRU: no counter -- the high field holds the HIGH bits of `last`, the low field its low bits: S = 32 - dual - tag_bits.
+// `last` is the batch number modulo 2^S; ages are circular: age = (n - last) mod 2^S, 0 = touched or filled by batch n.
+struct PolLayout {
+    unsigned tag_bits, tag_mask;
+    unsigned low_bits, low_mask;   // the low field
+    unsigned dual;                 // 1: bit 25 is the copy-select bit
+    unsigned lfu;                  // 1: LFU (counter in the high field), 0: LRU
+};
+constexpr unsigned kPolCntMax = 63u;
+__host__ __device__ inline PolLayout pol_layout(const SaGeom &g, int lfu) {
+    PolLayout l;
+    l.tag_bits = g.tag_bits; l.tag_mask = g.tag_mask;
+    l.low_bits = 26u - g.dual - g.tag_bits; l.low_mask = g.stamp_mask;
+    l.dual = g.dual; l.lfu = lfu ? 1u : 0u;
+    return l;
+}
+__host__ __device__ inline unsigned pol_stamp_bits(const PolLayout &l) { return l.low_bits + (l.lfu ? 0u : 6u); }
+__host__ __device__ inline unsigned pol_stamp_mask(const PolLayout &l) { return (1u << pol_stamp_bits(l)) - 1u; }   // (S <= 31: tag_bits >= 1)
+__host__ __device__ inline unsigned pol_last(const PolLayout &l, unsigned w) {
+    const unsigned lo = (w >> l.tag_bits) & l.low_mask;
+    return l.lfu ? lo : (lo | ((w >> kSaPrioShift) << l.low_bits));
+}
+__host__ __device__ inline unsigned pol_cnt(unsigned w) { return w >> kSaPrioShift; }   // LFU only
+__host__ __device__ inline unsigned pol_sel(const PolLayout &l, unsigned w) { return (w >> kSaSelShift) & l.dual; }
+// last: already reduced modulo 2^S
+__host__ __device__ inline unsigned pol_word(const PolLayout &l, unsigned tag1, unsigned last, unsigned cnt, unsigned sel) {
+    const unsigned hi = l.lfu ? cnt : (last >> l.low_bits);
+    return tag1 | ((last & l.low_mask) << l.tag_bits) | ((sel & l.dual) << kSaSelShift) | (hi << kSaPrioShift);
+}
+__host__ __device__ inline unsigned pol_age(const PolLayout &l, unsigned cur, unsigned w) { return (cur - pol_last(l, w)) & pol_stamp_mask(l); }
+
+// the replica rows the batch kernels add their totals into (evs_cache.hip owns the buffers and folds them: sampled_close_block)
+constexpr int kPolPartCols = 40;   // 0 resident-entry delta, 33 free ways taken, 34 evictions, 38 hits, 39 all-hit requests
+constexpr int kPolReplicas = 32;
+
+struct PolicyArgs {
+    SaGeom sa; SaUniverse sau;
+    PolLayout lay;
+    unsigned cur;                          // this batch's number modulo 2^S
+    const int *requests;                   // (B,T) int32 row ids
+    unsigned char *hit;                    // (B,T) out
+    long long *row_ptrs;                   // (B,T) out: address of each key's row (arena / table / 0) ...
+    int *row_ids;                          // ... or, when not NULL: bit 30 | arena entry, else the table row, -1 = none
+    uint4 *miss_rec; int *list_cnt; int list_cap;   // per probe block: its misses as (row, table, set, tag + 1), their number
+    int *part1, *part2;
+    const unsigned char *backing[32];
+    long long backing_rows[32];
+    unsigned char *arena;
+    long long B;
+    int T, row_bytes;
+};
+
+// probe + touch: grid blocks of 256 threads, block j walks requests 8 j, 8 (j + grid), ...; writes miss list j
+void policy_probe_launch(const PolicyArgs &a, int grid, hipStream_t st);
+// insert: block j (`threads` = 64 or 128) takes miss list j
+void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st);
+
+}  // namespace evs

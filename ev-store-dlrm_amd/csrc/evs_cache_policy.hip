@@ -1,0 +1,232 @@
+// Batched LRU and LFU on the set-associative tier (gfx950): the probe + touch kernel and the insert kernel of the
+// separate-launch chain  probe -> consumer -> insert  (evs_cache.hip: cache_batch_impl).  The rule: include/evstore_hip.h,
+// evs_cache_set_batch_policy, "the batched rule"; the word layout: evs_cache_policy.h.
+//
+// What keeps the two kernels simple is that they never run at the same time (one stream, one launch each):
+//   * the probe launch only TOUCHES ways (tag and copy-select bit stay): a prober's plain read of a set line sees every tag
+//     as it stood when the batch arrived, so hit flags are snapshot flags whatever the other blocks have touched so far --
+//     and a touch is a pure function of the word of before the batch, which makes it a plain store (see there);
+//   * the insert launch only REPLACES ways, each at most once (old word -> a word stamped n, which nobody takes again): a
+//     lost compare-and-swap means exactly "that way now belongs to this batch", so ranking again with the returned word
+//     ends after at most 8 rounds.
+#include <type_traits>
+
+#include "evs_cache_policy.h"
+
+namespace evs {
+namespace {
+
+// K1: one 32-lane half-wave per request (T <= 32), one lane per key -- the set line (one 32-byte request), the hit ballot,
+// the touch (one 4-byte store where the way does not carry stamp n yet), the row id / address for the consumer, the miss
+// record.
+__global__ void __launch_bounds__(256) policy_probe_kernel(const PolicyArgs args) {
+    __shared__ int s_sum[2];   // hits / all-hit requests of this block
+    __shared__ int s_list_n;
+    // per-table values out of LDS: a per-lane index into the kernel arguments is a memory round trip in front of the set loads
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    __shared__ const unsigned char *s_table[32];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_list_n = 0;
+    const int T = args.T;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.backing_rows[threadIdx.x] : 0;
+        s_table[threadIdx.x] = args.backing[threadIdx.x];
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const PolLayout &L = args.lay;
+    const unsigned cur = args.cur;
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool req_on = req < args.B;
+        const bool key_on = req_on && hl < T;
+        const int row = key_on ? args.requests[req * T + hl] : -1;
+        const bool ok = key_on && row >= 0 && row < s_rows[hl];
+        unsigned set = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(args.sau, s_base[hl] + (ok ? (unsigned)row : 0u)), set, tag1);
+        if (!ok) set = 0u;
+        SaLine line;
+        sa_load<8>(g, set, line);
+        const int way = sa_find<8>(g, line, tag1, w);
+        const bool is_hit = ok && way >= 0;
+        const unsigned long long hm = __ballot(is_hit);
+        const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+        if (is_hit && pol_last(L, w) != cur) {
+            // touch: last = n, LFU counter + 1 (saturating), ONCE per way and batch.  A plain store, no compare-and-swap:
+            // nothing but touches writes a way word during this launch, every lane that still reads the way's word of
+            // before the batch (stamp != n) derives the SAME new word from it, and a lane that reads the new word stores
+            // nothing -- so any number of writers, in any order and over stale copies, leave exactly that word.  (As a
+            // compare-and-swap the touch made the chain 34 us per batch instead of 21 at B = 2 048: the tables of 3 .. 30
+            // rows put every request of a batch on a handful of addresses, and same-address atomics take their turns.)
+            const unsigned c = pol_cnt(w);
+            sa_ways_ptr(g, set)[way] = pol_word(L, w & L.tag_mask, cur, c < kPolCntMax ? c + 1u : kPolCntMax, pol_sel(L, w));
+        }
+        if (key_on) {
+            const long long at = req * T + hl;
+            args.hit[at] = is_hit ? 1 : 0;
+            const unsigned e = is_hit ? sa_entry(g, set, (unsigned)way, w) : 0u;
+            if (args.row_ids) args.row_ids[at] = is_hit ? (int)(0x40000000u | e) : (ok ? row : -1);
+            else {
+                const unsigned char *src = nullptr;
+                if (is_hit) src = args.arena + (long long)e * args.row_bytes;
+                else if (ok) src = s_table[hl] + (long long)row * args.row_bytes;
+                args.row_ptrs[at] = (long long)src;
+            }
+        }
+        {   // the half-wave's misses, packed, behind the block's earlier ones
+            const bool is_miss = ok && way < 0;
+            const unsigned long long mm = __ballot(is_miss);
+            const unsigned mh = (unsigned)(half ? (mm >> 32) : mm);
+            int base = 0;
+            if (hl == 0 && mh) base = atomicAdd(&s_list_n, __popc(mh));
+            base = __shfl(base, half * 32, 64);
+            if (is_miss) {
+                const int at = base + __popc(mh & ((1u << hl) - 1u));
+                if (at < args.list_cap)
+                    args.miss_rec[(long long)blockIdx.x * args.list_cap + at] = make_uint4((unsigned)row, (unsigned)hl, set, tag1);
+            }
+        }
+        if (req_on && hl == 0) { atomicAdd(&s_sum[0], agg); if (agg == T) atomicAdd(&s_sum[1], 1); }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_sum[threadIdx.x])
+        atomicAdd(&args.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38 + threadIdx.x], s_sum[threadIdx.x]);
+    if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
+}
+
+struct NoTail {};
+// the piece types of a row as compiler vector types (loads through an address-space-1 pointer want non-class types)
+template <typename U> struct Native { using type = U; };
+template <> struct Native<float4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct Native<uint2> { typedef unsigned type __attribute__((ext_vector_type(2))); };
+template <> struct Native<NoTail> { using type = int; };
+
+// One missed key into its set.  Issue order: the set line, then the source row (global loads return in order: the ranking
+// and the compare-and-swap go out when the line is there, the row -- a random line of a large table -- still on its way),
+// then the CAS, then the row stores nobody waits for.  PIECES x U (+ TAIL) = row_bytes; PIECES = 0: any row size, copied
+// after the claim.
+template <int PIECES, typename U, typename TAIL>
+__device__ __forceinline__ void policy_insert_one(const PolicyArgs &args, const unsigned char *table, unsigned row, unsigned set, unsigned tag1,
+                                                  int *s_stat) {
+    const SaGeom &g = args.sa;
+    const PolLayout &L = args.lay;
+    const unsigned cur = args.cur;
+    unsigned *tags = sa_ways_ptr(g, set);
+    SaLine line;
+    sa_load<8>(g, set, line);
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned char *srow = table + (long long)row * args.row_bytes;
+    using NU = typename Native<U>::type;
+    using NT = typename Native<TAIL>::type;
+    constexpr int NP = PIECES > 0 ? PIECES : 1;
+    NU r[NP];
+    NT rt{};
+    if constexpr (PIECES > 0) {
+        typedef const __attribute__((address_space(1))) NU *gsrc_t;
+        const gsrc_t gs = reinterpret_cast<gsrc_t>(reinterpret_cast<uintptr_t>(srow));
+#pragma unroll
+        for (int k = 0; k < PIECES; k++) r[k] = gs[k];
+        if constexpr (!std::is_same<TAIL, NoTail>::value) {
+            typedef const __attribute__((address_space(1))) NT *gtail_t;
+            rt = *reinterpret_cast<gtail_t>(reinterpret_cast<uintptr_t>(srow + PIECES * sizeof(U)));
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    unsigned w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = sa_way_word(line, j);
+    const unsigned sbits = pol_stamp_bits(L), smask = pol_stamp_mask(L);
+    int way = -1;
+    unsigned old_word = 0u;
+#pragma unroll 1
+    for (int attempt = 0; attempt <= 8; attempt++) {
+        // rank: a free way beats everything (lowest index first); else, among the ways batch n has not touched or filled,
+        // LRU the largest circular age, LFU the lowest counter and then the largest age; equal keys: the lowest index
+        int best = -1;
+        bool dup = false;
+        unsigned bk = 0u, bw = 0u;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            dup = dup || (w[j] & L.tag_mask) == tag1;
+            const unsigned age = (cur - pol_last(L, w[j])) & smask;
+            const unsigned score = L.lfu ? (((kPolCntMax - pol_cnt(w[j])) << sbits) | age) : age;   // (< 2^31: 6 + S <= 31 bits under LFU)
+            const unsigned k = w[j] == 0u ? 0xffffffffu : (age != 0u ? score : 0u);                 // 0: not eligible (eligible ways have age >= 1)
+            const bool cand = k > bk;
+            best = cand ? j : best; bk = cand ? k : bk; bw = cand ? w[j] : bw;
+        }
+        if (dup || best < 0) return;   // another copy of the key got there first / every way belongs to this batch: turned away
+        const unsigned prev = atomicCAS(&tags[best], bw, pol_word(L, tag1, cur, 1u, pol_sel(L, bw) ^ 1u));
+        if (prev == bw) { way = best; old_word = bw; break; }
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = j == best ? prev : w[j];
+    }
+    if (way < 0) return;
+    atomicAdd(&s_stat[old_word == 0u ? 0 : 1], 1);
+    // (two-copy arena: the new row goes to the copy the victim's word does NOT name, as the word just installed says)
+    unsigned char *drow = args.arena + (long long)sa_entry(g, set, (unsigned)way, (pol_sel(L, old_word) ^ 1u) << kSaSelShift) * args.row_bytes;
+    if constexpr (PIECES > 0) {
+#pragma unroll
+        for (int k = 0; k < PIECES; k++) reinterpret_cast<NU *>(drow)[k] = r[k];
+        if constexpr (!std::is_same<TAIL, NoTail>::value) *reinterpret_cast<NT *>(drow + PIECES * sizeof(U)) = rt;
+    } else {
+        for (int c = 0; c < args.row_bytes; c++) drow[c] = srow[c];
+    }
+}
+
+// K2: block j takes the misses probe block j listed, a record per lane, dealt round-robin over the block's waves
+template <int PIECES, typename U, typename TAIL = NoTail>
+__global__ void __launch_bounds__(256) policy_insert_kernel(const PolicyArgs args) {
+    __shared__ int s_stat[2];   // [0] free ways taken, [1] evictions
+    __shared__ const unsigned char *s_table[32];
+    if (threadIdx.x < 2) s_stat[threadIdx.x] = 0;
+    if (threadIdx.x < 32) s_table[threadIdx.x] = args.backing[threadIdx.x];
+    const uint4 *rec = args.miss_rec + (long long)blockIdx.x * args.list_cap;
+    const int nw = (int)blockDim.x >> 6;
+    const int i0 = ((int)threadIdx.x & 63) * nw + ((int)threadIdx.x >> 6);
+    const int n = args.list_cnt[blockIdx.x];
+    __syncthreads();
+    for (int i = i0; i < n; i += 64 * nw) {
+        const uint4 r = rec[i];
+        policy_insert_one<PIECES, U, TAIL>(args, s_table[r.y & 31u], r.x, r.z, r.w, s_stat);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int *p = args.part2 + (blockIdx.x % kPolReplicas) * kPolPartCols;
+        if (s_stat[0]) { atomicAdd(&p[0], s_stat[0]); atomicAdd(&p[33], s_stat[0]); }   // (column 0: the one histogram bucket = size)
+        if (s_stat[1]) atomicAdd(&p[34], s_stat[1]);
+    }
+}
+
+template <int PIECES, typename U, typename TAIL = NoTail>
+void insert_launch_t(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) {
+    hipLaunchKernelGGL((policy_insert_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a);
+}
+
+}  // namespace
+
+void policy_probe_launch(const PolicyArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(policy_probe_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+// compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail)
+void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) {
+    switch (a.row_bytes) {
+    case 144: insert_launch_t<9, float4>(a, grid, threads, st); break;     // d = 36 fp32
+    case 256: insert_launch_t<16, float4>(a, grid, threads, st); break;    // d = 64 fp32
+    case 128: insert_launch_t<8, float4>(a, grid, threads, st); break;     // d = 32 fp32, d = 64 u16
+    case 64: insert_launch_t<4, float4>(a, grid, threads, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
+    case 32: insert_launch_t<2, float4>(a, grid, threads, st); break;
+    case 16: insert_launch_t<1, float4>(a, grid, threads, st); break;
+    case 72: insert_launch_t<4, float4, uint2>(a, grid, threads, st); break;            // d = 36 u16: 4 x 16 + 8
+    case 36: insert_launch_t<2, float4, unsigned>(a, grid, threads, st); break;         // d = 36 u8: 2 x 16 + 4
+    case 18: insert_launch_t<1, float4, unsigned short>(a, grid, threads, st); break;   // d = 36 u4: 16 + 2
+    case 8: insert_launch_t<1, uint2>(a, grid, threads, st); break;
+    default: insert_launch_t<0, float4>(a, grid, threads, st); break;
+    }
+}
+
+}  // namespace evs

@@ -158,7 +158,8 @@ class GpuCache:
     def set_batch_policy(self, policy):
         """'sampled' (one update kernel, victim = lowest priority of 8 sampled entries), 'plan' (insert / plan / evict /
         assign, clock-hand window) or 'setassoc' (8-way set-associative: one 64-byte line of key words per set, the
-        victim is the lowest priority of the key's own set; single tier, tables in HBM); before the first batched lookup."""
+        victim is the lowest priority of the key's own set; single tier, tables in HBM); before the first batched lookup.
+        An 'lru' / 'lfu' cache has the set-associative form only (its default): 'plan' and 'sampled' raise EVS_EINVAL."""
         _lib.check(_lib.lib().evs_cache_set_batch_policy(self._h, {"plan": 0, "sampled": 1, "setassoc": 2}[policy]))
         return self
 
@@ -235,7 +236,8 @@ class GpuCache:
     def set_inline_update(self, on=True):
         """the set-associative tier's policy update inside the probe + interaction launch (the default where it applies; hit
         flags then mean "served from the cache") or, on=False, the two-launch chain with strict snapshot flags
-        (include/evstore_hip.h: evs_cache_set_inline_update)"""
+        (include/evstore_hip.h: evs_cache_set_inline_update).  An 'lru' / 'lfu' cache always runs the chain: on=True raises
+        EVS_EINVAL, on=False is accepted."""
         _lib.check(_lib.lib().evs_cache_set_inline_update(self._h, 1 if on else 0))
         return self
 
@@ -243,7 +245,11 @@ class GpuCache:
         _lib.check(_lib.lib().evs_cache_serve_stop(self._h))
 
     def lookup_batch(self, rows, out=None, hit=None):
-        """Batched EvLFU lookup, snapshot semantics (see include/evstore_hip.h: evs_cache_lookup_batch)."""
+        """Batched lookup, snapshot semantics (see include/evstore_hip.h: evs_cache_lookup_batch).  EvLFU under any batch
+        policy; an 'lru' / 'lfu' cache as a single set-associative tier over tables in HBM, by "the batched rule" written
+        down at evs_cache_set_batch_policy: flags = residency at arrival, every way hit in the batch stamped with the batch
+        number (LFU: counter + 1 once per batch), every distinct missed key inserted into its own set over a free way, else
+        the least recently touched / least frequently counted way the running batch has not touched."""
         B = _check_batch(self, rows, out, hit)
         if out is None:
             out = torch.empty((B, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
@@ -255,7 +261,9 @@ class GpuCache:
 
     def lookup_interact(self, rows, x, itself=False, out=None, hit=None):
         """R = interact_features(x, cached rows of the B requests): probe + fused MFMA kernel reading the
-        rows through a pointer table (no (B,T,d) intermediate), then the batched policy update."""
+        rows through a pointer table (no (B,T,d) intermediate), then the batched policy update.  An 'lru' / 'lfu' cache
+        runs probe + touch, the row-id / pointer-table consumer and the insert as three launches (strict snapshot flags);
+        fp32 or 16 / 8 / 4-bit tiers."""
         F = self.n_tables + 1
         P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
         B = _check_batch(self, rows, out, hit, out_cols=self.dim + P)
@@ -275,6 +283,8 @@ class GpuCache:
         return hit, out
 
     def batch_stats(self):
+        """Counters of the batched path and the resident-entry histogram per priority.  An 'lru' / 'lfu' cache: n_flush stays
+        0, n_perfect_hits counts all-hit requests, hist[0] = size and the rest 0."""
         s = (C.c_int64 * 8)()
         hist = (C.c_int64 * (self.n_tables + 1))()
         _lib.check(_lib.lib().evs_cache_batch_stats(self._h, s, hist, torch.cuda.current_stream(self.device).cuda_stream))
@@ -284,6 +294,8 @@ class GpuCache:
         return d
 
     def batch_dump(self):
+        """Resident keys of the batched path, unordered: rows of (score, table_1based, row).  score: EvLFU the priority, 'lru'
+        the way's age in batches (0 = touched by the latest batch), 'lfu' its counter (1..63, one count per batch)."""
         import numpy as np
         st = torch.cuda.current_stream(self.device).cuda_stream
         n = _lib.lib().evs_cache_batch_dump(self._h, None, 0, st)

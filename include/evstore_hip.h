@@ -453,7 +453,40 @@ EVS_API int evs_cache_lookup_batch(evs_cache *c, int64_t B, const int32_t *rows,
  * the tables and not cached this time); which keys are resident after a batch depends on thread timing under 1 and 2.
  * Hit rate at the 10 % Criteo-Kaggle cache (Zipf 0.75, B = 16 384, 600 batches): 0 0.8868, 1 0.8862, 2 0.8840, the
  * sequential oracle on the same stream 0.884 (tests/test_gpu_fullsize.py asserts |batched - sequential| <= 0.01 over
- * ten batches at full size for all three; bench.py: cache_tier.hit_rate_vs_sequential_oracle). */
+ * ten batches at full size for all three; bench.py: cache_tier.hit_rate_vs_sequential_oracle).
+ *
+ * LRU AND LFU CACHES (evs_cache_create policy 1 / 2) take the batched path under policy 2 only -- a cache that was given no
+ * policy resolves to it; 0 and 1 are refused (EVS_EINVAL) -- as a single tier over tables in HBM, fp32 or 16 / 8 / 4-bit
+ * codec, 8 ways per set (csrc/evs_cache_policy.hip).  Set geometry, key permutation, tag field and the copy-select bit of
+ * the two-copy arena are the ones above, so evs_cache_batch_dump, evs_cache_update_rows and evs_cache_refresh_rows read such
+ * a tier unchanged; the bits above the tag hold `last`, the number of the batch that touched the way last, modulo 2^S, and
+ * for LFU a saturating 6-bit counter (1..63) in the six top bits.  LRU has no counter and its `last` takes those six bits
+ * too: S = 32 - tag bits - 1 (the copy-select bit; it is free, S one more, on the tiny geometries whose tags leave no room
+ * for it) for LRU, S = 26 - tag bits - 1 for LFU.  The 10 % Criteo-Kaggle tier (2^26 keys over 422 032 sets: tag + 1 <= 160,
+ * 8 tag bits) has S = 23 under LRU and S = 17 under LFU.  Ages are CIRCULAR, age = (n - last) mod 2^S:
+ * LRU orders correctly any two ways both touched within the last 2^S - 1 batches (a way left alone for longer looks
+ * younger than it is; one whose `last` equals n modulo 2^S looks touched by the running batch and is passed over once).
+ * THE BATCHED RULE.  n = the cache's batch number (1, 2, ...).  One call (evs_cache_lookup_batch / _lookup_interact) does:
+ *   1. probe (snapshot): hit[b, t] = 1 exactly when key (t + 1, rows[b, t]) was resident when the call started.  Served rows
+ *      are exactly the table rows (R: the usual float64-scaled bound).
+ *   2. touch: every way hit at least once in this batch gets last = n; under LFU its counter also goes up by ONE PER BATCH,
+ *      not one per occurrence, saturating at 63.  Per-batch counting makes the touched word a pure function of the word of
+ *      before the batch, so the probe launch writes it with a plain 4-byte store, skipped once the way carries stamp n: every
+ *      writer stores the same word (counting occurrences would put thousands of same-address atomics per batch on a hot key
+ *      and saturate the counter within one batch anyway).
+ *   3. insert: every distinct missed key is inserted once, into its own set.  Free ways first, lowest way index first.
+ *      Otherwise the victim is chosen among the ways with last != n -- a way touched or filled by the running batch is never
+ *      a victim -- LRU: the oldest `last` by circular age; LFU: the lowest counter, ties to the oldest `last`; remaining
+ *      ties to the lowest way index.  No eligible way: the key is turned away (served from its table, not cached this time).
+ *      A new way gets last = n and counter 1.  When several new keys of one batch fall into one set, which key takes which
+ *      way may depend on timing; each of them still evicts only an eligible way, and no key is ever resident twice.
+ *   4. counters: evs_cache_batch_stats keeps its meaning; n_flush stays 0, n_perfect_hits counts all-hit requests,
+ *      hist[0] = size and the rest 0.  evs_cache_batch_dump's first column is the way's score -- LRU: its age in batches
+ *      (0 = touched by the latest batch), LFU: its counter.
+ * evs_cache_lookup_interact on such a tier always runs probe, the row-id / pointer-table interaction consumer and insert as
+ * three launches (strict snapshot flags); evs_cache_set_inline_update(c, 1) is refused (EVS_EINVAL), on = 0 accepted.  Also
+ * refused, with a message that names the policy and the cache left usable: host-memory or file-backed tables (EVS_ESTATE), a
+ * capacity below 8, 2^32 rows or more over all tables, the tier as a member of a C1 + C2 (+ C3) lookup (EVS_EINVAL). */
 EVS_API int evs_cache_set_batch_policy(evs_cache *c, int policy);
 /* Batched two-tier lookup, snapshot semantics: the throughput form of evs_cache_request_c1c2 (no reference
  * counterpart).  Every key is probed in C1, then in C2, against the tiers as they stand when the call starts;
@@ -509,12 +542,13 @@ EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *ro
  * by one of this batch's own inserts) is the default wherever its conditions hold (a tier alone, 8 ways, two-copy arena, at
  * least 8 stamp bits in the way word).  on = 0 restores the two-launch chain with strict snapshot flags for this cache, on = 1
  * the default; the environment variable EVS_CACHE_INLINE=0 only changes the default of caches that were never told.  May be
- * called between batches. */
+ * called between batches.  LRU / LFU caches have the chain only: on = 1 is refused (EVS_EINVAL), on = 0 accepted. */
 EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
 /* out8: [size, n_free, n_tombstones, n_flush, n_evict, n_requests, n_perfect_hits, n_hits];
- * hist (may be NULL): n_tables+1 resident-entry counts per priority. */
+ * hist (may be NULL): n_tables+1 resident-entry counts per priority (LRU / LFU caches: hist[0] = size, the rest 0). */
 EVS_API int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist, void *stream);
-/* resident (priority, table_1based, row) triples of the batched path, unordered; returns the count. */
+/* resident (priority, table_1based, row) triples of the batched path, unordered; returns the count.  An LRU / LFU cache reports
+ * its score in the first column: LRU the way's age in batches (0 = touched by the latest batch), LFU its counter. */
 EVS_API int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t max_triples, void *stream);
 /* File-backed miss tier: the reference's mmap miss path (emb_storage/mmap_file_read.py:32-40,
  * reader pool mixed_precs_caching/evlfu_8.cpp:191-250) under the GPU cache.  evs_filetier_open maps every
