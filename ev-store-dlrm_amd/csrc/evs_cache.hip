@@ -3255,6 +3255,13 @@ struct evs_cache {
     uint4 *miss_rec = nullptr; int *list_cnt = nullptr;   // sampled update, list form
     unsigned char *row_tier = nullptr;   // two-tier batched lookup: which tier's codec decodes each row
     long long max_batch = 0;
+    // ragged bags (evs_cache_lookup_bags): per-call buffers sized by the positions and the samples of the largest call so far --
+    // the pointer table, flags for a caller that passes none, the probe's miss lists, one word per sample (zero between calls) --
+    // and the (T, B, d) block the interact form pools into
+    void *slab_bags = nullptr;
+    long long bag_max_pos = -1, bag_max_b = 0;
+    long long *bag_ptrs = nullptr; unsigned char *bag_hit = nullptr; uint4 *bag_rec = nullptr; int *bag_list_cnt = nullptr, *bag_sample = nullptr;
+    float *bag_pool = nullptr; long long bag_pool_floats = 0;
     int used = 0;  // 0 fresh, 1 exact path, 2 batched path
     int *estamp = nullptr;      // allocated when the backing tables live in host memory
     bool host_backing = false;
@@ -3448,7 +3455,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->bag_pool};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -3918,7 +3925,8 @@ extern "C" int evs_cache_request_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, c
 // ---- batched path --------------------------------------------------------------------------
 // allocate / grow the batched-path state of one cache and describe it in `a` (everything but the per-call outputs)
 static int resolved_batch_policy(evs_cache *c, bool single_tier = true);
-static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream_t st, evs::BatchArgs &a, const char *who) {
+// what the batched path refuses about the cache itself, before anything is allocated (shared by the (B, T) and the bag form)
+static int batch_check(evs_cache *c, const char *who) {
     using namespace evs;
     EVS_REQUIRE(c, "%s: NULL cache", who);
     EVS_REQUIRE(c->host.n_tables <= 32, "%s: at most 32 tables", who);
@@ -3935,10 +3943,14 @@ static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream
         for (int k = 0; k < c->host.n_tables; k++) universe += (unsigned long long)std::max<long long>(c->backing_rows[k], 0);
         EVS_REQUIRE(universe < (1ull << 32), "%s: the batched path of an %s cache needs fewer than 2^32 rows over all tables, not %llu", who, pn, universe);
     }
-    if (c->used == 1) { set_error("%s: this cache is used through the exact path", who); return EVS_ESTATE; }
+    if (c->used == 1) { set_error("%s: this %s cache is used through the exact path", who, policy_name(c->host.policy)); return EVS_ESTATE; }
     EVS_REQUIRE(c->host.cap <= kMaxBatchedCap, "%s: capacity above %lld entries needs wider hash words", who, kMaxBatchedCap);
-    EVS_REQUIRE(B > 0 && B < (1ll << 31) / 32 && rows, "%s: bad argument", who);
-    const int T = c->host.n_tables;
+    return EVS_OK;
+}
+// the state the batched path keeps between calls: the set records of a set-associative tier, the counters and their replica
+// rows -- allocated at the first batched call of either form, all or nothing
+static int batch_state(evs_cache *c, hipStream_t st, const char *who) {
+    using namespace evs;
     const long long cap = c->host.cap;
     const bool sa = resolved_batch_policy(c) == 2;   // set-associative policy: no hash, no entry arrays (the set records: c->sa)
     if (sa && !c->sa.tags) {   // (a tier that starts out in a pair got its geometry there: batch_c1c2_impl)
@@ -3979,6 +3991,16 @@ static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream
         c->bs = bs; c->eslot = eslot; c->bslots = bslots; c->part1 = part1; c->part2 = part2;
         c->host_tomb = host_tomb; c->host_tomb_dev = host_tomb_dev;
     }
+    return EVS_OK;
+}
+static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream_t st, evs::BatchArgs &a, const char *who) {
+    using namespace evs;
+    { const int rc = batch_check(c, who); if (rc) return rc; }
+    EVS_REQUIRE(B > 0 && B < (1ll << 31) / 32 && rows, "%s: bad argument", who);
+    { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    const int T = c->host.n_tables;
+    const long long cap = c->host.cap;
+    const bool sa = resolved_batch_policy(c) == 2;
     const long long g2 = (B * T + 255) / 256;
     if (B > c->max_batch) {   // grow the per-batch buffers: the new slab first, the old one goes only when the new one exists
         unsigned *miss_info = nullptr;
@@ -4936,6 +4958,139 @@ extern "C" int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t 
     EVS_REQUIRE((x && R) || B == 0, "evs_cache_lookup_interact: NULL x / R");
     EVS_REQUIRE(x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "evs_cache_lookup_interact: x must be 16-byte aligned, stride % 4 == 0");
     return cache_batch_impl(c, B, rows, nullptr, hit, x, x_stride, itself, R, stream);
+}
+
+// ---- ragged bags through an LRU / LFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) -----------------------
+// probe + touch over the flat position list -> pooling through the pointer table (-> the dense interaction) -> the insert
+// kernel of the (B, T) chain, unchanged, on one stream: the consumers read before the insert moves anything.
+static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
+                           float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, int itself,
+                           float *R, uint8_t *hit, void *stream, const char *who) {
+    using namespace evs;
+    const bool interact = R != nullptr || x != nullptr;
+    EVS_REQUIRE(B >= 0, "%s: B = %lld", who, (long long)B);
+    if (B == 0) return EVS_OK;
+    EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
+    EVS_REQUIRE(indices && offsets && nnz, "%s: NULL indices / offsets / nnz", who);
+    EVS_REQUIRE(interact ? (x && R) : pooled != nullptr, "%s: NULL %s", who, interact ? "x / R" : "pooled");
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
+    EVS_REQUIRE(c, "%s: NULL cache", who);
+    const int T = c->host.n_tables, d = c->host.dim;
+    EVS_REQUIRE(T <= 32, "%s: at most 32 tables", who);
+    EVS_REQUIRE(B < (1ll << 31), "%s: B = %lld", who, (long long)B);
+    long long n_pos = 0;
+    for (int k = 0; k < T; k++) {
+        EVS_REQUIRE(nnz[k] >= 0, "%s: nnz[%d] = %lld", who, k, (long long)nnz[k]);
+        EVS_REQUIRE(indices[k] || nnz[k] == 0, "%s: indices[%d] is NULL", who, k);
+        EVS_REQUIRE(offsets[k], "%s: offsets[%d] is NULL", who, k);
+        n_pos += nnz[k];
+        EVS_REQUIRE(n_pos < (1ll << 31), "%s: 2^31 lookups or more in one call", who);
+    }
+    EVS_REQUIRE(d % 4 == 0 && d <= 256, "%s: the pooling takes a dim that is a multiple of 4 up to 256, not %d", who, d);
+    if (interact)
+        EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
+                    who, EVS_MAX_FEATURES, T, d);
+    EVS_REQUIRE(c->host.policy != kEvLFU, "%s: an %s cache has no bag form (its priority counts a request's hit keys); lru / lfu caches take ragged bags",
+                who, policy_name(c->host.policy));
+    { const int rc = batch_check(c, who); if (rc) return rc; }
+    const int piece_bytes = c->host.codec / 2;   // what a lane reads of a row at once: 16 / 8 / 4 / 2 bytes
+    for (int k = 0; k < T; k++)
+        EVS_REQUIRE(reinterpret_cast<uintptr_t>(c->backing[k]) % piece_bytes == 0, "%s: table %d is not %d-byte aligned", who, k, piece_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    int *err = index_error_flag();
+    if (!err) return EVS_EHIP;
+
+    // the probe's grid: one lane per position, blocks of 256, looping past kProbeGridMax blocks; a miss list per block
+    long long grid = (n_pos + 255) / 256; if (grid > kProbeGridMax) grid = kProbeGridMax;
+    const long long iters = grid ? (n_pos + 256 * grid - 1) / (256 * grid) : 0;
+    if (n_pos > c->bag_max_pos || B > c->bag_max_b) {   // grow: the new slab first, the old one goes only when the new one exists
+        const long long np = std::max<long long>(n_pos, c->bag_max_pos), nb = std::max<long long>(B, c->bag_max_b);
+        long long *ptrs = nullptr; unsigned char *flags = nullptr; uint4 *rec = nullptr; int *cnt = nullptr, *sample = nullptr;
+        void *slab = nullptr;
+        SlabPlan sp;
+        // (a call of n <= np positions lists grid * iters * 256 records: n rounded up to 256 while one pass does, else < n + 256 * kProbeGridMax)
+        const long long n_rec = np <= 256ll * kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * kProbeGridMax;
+        sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, n_rec * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
+        sp.add(&sample, nb * 4);
+        if (!sp.carve(&slab)) { set_error("%s: allocating the buffers of a call of %lld lookups failed", who, n_pos); return EVS_ENOMEM; }
+        if (c->slab_bags) {
+            EVS_HIP_CHECK(hipStreamSynchronize(st));
+            (void)hipFree(c->slab_bags);
+        }
+        c->slab_bags = slab;
+        c->bag_ptrs = ptrs; c->bag_hit = flags; c->bag_rec = rec; c->bag_list_cnt = cnt; c->bag_sample = sample;
+        c->bag_max_pos = np; c->bag_max_b = nb;
+        EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
+    }
+    if (interact && (long long)T * B * d > c->bag_pool_floats) {
+        float *pool = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&pool), (size_t)T * B * d * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: allocating the (T, B, d) block of %lld samples failed", who, (long long)B);
+            return EVS_ENOMEM;
+        }
+        if (c->bag_pool) {
+            EVS_HIP_CHECK(hipStreamSynchronize(st));
+            (void)hipFree(c->bag_pool);
+        }
+        c->bag_pool = pool; c->bag_pool_floats = (long long)T * B * d;
+    }
+    c->used = 2;
+    c->batch_calls++;
+
+    BagArgs a;
+    PolicyArgs &pa = a.p;
+    pa.sa = c->sa; pa.sau = c->sau;
+    pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+    pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    pa.requests = nullptr; pa.hit = hit ? hit : c->bag_hit; pa.row_ptrs = c->bag_ptrs; pa.row_ids = nullptr;
+    pa.miss_rec = c->bag_rec; pa.list_cnt = c->bag_list_cnt; pa.list_cap = (int)(iters * 256);
+    pa.part1 = c->part1; pa.part2 = c->part2;
+    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = k < T ? c->backing_rows[k] : 0; }
+    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
+    a.pos0[0] = 0;
+    for (int k = 0; k < 32; k++) {
+        a.indices[k] = k < T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
+        a.offsets[k] = k < T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
+        a.pos0[k + 1] = a.pos0[k] + (k < T ? nnz[k] : 0);
+    }
+    a.n_pos = n_pos; a.iters = (int)iters; a.err = err;
+    a.out = interact ? c->bag_pool : pooled;
+    a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
+    a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
+    a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
+
+    if (grid) bags_probe_launch(a, (int)grid, st);
+    bags_pool_launch(a, c->host.codec, st);
+    if (interact) {
+        const float *feats[EVS_MAX_FEATURES];
+        int64_t strides[EVS_MAX_FEATURES];
+        feats[0] = x; strides[0] = x_stride;
+        for (int k = 0; k < T; k++) { feats[k + 1] = c->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
+        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+        if (rc) return rc;   // (nothing is inserted: the touches stand, as after any launch failure behind the probe)
+    }
+    if (grid) policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
+    c->pending_batches++; c->pending_requests += B;
+    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+
+extern "C" int evs_cache_lookup_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
+                                     const int64_t *nnz, float *pooled, int64_t out_table_stride, int64_t out_bag_stride,
+                                     uint8_t *hit, void *stream) {
+    return cache_bags_impl(c, B, indices, offsets, nnz, pooled, out_table_stride, out_bag_stride, nullptr, 0, 0, nullptr, hit, stream,
+                           "evs_cache_lookup_bags");
+}
+
+extern "C" int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
+                                              const int64_t *nnz, const float *x, int64_t x_stride, int itself, float *R,
+                                              uint8_t *hit, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(B <= 0 || (x && R), "evs_cache_lookup_bags_interact: NULL x / R");
+    return cache_bags_impl(c, B, indices, offsets, nnz, nullptr, 0, 0, x, x_stride, itself, R, hit, stream, "evs_cache_lookup_bags_interact");
 }
 
 // out8 (host): [size, n_free, n_tomb, n_flush, n_evict, n_requests, n_perfect_hits, n_hits]; hist: n_tables+1 priority counts

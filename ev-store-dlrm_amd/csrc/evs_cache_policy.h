@@ -68,4 +68,28 @@ void policy_probe_launch(const PolicyArgs &a, int grid, hipStream_t st);
 // insert: block j (`threads` = 64 or 128) takes miss list j
 void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st);
 
+// Ragged bags through the same tier (evs_cache_lookup_bags): a lookup is one POSITION of one table's index array, the
+// positions of all tables numbered table-major (table k's start at pos0[k]).  `p` is used as above except for requests / B / T
+// semantics: p.hit and p.row_ptrs are flat arrays of n_pos entries, p.row_ids is NULL, p.B the number of samples.
+struct BagArgs {
+    PolicyArgs p;
+    const long long *indices[32];          // per table: nnz[k] int64 row ids
+    const long long *offsets[32];          // per table: B bag starts (the last bag runs to nnz[k])
+    long long pos0[33];                    // prefix sums of nnz; pos0[T] = n_pos
+    long long n_pos;
+    int iters;                             // probe: block j walks positions 256 (j + i grid) + thread, i < iters
+    int *err;                              // the sticky index-error flag
+    // pooling
+    float *out; long long out_tstride, out_bstride;
+    const unsigned char *arena_end;        // a row address in [p.arena, arena_end) is a hit
+    int *sample_cnt;                       // B words, zero between launches: bags seen | bags with a lookup << 8 | bags with a miss << 16
+    long long chunks_per_table;
+    int d;
+};
+// probe + touch over the flat position list: grid blocks of 256 threads, one lane per position; writes miss list j (records as above)
+void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st);
+// pooled[k][b] = sum over the bag's positions of the rows the probe's pointer table names (d % 4 == 0, d <= 256); counts the
+// all-hit samples into column 39
+void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st);
+
 }  // namespace evs

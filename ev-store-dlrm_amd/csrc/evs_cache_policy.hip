@@ -9,12 +9,39 @@
 //   * the insert launch only REPLACES ways, each at most once (old word -> a word stamped n, which nobody takes again): a
 //     lost compare-and-swap means exactly "that way now belongs to this batch", so ranking again with the returned word
 //     ends after at most 8 rounds.
+// Ragged bags (evs_cache_lookup_bags; the rule: include/evstore_hip.h there) run the same chain with a probe over the flat
+// list of index positions and a pooling kernel as the consumer:  bags_probe -> bags_pool (-> dense interaction) -> insert.
 #include <type_traits>
 
 #include "evs_cache_policy.h"
 
 namespace evs {
 namespace {
+
+// One key against its set, shared by the two probe kernels: the set line (one 32-byte request), the way that holds the key
+// and the touch.  gid: the key's dense row number (anything in range when !ok: the lane then reads set 0 and hits nothing).
+struct PolKey { unsigned set, tag1, w; int way; };
+__device__ __forceinline__ bool policy_probe_key(const SaGeom &g, const SaUniverse &u, const PolLayout &L, unsigned cur, bool ok, unsigned gid,
+                                                 PolKey &k) {
+    k.set = 0u; k.tag1 = 0u; k.w = 0u;
+    sa_split(g, sa_perm(u, gid), k.set, k.tag1);
+    if (!ok) k.set = 0u;
+    SaLine line;
+    sa_load<8>(g, k.set, line);
+    k.way = sa_find<8>(g, line, k.tag1, k.w);
+    const bool is_hit = ok && k.way >= 0;
+    if (is_hit && pol_last(L, k.w) != cur) {
+        // touch: last = n, LFU counter + 1 (saturating), ONCE per way and batch.  A plain store, no compare-and-swap:
+        // nothing but touches writes a way word during this launch, every lane that still reads the way's word of
+        // before the batch (stamp != n) derives the SAME new word from it, and a lane that reads the new word stores
+        // nothing -- so any number of writers, in any order and over stale copies, leave exactly that word.  (As a
+        // compare-and-swap the touch made the chain 34 us per batch instead of 21 at B = 2 048: the tables of 3 .. 30
+        // rows put every request of a batch on a handful of addresses, and same-address atomics take their turns.)
+        const unsigned c = pol_cnt(k.w);
+        sa_ways_ptr(g, k.set)[k.way] = pol_word(L, k.w & L.tag_mask, cur, c < kPolCntMax ? c + 1u : kPolCntMax, pol_sel(L, k.w));
+    }
+    return is_hit;
+}
 
 // K1: one 32-lane half-wave per request (T <= 32), one lane per key -- the set line (one 32-byte request), the hit ballot,
 // the touch (one 4-byte store where the way does not carry stamp n yet), the row id / address for the consumer, the miss
@@ -46,25 +73,12 @@ __global__ void __launch_bounds__(256) policy_probe_kernel(const PolicyArgs args
         const bool key_on = req_on && hl < T;
         const int row = key_on ? args.requests[req * T + hl] : -1;
         const bool ok = key_on && row >= 0 && row < s_rows[hl];
-        unsigned set = 0u, tag1 = 0u, w = 0u;
-        sa_split(g, sa_perm(args.sau, s_base[hl] + (ok ? (unsigned)row : 0u)), set, tag1);
-        if (!ok) set = 0u;
-        SaLine line;
-        sa_load<8>(g, set, line);
-        const int way = sa_find<8>(g, line, tag1, w);
-        const bool is_hit = ok && way >= 0;
+        PolKey key;
+        const bool is_hit = policy_probe_key(g, args.sau, L, cur, ok, s_base[hl] + (ok ? (unsigned)row : 0u), key);
+        const unsigned set = key.set, tag1 = key.tag1, w = key.w;
+        const int way = key.way;
         const unsigned long long hm = __ballot(is_hit);
         const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
-        if (is_hit && pol_last(L, w) != cur) {
-            // touch: last = n, LFU counter + 1 (saturating), ONCE per way and batch.  A plain store, no compare-and-swap:
-            // nothing but touches writes a way word during this launch, every lane that still reads the way's word of
-            // before the batch (stamp != n) derives the SAME new word from it, and a lane that reads the new word stores
-            // nothing -- so any number of writers, in any order and over stale copies, leave exactly that word.  (As a
-            // compare-and-swap the touch made the chain 34 us per batch instead of 21 at B = 2 048: the tables of 3 .. 30
-            // rows put every request of a batch on a handful of addresses, and same-address atomics take their turns.)
-            const unsigned c = pol_cnt(w);
-            sa_ways_ptr(g, set)[way] = pol_word(L, w & L.tag_mask, cur, c < kPolCntMax ? c + 1u : kPolCntMax, pol_sel(L, w));
-        }
         if (key_on) {
             const long long at = req * T + hl;
             args.hit[at] = is_hit ? 1 : 0;
@@ -96,6 +110,191 @@ __global__ void __launch_bounds__(256) policy_probe_kernel(const PolicyArgs args
     if (threadIdx.x < 2 && s_sum[threadIdx.x])
         atomicAdd(&args.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38 + threadIdx.x], s_sum[threadIdx.x]);
     if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
+}
+
+// K1 over ragged bags: one lane per POSITION of the flat, table-major lookup list (evs_cache_lookup_bags).  The lane's table
+// comes from the prefix sums of nnz (five steps over an LDS table); per position the int64 index, its range check, the set
+// line, the touch (policy_probe_key), then the hit flag, the 8-byte row address for the pooling kernel and -- for a miss --
+// the record policy_insert_kernel reads.  An index out of range is no key: flag 0, address 0, no record, the sticky flag.
+__global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
+    __shared__ int s_hits, s_list_n;
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32], s_pos0[32];
+    __shared__ const long long *s_idx[32];
+    __shared__ const unsigned char *s_table[32];
+    const PolicyArgs &pa = args.p;
+    const int T = pa.T;
+    if (threadIdx.x == 0) { s_hits = 0; s_list_n = 0; }
+    if (threadIdx.x < 32) {
+        const bool tab = (int)threadIdx.x < T;
+        s_base[threadIdx.x] = pa.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = tab ? pa.backing_rows[threadIdx.x] : 0;
+        s_table[threadIdx.x] = pa.backing[threadIdx.x];
+        s_idx[threadIdx.x] = args.indices[threadIdx.x];
+        s_pos0[threadIdx.x] = tab ? args.pos0[threadIdx.x] : args.n_pos;   // (past the last table: no position is that far)
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = p < args.n_pos;
+        // the table of position p: the largest k with pos0[k] <= p (pos0 never falls, so "pos0[j] <= p" holds for a prefix of j;
+        // a table without indices shares its start with the next one and is passed over)
+        int k = 0;
+#pragma unroll
+        for (int step = 16; step >= 1; step >>= 1) k += (on && s_pos0[k + step] <= p) ? step : 0;
+        const long long row = on ? s_idx[k][p - s_pos0[k]] : -1;
+        const bool ok = on && row >= 0 && row < s_rows[k];
+        bad = bad || (on && !ok);
+        PolKey key;
+        const bool is_hit = policy_probe_key(pa.sa, pa.sau, pa.lay, pa.cur, ok, s_base[k] + (ok ? (unsigned)row : 0u), key);
+        if (on) {
+            pa.hit[p] = is_hit ? 1 : 0;
+            const unsigned char *src = nullptr;
+            if (is_hit) src = pa.arena + (long long)sa_entry(pa.sa, key.set, (unsigned)key.way, key.w) * pa.row_bytes;
+            else if (ok) src = s_table[k] + row * pa.row_bytes;
+            pa.row_ptrs[p] = (long long)src;
+        }
+        const unsigned long long hm = __ballot(is_hit);
+        if (lane == 0 && hm) atomicAdd(&s_hits, __popcll(hm));
+        {   // the wave's misses, packed, behind the block's earlier ones
+            const bool is_miss = ok && key.way < 0;
+            const unsigned long long mm = __ballot(is_miss);
+            int base = 0;
+            if (lane == 0 && mm) base = atomicAdd(&s_list_n, __popcll(mm));
+            base = __shfl(base, 0, 64);
+            if (is_miss) {
+                const int at = base + __popcll(mm & ((1ull << lane) - 1ull));
+                if (at < pa.list_cap)
+                    pa.miss_rec[(long long)blockIdx.x * pa.list_cap + at] = make_uint4((unsigned)row, (unsigned)k, key.set, key.tag1);
+            }
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_hits) atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38], s_hits);
+        pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
+    }
+}
+
+// Pooling through the probe's pointer table (embedding_bag_sum_kernel's shape, evs_gather.hip): a lane group of d / 4 lanes
+// owns a bag, UNROLL bags in flight per group, the table id wave-uniform (per-table values from scalar loads), index order,
+// unfused fp32 adds from +0 -- and the row address read from the table instead of computed from an index: the probe has done
+// the range check (address 0: no row).  The bag bounds check and its error flag stay.  A group also tells its sample's word
+// (sample_cnt) what the bag was -- empty or not, all hits or not; whoever brings a sample's T-th bag judges the sample,
+// counts it into column 39 (all-hit requests) and leaves the word zero for the next launch.
+template <int CODEC, int UNROLL>
+__global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
+    __shared__ float s_lut[CodecLut<CODEC>::kEntries];
+    __shared__ int s_perfect;
+    if constexpr (CODEC != 32) codec_lut_init<CODEC>(s_lut);
+    if (threadIdx.x == 0) s_perfect = 0;
+    __syncthreads();
+    const int T = args.p.T;
+    const int LPR = args.d / 4;
+    const int RPW = kWave / LPR;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int slot = lane / LPR;
+    const int piece = lane - slot * LPR;
+    const bool lane_on = slot < RPW;
+    const long long B = args.p.B;
+    const int bags_per_item = RPW * UNROLL;
+    const unsigned char *arena = args.p.arena, *arena_end = args.arena_end;
+    const int64_t n_items = (int64_t)T * args.chunks_per_table;
+    const XcdRange xr = xcd_range(n_items, 4, wave);
+    bool bad = false;
+    int n_perfect = 0;
+
+    for (int64_t item = xr.first; item < xr.end; item += xr.stride) {
+        const int t = __builtin_amdgcn_readfirstlane((int)(item / args.chunks_per_table));
+        const long long chunk = item - (long long)t * args.chunks_per_table;
+        const long long b0 = chunk * bags_per_item;
+        const long long *__restrict__ off = args.offsets[t];
+        const long long nnz = args.pos0[t + 1] - args.pos0[t];
+        const long long *__restrict__ ptrs = args.p.row_ptrs + args.pos0[t];
+
+        long long s[UNROLL], len[UNROLL];
+        long long maxlen = 0;
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const long long b = b0 + (long long)u * RPW + slot;
+            s[u] = 0;
+            len[u] = 0;
+            if (lane_on && b < B) {
+                const long long st = off[b];
+                const long long en = (b + 1 < B) ? off[b + 1] : nnz;
+                if (st >= 0 && en >= st && en <= nnz) {
+                    s[u] = st;
+                    len[u] = en - st;
+                } else {
+                    bad = true;
+                }
+            }
+            maxlen = len[u] > maxlen ? len[u] : maxlen;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {   // wave-wide max bag length (all lanes run the same trip count)
+            const long long o = __shfl_xor(maxlen, m, kWave);
+            maxlen = o > maxlen ? o : maxlen;
+        }
+
+        float4 acc[UNROLL];
+        bool miss[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) { acc[u] = make_float4(0.f, 0.f, 0.f, 0.f); miss[u] = false; }
+
+        for (long long j = 0; j < maxlen; j++) {
+            const unsigned char *r[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                r[u] = nullptr;
+                if (j < len[u]) {
+                    r[u] = reinterpret_cast<const unsigned char *>(ptrs[s[u] + j]);
+                    miss[u] = miss[u] || !(r[u] >= arena && r[u] < arena_end);
+                }
+            }
+            float4 v[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (r[u]) v[u] = RowPiece<CODEC>::load(r[u], piece, s_lut);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                if (r[u]) {
+                    acc[u].x = __fadd_rn(acc[u].x, v[u].x);
+                    acc[u].y = __fadd_rn(acc[u].y, v[u].y);
+                    acc[u].z = __fadd_rn(acc[u].z, v[u].z);
+                    acc[u].w = __fadd_rn(acc[u].w, v[u].w);
+                }
+            }
+        }
+
+        float *__restrict__ out = args.out + (long long)t * args.out_tstride + (long long)piece * 4;
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const long long b = b0 + (long long)u * RPW + slot;
+            if (lane_on && b < B) {
+                *reinterpret_cast<float4 *>(out + b * args.out_bstride) = acc[u];
+                if (piece == 0) {
+                    const int mine = 1 | (len[u] > 0 ? 1 << 8 : 0) | (miss[u] ? 1 << 16 : 0);
+                    const int all = atomicAdd(&args.sample_cnt[b], mine) + mine;
+                    if ((all & 0xff) == T) {   // the sample's last bag: nobody else writes the word any more
+                        args.sample_cnt[b] = 0;
+                        if (((all >> 8) & 0xff) != 0 && (all >> 16) == 0) n_perfect++;
+                    }
+                }
+            }
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    if (n_perfect) atomicAdd(&s_perfect, n_perfect);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_perfect)
+        atomicAdd(&args.p.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 39], s_perfect);
 }
 
 struct NoTail {};
@@ -210,6 +409,27 @@ void insert_launch_t(const PolicyArgs &a, int grid, unsigned threads, hipStream_
 
 void policy_probe_launch(const PolicyArgs &a, int grid, hipStream_t st) {
     hipLaunchKernelGGL(policy_probe_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_probe_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st) {
+    constexpr int kUnroll = 4;   // bags in flight per lane group, as the uncached pooling keeps them
+    BagArgs args = a;
+    const int bags_per_item = (kWave / (a.d / 4)) * kUnroll;
+    args.chunks_per_table = (a.p.B + bags_per_item - 1) / bags_per_item;
+    const long long n_items = (long long)a.p.T * args.chunks_per_table;
+    long long blocks = (n_items + 3) / 4;
+    if (blocks > (long long)kNumCu * 8) blocks = (long long)kNumCu * 8;
+    blocks = round_up((int)blocks, kNumXcd);
+    switch (codec) {
+    case 32: hipLaunchKernelGGL((bags_pool_kernel<32, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
+    case 16: hipLaunchKernelGGL((bags_pool_kernel<16, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
+    case 8: hipLaunchKernelGGL((bags_pool_kernel<8, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
+    default: hipLaunchKernelGGL((bags_pool_kernel<4, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
+    }
 }
 
 // compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail)

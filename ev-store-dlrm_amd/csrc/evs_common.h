@@ -138,6 +138,39 @@ __device__ __forceinline__ float4 dec_chunk(unsigned w0, unsigned w1, const floa
     }
 }
 
+// 4 consecutive elements of a row -> float4 (the pooling kernels: evs_gather.hip, evs_cache_policy.hip)
+template <int CODEC>
+struct RowPiece;
+template <>
+struct RowPiece<32> {
+    static constexpr int kBytes = 16;
+    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *) {
+        return reinterpret_cast<const float4 *>(row)[piece];
+    }
+};
+template <>
+struct RowPiece<16> {
+    static constexpr int kBytes = 8;
+    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
+        const uint2 v = reinterpret_cast<const uint2 *>(row)[piece];  // 4 native-endian ushorts
+        return dec_chunk<16>(v.x, v.y, lut);
+    }
+};
+template <>
+struct RowPiece<8> {
+    static constexpr int kBytes = 4;
+    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
+        return dec_chunk<8>(reinterpret_cast<const unsigned *>(row)[piece], 0u, lut);
+    }
+};
+template <>
+struct RowPiece<4> {
+    static constexpr int kBytes = 2;
+    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
+        return dec_chunk<4>(reinterpret_cast<const unsigned short *>(row)[piece], 0u, lut);  // byte0 | byte1<<8
+    }
+};
+
 // XCD-aware split of `n_items` (ordered so that neighbours share data, e.g. table-major)
 // over the grid: blocks b and b+8 share an XCD (and its 4 MiB L2), so XCD x owns the
 // contiguous item range [x*n/8, (x+1)*n/8) and its blocks stride through it.

@@ -50,38 +50,7 @@ struct GatherArgs {
     const void *zeros;   // the zero page (rows-in-registers gather: what a lane reads for a bag that has no row)
 };
 
-template <int CODEC>
-struct RowPiece;  // 4 consecutive elements of a row -> float4
-
-template <>
-struct RowPiece<32> {
-    static constexpr int kBytes = 16;
-    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *) {
-        return reinterpret_cast<const float4 *>(row)[piece];
-    }
-};
-template <>
-struct RowPiece<16> {
-    static constexpr int kBytes = 8;
-    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
-        const uint2 v = reinterpret_cast<const uint2 *>(row)[piece];  // 4 native-endian ushorts
-        return dec_chunk<16>(v.x, v.y, lut);
-    }
-};
-template <>
-struct RowPiece<8> {
-    static constexpr int kBytes = 4;
-    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
-        return dec_chunk<8>(reinterpret_cast<const unsigned *>(row)[piece], 0u, lut);
-    }
-};
-template <>
-struct RowPiece<4> {
-    static constexpr int kBytes = 2;
-    __device__ static __forceinline__ float4 load(const void *row, int piece, const float *lut) {
-        return dec_chunk<4>(reinterpret_cast<const unsigned short *>(row)[piece], 0u, lut);  // byte0 | byte1<<8
-    }
-};
+// (RowPiece<CODEC>: 4 consecutive elements of a row -> float4, evs_common.h)
 
 // LPR = lanes per row (d = 4*LPR).  LPR_T > 0: compile-time, LPR_T == 0: runtime (args.d/4).
 template <int CODEC, int LPR_T, int UNROLL, bool BAG1>

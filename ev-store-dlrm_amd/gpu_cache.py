@@ -282,6 +282,66 @@ class GpuCache:
             out.data_ptr(), hit.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
         return hit, out
 
+    # ---- ragged bags through an 'lru' / 'lfu' tier (include/evstore_hip.h: evs_cache_lookup_bags) ----
+    def _bags_call(self, lS_o, lS_i):
+        """lS_o / lS_i as apply_emb takes them -- a (T, B) int64 tensor or a list of T 1-D int64 tensors, on the device ->
+        (B, the C arrays of the call, the flat flag tensor and its per-table views, what must stay alive)"""
+        T = self.n_tables
+        for name, t in (("lS_o", lS_o), ("lS_i", lS_i)):
+            if torch.is_tensor(t):
+                if not (t.dim() == 2 and t.shape[0] == T):
+                    raise ValueError("%s must be a (%d, n) tensor or a list of %d tensors, got %s" % (name, T, T, tuple(t.shape)))
+            elif len(t) != T:
+                raise ValueError("%s must hold %d tensors, got %d" % (name, T, len(t)))
+        lo, li = [lS_o[k] for k in range(T)], [lS_i[k] for k in range(T)]
+        for t in lo + li:
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and (t.numel() == 0 or t.stride(0) == 1)):
+                raise ValueError("offsets and indices must be 1-D int64 device tensors with unit stride")
+        B = int(lo[0].shape[0])
+        if any(int(t.shape[0]) != B for t in lo):
+            raise ValueError("every table needs %d bag offsets" % B)
+        nnz = [int(t.numel()) for t in li]
+        flat = torch.empty((sum(nnz),), dtype=torch.uint8, device=self.device)
+        hits = list(torch.split(flat, nnz))
+        idx_c = (C.c_void_p * T)(*[t.data_ptr() if t.numel() else None for t in li])
+        off_c = (C.c_void_p * T)(*[t.data_ptr() for t in lo])
+        nnz_c = (C.c_int64 * T)(*nnz)
+        return B, idx_c, off_c, nnz_c, flat, hits, (lo, li)
+
+    def lookup_bags(self, lS_o, lS_i, out=None):
+        """Multi-hot lookup on an 'lru' / 'lfu' tier: every position of every index array is one lookup of "the batched rule"
+        (flags = residency at arrival, one touch per way and batch, every distinct missed key inserted once), the bags pool the
+        served rows bit-equal to apply_emb over the backing tables (include/evstore_hip.h: evs_cache_lookup_bags).
+        -> (hits: T uint8 tensors, one flag per index, views of one flat array; ly: T (B, dim) fp32 tensors, views of one
+        (T, B, dim) block -- `out`, when given)."""
+        B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
+        T, d = self.n_tables, self.dim
+        if out is None:
+            out = torch.empty((T, B, d), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, B, d)):
+            raise ValueError("out must be a contiguous (%d, %d, %d) fp32 device tensor" % (T, B, d))
+        _lib.check(_lib.lib().evs_cache_lookup_bags(self._h, B, idx_c, off_c, nnz_c, out.data_ptr(), B * d, d, flat.data_ptr(),
+                                                    torch.cuda.current_stream(self.device).cuda_stream))
+        return hits, list(out.unbind(0))
+
+    def lookup_bags_interact(self, lS_o, lS_i, x, itself=False, out=None):
+        """R = interact_features(x, the T pooled bags of lookup_bags): probe, pooling into a (T, B, dim) block the cache owns,
+        the dense interaction, insert -- the rule and the flags of lookup_bags (include/evstore_hip.h:
+        evs_cache_lookup_bags_interact).  -> (hits as lookup_bags gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
+        B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
+        F = self.n_tables + 1
+        P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
+        if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (B, self.dim) and x.stride(1) == 1):
+            raise ValueError("x must be a (B, %d) fp32 device tensor with unit inner stride" % self.dim)
+        if out is None:
+            out = torch.empty((B, self.dim + P), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * (self.dim + P)):
+            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * (self.dim + P)))
+        _lib.check(_lib.lib().evs_cache_lookup_bags_interact(
+            self._h, B, idx_c, off_c, nnz_c, x.data_ptr(), int(x.stride(0)) if B > 1 else self.dim, int(bool(itself)),
+            out.data_ptr(), flat.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        return hits, out
+
     def batch_stats(self):
         """Counters of the batched path and the resident-entry histogram per priority.  An 'lru' / 'lfu' cache: n_flush stays
         0, n_perfect_hits counts all-hit requests, hist[0] = size and the rest 0."""
