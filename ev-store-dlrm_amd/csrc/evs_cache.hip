@@ -3955,7 +3955,13 @@ static int batch_state(evs_cache *c, hipStream_t st, const char *who) {
     const bool sa = resolved_batch_policy(c) == 2;   // set-associative policy: no hash, no entry arrays (the set records: c->sa)
     if (sa && !c->sa.tags) {   // (a tier that starts out in a pair got its geometry there: batch_c1c2_impl)
         if (!sa_single_feasible(c, &c->sau, &c->sa)) {
-            set_error("%s: the set-associative batch policy needs fewer than 2^32 rows over all tables and a capacity of at least rows / 2^19 entries", who);
+            // (sa_make_geom: tag + 1 in at most 22 bits, i.e. more than R / 2^22 sets)
+            if (c->host.policy != kEvLFU)
+                set_error("%s: the batched path of an %s cache is set-associative: it needs fewer than 2^32 rows over all tables and more than R / 2^22 sets of 8 "
+                          "entries, R the row total rounded up to a power of two (a capacity of at least R / 2^19 + 8 entries)", who, policy_name(c->host.policy));
+            else
+                set_error("%s: the set-associative batch policy needs fewer than 2^32 rows over all tables and more than R / 2^22 sets of 8 entries, R the row "
+                          "total rounded up to a power of two (a capacity of at least R / 2^19 + 8 entries)", who);
             return EVS_EINVAL;
         }
         const int arc = sa_alloc(c, nullptr, st);

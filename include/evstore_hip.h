@@ -429,8 +429,14 @@ EVS_API int evs_cache_lookup_batch(evs_cache *c, int64_t B, const int32_t *rows,
  *     can be retired by one of the batch's own inserts before a later block looks for it.  So under this form a hit flag
  *     says "served from the cache": flag = 1 => the key was resident when the batch arrived (always); flag = 0 => it was not,
  *     OR one of this batch's inserts retired it first (at most as many keys as the batch evicted; the row is then served from
- *     the table, exact as ever, and the key is inserted again like any other miss).  Keys inserted by batch k are hits from
- *     batch k + 1 on.  Everything listed under "WHAT IS THE SAME" below holds unchanged.  EVS_CACHE_INLINE=0 (environment)
+ *     the table, exact as ever, and the key is inserted again like any other miss), OR its way was FILLED k 2^S batches ago,
+ *     k >= 1: the stamp is the batch number modulo 2^S (S = 26 - 1 - tag bits), so such a way carries the running batch's
+ *     stamp and is hidden from this launch's probers like one the batch filled itself.  The row is served from the table,
+ *     exact as ever; the request's agg_hit does not count the key; the insert that follows the miss finds the key in its set
+ *     and leaves the way as it is (priority folded, stamp unchanged), so the key is hidden again 2^S batches later.  The form
+ *     is taken only with S >= 8: a resident key is hidden in one batch of 2^S, those whose number shares the residue of the
+ *     batch that filled it -- at most one lookup in 256.  Keys inserted by batch k are hits from batch k + 1 on (batches
+ *     k + j 2^S excepted).  Everything listed under "WHAT IS THE SAME" below holds unchanged.  EVS_CACHE_INLINE=0 (environment)
  *     keeps the update as a launch of its own behind the probe: strict snapshot flags, as evs_cache_lookup_batch always has.
  *     (A single reduced-precision tier -- codec 16 / 8 / 4, d in {16, 32, 36} -- takes the same one-launch form.)
  *     A C1 + C2 pair that starts out together SHARES its set records: one
@@ -466,6 +472,10 @@ EVS_API int evs_cache_lookup_batch(evs_cache *c, int64_t B, const int32_t *rows,
  * 8 tag bits) has S = 23 under LRU and S = 17 under LFU.  Ages are CIRCULAR, age = (n - last) mod 2^S:
  * LRU orders correctly any two ways both touched within the last 2^S - 1 batches (a way left alone for longer looks
  * younger than it is; one whose `last` equals n modulo 2^S looks touched by the running batch and is passed over once).
+ * The same reading holds in step 2 below: a HIT on a way whose `last` equals n modulo 2^S -- last touched k 2^S batches ago
+ * -- finds the way stamped n already and leaves `last` and, under LFU, the counter as they are (one count lost per 2^S batches
+ * of silence, the flag and the served row unaffected); and in step 3 a set whose other ways were all touched by batch n
+ * turns a new key away although that way is stale.  S >= 4 always; the Kaggle tiers above wrap every 2^17 batches (LFU).
  * THE BATCHED RULE.  n = the cache's batch number (1, 2, ...).  One call (evs_cache_lookup_batch / _lookup_interact) does:
  *   1. probe (snapshot): hit[b, t] = 1 exactly when key (t + 1, rows[b, t]) was resident when the call started.  Served rows
  *      are exactly the table rows (R: the usual float64-scaled bound).
@@ -486,7 +496,9 @@ EVS_API int evs_cache_lookup_batch(evs_cache *c, int64_t B, const int32_t *rows,
  * evs_cache_lookup_interact on such a tier always runs probe, the row-id / pointer-table interaction consumer and insert as
  * three launches (strict snapshot flags); evs_cache_set_inline_update(c, 1) is refused (EVS_EINVAL), on = 0 accepted.  Also
  * refused, with a message that names the policy and the cache left usable: host-memory or file-backed tables (EVS_ESTATE), a
- * capacity below 8, 2^32 rows or more over all tables, the tier as a member of a C1 + C2 (+ C3) lookup (EVS_EINVAL). */
+ * capacity below 8, 2^32 rows or more over all tables, R / 2^22 sets or fewer with R the row total rounded up to a power of two
+ * (the tag would leave the stamp fewer than 4 bits; an EvLFU cache that was given no policy resolves to policy 1 there, an
+ * explicit policy 2 is refused the same way), the tier as a member of a C1 + C2 (+ C3) lookup (EVS_EINVAL). */
 EVS_API int evs_cache_set_batch_policy(evs_cache *c, int policy);
 /* Batched two-tier lookup, snapshot semantics: the throughput form of evs_cache_request_c1c2 (no reference
  * counterpart).  Every key is probed in C1, then in C2, against the tiers as they stand when the call starts;
@@ -575,7 +587,7 @@ EVS_API int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int64_
                                            int itself, float *R, uint8_t *hit, void *stream);
 /* The one-launch form of a set-associative tier (round 5: the policy update runs INSIDE evs_cache_lookup_interact's probe +
  * interaction launch; a hit flag then says "served from the cache": 1 => resident at arrival, 0 => not resident OR retired
- * by one of this batch's own inserts) is the default wherever its conditions hold (a tier alone, 8 ways, two-copy arena, at
+ * by one of this batch's own inserts OR resident in a way filled k 2^S batches ago, see evs_cache_set_batch_policy) is the default wherever its conditions hold (a tier alone, 8 ways, two-copy arena, at
  * least 8 stamp bits in the way word).  on = 0 restores the two-launch chain with strict snapshot flags for this cache, on = 1
  * the default; the environment variable EVS_CACHE_INLINE=0 only changes the default of caches that were never told.  May be
  * called between batches.  LRU / LFU caches have the chain only: on = 1 is refused (EVS_EINVAL), on = 0 accepted. */

@@ -27,6 +27,7 @@ class BagPolicyModel(M.BatchedPolicyModel):
     def batch_keys(self, keys):
         """one call over a position-ordered list of (table_1based, row) -> bool flags, one per position"""
         self.n += 1
+        cur = self._cur()
         flags = np.zeros(len(keys), bool)
         missed, seen = [], set()
         for p, key in enumerate(keys):
@@ -40,9 +41,12 @@ class BagPolicyModel(M.BatchedPolicyModel):
         for p in np.nonzero(flags)[0]:                      # touch: once per way and batch
             s, j = self.where[keys[p]]
             w = self.sets[s][j]
-            if w[2] != self.n:
-                w[2] = self.n
+            if w[2] != cur:
+                w[2] = cur
                 w[1] = w[1] + 1 if self.cnt_max is None else min(w[1] + 1, self.cnt_max)
+            elif w[3] != self.n and self.policy == "lfu" and (self.cnt_max is None or w[1] < self.cnt_max):
+                self.events["count_skipped"] += 1           # (only with stamp_bits, as in BatchedPolicyModel.batch)
+            w[3] = self.n
         if missed:                                          # insert: every distinct missed key once
             sets = M.set_of([t - 1 for t, _ in missed], [r for _, r in missed], self.nset, self.n_rows, self.bits)
             for key, s in zip(missed, sets):
@@ -53,7 +57,7 @@ class BagPolicyModel(M.BatchedPolicyModel):
                 if ways[j] is not None:
                     del self.where[ways[j][0]]
                     self.n_evict += 1
-                ways[j] = [key, 1, self.n]
+                ways[j] = [key, 1, cur, self.n]           # [key, counter, last, true_last], BatchedPolicyModel's ways
                 self.where[key] = (int(s), j)
         return flags
 

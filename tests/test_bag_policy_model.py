@@ -18,9 +18,14 @@ def _stream(policy, shape):
     return BM.conflict_free_bag_stream(policy, shape[0], N_ROWS, shape[1], shape[2], shape[3], 3)
 
 
+@functools.lru_cache(maxsize=None)
+def _rect_stream():
+    return M.conflict_free_stream("lfu", 512, N_ROWS, 4, 100, 3)
+
+
 def test_one_index_per_bag_is_the_rectangular_rule():
     """every bag of size 1: batch_keys gives the flags, the resident set and n_evict of BatchedPolicyModel.batch"""
-    reqs, hits, want = M.conflict_free_stream("lfu", 512, N_ROWS, 4, 100, 3)
+    reqs, hits, want = _rect_stream()
     m = BM.BagPolicyModel("lfu", 512, N_ROWS)
     ref = M.BatchedPolicyModel("lfu", 512, N_ROWS)
     for i in range(len(reqs)):
@@ -38,6 +43,28 @@ def test_one_index_per_bag_is_the_rectangular_rule():
         assert np.array_equal(np.stack(flags, 1), hits[i])
     assert m.n_requests == hits.shape[0] * hits.shape[1] and m.n_hits == int(hits.sum())
     assert m.n_perfect == int(hits.all(2).sum())
+
+
+@pytest.mark.parametrize("stamp_bits", [None, 3])
+@pytest.mark.parametrize("policy", ["lru", "lfu"])
+def test_the_two_forms_alternate_on_one_model(policy, stamp_bits):
+    """batch and batch_keys keep one model's ways in one layout: alternating them call by call (one index per bag) gives
+    the flags, the resident set, the scores and the event counts of batch alone -- with plain batch numbers and with a
+    3-bit stamp that wraps every 8 calls"""
+    reqs = _rect_stream()[0]         # (LFU's conflict-free stream; LRU replays the same requests)
+    m = BM.BagPolicyModel(policy, 512, N_ROWS, stamp_bits=stamp_bits)
+    ref = M.BatchedPolicyModel(policy, 512, N_ROWS, stamp_bits=stamp_bits)
+    for i in range(len(reqs)):
+        B, T = reqs[i].shape
+        want = ref.batch(reqs[i])
+        if i % 3 == 1:
+            flags = m.batch(reqs[i])
+        else:
+            # (positions in batch's own order: under LRU or the wrapping stamp the stream need not stay conflict-free)
+            flags = m.batch_keys([(t + 1, int(reqs[i][b, t])) for b in range(B) for t in range(T)]).reshape(B, T)
+        assert np.array_equal(flags, want), "call %d" % i
+        assert m.resident() == ref.resident() and m.sets == ref.sets and m.events == ref.events, "call %d" % i
+    assert ref.n_evict > 0 and m.n_evict == ref.n_evict
 
 
 @pytest.mark.parametrize("shape", SHAPES)

@@ -100,6 +100,92 @@ def test_policy_pinned_on_conflict_free_streams(E, policy, shape, codec):
     assert model.n_evict > 10 * cap
 
 
+# ------------------------------------------------------------------------------------------- 1b. policy pinned across wraps
+@pytest.fixture(scope="module")
+def wrap_tables():
+    """(geometry, codec) -> the tables of one of M.WRAP_GEOMETRIES, filled on the device: fp32 uniform in (-1, 1), or raw
+    random bytes for a codec-8 tier.  Kept for the module, freed behind it."""
+    made = {}
+
+    def get(geom, codec):
+        if (geom, codec) not in made:
+            n_rows = M.WRAP_GEOMETRIES[geom][1]
+            g = torch.Generator(device="cuda")
+            g.manual_seed(len(geom) + codec)
+            if codec == 32:
+                made[geom, codec] = [torch.empty(n, 36, device="cuda").uniform_(-1, 1, generator=g) for n in n_rows]
+            else:
+                made[geom, codec] = [torch.randint(0, 256, (n, 36), dtype=torch.uint8, device="cuda", generator=g) for n in n_rows]
+        return made[geom, codec]
+    yield get
+    made.clear()
+
+
+@functools.lru_cache(maxsize=None)
+def _wrap_case(policy, geom):
+    return M.wrap_case(policy, geom)
+
+
+@pytest.mark.parametrize("policy,geom,codec,bags", [("lfu", "tiny", 32, False), ("lfu", "tiny-dual", 32, True), ("lru", "tiny", 32, False),
+                                                    ("lru", "tiny-dual", 32, False), ("lfu", "tiny-dual", 8, False)])
+def test_policy_pinned_across_stamp_wraps(E, orc, wrap_tables, policy, geom, codec, bags):
+    """Two sets of eight ways under a key universe of 2^22 / 2^19 rows: the tag leaves the batch stamp S = 4 / 6 bits under
+    LFU and 10 / 12 under LRU (asserted: M.stamp_bits_of restates sa_make_geom), so a run of a few hundred batches wraps it
+    many times.  M.wrap_stream leaves ways alone for 2^S batches and longer, re-hits them exactly 2^S batches after their
+    last touch and brings new keys to sets whose only stale way is such a lapped one; the modular model
+    (BatchedPolicyModel(stamp_bits=S)) says what "ages are CIRCULAR" of include/evstore_hip.h then means, and the cache is
+    held to it after EVERY batch: hit flags, rows bit-equal to the table rows, the dump's keys and scores (LRU: the circular
+    age), the statistics.  The stream parts from a plain-integer model (asserted from its event counts, as
+    tests/test_batched_policy_model.py asserts them), so a geometry change cannot turn this back into a no-wrap run.
+    LRU on `tiny-dual` (S = 12) does not wrap in 640 batches: there `last` carries from its 6-bit low field into the high
+    one, across the copy-select bit, ten times while replacements flip that bit.  bags: every third batch goes through
+    lookup_bags with one index per bag -- the two forms share the batch counter and count alike, the model is unchanged."""
+    cap, n_rows, S = M.WRAP_GEOMETRIES[geom]
+    S, T = S[policy], len(n_rows)
+    assert M.stamp_bits_of(policy, cap, n_rows)[2] == S == {("lfu", "tiny"): 4, ("lfu", "tiny-dual"): 6, ("lru", "tiny"): 10,
+                                                            ("lru", "tiny-dual"): 12}[policy, geom]
+    batches, hits, _, parted = _wrap_case(policy, geom)
+    n_batches = len(batches)
+    if (policy, geom) == ("lru", "tiny-dual"):
+        assert n_batches >= 600 and n_batches >> 6 >= 9 and parted["evictions"] >= 36
+    else:
+        assert n_batches >= (3 if policy == "lfu" else 2.5) * (1 << S)
+        kinds = [k for k in M.EVENTS if policy == "lfu" or k != "count_skipped"]
+        assert all(parted[k] >= 5 for k in kinds) and parted["flags"] >= 5 and parted["dumps"] >= 5, parted
+    dev = wrap_tables(geom, codec)
+    # the reference rows of the whole stream: the requested rows gathered on the device and copied back, once
+    flat = np.concatenate(batches)
+    rows = [dev[t][_dev(flat[:, t].astype(np.int64))].cpu().numpy() for t in range(T)]
+    if codec != 32:
+        rows = [orc.decode(a, codec, 36) for a in rows]
+    want_rows = np.stack(rows, 1)                              # (all samples, T, 36)
+    c = E.GpuCache(policy, cap, T, 36, codec)
+    c.set_backing(dev)
+    model = M.BatchedPolicyModel(policy, cap, n_rows, stamp_bits=S)
+    arange = [_dev(np.arange(b, dtype=np.int64)) for b in range(5)]
+    at = n_hits = n_req = 0
+    for i, rq in enumerate(batches):
+        B = len(rq)
+        if bags and i % 3 == 2:
+            hit, out = c.lookup_bags([arange[B]] * T, [_dev(rq[:, t].astype(np.int64)) for t in range(T)])
+            hit, out = torch.stack(hit, 1), torch.stack(out, 1)
+        else:
+            hit, out = c.lookup_batch(_dev(rq))
+        want = model.batch(rq)
+        assert np.array_equal(want, hits[i])
+        hit = hit.cpu().numpy().astype(bool)
+        assert np.array_equal(hit, want), "batch %d (cur = %d): flags\n%s\nthe model's\n%s" % (i + 1, model._cur(), hit, want)
+        assert np.array_equal(out.cpu().numpy().view(np.uint32), want_rows[at:at + B].view(np.uint32)), "batch %d: rows" % (i + 1)
+        at, n_hits, n_req = at + B, n_hits + int(hit.sum()), n_req + B
+        assert _dump(c) == model.resident(), "batch %d (cur = %d): resident set / scores" % (i + 1, model._cur())
+        if i % 25 == 0 or i == n_batches - 1:
+            st = c.batch_stats()
+            assert st["size"] == model.size() <= cap and st["n_hits"] == n_hits and st["n_requests"] == n_req
+            assert st["n_flush"] == 0 and st["n_evict"] == model.n_evict
+            assert st["hist"] == [st["size"]] + [0] * T
+    assert model.events == {k: parted[k] for k in M.EVENTS}
+
+
 # ------------------------------------------------------------------------------------------------------ 2. contended batches
 def _zipf_requests(n_rows, n_req, seed, alpha=1.15):
     """(tests/test_gpu_cache.py: _zipf_requests, restated)"""
@@ -304,6 +390,56 @@ def test_refusals_leave_the_cache_serving(E, orc, policy, tmp_path):
     _refused(E, L.EVS_EINVAL, policy, lambda: gpu_cache.lookup_interact_c1c2(e, c2, rq, x))
     _serves(c1, tabs, n_rows)
     _serves(c2, tabs, n_rows)
+
+
+def _serves_exact(c, dev, n_rows, seed):
+    rs = np.random.RandomState(seed)
+    rq = np.stack([rs.randint(0, 2, 5) for _ in n_rows], 1).astype(np.int32)
+    for _ in range(2):
+        hit, out = c.lookup_batch(_dev(rq))
+        out = out.cpu().numpy()
+        for t in range(rq.shape[1]):
+            want = dev[t][_dev(rq[:, t].astype(np.int64))].cpu().numpy()
+            assert np.array_equal(out[:, t].view(np.uint32), want.view(np.uint32))
+    return hit.cpu().numpy()
+
+
+def test_one_set_under_23_tag_bits_is_where_the_form_ends(E, wrap_tables):
+    """The `tiny` tables (2^22 keys) with capacity 8 are one set: tag + 1 needs 23 bits and the way word has no room for a
+    stamp of 4 (sa_make_geom).  An explicit "setassoc" on an EvLFU cache is refused (EVS_EINVAL) at the first batched call;
+    an EvLFU cache that was given no policy resolves to another form and serves exact rows; LRU / LFU have no other form: refused
+    with a message that names the policy, and served once set_backing brings smaller tables.  Capacity 16 is served by all."""
+    L = E._lib
+    _, n_rows, _ = M.WRAP_GEOMETRIES["tiny"]
+    T = len(n_rows)
+    dev = wrap_tables("tiny", 32)
+    small = [t[:1000] for t in dev]
+    with pytest.raises(ValueError):
+        M.stamp_bits_of("evlfu", 8, n_rows)
+    rq = _dev(np.zeros((2, T), np.int32))
+    c = E.GpuCache("evlfu", 8, T, 36, 32, "python").set_batch_policy("setassoc")
+    c.set_backing(dev)
+    with pytest.raises(L.EvsError) as ei:
+        c.lookup_batch(rq)
+    assert ei.value.code == L.EVS_EINVAL and "set-associative" in str(ei.value)
+    c = E.GpuCache("evlfu", 8, T, 36, 32, "python")
+    c.set_backing(dev)
+    assert _serves_exact(c, dev, n_rows, 0).mean() > 0.5                 # (the second call finds what the first one inserted)
+    for policy in ("lru", "lfu"):
+        c = E.GpuCache(policy, 8, T, 36, 32)
+        c.set_backing(dev)
+        with pytest.raises(L.EvsError) as ei:
+            c.lookup_batch(rq)
+        assert ei.value.code == L.EVS_EINVAL and policy in str(ei.value), str(ei.value)
+        c.set_backing(small)
+        assert _serves_exact(c, small, [1000] * T, 1).mean() > 0.5
+    for policy in ("evlfu", "lru", "lfu"):
+        assert M.stamp_bits_of(policy, 16, n_rows)[:2] == (22, 0)
+        c = E.GpuCache(policy, 16, T, 36, 32)
+        if policy == "evlfu":
+            c.set_batch_policy("setassoc")
+        c.set_backing(dev)
+        assert _serves_exact(c, dev, n_rows, 2).mean() > 0.5
 
 
 # ----------------------------------------------------------------------------------------------------------- 5. row updates
