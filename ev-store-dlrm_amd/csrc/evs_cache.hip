@@ -3261,6 +3261,9 @@ struct evs_cache {
     void *slab_bags = nullptr;
     long long bag_max_pos = -1, bag_max_b = 0;
     long long *bag_ptrs = nullptr; unsigned char *bag_hit = nullptr; uint4 *bag_rec = nullptr; int *bag_list_cnt = nullptr, *bag_sample = nullptr;
+    // ... and for EvLFU under the "served bags" rule: the probe's record per position, the position -> sample map, a count per sample
+    uint4 *bag_prov = nullptr; int *bag_pos_sample = nullptr, *bag_agg = nullptr;
+    int bag_rule = 0;           // evs_cache_set_bag_rule: 0 none (an EvLFU cache has no bag form), 1 "served bags"
     float *bag_pool = nullptr; long long bag_pool_floats = 0;
     int used = 0;  // 0 fresh, 1 exact path, 2 batched path
     int *estamp = nullptr;      // allocated when the backing tables live in host memory
@@ -3577,6 +3580,18 @@ extern "C" int evs_cache_set_inline_update(evs_cache *c, int on) {
     EVS_REQUIRE(on == 0 || c->host.policy == kEvLFU, "evs_cache_set_inline_update: the one-launch form is EvLFU's; an %s cache runs probe, consumer and insert as launches of their own",
                 policy_name(c->host.policy));
     c->inline_mode = on;
+    return EVS_OK;
+}
+
+// What a sample's hit count is over ragged bags (an EvLFU cache's priority is that count): 0 none -- the bag entry points
+// refuse an EvLFU cache --, 1 "served bags" (the rule: include/evstore_hip.h at evs_cache_lookup_bags).  May be set between calls.
+extern "C" int evs_cache_set_bag_rule(evs_cache *c, int rule) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_set_bag_rule: NULL cache");
+    EVS_REQUIRE(rule == 0 || rule == 1, "evs_cache_set_bag_rule: rule %d on an %s cache (0 none, 1 \"served bags\")", rule, policy_name(c->host.policy));
+    EVS_REQUIRE(rule == 0 || c->host.policy == kEvLFU, "evs_cache_set_bag_rule: an %s cache takes ragged bags as they are (one touch per way and batch); "
+                "the \"served bags\" count is the evlfu priority's", policy_name(c->host.policy));
+    c->bag_rule = rule;
     return EVS_OK;
 }
 
@@ -4966,9 +4981,11 @@ extern "C" int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t 
     return cache_batch_impl(c, B, rows, nullptr, hit, x, x_stride, itself, R, stream);
 }
 
-// ---- ragged bags through an LRU / LFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) -----------------------
+// ---- ragged bags through an LRU / LFU / EvLFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) ---------------
 // probe + touch over the flat position list -> pooling through the pointer table (-> the dense interaction) -> the insert
 // kernel of the (B, T) chain, unchanged, on one stream: the consumers read before the insert moves anything.
+// EvLFU ("served bags", evs_cache_set_bag_rule): probe without a touch -> pooling, which also counts every sample's served
+// bags -> (the dense interaction) -> raise + list -> the set-associative update of the (B, T) chain (cache_batch_sa_list_kernel).
 static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
                            float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, int itself,
                            float *R, uint8_t *hit, void *stream, const char *who) {
@@ -4996,9 +5013,31 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     if (interact)
         EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
                     who, EVS_MAX_FEATURES, T, d);
-    EVS_REQUIRE(c->host.policy != kEvLFU, "%s: an %s cache has no bag form (its priority counts a request's hit keys); lru / lfu caches take ragged bags",
-                who, policy_name(c->host.policy));
+    const bool evlfu = c->host.policy == kEvLFU;
+    EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule says what a request's hit count is over bags "
+                "(its priority counts a request's hit keys); lru / lfu caches take ragged bags as they are", who, policy_name(c->host.policy));
     { const int rc = batch_check(c, who); if (rc) return rc; }
+    if (evlfu) {   // the set-associative tier alone, 8 ways, tables in HBM: refused before anything is allocated
+        const char *pn = policy_name(c->host.policy);
+        if (c->host_backing || c->ft) {
+            set_error("%s: the bag form of an %s cache reads its tables in place from HBM (no host-memory / file-backed tables)", who, pn);
+            return EVS_ESTATE;
+        }
+        // (a refusal leaves the cache as it was: a policy that was only resolved here, not given, is forgotten again -- other
+        //  tables may resolve differently)
+        const int given = c->batch_policy;
+        const int bp = resolved_batch_policy(c);
+        const bool alone8 = c->sa.tags ? (c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u) : sa_single_ways() == 8u;
+        if (bp != 2 || !alone8) {
+            c->batch_policy = given;
+            if (bp != 2)
+                set_error("%s: the bag form of an %s cache is the set-associative tier's (batch policy 2); this cache's batch policy is %s", who, pn,
+                          bp == 0 ? "plan" : "sampled");
+            else
+                set_error("%s: the bag form of an %s cache needs a tier alone with sets of 8 ways", who, pn);
+            return EVS_EINVAL;
+        }
+    }
     const int piece_bytes = c->host.codec / 2;   // what a lane reads of a row at once: 16 / 8 / 4 / 2 bytes
     for (int k = 0; k < T; k++)
         EVS_REQUIRE(reinterpret_cast<uintptr_t>(c->backing[k]) % piece_bytes == 0, "%s: table %d is not %d-byte aligned", who, k, piece_bytes);
@@ -5019,6 +5058,8 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         const long long n_rec = np <= 256ll * kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * kProbeGridMax;
         sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, n_rec * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
         sp.add(&sample, nb * 4);
+        uint4 *prov = nullptr; int *pos_sample = nullptr, *agg = nullptr;
+        if (evlfu) { sp.add(&prov, np * 16); sp.add(&pos_sample, np * 4); sp.add(&agg, nb * 4); }
         if (!sp.carve(&slab)) { set_error("%s: allocating the buffers of a call of %lld lookups failed", who, n_pos); return EVS_ENOMEM; }
         if (c->slab_bags) {
             EVS_HIP_CHECK(hipStreamSynchronize(st));
@@ -5026,6 +5067,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         }
         c->slab_bags = slab;
         c->bag_ptrs = ptrs; c->bag_hit = flags; c->bag_rec = rec; c->bag_list_cnt = cnt; c->bag_sample = sample;
+        c->bag_prov = prov; c->bag_pos_sample = pos_sample; c->bag_agg = agg;
         c->bag_max_pos = np; c->bag_max_b = nb;
         EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
     }
@@ -5048,8 +5090,15 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     BagArgs a;
     PolicyArgs &pa = a.p;
     pa.sa = c->sa; pa.sau = c->sau;
-    pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
-    pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    pa.lay = PolLayout{}; pa.cur = 0u;
+    int stamp = 0;
+    if (evlfu) {   // the (B, T) chain's batch stamp, and the flush the close of an earlier batch asked for: before this batch's probe
+        stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;
+        sampled_flush_if_wanted(c, st);
+    } else {
+        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    }
     pa.requests = nullptr; pa.hit = hit ? hit : c->bag_hit; pa.row_ptrs = c->bag_ptrs; pa.row_ids = nullptr;
     pa.miss_rec = c->bag_rec; pa.list_cnt = c->bag_list_cnt; pa.list_cap = (int)(iters * 256);
     pa.part1 = c->part1; pa.part2 = c->part2;
@@ -5066,6 +5115,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
     a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
     a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
+    a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
 
     if (grid) bags_probe_launch(a, (int)grid, st);
     bags_pool_launch(a, c->host.codec, st);
@@ -5077,7 +5127,21 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
         if (rc) return rc;   // (nothing is inserted: the touches stand, as after any launch failure behind the probe)
     }
-    if (grid) policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
+    if (grid && evlfu) {
+        // every sample's count is known: the hit ways go up, the misses are listed with their counts, and the (B, T) chain's
+        // update inserts them -- priorities read after all raises, the launches in stream order
+        bags_raise_list_launch(a, (int)grid, st);
+        BatchArgs u{};
+        u.bs = c->bs; u.a = c->a; u.sa = c->sa; u.sau = c->sau; u.stamp = stamp; u.tomb_parity = -1;
+        for (int k = 0; k < kMaxTables; k++) { u.backing[k] = c->backing[k]; u.backing_rows[k] = c->backing_rows[k]; }
+        u.B = B; u.cap = (int)c->host.cap; u.T = T; u.d = d; u.codec = c->host.codec; u.row_bytes = c->host.row_bytes;
+        u.max_perfect = c->host.max_perfect; u.flush_n = c->host.flush_n;
+        u.part1 = c->part1; u.part2 = c->part2; u.host_tomb = c->host_tomb_dev;
+        u.miss_rec = c->bag_rec; u.list_cnt = c->bag_list_cnt; u.list_cap = pa.list_cap; u.g1 = (int)grid;
+        launch_sa_update(u, st);
+    } else if (grid) {
+        policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
+    }
     c->pending_batches++; c->pending_requests += B;
     if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
     EVS_HIP_CHECK(hipGetLastError());

@@ -85,11 +85,24 @@ struct BagArgs {
     int *sample_cnt;                       // B words, zero between launches: bags seen | bags with a lookup << 8 | bags with a miss << 16
     long long chunks_per_table;
     int d;
+    // EvLFU under the "served bags" rule (evlfu != 0; include/evstore_hip.h at evs_cache_lookup_bags): p.sa / p.sau are used as
+    // above, p.lay and p.cur are not (the way words are evs_hash.h's: priority | filling batch | tag).  A sample's count is known
+    // only when all its bags have been judged, so the probe leaves a provisional record per position, the pooling writes the
+    // counts and the position -> sample map, and a third launch raises the hit ways and lists the misses:
+    int evlfu;
+    uint4 *prov;                           // n_pos records: (row, table, set, bit 31 | hit way -- or tag + 1 of a miss -- or 0: no key)
+    int *pos_sample;                       // n_pos words: the sample whose bag covers the position (-1: no valid bag does)
+    int *agg;                              // B words: the sample's served bags (0 .. T)
 };
-// probe + touch over the flat position list: grid blocks of 256 threads, one lane per position; writes miss list j (records as above)
+// probe over the flat position list: grid blocks of 256 threads, one lane per position.  LRU / LFU: probe + touch, writes miss
+// list j (records as above).  EvLFU: no way word is written; writes prov and presets pos_sample to -1
 void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st);
 // pooled[k][b] = sum over the bag's positions of the rows the probe's pointer table names (d % 4 == 0, d <= 256); counts the
-// all-hit samples into column 39
+// all-hit samples into column 39.  EvLFU: also agg and pos_sample
 void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st);
+// EvLFU, behind the pooling: one lane per position (the probe's grid) -- every hit way to max(old, agg of the position's
+// sample) with the histogram moves into part1 columns 0 .. T, every miss into list j as (row, table | agg << 8, set, tag + 1),
+// the record cache_batch_sa_list_kernel (evs_cache.hip) reads
+void bags_raise_list_launch(const BagArgs &a, int grid, hipStream_t st);
 
 }  // namespace evs

@@ -11,6 +11,9 @@
 //     ends after at most 8 rounds.
 // Ragged bags (evs_cache_lookup_bags; the rule: include/evstore_hip.h there) run the same chain with a probe over the flat
 // list of index positions and a pooling kernel as the consumer:  bags_probe -> bags_pool (-> dense interaction) -> insert.
+// EvLFU under the "served bags" rule runs  bags_probe (no touch) -> bags_pool (+ the samples' counts) (-> dense interaction) ->
+// bags_raise_list -> cache_batch_sa_list_kernel (evs_cache.hip): a sample's count exists only after the pooling has seen all
+// its bags, so the raises and the miss lists come from a launch of their own behind it.
 #include <type_traits>
 
 #include "evs_cache_policy.h"
@@ -20,7 +23,9 @@ namespace {
 
 // One key against its set, shared by the two probe kernels: the set line (one 32-byte request), the way that holds the key
 // and the touch.  gid: the key's dense row number (anything in range when !ok: the lane then reads set 0 and hits nothing).
+// TOUCH = false (EvLFU bags): the way words are left alone and L / cur are not read.
 struct PolKey { unsigned set, tag1, w; int way; };
+template <bool TOUCH = true>
 __device__ __forceinline__ bool policy_probe_key(const SaGeom &g, const SaUniverse &u, const PolLayout &L, unsigned cur, bool ok, unsigned gid,
                                                  PolKey &k) {
     k.set = 0u; k.tag1 = 0u; k.w = 0u;
@@ -30,7 +35,7 @@ __device__ __forceinline__ bool policy_probe_key(const SaGeom &g, const SaUniver
     sa_load<8>(g, k.set, line);
     k.way = sa_find<8>(g, line, k.tag1, k.w);
     const bool is_hit = ok && k.way >= 0;
-    if (is_hit && pol_last(L, k.w) != cur) {
+    if (TOUCH && is_hit && pol_last(L, k.w) != cur) {
         // touch: last = n, LFU counter + 1 (saturating), ONCE per way and batch.  A plain store, no compare-and-swap:
         // nothing but touches writes a way word during this launch, every lane that still reads the way's word of
         // before the batch (stamp != n) derives the SAME new word from it, and a lane that reads the new word stores
@@ -116,6 +121,9 @@ __global__ void __launch_bounds__(256) policy_probe_kernel(const PolicyArgs args
 // comes from the prefix sums of nnz (five steps over an LDS table); per position the int64 index, its range check, the set
 // line, the touch (policy_probe_key), then the hit flag, the 8-byte row address for the pooling kernel and -- for a miss --
 // the record policy_insert_kernel reads.  An index out of range is no key: flag 0, address 0, no record, the sticky flag.
+// EVLFU: no touch and no list -- a provisional record per position for bags_raise_list_kernel (the hit way, or the set and the
+// tag of a miss: nothing is searched twice) and pos_sample preset to "no bag covers it".
+template <bool EVLFU>
 __global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
     __shared__ int s_hits, s_list_n;
     __shared__ unsigned s_base[32];
@@ -148,17 +156,21 @@ __global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
         const bool ok = on && row >= 0 && row < s_rows[k];
         bad = bad || (on && !ok);
         PolKey key;
-        const bool is_hit = policy_probe_key(pa.sa, pa.sau, pa.lay, pa.cur, ok, s_base[k] + (ok ? (unsigned)row : 0u), key);
+        const bool is_hit = policy_probe_key<!EVLFU>(pa.sa, pa.sau, pa.lay, pa.cur, ok, s_base[k] + (ok ? (unsigned)row : 0u), key);
         if (on) {
             pa.hit[p] = is_hit ? 1 : 0;
             const unsigned char *src = nullptr;
             if (is_hit) src = pa.arena + (long long)sa_entry(pa.sa, key.set, (unsigned)key.way, key.w) * pa.row_bytes;
             else if (ok) src = s_table[k] + row * pa.row_bytes;
             pa.row_ptrs[p] = (long long)src;
+            if constexpr (EVLFU) {
+                args.prov[p] = make_uint4((unsigned)row, (unsigned)k, key.set, is_hit ? (0x80000000u | (unsigned)key.way) : (ok ? key.tag1 : 0u));
+                args.pos_sample[p] = -1;
+            }
         }
         const unsigned long long hm = __ballot(is_hit);
         if (lane == 0 && hm) atomicAdd(&s_hits, __popcll(hm));
-        {   // the wave's misses, packed, behind the block's earlier ones
+        if constexpr (!EVLFU) {   // the wave's misses, packed, behind the block's earlier ones
             const bool is_miss = ok && key.way < 0;
             const unsigned long long mm = __ballot(is_miss);
             int base = 0;
@@ -175,7 +187,7 @@ __global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
     __syncthreads();
     if (threadIdx.x == 0) {
         if (s_hits) atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38], s_hits);
-        pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
+        if constexpr (!EVLFU) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
     }
 }
 
@@ -185,7 +197,10 @@ __global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
 // the range check (address 0: no row).  The bag bounds check and its error flag stay.  A group also tells its sample's word
 // (sample_cnt) what the bag was -- empty or not, all hits or not; whoever brings a sample's T-th bag judges the sample,
 // counts it into column 39 (all-hit requests) and leaves the word zero for the next launch.
-template <int CODEC, int UNROLL>
+// EVLFU ("served bags"): the judge also writes agg[b] = T - the sample's bags with a miss, and the piece-0 lane of a group tells
+// every position its bag covers which sample it belongs to (pos_sample; the probe preset -1).  The map comes from this walk
+// and not from a search over the offsets: a bag the bounds check calls empty covers nothing, exactly as it pools nothing.
+template <int CODEC, int UNROLL, bool EVLFU>
 __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
     __shared__ float s_lut[CodecLut<CODEC>::kEntries];
     __shared__ int s_perfect;
@@ -254,6 +269,9 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
                 if (j < len[u]) {
                     r[u] = reinterpret_cast<const unsigned char *>(ptrs[s[u] + j]);
                     miss[u] = miss[u] || !(r[u] >= arena && r[u] < arena_end);
+                    if constexpr (EVLFU) {
+                        if (piece == 0) args.pos_sample[args.pos0[t] + s[u] + j] = (int)(b0 + (long long)u * RPW + slot);
+                    }
                 }
             }
             float4 v[UNROLL];
@@ -285,6 +303,7 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
                     if ((all & 0xff) == T) {   // the sample's last bag: nobody else writes the word any more
                         args.sample_cnt[b] = 0;
                         if (((all >> 8) & 0xff) != 0 && (all >> 16) == 0) n_perfect++;
+                        if constexpr (EVLFU) args.agg[b] = T - (all >> 16);
                     }
                 }
             }
@@ -295,6 +314,57 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
     __syncthreads();
     if (threadIdx.x == 0 && s_perfect)
         atomicAdd(&args.p.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 39], s_perfect);
+}
+
+// EvLFU "served bags", behind the pooling: one lane per position, the probe's grid and walk.  a = agg of the position's sample
+// (0 when no valid bag covers it).  A hit way goes to max(old, a): a plain read of the word first, the compare-and-swap
+// (sa_raise) only while the priority is below a -- the tables of a few rows put thousands of positions on one word, and every
+// one of them after the first finds nothing left to do.  A miss goes into the block's list with its count, in the record
+// cache_batch_sa_list_kernel reads; copies of a key fold their counts there.  Nothing but raises writes a way word during
+// this launch, so a way the probe found still holds its key.
+__global__ void __launch_bounds__(256) bags_raise_list_kernel(const BagArgs args) {
+    __shared__ int s_delta[64];   // priority histogram moves (0 .. T, T <= 32; sized by the word's 6-bit field)
+    __shared__ int s_list_n;
+    const PolicyArgs &pa = args.p;
+    const SaGeom &g = pa.sa;
+    const int T = pa.T;
+    if (threadIdx.x < 64) s_delta[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_list_n = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballot below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+        int a = 0;
+        if (p < args.n_pos) {
+            r = args.prov[p];
+            const int b = args.pos_sample[p];
+            if (b >= 0) a = args.agg[b];
+        }
+        const bool is_hit = (r.w & 0x80000000u) != 0u;
+        const bool is_miss = !is_hit && r.w != 0u;
+        if (is_hit && a > 0) {
+            unsigned *wp = sa_ways_ptr(g, r.z) + (r.w & 7u);
+            const unsigned w = *wp;
+            if (sa_prio(w) < a) {
+                const int old = sa_raise(g, wp, w, a);
+                if (old >= 0) { atomicSub(&s_delta[old], 1); atomicAdd(&s_delta[a], 1); }
+            }
+        }
+        const unsigned long long mm = __ballot(is_miss);
+        int base = 0;
+        if (lane == 0 && mm) base = atomicAdd(&s_list_n, __popcll(mm));
+        base = __shfl(base, 0, 64);
+        if (is_miss) {
+            const int at = base + __popcll(mm & ((1ull << lane) - 1ull));
+            if (at < pa.list_cap)
+                pa.miss_rec[(long long)blockIdx.x * pa.list_cap + at] = make_uint4(r.x, r.y | ((unsigned)a << 8), r.z, r.w);
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= T && s_delta[threadIdx.x])
+        atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], s_delta[threadIdx.x]);
+    if (threadIdx.x == 0) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
 }
 
 struct NoTail {};
@@ -412,7 +482,18 @@ void policy_probe_launch(const PolicyArgs &a, int grid, hipStream_t st) {
 }
 
 void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(bags_probe_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+    if (a.evlfu) hipLaunchKernelGGL(bags_probe_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bags_probe_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_raise_list_launch(const BagArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_raise_list_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+template <int CODEC, int UNROLL>
+static void bags_pool_launch_t(const BagArgs &args, unsigned blocks, hipStream_t st) {
+    if (args.evlfu) hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, true>), dim3(blocks), dim3(256), 0, st, args);
+    else hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, false>), dim3(blocks), dim3(256), 0, st, args);
 }
 
 void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st) {
@@ -425,10 +506,10 @@ void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st) {
     if (blocks > (long long)kNumCu * 8) blocks = (long long)kNumCu * 8;
     blocks = round_up((int)blocks, kNumXcd);
     switch (codec) {
-    case 32: hipLaunchKernelGGL((bags_pool_kernel<32, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
-    case 16: hipLaunchKernelGGL((bags_pool_kernel<16, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
-    case 8: hipLaunchKernelGGL((bags_pool_kernel<8, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
-    default: hipLaunchKernelGGL((bags_pool_kernel<4, kUnroll>), dim3((unsigned)blocks), dim3(256), 0, st, args); break;
+    case 32: bags_pool_launch_t<32, kUnroll>(args, (unsigned)blocks, st); break;
+    case 16: bags_pool_launch_t<16, kUnroll>(args, (unsigned)blocks, st); break;
+    case 8: bags_pool_launch_t<8, kUnroll>(args, (unsigned)blocks, st); break;
+    default: bags_pool_launch_t<4, kUnroll>(args, (unsigned)blocks, st); break;
     }
 }
 

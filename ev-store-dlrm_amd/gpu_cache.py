@@ -282,7 +282,17 @@ class GpuCache:
             out.data_ptr(), hit.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
         return hit, out
 
-    # ---- ragged bags through an 'lru' / 'lfu' tier (include/evstore_hip.h: evs_cache_lookup_bags) ----
+    # ---- ragged bags through an 'lru' / 'lfu' / 'evlfu' tier (include/evstore_hip.h: evs_cache_lookup_bags) ----
+    def set_bag_rule(self, rule):
+        """What a request's hit count is over ragged bags, for an 'evlfu' cache: 'served-bags' (agg_hit of a sample = the number
+        of its T bags without a missed or out-of-range position; empty bags count) or None (the default: lookup_bags /
+        lookup_bags_interact refuse an 'evlfu' cache).  An 'lru' / 'lfu' cache needs no rule: 'served-bags' raises EVS_EINVAL,
+        None is accepted (include/evstore_hip.h: evs_cache_set_bag_rule)."""
+        if rule not in (None, "served-bags"):
+            raise ValueError("rule must be 'served-bags' or None, got %r" % (rule,))
+        _lib.check(_lib.lib().evs_cache_set_bag_rule(self._h, 1 if rule else 0))
+        return self
+
     def _bags_call(self, lS_o, lS_i):
         """lS_o / lS_i as apply_emb takes them -- a (T, B) int64 tensor or a list of T 1-D int64 tensors, on the device ->
         (B, the C arrays of the call, the flat flag tensor and its per-table views, what must stay alive)"""
@@ -312,6 +322,8 @@ class GpuCache:
         """Multi-hot lookup on an 'lru' / 'lfu' tier: every position of every index array is one lookup of "the batched rule"
         (flags = residency at arrival, one touch per way and batch, every distinct missed key inserted once), the bags pool the
         served rows bit-equal to apply_emb over the backing tables (include/evstore_hip.h: evs_cache_lookup_bags).
+        An 'evlfu' tier (set-associative, after set_bag_rule('served-bags')): strict snapshot flags, every hit way raised to
+        the served-bag count of the samples that name it, every distinct missed key inserted once at the largest such count.
         -> (hits: T uint8 tensors, one flag per index, views of one flat array; ly: T (B, dim) fp32 tensors, views of one
         (T, B, dim) block -- `out`, when given)."""
         B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
@@ -326,8 +338,8 @@ class GpuCache:
 
     def lookup_bags_interact(self, lS_o, lS_i, x, itself=False, out=None):
         """R = interact_features(x, the T pooled bags of lookup_bags): probe, pooling into a (T, B, dim) block the cache owns,
-        the dense interaction, insert -- the rule and the flags of lookup_bags (include/evstore_hip.h:
-        evs_cache_lookup_bags_interact).  -> (hits as lookup_bags gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
+        the dense interaction, insert ('evlfu': raise + list, then the insert) -- the rule and the flags of lookup_bags
+        (include/evstore_hip.h: evs_cache_lookup_bags_interact).  -> (hits as lookup_bags gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
         B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
         F = self.n_tables + 1
         P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
@@ -344,7 +356,8 @@ class GpuCache:
 
     def batch_stats(self):
         """Counters of the batched path and the resident-entry histogram per priority.  An 'lru' / 'lfu' cache: n_flush stays
-        0, n_perfect_hits counts all-hit requests, hist[0] = size and the rest 0."""
+        0, n_perfect_hits counts all-hit requests, hist[0] = size and the rest 0.  After lookup_bags on an 'evlfu' cache
+        n_perfect_hits counts the samples with a lookup whose T bags were all served, hist the priorities 0 .. T."""
         s = (C.c_int64 * 8)()
         hist = (C.c_int64 * (self.n_tables + 1))()
         _lib.check(_lib.lib().evs_cache_batch_stats(self._h, s, hist, torch.cuda.current_stream(self.device).cuda_stream))

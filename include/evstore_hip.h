@@ -549,19 +549,19 @@ EVS_API int64_t evs_aprx_batch_dump(evs_aprx *p, int64_t *triples, int64_t max_t
  * interaction kernel (the reference's one-layer reduced-precision builds, cache_manager.cpp:13-20). */
 EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *rows, const float *x, int64_t x_stride,
                                       int itself, float *R, uint8_t *hit, void *stream);
-/* RAGGED BAGS THROUGH AN LRU / LFU TIER (multi-hot features behind the cache; csrc/evs_cache_policy.hip).  Input as
+/* RAGGED BAGS THROUGH AN LRU / LFU / EvLFU TIER (multi-hot features behind the cache; csrc/evs_cache_policy.hip).  Input as
  * evs_embedding_bag_sum takes it: indices / offsets / nnz are HOST arrays of n_tables entries -- per table k a DEVICE int64
  * index array of nnz[k] entries and a DEVICE array of B bag start offsets (the last bag runs to nnz[k]).
  * THE RULE.  One call is batch n (1, 2, ...) of "the batched rule" (evs_cache_set_batch_policy, above); it shares the batch
  * counter with evs_cache_lookup_batch / _lookup_interact, and calls of the two forms may alternate on one cache.
  *   a lookup  is one POSITION of one index array; all sum(nnz) positions are probed, whether or not a bag covers them --
- *             offsets shape the pooling only.
+ *             offsets shape the pooling (EvLFU: and the counts) only.
  *   probe     (snapshot) hit[p] = 1 exactly when key (k + 1, indices[k][p]) was resident when the call started.  An index
  *             outside [0, n_rows[k]) is not a key: flag 0, it contributes nothing, it is never inserted, and it raises the
  *             sticky flag evs_check_index_errors reads.  All positions that carry the same key get the same flag.
- *   touch, insert  steps 2 and 3 of the batched rule, unchanged, over the DISTINCT keys of the call: one touch per way and
- *             batch (the LFU counter rises by 1 per batch however many positions name the key), every distinct missed key
- *             inserted once.
+ *   touch, insert  (LRU / LFU) steps 2 and 3 of the batched rule, unchanged, over the DISTINCT keys of the call: one touch per
+ *             way and batch (the LFU counter rises by 1 per batch however many positions name the key), every distinct missed
+ *             key inserted once.
  *   pooled    pooled[k][b] = sum over the bag's positions, in index order, of the served rows; fp32 adds, unfused, the
  *             accumulator starts at +0.0f.  Served rows are exactly the table rows, so the output is bit-equal to
  *             evs_embedding_bag_sum's general pooling over the backing tables for every input that call accepts -- a bag whose
@@ -569,6 +569,30 @@ EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *ro
  *   counters  (evs_cache_batch_stats) n_requests += B; n_hits += the hit positions; n_perfect_hits += the samples that have
  *             at least one lookup and none missed or out of range, over all their bags; n_evict, size and hist keep their
  *             meaning.  With one index per bag this is what the (B, T) form counts.
+ * AN EvLFU CACHE'S priority is a request's hit count.  The reference's EvLFU sees one key per table; what the count is over
+ * bags is a choice it does not make, so the caller declares it: evs_cache_set_bag_rule(c, 1), "served bags" (below).  Without
+ * it both entry points refuse an EvLFU cache (EVS_EINVAL).  With it one call is batch n of the batched EvLFU rule -- "WHAT IS
+ * THE SAME" at evs_cache_set_batch_policy keeps holding -- on the set-associative tier alone (batch policy 2, 8 ways), with:
+ *   probe     strict snapshot, as above.  The probe writes no way word and no way is hidden by its stamp (unlike the
+ *             one-launch form of evs_cache_lookup_interact).
+ *   served bag  bag (b, k) is served when none of its positions is a miss or out of range.  An empty bag is served; a bag
+ *             whose offsets are backwards or past nnz[k] is empty (and raises the sticky flag), hence served.
+ *   agg_hit(b)  the number of sample b's T bags that are served, 0 .. T.  With one index per bag: the (B, T) form's count.
+ *   raise     every hit way named by a position of sample b gets priority max(old, agg_hit(b)) -- a monotone maximum over all
+ *             positions that name it; its stamp stays.
+ *   insert    every distinct missed key once, with priority = the maximum of agg_hit over the samples that name it, into its
+ *             own set: free ways first (lowest index), else the lowest priority among the ways NOT stamped by this batch,
+ *             lowest index among equals; no such way: turned away.  Priorities are read after all raises of the call (the
+ *             raise launch ends before the insert launch starts).  The new way carries this batch's stamp.
+ *   uncovered a position no valid bag covers is a lookup with count 0: a hit is not raised, a miss is inserted at priority 0.
+ *             (Offsets that go back can make two valid bags of different samples cover one position; it then counts for one
+ *             of them, which one is not specified.  Pooling and flags are unaffected.)
+ *   counters  n_requests += B; n_hits += the hit positions; n_perfect_hits += the samples with at least one lookup and
+ *             agg_hit = T; hist is the per-priority count of resident entries; n_evict, n_flush keep their meaning.
+ *   flush     the EvLFU flush as it is: the close asks for it when the top bucket holds max_perfect entries, and the next
+ *             batched call of either form runs it before its probe.
+ *   mixing    calls may alternate with evs_cache_lookup_batch / _lookup_interact on one cache, under either setting of
+ *             evs_cache_set_inline_update; they share the batch stamp and the batch counter.
  * hit: flat DEVICE uint8 array of sum(nnz) entries, table-major (table k's flags start at sum of nnz[j], j < k); may be NULL.
  * pooled: table k's bag b at pooled + k * out_table_stride + b * out_bag_stride (floats; 16-byte aligned, strides multiples of
  * 4), dim a multiple of 4 up to 256.  The interact form pools into a (T, B, d) scratch buffer the cache owns (grown on demand)
@@ -576,15 +600,21 @@ EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *ro
  * Checked before the device is touched: EVS_EINVAL for B < 0, strides not multiples of 4, a NULL argument (cache, host arrays,
  * pooled / x / R, indices[k] with nnz[k] > 0, offsets[k]), nnz[k] < 0, sum(nnz) >= 2^31, a dim the pooling (interact form:
  * the interaction, evs_fused_dim_supported) does not take, n_tables + 1 > 32 features; B == 0 is success.  Refused with a
- * message that names the policy and the cache left usable: an EvLFU cache (EVS_EINVAL: its priority is a per-request count
- * that has no bag form yet), host-memory or file-backed tables (EVS_ESTATE), a cache driven by the exact path (EVS_ESTATE), a
- * capacity below 8 or 2^32 rows over all tables (EVS_EINVAL, as evs_cache_lookup_batch refuses them). */
+ * message that names the policy and the cache left usable: an EvLFU cache without a bag rule (EVS_EINVAL), host-memory or
+ * file-backed tables (EVS_ESTATE), a cache driven by the exact path (EVS_ESTATE), a capacity below 8 or 2^32 rows over all
+ * tables (EVS_EINVAL, as evs_cache_lookup_batch refuses them); an EvLFU cache whose batch policy is or resolves to plan or
+ * sampled (set explicitly, through EVS_CACHE_POLICY, or because the geometry has no set-associative form), and 16-way sets
+ * (EVS_SA_WAYS=16) or a tier of a C1 + C2 pair (EVS_EINVAL). */
 EVS_API int evs_cache_lookup_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
                                   const int64_t *nnz, float *pooled, int64_t out_table_stride, int64_t out_bag_stride,
                                   uint8_t *hit, void *stream);
 EVS_API int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int64_t *const *indices,
                                            const int64_t *const *offsets, const int64_t *nnz, const float *x, int64_t x_stride,
                                            int itself, float *R, uint8_t *hit, void *stream);
+/* What a request's hit count is over ragged bags, for an EvLFU cache (the rule: evs_cache_lookup_bags, above): 0 none (the
+ * default: the bag entry points refuse the cache), 1 "served bags".  May be called between calls.  EVS_EINVAL, with the policy
+ * named: a rule outside {0, 1}; rule 1 on an LRU / LFU cache (their bag form needs none; rule 0 is accepted). */
+EVS_API int evs_cache_set_bag_rule(evs_cache *c, int rule);
 /* The one-launch form of a set-associative tier (round 5: the policy update runs INSIDE evs_cache_lookup_interact's probe +
  * interaction launch; a hit flag then says "served from the cache": 1 => resident at arrival, 0 => not resident OR retired
  * by one of this batch's own inserts OR resident in a way filled k 2^S batches ago, see evs_cache_set_batch_policy) is the default wherever its conditions hold (a tier alone, 8 ways, two-copy arena, at

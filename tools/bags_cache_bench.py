@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Multi-hot bags behind the LRU / LFU cache tier: the chain  probe -> pooling -> dense interaction -> insert
-(GpuCache.lookup_bags_interact) beside the uncached apply_emb_interact on the same batches, as ONE JSON file.
+"""Multi-hot bags behind the LRU / LFU / EvLFU cache tier: the chain  probe -> pooling -> dense interaction -> insert
+(GpuCache.lookup_bags_interact; EvLFU under set_bag_rule("served-bags"): probe -> pooling -> dense interaction -> raise + list
+-> insert) beside the uncached apply_emb_interact on the same batches, as ONE JSON file.  Every policy's leg draws the same
+batches (one seed), so the LRU chain of the same run is the yardstick for the EvLFU one.
 
 Shape: the Criteo-Kaggle cardinalities with the 10 % tier, bags of 1 .. 10 indices drawn as tools/multihot_bench.py draws them,
 rows Zipf(0.75) as bench.make_batches draws them, B = 2 048 and 16 384.  The tier is warmed until its size stops growing;
@@ -10,8 +12,9 @@ timed batches.
 
 The per-kernel split comes from a profiler run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bags_cache_bench.py --chain-only --batch 2048
-    python tools/bags_cache_bench.py --kernel-stats 2048=DIR/.../..._kernel_stats.csv 16384=... --out profiles/bags_cache.json
-(--chain-only runs the warm-up and the chain alone; --kernel-stats folds the library's rows of those files into the JSON.)
+    python tools/bags_cache_bench.py --kernel-stats 2048=DIR/.../..._kernel_stats.csv evlfu:16384=... --out profiles/bags_cache.json
+(--chain-only runs the warm-up and the chain alone, one --policy per profiler run; --kernel-stats folds the library's rows of
+those files into the JSON under kernel_split[policy], the policy named in front of the batch size, lru when it is left out.)
 Needs a GPU."""
 import argparse
 import csv
@@ -63,6 +66,8 @@ def run(policy, B, ev, ln, dev, args):
     cap = int(args.frac * sum(ln))
     c = E.GpuCache(policy, cap, T, d, 32, "python", dev)
     c.set_backing(ev)
+    if policy == "evlfu":
+        c.set_bag_rule("served-bags")
     g = torch.Generator(device=dev).manual_seed(7)
     x = torch.rand((B, d), device=dev)
     n_warm = warm(c, ln, B, g, dev, x, args)
@@ -95,6 +100,7 @@ def run(policy, B, ev, ln, dev, args):
             "lookups_per_batch": round(n_pos / args.steps, 1), "size": s1["size"],
             "hit_rate": round((s1["n_hits"] - s0["n_hits"]) / n_pos, 4),
             "all_hit_samples": s1["n_perfect_hits"] - s0["n_perfect_hits"], "evictions": s1["n_evict"] - s0["n_evict"],
+            "flushes": s1["n_flush"] - s0["n_flush"],
             "chain_us_per_batch": {"mean": round(float(chain.mean()), 2), "median": round(float(np.median(chain)), 2)},
             "uncached_apply_emb_interact_us_per_batch": {"mean": round(float(plain.mean()), 2), "median": round(float(np.median(plain)), 2)}}
 
@@ -113,7 +119,7 @@ def kernel_split(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[2048, 16384])
-    ap.add_argument("--policy", nargs="+", default=["lru", "lfu"])
+    ap.add_argument("--policy", nargs="+", default=["lru", "lfu", "evlfu"])
     ap.add_argument("--frac", type=float, default=0.10)
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--max-bag", type=int, default=10)
@@ -122,7 +128,7 @@ def main():
     ap.add_argument("--max-rows", type=int, default=0, help="clamp every table to this many rows (0: full size)")
     ap.add_argument("--dim", type=int, default=36)
     ap.add_argument("--chain-only", action="store_true", help="warm-up and the chain alone: the run a profiler wraps")
-    ap.add_argument("--kernel-stats", nargs="*", default=[], metavar="B=CSV", help="kernel_stats.csv of a --chain-only profiler run per batch size")
+    ap.add_argument("--kernel-stats", nargs="*", default=[], metavar="[POLICY:]B=CSV", help="kernel_stats.csv of a --chain-only profiler run per batch size")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -136,7 +142,8 @@ def main():
         for p in args.policy:
             runs.append(run(p, B, ev, ln, dev, args))
             print("bags_cache_bench: %s" % json.dumps(runs[-1]), file=sys.stderr, flush=True)
-    res = {"tool": "bags_cache_bench", "chain": "bags_probe_kernel -> bags_pool_kernel -> dense interaction -> policy_insert_kernel",
+    res = {"tool": "bags_cache_bench", "chain": "bags_probe_kernel -> bags_pool_kernel -> dense interaction -> policy_insert_kernel"
+           " (evlfu: ... -> bags_raise_list_kernel -> cache_batch_sa_list_kernel)",
            "shape": {"rows": sum(ln), "frac": args.frac, "dim": args.dim, "zipf_alpha": args.alpha, "bags": "1 .. %d" % args.max_bag},
            "timing": "device events around every call, the chain and the uncached call alternating batch by batch; dispatch gaps included",
            "runs": runs}
@@ -144,7 +151,8 @@ def main():
         res["kernel_split"] = {"source": "rocprofv3 --kernel-trace --stats over a --chain-only run (warm-up launches included in the averages)"}
         for item in args.kernel_stats:
             b, path = item.split("=", 1)
-            res["kernel_split"]["B=%s" % b] = kernel_split(path)
+            policy, b = b.split(":", 1) if ":" in b else ("lru", b)
+            res["kernel_split"].setdefault(policy, {})["B=%s" % b] = kernel_split(path)
     line = json.dumps(res)
     if args.out:
         with open(args.out, "w") as f:
