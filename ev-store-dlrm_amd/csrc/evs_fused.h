@@ -66,6 +66,24 @@ struct FusedArgs {
 
 constexpr int kTileMaxF = 28;   // index-tile launches: x + at most 27 tables
 
+// evs_fused_rf_lean.hip: what a MODEL contributes to the stacked call of the rows-in-registers kernel, kept in device memory --
+// one 16-byte record per feature (record 0, x, is filled from the launch's scalars) and the library's per-device constants the
+// body reads.  Built once per distinct model (evs_desc_cache.h), so the blocks of a launch read lines no host write has touched
+// since the model was first used instead of the freshly written kernel-argument segment.
+struct RfModelFeat { unsigned long long base; unsigned n_rows, row_bytes; };
+struct RfModelDesc {
+    RfModelFeat feat[EVS_MAX_FEATURES];   // 512 bytes
+    const void *zeros;                    // FusedArgs::zeros
+    int *err;                             // FusedArgs::err
+};
+// the lean entry of launch_rf / launch_rf_check for the stacked call (FusedArgs::stk): scalar kernel arguments, the leading ones
+// preloaded into SGPRs, and the model descriptor above.  false: not taken (strides or B beyond 32 bits, the model unknown while
+// the stream is capturing, every descriptor pinned by a captured graph, built with -DEVS_RF_LEAN=0) -- the caller launches the
+// FusedArgs entry as before.  Same bits either way.
+bool launch_rf_lean(const FusedArgs &a, int tile_per, hipStream_t st);
+// developer instrumentation (-DEVS_X_PT on BOTH units; tools/probe_stage_probe.py): adds the lean entries' stage ticks to h[1024 * 16]
+int rf_lean_pt_add(unsigned long long *h, int reset);
+
 // evs_fused_rf.hip: the rows-in-flight-in-registers form of the bag-1 index-tile loop (fp32 tables, d in {16, 32, 36},
 // F <= kTileMaxF); returns false when it has no kernel for the shape (the caller then uses the LDS-DMA loop)
 bool launch_rf(const FusedArgs &a, hipStream_t st);
