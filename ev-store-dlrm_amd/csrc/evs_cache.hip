@@ -25,6 +25,7 @@
 #include "evs_hash.h"
 #include "evs_update.h"
 #include "evs_cache_policy.h"
+#include "evs_cache_warm.h"
 #include <type_traits>
 
 #include <mutex>
@@ -3382,15 +3383,18 @@ unsigned sa_single_ways() {
     if (w < 0) { const char *e = evs::env_switch("EVS_SA_WAYS"); w = (e && atoi(e) == 16) ? 16 : (int)kSaSingleWays; }
     return (unsigned)w;
 }
+// a tier alone keeps two arena rows per way (evs_hash.h: the two-copy arena; EVS_SA_DUAL=0: one, developer A/B)
+unsigned sa_single_dual() {
+    static const unsigned dual_on = (evs::env_switch("EVS_SA_DUAL") && evs::env_switch("EVS_SA_DUAL")[0] == '0') ? 0u : 1u;
+    return dual_on;
+}
 // can this cache take the set-associative form on its own (universe below 2^32 keys, tags that fit the word)
 bool sa_single_feasible(const evs_cache *c, evs::SaUniverse *u_out = nullptr, evs::SaGeom *g_out = nullptr) {
     evs::SaUniverse u; evs::SaGeom g;
     const unsigned ways = c->host.policy == evs::kEvLFU ? sa_single_ways() : kSaSingleWays;   // (the LRU / LFU kernels are compiled for 8-way sets)
     if (!c->has_backing || c->host.cap < (long long)ways) return false;
     if (!sa_make_universe(c->backing_rows, nullptr, c->host.n_tables, u)) return false;
-    // a tier alone keeps two arena rows per way (evs_hash.h: the two-copy arena; EVS_SA_DUAL=0: one, developer A/B)
-    static const unsigned dual_on = (evs::env_switch("EVS_SA_DUAL") && evs::env_switch("EVS_SA_DUAL")[0] == '0') ? 0u : 1u;
-    if (!sa_make_geom(g, (unsigned)(c->host.cap / ways), ways, 0, ways, u, 0, dual_on)) return false;
+    if (!sa_make_geom(g, (unsigned)(c->host.cap / ways), ways, 0, ways, u, 0, sa_single_dual())) return false;
     if (u_out) *u_out = u;
     if (g_out) *g_out = g;
     return true;
@@ -5221,6 +5225,170 @@ extern "C" int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t 
         n++;
     }
     return n;
+}
+
+// ---- warm start (evs_cache_warm.h): what a set-associative tier alone holds, exported and loaded back ------------------------
+// The geometry a tier ALONE of `cap` entries takes over tables of rows[] rows, as batch_state gives it to a cache
+// (sa_single_feasible); -> nullptr or why there is none.
+static const char *warm_geometry(int policy, long long cap, int T, const long long *rows, evs::SaUniverse &u, evs::SaGeom &g) {
+    if (policy == evs::kEvLFU && sa_single_ways() != kSaSingleWays) return "sets of 16 ways (EVS_SA_WAYS=16) have no warm start: the load places into 8-way sets";
+    if (cap < (long long)kSaSingleWays) return "a capacity below one set of 8 entries";
+    if (!sa_make_universe(rows, nullptr, T, u) || !sa_make_geom(g, (unsigned)(cap / kSaSingleWays), kSaSingleWays, 0, kSaSingleWays, u, 0, sa_single_dual()))
+        return "the set-associative form needs fewer than 2^32 rows over all tables and more than R / 2^22 sets of 8 entries";
+    return nullptr;
+}
+// what export and load refuse about the cache itself; a policy that was only resolved here is forgotten again on a refusal
+static int warm_check(evs_cache *c, bool load, const char *who) {
+    using namespace evs;
+    { const int rc = batch_check(c, who); if (rc) return rc; }
+    EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this cache is a tier of a C1 + C2 (+ C3) lookup; the warm start is a tier alone's", who);
+    EVS_REQUIRE(c->sa.tags ? c->sa.ways == kSaSingleWays : (c->host.policy != kEvLFU || sa_single_ways() == kSaSingleWays),
+                "%s: sets of 16 ways (EVS_SA_WAYS=16) have no warm start: the load places into 8-way sets", who);
+    if (c->host_backing || c->ft) { set_error("%s: the warm start reads the tables in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
+    if (c->serving) { set_error("%s: a resident server is running on this cache", who); return EVS_ESTATE; }
+    const int given = c->batch_policy;
+    const int bp = resolved_batch_policy(c);
+    if (bp != 2) {
+        c->batch_policy = given;
+        set_error("%s: the warm start is the set-associative tier's (batch policy 2); this cache's batch policy is %s", who, bp == 0 ? "plan" : "sampled");
+        return EVS_EINVAL;
+    }
+    if (load && (c->used == 2 || c->bs)) {
+        c->batch_policy = given;
+        set_error("%s: the batched path of this cache already holds state; a load goes into a fresh cache", who);
+        return EVS_ESTATE;
+    }
+    return EVS_OK;
+}
+
+extern "C" int evs_cache_load_plan(int policy, int64_t capacity, int n_tables, const int64_t *n_rows, int64_t n, const int64_t *entries,
+                                   const int64_t *state16, int strict, int64_t *dest_slot, uint32_t *words, int64_t *out4) {
+    using namespace evs;
+    EVS_REQUIRE(policy >= 0 && policy <= 2, "evs_cache_load_plan: policy %d", policy);
+    EVS_REQUIRE(n_tables >= 1 && n_tables <= 32 && n_rows, "evs_cache_load_plan: n_tables %d (1 .. 32) or NULL n_rows", n_tables);
+    EVS_REQUIRE(capacity >= 1 && capacity < (1ll << 30), "evs_cache_load_plan: capacity %lld", (long long)capacity);
+    long long rows[32];
+    for (int k = 0; k < n_tables; k++) { EVS_REQUIRE(n_rows[k] >= 0, "evs_cache_load_plan: n_rows[%d] = %lld", k, (long long)n_rows[k]); rows[k] = n_rows[k]; }
+    SaUniverse u; SaGeom g;
+    if (const char *why = warm_geometry(policy, capacity, n_tables, rows, u, g)) { set_error("evs_cache_load_plan: %s", why); return EVS_EINVAL; }
+    if (const char *why = warm_plan(u, g, policy, capacity, n_tables, n_rows, n, entries, state16, strict, dest_slot, words, out4)) {
+        set_error("evs_cache_load_plan: %s", why);
+        return EVS_EINVAL;
+    }
+    return EVS_OK;
+}
+
+// rows of (table_1based, row, score, age, slot) sorted by slot (host); returns the count
+extern "C" int64_t evs_cache_batch_export(evs_cache *c, int64_t *entries, int64_t max_entries, int64_t *state16, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c && c->bs, "evs_cache_batch_export: the batched path has not been used");
+    { const int rc = warm_check(c, false, "evs_cache_batch_export"); if (rc) return rc; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    sampled_close_pending(c, 0, st);
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    sampled_flush_if_wanted(c, st);
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    const SaGeom &g = c->sa;
+    const int policy = c->host.policy;
+    std::vector<unsigned> tags((size_t)g.nset * kSaSingleWays);
+    EVS_HIP_CHECK(hipMemcpy(tags.data(), g.tags, tags.size() * 4, hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (size_t slot = 0; slot < tags.size(); slot++) {
+        const unsigned word = tags[slot];
+        if (!word) continue;
+        if (entries && n < max_entries) {
+            const unsigned long long key = sa_key_of_host(c->sau, g, (unsigned)(slot / kSaSingleWays), word);
+            int64_t *e = entries + 5 * n;
+            long long score, age;
+            warm_word_fields(g, policy, c->stamp_counter, word, score, age);
+            e[0] = (int64_t)(key >> 32); e[1] = (int64_t)(key & 0xffffffffull); e[2] = score; e[3] = age; e[4] = (int64_t)slot;
+        }
+        n++;
+    }
+    if (state16) {
+        BatchState h;
+        EVS_HIP_CHECK(hipMemcpy(&h, c->bs, sizeof h, hipMemcpyDeviceToHost));
+        const int64_t s[16] = {kWarmVersion, policy, c->host.cap, c->host.n_tables, c->host.dim, c->host.codec, c->stamp_counter, h.n_flush, h.n_evict,
+                               h.n_requests, h.n_perfect_hits, h.n_hits, (int64_t)warm_stamp_bits(g, policy), c->bag_rule, c->inline_mode, 0};
+        for (int i = 0; i < 16; i++) state16[i] = s[i];
+    }
+    return n;
+}
+
+// developer probe (tools/warm_start_bench.py: the load's launch alone, timed by the caller's events beside a device copy): the
+// kernel of evs_cache_batch_load over a record list, set words and an arena that are the caller's; not part of the ABI
+extern "C" __attribute__((visibility("default"))) int evs_x_warm_launch(const void *recs, long long n, unsigned *tags, unsigned char *arena,
+                                                                        unsigned dual, int row_bytes, void *stream) {
+    evs::warm_load_launch(evs::WarmArgs{reinterpret_cast<const evs::WarmRec *>(recs), n, tags, arena, dual, row_bytes}, reinterpret_cast<hipStream_t>(stream));
+    return hipGetLastError() == hipSuccess ? EVS_OK : EVS_EHIP;
+}
+
+extern "C" int evs_cache_batch_load(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state16, int strict, int64_t *out4, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_batch_load";
+    EVS_REQUIRE(n >= 0 && (n == 0 || entries) && (strict == 0 || strict == 1), "%s: a negative count, NULL entries or strict outside {0, 1}", who);
+    { const int rc = warm_check(c, true, who); if (rc) return rc; }
+    const int T = c->host.n_tables, policy = c->host.policy;
+    // the plan: pure host code, the same function evs_cache_load_plan exports
+    std::vector<int64_t> dest((size_t)std::max<int64_t>(n, 1));
+    std::vector<uint32_t> words((size_t)std::max<int64_t>(n, 1));
+    int64_t o4[4] = {0, 0, 0, 0}, rows64[32];
+    for (int k = 0; k < T; k++) rows64[k] = c->backing_rows[k];
+    { const int rc = evs_cache_load_plan(policy, c->host.cap, T, rows64, n, entries, state16, strict, dest.data(), words.data(), o4); if (rc) return rc; }
+    std::vector<WarmRec> recs;
+    recs.reserve((size_t)o4[0]);
+    BatchState h{};
+    {   // the packed list in slot order (the arena stores then run forward): slot -> entry, then one sweep over the slots
+        std::vector<int64_t> owner((size_t)(c->host.cap / kSaSingleWays) * kSaSingleWays, -1);
+        for (int64_t i = 0; i < n; i++) if (dest[(size_t)i] >= 0) owner[(size_t)dest[(size_t)i]] = i;
+        for (size_t slot = 0; slot < owner.size(); slot++) {
+            const int64_t i = owner[slot];
+            if (i < 0) continue;
+            const int64_t *e = entries + 5 * i;
+            recs.push_back(WarmRec{(unsigned long long)reinterpret_cast<uintptr_t>(c->backing[e[0] - 1]) + (unsigned long long)e[1] * (unsigned long long)c->host.row_bytes,
+                                   (unsigned)slot, words[(size_t)i]});
+            h.cnt[policy == kEvLFU ? e[2] : 0]++;
+        }
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the record list goes up BEFORE the batched-path state is made: a failure up to here leaves the cache fresh
+    WarmRec *dev = nullptr;
+    if (!recs.empty()) {
+        if (hipMalloc(reinterpret_cast<void **>(&dev), recs.size() * sizeof(WarmRec)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: allocating the list of %lld entries failed", who, (long long)recs.size());
+            return EVS_ENOMEM;
+        }
+        const hipError_t err = hipMemcpy(dev, recs.data(), recs.size() * sizeof(WarmRec), hipMemcpyHostToDevice);
+        if (err != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); set_error("%s: %s", who, hipGetErrorString(err)); return EVS_EHIP; }
+    }
+    { const int rc = batch_state(c, st, who); if (rc) { if (dev) (void)hipFree(dev); return rc; } }   // the set records (zeroed on st), the counters, the replica rows
+    if (dev) {
+        warm_load_launch(WarmArgs{dev, (long long)recs.size(), c->sa.tags, c->a.arena, c->sa.dual, c->host.row_bytes}, st);
+        hipError_t err = hipGetLastError();
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        (void)hipFree(dev);
+        if (err != hipSuccess) { (void)hipGetLastError(); set_error("%s: %s", who, hipGetErrorString(err)); return EVS_EHIP; }
+    }
+    // the counters: what was placed, and what the state carries
+    h.count = (int)o4[0]; h.n_free = (int)c->host.cap - h.count;
+    h.batch_id = o4[3];
+    if (state16) {
+        h.n_flush = state16[kWsFlush]; h.n_evict = state16[kWsEvict]; h.n_requests = state16[kWsRequests];
+        h.n_perfect_hits = state16[kWsPerfect]; h.n_hits = state16[kWsHits];
+    }
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    EVS_HIP_CHECK(hipMemcpy(c->bs, &h, sizeof h, hipMemcpyHostToDevice));
+    // the words a close leaves in mapped host memory (sampled_close_block): [1] the EvLFU flush is wanted, [3] "full"
+    const long long cap = c->host.cap;
+    c->host_tomb[0] = 0; c->host_tomb[2] = (int)h.batch_id;
+    c->host_tomb[1] = h.cnt[T] >= c->host.max_perfect ? 1 : 0;
+    c->host_tomb[3] = h.count >= cap - (cap > 65536 ? cap / 256 : 0) ? 1 : 0;
+    c->stamp_counter = o4[3];
+    c->pending_batches = 0; c->pending_requests = 0;
+    c->used = 2;
+    if (out4) for (int i = 0; i < 4; i++) out4[i] = o4[i];
+    return EVS_OK;
 }
 
 // ---- online row updates (evs_update.h): the table row and every cached copy of it, in stream order ----------------------------

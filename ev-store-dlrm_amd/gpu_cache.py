@@ -139,6 +139,7 @@ class GpuCache:
         rb = self.dim * self.codec // 8
         n_rows = [int(t.numel() * t.element_size() // rb) for t in raws]
         self._backing = raws  # keep alive
+        self._n_rows = n_rows
         self._backing_ev = tables if hasattr(tables, "raw") else None   # (update_rows: deferred apply_emb results of these tables)
         ptrs = (C.c_void_p * self.n_tables)(*[_dev_ptr(t) for t in raws])   # pinned host tables: their device-side address
         rows = (C.c_int64 * self.n_tables)(*n_rows)
@@ -239,6 +240,7 @@ class GpuCache:
         (include/evstore_hip.h: evs_cache_set_inline_update).  An 'lru' / 'lfu' cache always runs the chain: on=True raises
         EVS_EINVAL, on=False is accepted."""
         _lib.check(_lib.lib().evs_cache_set_inline_update(self._h, 1 if on else 0))
+        self._inline_told = True
         return self
 
     def serve_stop(self):
@@ -291,6 +293,7 @@ class GpuCache:
         if rule not in (None, "served-bags"):
             raise ValueError("rule must be 'served-bags' or None, got %r" % (rule,))
         _lib.check(_lib.lib().evs_cache_set_bag_rule(self._h, 1 if rule else 0))
+        self._bag_rule_told = True
         return self
 
     def _bags_call(self, lS_o, lS_i):
@@ -377,6 +380,72 @@ class GpuCache:
         out = np.zeros((max(n, 1), 3), np.int64)
         _lib.lib().evs_cache_batch_dump(self._h, out.ctypes.data, n, st)
         return out[:n]
+
+    # ---- warm start (include/evstore_hip.h: evs_cache_batch_export / evs_cache_batch_load) ----
+    def export_state(self):
+        """What the batched set-associative tier holds, at rest (pending closes folded, a wanted EvLFU flush run) -> a dict of
+        numpy arrays: 'entries' (n, 5) int64 rows of (table_1based, row, score, age, slot) sorted by slot, 'state' (16,) int64
+        (format version, policy, capacity, n_tables, dim, codec, batch number, five counters, stamp bits S, bag rule,
+        inline-update setting, 0) and 'n_rows' (T,) int64, the rows of the backing tables."""
+        import numpy as np
+        L, st = _lib.lib(), torch.cuda.current_stream(self.device).cuda_stream
+        state = np.zeros(16, np.int64)
+        with torch.cuda.device(self.device):
+            n = L.evs_cache_batch_export(self._h, None, 0, None, st)
+            if n < 0:
+                _lib.check(int(n))
+            entries = np.zeros((max(n, 1), 5), np.int64)
+            n2 = L.evs_cache_batch_export(self._h, entries.ctypes.data, n, state.ctypes.data, st)
+        if n2 != n:
+            raise _lib.EvsError(_lib.EVS_ESTATE, "export_state: the cache changed between the count and the export")
+        return {"entries": entries[:n], "state": state, "n_rows": np.asarray(getattr(self, "_n_rows", []), np.int64)}
+
+    def save_state(self, path):
+        """export_state() into an .npz file (np.savez; read back by load_state with allow_pickle=False)"""
+        import numpy as np
+        with open(path, "wb") as f:
+            np.savez(f, **self.export_state())
+
+    def load_state(self, state_or_path, strict=True):
+        """Warm start: the exported entries into this cache, which must be fresh with its backing set -- one launch copies every
+        entry's row from the backing table into the arena and stores its way word; the host decides every placement.
+        state_or_path: what export_state returned, or the path of a save_state file.  strict=True: the cache must have the
+        exporter's capacity, tables and key universe, and continues exactly as the exporter would have; strict=False: the
+        entries are placed anew in this cache's geometry (another capacity: per set the 8 highest scores, youngest first, the
+        rest turned away); 'state' may then be None (batch number = the largest age, counters 0).  The exported bag rule and
+        inline-update setting are applied through set_bag_rule / set_inline_update unless this cache was told already.
+        -> {'placed', 'turned_away', 'batch'}"""
+        import numpy as np
+        if isinstance(state_or_path, dict):
+            d = state_or_path
+        else:
+            try:
+                with np.load(state_or_path, allow_pickle=False) as z:
+                    d = {k: z[k] for k in z.files}
+            except Exception as e:
+                raise _lib.EvsError(_lib.EVS_EIO, "load_state: %s is not a readable state file (%s)" % (state_or_path, e))
+        missing = [k for k in ("entries", "state") + (() if isinstance(state_or_path, dict) else ("n_rows",)) if k not in d]
+        if missing:
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: the state lacks %s" % ", ".join(repr(k) for k in missing))
+        entries = np.ascontiguousarray(d["entries"], np.int64)
+        state = None if d["state"] is None else np.ascontiguousarray(d["state"], np.int64)
+        if entries.ndim != 2 or entries.shape[1] != 5 or (state is not None and state.shape != (16,)):
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: 'entries' must be (n, 5) and 'state' (16,)")
+        if state is not None and int(state[0]) != 1:
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: unknown format version %d" % int(state[0]))
+        if strict and d.get("n_rows") is not None and hasattr(self, "_n_rows") and list(np.asarray(d["n_rows"]).astype(np.int64)) != list(self._n_rows):
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: a strict load needs backing tables of the exporter's row counts")
+        out4 = np.zeros(4, np.int64)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().evs_cache_batch_load(self._h, int(entries.shape[0]), entries.ctypes.data if entries.shape[0] else None,
+                                                       None if state is None else state.ctypes.data, 1 if strict else 0, out4.ctypes.data,
+                                                       torch.cuda.current_stream(self.device).cuda_stream))
+        if state is not None:
+            if int(state[13]) == 1 and not getattr(self, "_bag_rule_told", False):
+                self.set_bag_rule("served-bags")
+            if int(state[14]) >= 0 and not getattr(self, "_inline_told", False) and (self.policy == "evlfu" or int(state[14]) == 0):
+                self.set_inline_update(bool(state[14]))
+        return {"placed": int(out4[0]), "turned_away": int(out4[1]), "batch": int(out4[3])}
 
     # ---- online row updates (include/evstore_hip.h: evs_cache_update_rows / evs_cache_refresh_rows) ----
     def _rows_call(self, keys, values, count, assume_distinct=False):

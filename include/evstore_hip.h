@@ -628,6 +628,54 @@ EVS_API int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist, vo
 /* resident (priority, table_1based, row) triples of the batched path, unordered; returns the count.  An LRU / LFU cache reports
  * its score in the first column: LRU the way's age in batches (0 = touched by the latest batch), LFU its counter. */
 EVS_API int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t max_triples, void *stream);
+/* Warm start of the batched set-associative tier: what a tier holds, exported and given back without replaying a workload.
+ * The envelope is evs_cache_lookup_bags': a tier ALONE under batch policy 2, 8-way sets, tables in HBM; EvLFU, LRU or LFU;
+ * codec 32 / 16 / 8 / 4; the two-copy arena or the single-copy one.  The host decides every placement (evs_cache_load_plan),
+ * the device only places: one launch copies each entry's row from its backing table into the arena row its way owns and stores
+ * the way word.  The exact batch-1 engines and the alt-key tier have no warm start.
+ *
+ * evs_cache_batch_export first brings the cache to rest as evs_cache_batch_dump does (pending closes folded, an EvLFU flush the
+ * last close asked for run), so an export never carries pending work, and returns the resident count (a negative error code
+ * otherwise; entries == NULL: the count only).
+ *   entries (host): rows of 5 int64 sorted by slot -- (table_1based, row, score, age, slot)
+ *     score  EvLFU the priority 0 .. n_tables; LFU the counter 1 .. 63; LRU 0
+ *     age    (stamp of batch n - the way's stamp) mod 2^S, n the cache's batch number: 0 = filled (LRU / LFU: or touched) by
+ *            the latest batch.  The way's stamp is its word's stamp field under the policy's layout; LRU / LFU stamp batch n
+ *            with n mod 2^S, EvLFU with (n mod 0x7ffffffe) + 1 mod 2^S
+ *     slot   8 * set + way: the arena row the way owns, the copy-select bit of a two-copy arena not counted
+ *   state16 (host, may be NULL): [format version = 1, policy, capacity, n_tables, dim, codec, n, n_flush, n_evict, n_requests,
+ *     n_perfect_hits, n_hits, S, bag rule, inline-update setting (-1: never told), 0].  (n_tombstones of evs_cache_batch_stats
+ *     means nothing to a set-associative tier and is not carried: a loaded cache starts it at 0.)
+ *
+ * evs_cache_batch_load takes n such rows into a cache whose backing is set and whose batched path holds nothing yet (fresh;
+ * anything else is EVS_ESTATE).  Everything is checked on the host before the device is touched and a failure loads nothing:
+ * EVS_EINVAL for a table outside 1 .. n_tables, a row outside its table, a duplicate key, a score outside the policy's range,
+ * a negative age, a format version other than 1, a state of another policy.
+ *   strict = 1  state16 is required; its capacity, n_tables and S must be the cache's (the key universe is held by S and by the
+ *               slot check).  Every entry goes to its own slot, which must lie in the key's set and hold one entry (EVS_EINVAL);
+ *               the way words come back as exported: score, stamp = (stamp of batch n - age) mod 2^S, copy-select bit 0.
+ *   strict = 0  re-placement into THIS cache's geometry: every key's set is computed anew, ages are clamped to 2^S' - 2 (no
+ *               loaded way carries the next batch's stamp), the entries are sorted by (set, score descending, age ascending,
+ *               table, row), the first 8 of a set take its ways 0 .. 7 in that order and the rest are turned away.
+ *   state16 given: n and the five counters are restored; NULL: n = the largest (clamped) age, the counters 0.
+ *   Size, the free count and the EvLFU histogram are rebuilt from what was placed; a top bucket of max_perfect entries or more
+ *   asks for the flush exactly as a close does (it runs with the next batched call).  The bag rule and the inline-update setting
+ *   are reported, not applied.  out4 (host, may be NULL) = [placed, turned away, S of this cache, batch number after the load].
+ *   n = 0 is success without a launch.  The call returns when the load has run.  (EVS_EHIP from the launch itself -- a device
+ *   failure -- is the one error behind which the cache is no longer fresh: its batched-path state exists, another load is refused.)
+ * Refused with the reason named and the cache left usable: a tier of a C1 + C2 (+ C3) lookup, 16-way sets (EVS_SA_WAYS=16), a
+ * batch policy that is or resolves to plan / sampled (EVS_EINVAL); host-memory or file-backed tables, a cache driven by the exact
+ * path or with a resident server running, a cache whose batched path already holds state (EVS_ESTATE).
+ *
+ * evs_cache_load_plan is the placement itself, pure host code without a GPU call -- evs_cache_batch_load runs exactly this
+ * function: for a tier alone of `capacity` entries over n_tables tables of n_rows[k] rows it writes, per entry, dest_slot (-1:
+ * turned away) and the way word, and out4 as above.  EVS_EINVAL as listed, and for a geometry the set-associative form cannot
+ * take. */
+EVS_API int64_t evs_cache_batch_export(evs_cache *c, int64_t *entries, int64_t max_entries, int64_t *state16, void *stream);
+EVS_API int evs_cache_batch_load(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state16, int strict,
+                                 int64_t *out4, void *stream);
+EVS_API int evs_cache_load_plan(int policy, int64_t capacity, int n_tables, const int64_t *n_rows, int64_t n, const int64_t *entries,
+                                const int64_t *state16, int strict, int64_t *dest_slot, uint32_t *words, int64_t *out4);
 /* File-backed miss tier: the reference's mmap miss path (emb_storage/mmap_file_read.py:32-40,
  * reader pool mixed_precs_caching/evlfu_8.cpp:191-250) under the GPU cache.  evs_filetier_open maps every
  * ev-table-N.bin read-only (row r at byte row_bytes * r) and REGISTERS tables with the GPU (hipHostRegister, mapped:

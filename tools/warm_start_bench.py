@@ -1,0 +1,189 @@
+"""Warm start of the set-associative cache tier against the replay it replaces: for EvLFU, LRU and LFU in one run, on the
+bench's cache shape (10 % of the Criteo-Kaggle rows, B = 16 384, Zipf 0.75), the time of
+  replay   the --warmup fill batches bench.py pushes through a fresh tier before it measures (device events, batches ready)
+  export   GpuCache.export_state of the filled tier (host clock around a call that ends in a synchronise)
+  plan     evs_cache_load_plan over the exported entries, strict (host clock: pure host code)
+  load     evs_cache_batch_load into a fresh twin -- the same plan, the upload of the packed entry list, the launch (host clock
+           around the call, which returns when the load has run)
+  launch   the load's kernel alone over the same record list, into set words and an arena of the tool's own (the library's
+           developer entry evs_x_warm_launch), by device events
+  copy     a device-to-device copy of the bytes the launch moves (placed entries x row bytes), the yardstick of the launch
+and the hit rate of ten further batches on the original and on the loaded twin (the stream has set conflicts, so the flags are
+not bit-equal; the rates must lie within 0.01 of each other, the band tests/test_gpu_fullsize.py holds the tier to against the
+sequential oracle).  Acceptance: load (plan included) is shorter than the replay, host clock against host clock, per policy.
+ONE JSON line, also written to --out.  Every tier runs the form bench.py runs: EvLFU its one-launch update, LRU / LFU the probe / consumer / insert chain.
+
+    python tools/warm_start_bench.py [--max-rows 200000 --batch 2048] [--out profiles/warm_start.json]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import bench
+import evstore_dlrm_amd as E
+
+POLICIES = ("evlfu", "lru", "lfu")
+POLICY_ID = {"evlfu": 0, "lru": 1, "lfu": 2}
+
+
+def ms_since(t0):
+    return round((time.perf_counter() - t0) * 1e3, 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frac", type=float, default=0.10)
+    ap.add_argument("--batch", type=int, default=16384)
+    ap.add_argument("--alpha", type=float, default=0.75)
+    ap.add_argument("--warmup", type=int, default=60, help="fill batches: bench.py's replay")
+    ap.add_argument("--cmp", type=int, default=10, help="further batches on which the two hit rates are taken")
+    ap.add_argument("--rounds", type=int, default=3, help="loads per policy, each into a fresh twin")
+    ap.add_argument("--max-rows", type=int, default=0, help="clamp every table to this many rows (0: full size)")
+    ap.add_argument("--dim", type=int, default=36)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "warm_start.json"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "warm_start_bench measures on the GPU"
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    lib = E._lib.lib()
+    x_launch = C.CDLL(E._lib.LIB_PATH).evs_x_warm_launch
+    x_launch.restype, x_launch.argtypes = C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p]
+    ln = [min(n, args.max_rows) if args.max_rows else n for n in bench.KAGGLE_LN]
+    T, d, B = len(ln), args.dim, args.batch
+    cap = int(args.frac * sum(ln))
+    ev = bench.make_tables(ln, d, seed=0, device=dev)
+    rows = [b[1].t().contiguous().to(torch.int32) for b in
+            bench.make_batches(ln, B, args.warmup + args.cmp, seed=3, device=dev, dist="zipf", alpha=args.alpha)]
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    out = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+    hit = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    n_rows = np.asarray(ln, np.int64)
+    table_ptr = np.array([ev.raw[k].data_ptr() for k in range(T)], np.uint64)
+
+    def fresh(policy):
+        c = E.GpuCache(policy, cap, T, d, 32, "python", dev)
+        c.set_backing(ev)
+        return c
+
+    def replay(c, lo, hi):
+        for i in range(lo, hi):
+            c.lookup_interact(rows[i], x, out=out, hit=hit)
+
+    # every kernel of the three chains has run once before anything is timed
+    for p in POLICIES:
+        c = fresh(p)
+        replay(c, 0, 2)
+        w = fresh(p)
+        w.load_state(c.export_state())
+        del c, w
+    torch.cuda.synchronize()
+
+    res, ok = {}, True
+    for p in POLICIES:
+        r = {"replay_ms": [], "replay_wall_ms": [], "export_ms": [], "plan_ms": [], "load_ms": [], "load_launch_ms": [], "copy_ms": []}
+        state = orig = None
+        for rnd in range(args.rounds):
+            c = fresh(p)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            replay(c, 0, args.warmup)
+            e1.record()
+            torch.cuda.synchronize()
+            r["replay_wall_ms"].append(ms_since(t0))
+            r["replay_ms"].append(round(e0.elapsed_time(e1), 3))
+            t0 = time.perf_counter()
+            s = c.export_state()
+            r["export_ms"].append(ms_since(t0))
+            n = len(s["entries"])
+            dest, words, out4 = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint32), np.zeros(4, np.int64)
+            t0 = time.perf_counter()
+            E._lib.check(lib.evs_cache_load_plan(POLICY_ID[p], cap, T, n_rows.ctypes.data, n, s["entries"].ctypes.data, s["state"].ctypes.data,
+                                                 1, dest.ctypes.data, words.ctypes.data, out4.ctypes.data))
+            r["plan_ms"].append(ms_since(t0))
+            w = fresh(p)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            info = w.load_state(s)
+            r["load_ms"].append(ms_since(t0))
+            assert info["placed"] == n and info["turned_away"] == 0
+            # the launch alone: the record list the load builds (row address, slot, word), buffers of the tool's own
+            recs = np.zeros(n, np.dtype([("src", "<u8"), ("slot", "<u4"), ("word", "<u4")]))
+            recs["src"] = table_ptr[s["entries"][:, 0] - 1] + s["entries"][:, 1].astype(np.uint64) * np.uint64(d * 4)
+            recs["slot"], recs["word"] = dest[:n], words[:n]
+            recs_dev = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
+            n_slots = cap // 8 * 8
+            tags, arena = torch.zeros(n_slots, dtype=torch.int32, device=dev), torch.empty(2 * n_slots * d * 4, dtype=torch.uint8, device=dev)
+            st_ = torch.cuda.current_stream(dev).cuda_stream
+            best = None
+            nbytes = n * d * 4
+            src, dst = torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            for rep_ in range(4):          # (the first one warms the buffers' pages; a copy in front of each pushes the rows out of the caches)
+                dst.copy_(src)
+                torch.cuda.synchronize()
+                e0.record()
+                assert x_launch(recs_dev.data_ptr(), n, tags.data_ptr(), arena.data_ptr(), 1, d * 4, st_) == 0
+                e1.record()
+                torch.cuda.synchronize()
+                if rep_:
+                    best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
+            r["load_launch_ms"].append(round(best, 4))
+            assert torch.equal(tags.view(torch.int32)[torch.from_numpy(dest[:n]).to(dev)], torch.from_numpy(words[:n].view(np.int32)).to(dev))
+            del recs_dev, tags, arena
+            dst.copy_(src)
+            torch.cuda.synchronize()
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            r["copy_ms"].append(round(e0.elapsed_time(e1), 4))
+            del src, dst
+            if rnd == 0:
+                state, orig, twin = s, c, w
+            else:
+                del c, w
+        # ten further batches on the original and on the restored twin
+        rates = []
+        for c in (orig, twin):
+            s0 = c.batch_stats()
+            replay(c, args.warmup, args.warmup + args.cmp)
+            s1 = c.batch_stats()
+            rates.append((s1["n_hits"] - s0["n_hits"]) / float(T * B * args.cmp))
+        n = len(state["entries"])
+        r.update(entries=n, bytes_moved=n * d * 4, hit_rate_original=round(rates[0], 5), hit_rate_restored=round(rates[1], 5),
+                 hit_rate_gap=round(abs(rates[0] - rates[1]), 5))
+        r["launch_rate_of_copy"] = round(min(r["copy_ms"]) / min(r["load_launch_ms"]), 3)
+        r["load_shorter_than_replay"] = bool(min(r["load_ms"]) < min(r["replay_wall_ms"]))
+        r["hit_rates_within_0.01"] = bool(r["hit_rate_gap"] <= 0.01)
+        ok = ok and r["load_shorter_than_replay"] and r["hit_rates_within_0.01"]
+        res[p] = r
+        print("warm_start_bench: %s replay %.2f ms, export %.1f, plan %.1f, load %.1f (launch %.3f, copy %.3f), hit rate %.4f / %.4f"
+              % (p, min(r["replay_ms"]), min(r["export_ms"]), min(r["plan_ms"]), min(r["load_ms"]), min(r["load_launch_ms"]), min(r["copy_ms"]),
+                 rates[0], rates[1]), file=sys.stderr, flush=True)
+        del orig, twin, state
+    line = json.dumps({"tool": "warm_start_bench",
+                       "shape": {"rows": int(sum(ln)), "capacity": cap, "frac": args.frac, "batch": B, "dim": d, "codec": 32, "zipf_alpha": args.alpha,
+                                 "replay_batches": args.warmup, "hit_rate_batches": args.cmp, "rounds": args.rounds},
+                       "what": {"replay_ms": "device events around the fill batches", "replay_wall_ms": "host clock around them, ending in a synchronise",
+                                "load_ms": "host clock around evs_cache_batch_load: plan + upload + launch",
+                                "load_launch_ms": "device events around the load's kernel alone (evs_x_warm_launch, best of 3)",
+                                "copy_ms": "device-to-device copy of bytes_moved", "launch_rate_of_copy": "copy_ms / load_launch_ms, best of each",
+                                "load_shorter_than_replay": "min load_ms < min replay_wall_ms: host clock against host clock"},
+                       "policies": res, "accepted": ok})
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
