@@ -139,6 +139,13 @@ _PROTOS = {
     "evs_cache_batch_export": (_i64, [_vp, _vp, _i64, _vp, _vp]),
     "evs_cache_batch_load": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp]),
     "evs_cache_load_plan": (_int, [_int, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
+    "evs_cache_exact_export": (_i64, [_vp, _vp, _i64, _vp, _vp]),
+    "evs_cache_exact_load": (_int, [_vp, _i64, _vp, _vp, _int, _vp]),
+    "evs_exact_load_check": (_int, [_int, _i64, _int, _vp, _i64, _vp, _vp, _int, _i64]),
+    "evs_hostcache_export": (_i64, [_vp, _vp, _i64, _vp]),
+    "evs_hostcache_load": (_int, [_vp, _i64, _vp, _vp, _int]),
+    "evs_manager_export": (_i64, [_int, _vp, _i64, _vp]),
+    "evs_manager_load": (_int, [_int, _i64, _vp, _vp]),
     "evs_aprx_create": (_int, [_pp, _i64, _int]),
     "evs_aprx_destroy": (_int, [_vp]),
     "evs_aprx_set_altkeys": (_int, [_vp, _pp, _i64p]),

@@ -85,6 +85,21 @@ class _ModuleCache:
             self._bind()
         return self.cache.stats()
 
+    # ---- warm start ---------------------------------------------------------------------------------------------------------
+    def save_state(self, path):
+        """the bound engine's exact state into an .npz file (GpuCache / HostCache.save_exact_state: one format for both);
+        binds the engine first, as stats() does"""
+        if self.cache is None:
+            self._bind()
+        self.cache.save_exact_state(path)
+
+    def load_state(self, path, strict=True):
+        """a save_state file into the cache of this module, which must not have served a request since init() -- instead of
+        replaying a workload to warm it.  The file may come from either engine."""
+        if self.cache is None:
+            self._bind()
+        self.cache.load_exact_state(path, strict=strict)
+
     # ---- online row updates ----------------------------------------------------------------------------------------------
     def update_rows(self, keys, values):
         """a delta of (table index 0-based, row) -> new fp32 vector into the tables AND the cache's copies, whichever engine

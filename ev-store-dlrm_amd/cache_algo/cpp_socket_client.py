@@ -56,3 +56,44 @@ def request_to_cpp_cache(group_rowIds, use_gpu=False, use_socket=False, evstore_
     for table_idx in range(N_EVTable):
         emb_weights_in_tensor[table_idx] = flat[table_idx * EV_DIMENSION:(table_idx + 1) * EV_DIMENSION].view(1, -1)
     return emb_weights_in_tensor
+
+
+def save_state(path):
+    """warm start of the manager's tiers (evs_manager_export; no reference counterpart -- the reference's manager is warmed
+    by replaying the workload): one .npz with 'entries1' / 'state1' (and 'entries2' / 'state2' of a two-layer manager)."""
+    import numpy as np
+    L = _lib.lib() if cache_manager_cpp is None else cache_manager_cpp
+    arrays = {}
+    for tier in (1, 2):
+        if tier == 2 and L.evs_manager_tier_capacity(2) <= 0:
+            break
+        n = L.evs_manager_export(tier, None, 0, None)
+        if n < 0:
+            _lib.check(int(n))
+        entries, state = np.zeros((max(n, 1), 3), np.int64), np.zeros(20, np.int64)
+        n2 = L.evs_manager_export(tier, entries.ctypes.data, n, state.ctypes.data)
+        if n2 < 0:
+            _lib.check(int(n2))
+        arrays["entries%d" % tier], arrays["state%d" % tier] = entries[:n], state
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def load_state(path):
+    """a save_state file into the manager's tiers (evs_manager_load, strict), before the first lookup"""
+    import numpy as np
+    L = _lib.lib() if cache_manager_cpp is None else cache_manager_cpp
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            d = {k: np.ascontiguousarray(z[k], np.int64) for k in z.files}
+    except Exception as e:
+        raise _lib.EvsError(_lib.EVS_EIO, "load_state: %s is not a readable state file (%s)" % (path, e))
+    if "entries1" not in d or "state1" not in d:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: the file lacks 'entries1' / 'state1'")
+    for tier in (1, 2):
+        if "entries%d" % tier not in d:
+            break
+        entries, state = d["entries%d" % tier], d.get("state%d" % tier)
+        if entries.ndim != 2 or entries.shape[1] != 3 or state is None or state.shape != (20,):
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state: tier %d needs (n, 3) entries and a (20,) state" % tier)
+        _lib.check(L.evs_manager_load(tier, int(entries.shape[0]), entries.ctypes.data if entries.shape[0] else None, state.ctypes.data))

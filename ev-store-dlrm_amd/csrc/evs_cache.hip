@@ -26,8 +26,10 @@
 #include "evs_update.h"
 #include "evs_cache_policy.h"
 #include "evs_cache_warm.h"
+#include "evs_exact_warm.h"
 #include <type_traits>
 
+#include <chrono>
 #include <mutex>
 #include <vector>
 #include <stdlib.h>
@@ -950,6 +952,86 @@ __device__ __forceinline__ void cache_exact_body(const CacheArgs &args, const Se
 }
 __global__ void __launch_bounds__(64) cache_exact_kernel(const CacheArgs args) { cache_exact_body<false>(args, ServeArgs{}); }
 __global__ void __launch_bounds__(64) cache_serve_kernel(const CacheArgs args, const ServeArgs sv) { cache_exact_body<true>(args, sv); }
+
+// ---- warm start of the exact engine (evs_cache_exact_load): the bulk build of the map, the entry records and the arena ----------
+// The host has checked the state (evs_exact_warm.h), numbered the entries in array order -- entry i of the array IS entry index
+// i, so arena row i -- and written the list heads / tails / lengths and the scalars into CacheState.  This launch does the rest
+// in parallel, with no lane-0 loop over entries: a group of 16 lanes per entry copies the row from its backing table (HBM, or
+// host memory over the bus as the exact kernel's miss path reads it) into arena row i; the group's first lane writes the entry
+// record -- key, score, and the list links, which are i -+ 1 exactly where the neighbouring record carries the same score (the
+// lists are contiguous runs of the array) -- and inserts the key into the open-address map with the engine's own hash and
+// linear probing, claiming a slot with one 64-bit compare-and-swap on keys[] (the packed word: key and entry in that one
+// word).  Inserts only, of distinct keys: whatever the interleaving, every key ends up in the first slot of its probe walk
+// that was free when it came by and no slot before it is empty, which is all map_find and map_del's backward shift ask of
+// the table.  The same launch writes the free stack (the unused entry indices) and, for LFU, the per-frequency list heads
+// from the host's run list.  The exact kernels read all of this in a LATER launch: the kernel boundary is the only
+// visibility that is needed, so the stores are plain and the compare-and-swap is relaxed, at agent scope because the groups
+// that contend for a slot run on different compute units.
+struct ExactLoadRec { unsigned long long key; long long score; };
+static_assert(sizeof(ExactLoadRec) == 16, "one 16-byte load per entry");
+struct ExactLoadRun { long long freq; int first, last, len, pad; };
+struct ExactLoadArgs {
+    const ExactLoadRec *recs; long long n;
+    const ExactLoadRun *runs; int n_runs;     // LFU: one run per frequency present
+    CacheState *st;
+    CacheArrays a;
+    unsigned long long mask;
+    int cap, row_bytes, lfu;
+    const unsigned char *backing[kMaxTables];
+};
+constexpr int kExactLoadLanes = 16;                      // lanes per entry
+constexpr int kExactLoadGroups = 256 / kExactLoadLanes;  // entries a block takes side by side
+__global__ void __launch_bounds__(256) cache_exact_load_kernel(const ExactLoadArgs args) {
+    const int lane = (int)threadIdx.x & (kExactLoadLanes - 1), group = (int)threadIdx.x / kExactLoadLanes;
+    const CacheArrays &a = args.a;
+    const int rb = args.row_bytes;
+    for (long long i = (long long)blockIdx.x * kExactLoadGroups + group; i < args.n; i += (long long)gridDim.x * kExactLoadGroups) {
+        const ExactLoadRec r = args.recs[i];
+        const int table0 = (int)(r.key >> 32) - 1;
+        const unsigned char *src = args.backing[table0] + (unsigned long long)(unsigned)r.key * (unsigned long long)rb;
+        unsigned char *dst = a.arena + (unsigned long long)i * (unsigned long long)rb;
+        // the row: 16-byte pieces where source and destination allow them, then 4-byte pieces, then bytes
+        const unsigned long long al = (unsigned long long)reinterpret_cast<uintptr_t>(src) | (unsigned long long)reinterpret_cast<uintptr_t>(dst);
+        int off = 0;
+        if ((al & 15ull) == 0ull) {
+            const int n16 = rb >> 4;
+            for (int p = lane; p < n16; p += kExactLoadLanes) reinterpret_cast<uint4 *>(dst)[p] = reinterpret_cast<const uint4 *>(src)[p];
+            off = n16 << 4;
+        }
+        if ((al & 3ull) == 0ull) {
+            const int n4 = (rb - off) >> 2;
+            for (int p = lane; p < n4; p += kExactLoadLanes)
+                reinterpret_cast<unsigned *>(dst + off)[p] = reinterpret_cast<const unsigned *>(src + off)[p];
+            off += n4 << 2;
+        }
+        for (int b = off + lane; b < rb; b += kExactLoadLanes) dst[b] = src[b];
+        if (lane != 0) continue;
+        const int e = (int)i;
+        a.ekey[e] = r.key;
+        if (args.lfu) a.efreq[e] = r.score; else a.eagg[e] = (int)r.score;
+        a.prev[e] = (i > 0 && args.recs[i - 1].score == r.score) ? e - 1 : -1;
+        a.next[e] = (i + 1 < args.n && args.recs[i + 1].score == r.score) ? e + 1 : -1;
+        const unsigned long long word = map_word(a, r.key, e);
+        unsigned long long slot = mix64(r.key) & args.mask, tries = 0;
+        for (;; tries++) {
+            unsigned long long expect = kEmpty;
+            if (__hip_atomic_compare_exchange_strong(&a.keys[slot], &expect, word, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                a.slot_entry[slot] = e;
+                break;
+            }
+            if (tries > args.mask) { args.st->error = 2; break; }   // (no empty slot: cannot happen at load <= 0.5; never spin)
+            slot = (slot + 1) & args.mask;
+        }
+    }
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (long long)gridDim.x * blockDim.x;
+    // the free stack: pops take its top, so the unused indices n .. cap - 1 sit in slots [0, cap - n), highest first as in a fresh cache
+    for (long long j = tid; j < (long long)args.cap - args.n; j += nthreads) a.free_stack[j] = (int)((long long)args.cap - 1 - j);
+    for (long long k = tid; k < args.n_runs; k += nthreads) {
+        const ExactLoadRun u = args.runs[k];
+        a.lfu_head[u.freq] = u.first; a.lfu_tail[u.freq] = u.last; a.lfu_len[u.freq] = u.len;
+    }
+}
+
 
 
 // ------------------------------------------------------------------------------------------
@@ -3267,6 +3349,7 @@ struct evs_cache {
     int bag_rule = 0;           // evs_cache_set_bag_rule: 0 none (an EvLFU cache has no bag form), 1 "served bags"
     float *bag_pool = nullptr; long long bag_pool_floats = 0;
     int used = 0;  // 0 fresh, 1 exact path, 2 batched path
+    bool exact_touched = false;   // an exact-path request or a resident server has run on the state, or a state was loaded (evs_cache_exact_load takes untouched caches only)
     int *estamp = nullptr;      // allocated when the backing tables live in host memory
     bool host_backing = false;
     long long stamp_counter = 0;
@@ -3671,7 +3754,7 @@ extern "C" int evs_cache_request(evs_cache *c, int64_t B, const int32_t *rows, f
     for (int k = 0; k < kMaxTables; k++) { args.backing[k] = c->backing[k]; args.backing_rows[k] = c->backing_rows[k]; }
     args.requests = rows; args.out = out; args.hit = hit; args.B = B; args.approx_thres = approx_thres;
     if (c->used == 2) { set_error("evs_cache_request: this cache is used through the batched path"); return EVS_ESTATE; }
-    c->used = 1;
+    c->used = 1; c->exact_touched = true;
     { const int prc = serve_pause(c); if (prc) return prc; }
     hipLaunchKernelGGL(cache_exact_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), args);
     EVS_HIP_CHECK(hipGetLastError());
@@ -3691,6 +3774,7 @@ static void serve_launch(evs_cache *c) {
     // an exact-path launch of the caller's (evs_cache_request, evs_cache_request_c1c2[c3]) may still be running on ITS stream:
     // the server starts behind it
     if (c->exact_pending) { (void)hipStreamWaitEvent(c->serve_stream, c->exact_done, 0); c->exact_pending = false; }
+    c->exact_touched = true;
     hipLaunchKernelGGL(cache_serve_kernel, dim3(1), dim3(64), 0, c->serve_stream, args, sv);
 }
 // behind every exact-path launch: where a server started later has to wait (only caches that have a server pay the record)
@@ -3931,6 +4015,144 @@ extern "C" int64_t evs_cache_dump(evs_cache *c, int64_t *triples, int64_t max_tr
         for (int b = 0; b <= c->host.n_tables; b++) walk(h.head[b], b);
     }
     return n;
+}
+
+// ---- warm start of the exact engine (include/evstore_hip.h: evs_cache_exact_export / evs_cache_exact_load) -----------------
+// export = evs_cache_dump + the scalars of CacheState
+extern "C" int64_t evs_cache_exact_export(evs_cache *c, int64_t *entries, int64_t max_entries, int64_t *state20, void *stream) {
+    using namespace evs;
+    if (!c) { set_error("evs_cache_exact_export: NULL cache"); return EVS_EINVAL; }
+    if (c->used == 2) { set_error("evs_cache_exact_export: this cache is used through the batched path (evs_cache_batch_export)"); return EVS_ESTATE; }
+    const int64_t n = evs_cache_dump(c, entries, entries ? max_entries : 0, stream);   // (sends a resident server home first)
+    if (n < 0) { set_error("evs_cache_exact_export: reading the cache failed"); return n; }
+    if (state20) {
+        CacheState h;
+        if (hipMemcpy(&h, c->st, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); set_error("evs_cache_exact_export: reading the state failed"); return EVS_EHIP; }
+        if (h.error) { set_error("evs_cache_exact_export: cache policy error %d", h.error); return EVS_ESTATE; }
+        ExactScalars s;
+        s.min_c1 = h.min_c1; s.n_perfect = h.n_perfect; s.least_freq = h.least_freq; s.n_flush = h.n_flush; s.n_evict = h.n_evict;
+        s.n_requests = h.n_requests; s.n_perfect_hits = h.n_perfect_hits; s.n_hits = h.n_hits;
+        exact_state_fill(state20, h.policy, h.cap, h.n_tables, h.dim, h.codec, s, h.max_perfect, h.flush_n, h.perfect_mode);
+    }
+    return n;
+}
+
+// the load in its three steps: what the target and the state must be (nothing is touched), the host plan, and the device's part
+namespace {
+struct ExactLoadPlan {
+    evs::CacheState h;                       // what goes to c->st: configuration, scalars, list heads / tails / lengths
+    std::vector<evs::ExactLoadRec> recs;     // entry i of the array = entry index i
+    std::vector<evs::ExactLoadRun> runs;     // LFU: one run per frequency present
+};
+int exact_load_checked(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state20, int strict) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_exact_load: NULL cache");
+    const CacheState &cfg = c->host;
+    if (!c->has_backing) { set_error("evs_cache_exact_load: call evs_cache_set_backing first"); return EVS_ESTATE; }
+    if (c->staged_mask) { set_error("evs_cache_exact_load: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
+    if (c->used == 2) { set_error("evs_cache_exact_load: this cache is used through the batched path"); return EVS_ESTATE; }
+    if (c->serving) { set_error("evs_cache_exact_load: a resident server runs on this cache (evs_cache_serve_stop first)"); return EVS_ESTATE; }
+    if (c->tsrv) { set_error("evs_cache_exact_load: this cache belongs to a tier server"); return EVS_ESTATE; }
+    if (c->exact_touched) { set_error("evs_cache_exact_load: the cache is not fresh (the exact path has served requests or a state was loaded already)"); return EVS_ESTATE; }
+    const char *why = exact_load_check(cfg.policy, cfg.cap, cfg.n_tables, (const int64_t *)c->backing_rows, n, entries, state20, strict, c->a.lfu_max_freq);
+    if (!why && strict) why = exact_constants_check(state20, cfg.max_perfect, cfg.flush_n, cfg.perfect_mode);
+    EVS_REQUIRE(!why, "evs_cache_exact_load: %s", why);
+    return EVS_OK;
+}
+// entry i of the array takes entry index i; the lists are the runs of equal scores
+void exact_load_planned(const evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state20, ExactLoadPlan &p) {
+    using namespace evs;
+    const CacheState &cfg = c->host;
+    CacheState &h = p.h;
+    h = cfg;
+    const ExactScalars sc = exact_scalars(cfg.policy, cfg.n_tables, n, entries, state20);
+    h.min_c1 = (int)sc.min_c1; h.n_perfect = (int)sc.n_perfect; h.least_freq = sc.least_freq; h.n_flush = sc.n_flush; h.n_evict = sc.n_evict;
+    h.n_requests = sc.n_requests; h.n_perfect_hits = sc.n_perfect_hits; h.n_hits = sc.n_hits;
+    h.count = (int)n; h.n_free = cfg.cap - (int)n; h.error = 0;
+    p.recs.resize((size_t)n);
+    p.runs.clear();
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t *e = entries + 3 * i;
+        p.recs[(size_t)i].key = ((unsigned long long)e[1] << 32) | (unsigned long long)e[2];
+        p.recs[(size_t)i].score = e[0];
+        const bool first = i == 0 || e[-3] != e[0];
+        if (cfg.policy == kLFU) {
+            if (first) p.runs.push_back(ExactLoadRun{e[0], (int)i, (int)i, 0, 0});
+            p.runs.back().last = (int)i; p.runs.back().len++;
+        } else {
+            if (first) h.head[e[0]] = (int)i;
+            h.tail[e[0]] = (int)i; h.len[e[0]]++;
+        }
+    }
+}
+// upload, state copy, the one launch, the wait.  around (may be NULL): two events of the caller's, recorded around the kernel.
+int exact_load_run(evs_cache *c, const ExactLoadPlan &p, hipStream_t st, hipEvent_t *around) {
+    using namespace evs;
+    const CacheState &cfg = c->host;
+    const int64_t n = (int64_t)p.recs.size();
+    void *tmp = nullptr;
+    const size_t rec_bytes = (size_t)n * sizeof(ExactLoadRec), run_off = (rec_bytes + 255) & ~(size_t)255, run_bytes = p.runs.size() * sizeof(ExactLoadRun);
+    if (n > 0) {
+        if (hipMalloc(&tmp, run_off + run_bytes + 16) != hipSuccess) { (void)hipGetLastError(); set_error("evs_cache_exact_load: hipMalloc(%lld bytes) failed", (long long)(run_off + run_bytes)); return EVS_ENOMEM; }
+        auto fail = [&](const char *what) { (void)hipGetLastError(); (void)hipFree(tmp); set_error("evs_cache_exact_load: %s failed", what); return EVS_EHIP; };
+        if (hipMemcpyAsync(tmp, p.recs.data(), rec_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return fail("the upload of the records");
+        if (run_bytes && hipMemcpyAsync(static_cast<char *>(tmp) + run_off, p.runs.data(), run_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return fail("the upload of the run list");
+    }
+    // from here on the cache is no longer fresh, whatever happens
+    c->used = 1; c->exact_touched = true;
+    if (hipMemcpyAsync(c->st, &p.h, sizeof p.h, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); if (tmp) (void)hipFree(tmp); set_error("evs_cache_exact_load: the state copy failed"); return EVS_EHIP; }
+    if (n > 0) {
+        ExactLoadArgs la;
+        la.recs = static_cast<const ExactLoadRec *>(tmp); la.n = n;
+        la.runs = reinterpret_cast<const ExactLoadRun *>(static_cast<char *>(tmp) + run_off); la.n_runs = (int)p.runs.size();
+        la.st = c->st; la.a = c->a; la.mask = cfg.nslot_mask; la.cap = cfg.cap; la.row_bytes = cfg.row_bytes; la.lfu = cfg.policy == kLFU;
+        for (int k = 0; k < kMaxTables; k++) la.backing[k] = c->backing[k];
+        long long grid = (n + kExactLoadGroups - 1) / kExactLoadGroups;
+        if (grid > (long long)kNumCu * 8) grid = (long long)kNumCu * 8;
+        if (around) (void)hipEventRecord(around[0], st);
+        hipLaunchKernelGGL(cache_exact_load_kernel, dim3((unsigned)grid), dim3(256), 0, st, la);
+        if (around) (void)hipEventRecord(around[1], st);
+        if (hipGetLastError() != hipSuccess) { (void)hipFree(tmp); set_error("evs_cache_exact_load: the launch failed"); return EVS_EHIP; }
+    }
+    const hipError_t se = hipStreamSynchronize(st);   // (the records are freed below; the plan is the caller's until this returns)
+    if (tmp) (void)hipFree(tmp);
+    if (se != hipSuccess) { (void)hipGetLastError(); set_error("evs_cache_exact_load: the load did not finish: %s", hipGetErrorString(se)); return EVS_EHIP; }
+    return exact_launched(c, st);
+}
+}  // namespace
+
+extern "C" int evs_cache_exact_load(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state20, int strict, void *stream) {
+    const int rc = exact_load_checked(c, n, entries, state20, strict);
+    if (rc) return rc;
+    ExactLoadPlan plan;
+    exact_load_planned(c, n, entries, state20, plan);
+    return exact_load_run(c, plan, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+// developer entry (tools/warm_start_bench.py --exact; not part of the ABI): evs_cache_exact_load's three steps with a clock
+// between them.  out4 (ms): [the host checks, the host plan, upload + launch + wait by the host clock, the kernel alone by
+// device events].  The timing lives here, not in the entry point: a load of the product reads no clock and makes no event.
+extern "C" __attribute__((visibility("default"))) int evs_x_exact_load_timed(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state20,
+                                                                             int strict, void *stream, double *out4) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = clk::now();
+    int rc = exact_load_checked(c, n, entries, state20, strict);
+    if (rc) return rc;
+    const auto t1 = clk::now();
+    ExactLoadPlan plan;
+    exact_load_planned(c, n, entries, state20, plan);
+    const auto t2 = clk::now();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool have = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (!have) (void)hipGetLastError();
+    rc = exact_load_run(c, plan, reinterpret_cast<hipStream_t>(stream), have && n > 0 ? ev : nullptr);
+    const auto t3 = clk::now();
+    float kernel_ms = 0.0f;
+    if (rc == EVS_OK && have && n > 0 && hipEventElapsedTime(&kernel_ms, ev[0], ev[1]) != hipSuccess) { (void)hipGetLastError(); kernel_ms = 0.0f; }
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (out4) { out4[0] = ms(t0, t1); out4[1] = ms(t1, t2); out4[2] = ms(t2, t3); out4[3] = kernel_ms; }
+    return rc;
 }
 
 extern "C" int evs_cache_request_c1c2c3(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B, const int32_t *rows,
@@ -5605,6 +5827,7 @@ static void tiers_launch(evs_tier_server *s) {
     sv.ring = s->ring; sv.n_slots = s->slots; sv.idle_ticks = s->idle_ticks;
     // a launch-per-call request on the members may still be running on the caller's stream: the server starts behind it
     if (s->exact_pending) { (void)hipStreamWaitEvent(s->stream, s->exact_done, 0); s->exact_pending = false; }
+    s->c1->exact_touched = s->c2->exact_touched = true;
     hipLaunchKernelGGL(cache_c1c2_serve_kernel, dim3(1), dim3(64), 0, s->stream, args, sv);
 }
 static int tiers_launched(evs_tier_server *s, hipStream_t st) {
@@ -5793,7 +6016,7 @@ extern "C" int evs_cache_request_c1c2c3(evs_cache *c1, evs_cache *c2, evs_aprx *
     EVS_REQUIRE(B > 0 && rows && out && tier, "evs_cache_request_c1c2c3: NULL argument");
     if (c1->used == 2 || c2->used == 2) { set_error("evs_cache_request_c1c2c3: a tier is used through the batched path"); return EVS_ESTATE; }
     { const int p1 = serve_pause(c1), p2 = serve_pause(c2), p3 = aprx_pause(c3); if (p1 || p2 || p3) return EVS_EHIP; }
-    c1->used = c2->used = 1;
+    c1->used = c2->used = 1; c1->exact_touched = c2->exact_touched = true;
     C1C2Args args;
     tiers_args(c1, c2, c3, high_agghit_threshold, args);
     args.requests = rows; args.out = out; args.tier_out = tier; args.B = B;

@@ -22,6 +22,7 @@
 //   + alt keys  evlfu_8.cpp:474-490,492-667 with aprx_embedding.cpp as the deterministic re-specification of
 //           include/evstore_hip.h (evs_aprx_*): evicted keys become visible 50 at a time, at the start of a request.
 #include "evs_common.h"
+#include "evs_exact_warm.h"
 
 #include <algorithm>
 #include <math.h>
@@ -153,6 +154,7 @@ struct Tier {
     const uint8_t *tables[kMaxT] = {nullptr};
     int64_t n_rows[kMaxT] = {0};
     bool bound = false;
+    bool used = false;   // a request has run or a state was loaded: no longer a target of evs_hostcache_load
 
     ~Tier() { map.destroy(); free(ent); free(arena); free(free_stack); }
 
@@ -620,6 +622,7 @@ extern "C" int evs_hostcache_request(evs_hostcache *c, int64_t B, const int32_t 
     if (!c->t.bound) { set_error("evs_hostcache_request: no backing tables (evs_hostcache_set_backing)"); return EVS_ESTATE; }
     if (c->t.error) { set_error("evs_hostcache_request: the policy hit an inconsistency earlier (%d)", c->t.error); return EVS_ESTATE; }
     host::Tier &t = c->t;
+    t.used = true;
     for (int64_t b = 0; b < B; b++) {
         const int32_t *r = rows + b * t.T;
         float *o = out + b * (int64_t)t.T * t.dim;
@@ -648,6 +651,7 @@ extern "C" int evs_hostcache_request_c1c2c3(evs_hostcache *c1, evs_hostcache *c2
         }
     }
     if (c1->t.error || c2->t.error) { set_error("evs_hostcache_request_c1c2c3: the policy hit an inconsistency earlier"); return EVS_ESTATE; }
+    c1->t.used = c2->t.used = true;
     for (int64_t b = 0; b < B; b++) {
         const int rc = host::tiers_request(c1->t, c2->t, c3 ? &c3->a : nullptr, rows + b * c1->t.T, tier + b * c1->t.T,
                                            out + b * (int64_t)c1->t.T * c1->t.dim, high_agghit_threshold);
@@ -719,6 +723,53 @@ extern "C" int64_t evs_hostcache_dump(evs_hostcache *c, int64_t *triples, int64_
         for (int64_t f : fs) emit(f, t.freq.at(f));
     }
     return n;
+}
+
+// ---- warm start (include/evstore_hip.h: evs_hostcache_export / evs_hostcache_load; the format and the checks: evs_exact_warm.h) ----
+extern "C" int evs_exact_load_check(int policy, int64_t capacity, int n_tables, const int64_t *n_rows, int64_t n, const int64_t *entries,
+                                    const int64_t *state20, int strict, int64_t max_freq) {
+    using namespace evs;
+    const char *why = exact_load_check(policy, capacity, n_tables, n_rows, n, entries, state20, strict, max_freq);
+    EVS_REQUIRE(!why, "evs_exact_load_check: %s", why);
+    return EVS_OK;
+}
+
+extern "C" int64_t evs_hostcache_export(evs_hostcache *c, int64_t *entries, int64_t max_entries, int64_t *state20) {
+    using namespace evs;
+    if (!c) { set_error("evs_hostcache_export: NULL"); return EVS_EINVAL; }
+    const host::Tier &t = c->t;
+    if (t.error) { set_error("evs_hostcache_export: the policy hit an inconsistency (%d)", t.error); return EVS_ESTATE; }
+    const int64_t n = evs_hostcache_dump(c, entries, entries ? max_entries : 0);
+    if (state20) {
+        ExactScalars s;
+        s.min_c1 = t.min_c1; s.n_perfect = t.n_perfect; s.least_freq = t.least_freq; s.n_flush = t.n_flush; s.n_evict = t.n_evict;
+        s.n_requests = t.n_requests; s.n_perfect_hits = t.n_perfect_hits; s.n_hits = t.n_hits;
+        exact_state_fill(state20, t.policy, t.cap, t.T, t.dim, t.codec, s, t.max_perfect, (int64_t)(t.flush_rate * t.cap) + t.flush_extra, t.perfect_mode);
+    }
+    return n;
+}
+
+extern "C" int evs_hostcache_load(evs_hostcache *c, int64_t n, const int64_t *entries, const int64_t *state20, int strict) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_hostcache_load: NULL cache");
+    host::Tier &t = c->t;
+    if (!t.bound) { set_error("evs_hostcache_load: no backing tables (evs_hostcache_set_backing)"); return EVS_ESTATE; }
+    if (t.used) { set_error("evs_hostcache_load: the cache is not fresh (it has served requests or was loaded already)"); return EVS_ESTATE; }
+    const char *why = exact_load_check(t.policy, t.cap, t.T, t.n_rows, n, entries, state20, strict, 0);
+    if (!why && strict) why = exact_constants_check(state20, t.max_perfect, (int64_t)(t.flush_rate * t.cap) + t.flush_extra, t.perfect_mode);
+    EVS_REQUIRE(!why, "evs_hostcache_load: %s", why);
+    // array order is list order: every entry goes to the tail of its score's list (entry i takes entry index i)
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t *e = entries + 3 * i;
+        const int32_t en = t.take(host::make_key((int)e[1] - 1, (int32_t)(uint32_t)e[2]), t.backing_row((int)e[1] - 1, e[2]));
+        t.ent[en].prio = e[0];
+        t.push_back(t.policy == 2 ? t.freq[e[0]] : t.buckets[e[0]], en);
+    }
+    const ExactScalars s = exact_scalars(t.policy, t.T, n, entries, state20);
+    t.min_c1 = (int)s.min_c1; t.n_perfect = s.n_perfect; t.least_freq = s.least_freq; t.n_flush = s.n_flush; t.n_evict = s.n_evict;
+    t.n_requests = s.n_requests; t.n_perfect_hits = s.n_perfect_hits; t.n_hits = s.n_hits;
+    t.used = true;
+    return EVS_OK;
 }
 
 extern "C" int evs_hostaprx_create(evs_hostaprx **out, int64_t capacity, int n_tables) {

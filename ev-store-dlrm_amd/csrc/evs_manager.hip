@@ -354,6 +354,50 @@ extern "C" int evs_manager_configure(int n_caching_layer, int main_precision, in
     return ensure_ready();
 }
 
+// Warm start of the manager's tiers (include/evstore_hip.h: evs_manager_export / evs_manager_load): tier 1 / 2 of whichever
+// engine ev_lookup runs, each exported and loaded on its own -- a C1 + C2 pair keeps no state outside its two caches.
+static int manager_tier_check(const char *who, int tier) {
+    using namespace evs;
+    const int rc = ensure_ready();
+    if (rc) return rc;
+    EVS_REQUIRE(g_mgr.n_layer != 3, "%s: N_CACHING_LAYER=3 has no warm start (the alt-key tier's pending evictions cannot be exported)", who);
+    EVS_REQUIRE(tier == 1 || (tier == 2 && g_mgr.n_layer == 2), "%s: tier %d of a manager with %d layer(s)", who, tier, g_mgr.n_layer);
+    return EVS_OK;
+}
+
+extern "C" int64_t evs_manager_export(int tier, int64_t *entries, int64_t max, int64_t *state20) {
+    using namespace evs;
+    const int rc = manager_tier_check("evs_manager_export", tier);
+    if (rc) return rc;
+    Manager &m = g_mgr;
+    if (m.h1) return evs_hostcache_export(tier == 1 ? m.h1 : m.h2, entries, max, state20);
+    return evs_cache_exact_export(tier == 1 ? m.c1 : m.c2, entries, max, state20, m.stream);   // (a resident server goes home first; the next lookup starts it again)
+}
+
+extern "C" int evs_manager_load(int tier, int64_t n, const int64_t *entries, const int64_t *state20) {
+    using namespace evs;
+    int rc = manager_tier_check("evs_manager_load", tier);
+    if (rc) return rc;
+    Manager &m = g_mgr;
+    if (m.h1) return evs_hostcache_load(tier == 1 ? m.h1 : m.h2, n, entries, state20, 1);
+    evs_cache *c = tier == 1 ? m.c1 : m.c2;
+    if (!m.serve) {
+        rc = evs_cache_exact_load(c, n, entries, state20, 1, m.stream);
+        return rc;
+    }
+    // behind a resident server: the server is taken off the tiers, the load runs, the server is armed again (its kernel starts
+    // with the next lookup) -- also when the load was refused, so that the manager stays usable
+    constexpr int64_t kIdleUs = 200;
+    if (m.tsrv) { (void)evs_tiers_serve_destroy(m.tsrv); m.tsrv = nullptr; }
+    else { rc = evs_cache_serve_stop(m.c1); if (rc) return rc; }
+    rc = evs_cache_exact_load(c, n, entries, state20, 1, m.stream);
+    std::string why = rc ? evs_last_error() : "";
+    const int src = m.c2 ? evs_tiers_serve_start(&m.tsrv, m.c1, m.c2, m.c3, 23 /* evlfu_8.hpp:70 */, m.serve_ring, 1, kIdleUs)
+                         : evs_cache_serve_start(m.c1, -1, m.serve_ring, 1, kIdleUs);
+    if (rc) { set_error("%s", why.c_str()); return rc; }
+    return src;
+}
+
 // cache_manager.cpp:231-237.  Reads N_EV_TABLE int32 row ids (table = position), returns the
 // library-owned static float[26*36] (valid until the next call; single caller thread).
 // On a configuration error the reference prints and exit(-1)s; this returns NULL after printing.

@@ -87,6 +87,40 @@ class FileTier:
             pass
 
 
+def read_exact_state(state_or_path, who="load_exact_state"):
+    """what export_exact_state returned, or the path of a save_exact_state file (read with allow_pickle=False) ->
+    (entries (n, 3) int64, state (20,) int64 or None, n_rows int64 array or None); shared by GpuCache and HostCache"""
+    import numpy as np
+    if isinstance(state_or_path, dict):
+        d = state_or_path
+    else:
+        try:
+            with np.load(state_or_path, allow_pickle=False) as z:
+                d = {k: z[k] for k in z.files}
+        except Exception as e:
+            raise _lib.EvsError(_lib.EVS_EIO, "%s: %s is not a readable state file (%s)" % (who, state_or_path, e))
+    missing = [k for k in ("entries", "state") + (() if isinstance(state_or_path, dict) else ("n_rows",)) if k not in d]
+    if missing:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "%s: the state lacks %s" % (who, ", ".join(repr(k) for k in missing)))
+    entries = np.ascontiguousarray(d["entries"], np.int64)
+    state = None if d["state"] is None else np.ascontiguousarray(d["state"], np.int64)
+    if entries.ndim != 2 or entries.shape[1] != 3:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "%s: 'entries' must be (n, 3) rows of (score, table_1based, row) -- is this a state of the "
+                                             "batched tier (export_state / load_state)?" % who)
+    if state is not None and int(state.reshape(-1)[0] if state.size else 0) != 2:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "%s: unknown format version (the exact engines take version 2)" % who)
+    if state is not None and state.shape != (20,):
+        raise _lib.EvsError(_lib.EVS_EINVAL, "%s: 'state' must be (20,)" % who)
+    n_rows = d.get("n_rows")
+    return entries, state, None if n_rows is None else np.asarray(n_rows).astype(np.int64)
+
+
+def check_exact_rows(n_rows, mine, strict, who="load_exact_state"):
+    """a strict load needs backing tables of the exporter's row counts"""
+    if strict and n_rows is not None and n_rows.size and mine is not None and list(n_rows) != [int(v) for v in mine]:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "%s: a strict load needs backing tables of the exporter's row counts" % who)
+
+
 _hwq_warned = False
 
 
@@ -446,6 +480,47 @@ class GpuCache:
             if int(state[14]) >= 0 and not getattr(self, "_inline_told", False) and (self.policy == "evlfu" or int(state[14]) == 0):
                 self.set_inline_update(bool(state[14]))
         return {"placed": int(out4[0]), "turned_away": int(out4[1]), "batch": int(out4[3])}
+
+    # ---- warm start of the exact path (include/evstore_hip.h: evs_cache_exact_export / evs_cache_exact_load) ----
+    def export_exact_state(self):
+        """What the exact (batch-1) engine holds -> a dict of numpy arrays: 'entries' (n, 3) int64 = dump()'s rows in list
+        order, 'state' (20,) int64 (format version 2, policy, capacity, n_tables, dim, codec, min_C1, n_perfect, least_freq,
+        five counters, max_perfect, flush_n, perfect_mode, 0, 0, 0) and 'n_rows' (T,) int64, the rows of the backing tables.
+        A resident server is sent home first.  HostCache.export_exact_state gives the same arrays for the same requests."""
+        import numpy as np
+        L, st = _lib.lib(), torch.cuda.current_stream(self.device).cuda_stream
+        state = np.zeros(20, np.int64)
+        with torch.cuda.device(self.device):
+            n = L.evs_cache_exact_export(self._h, None, 0, None, st)
+            if n < 0:
+                _lib.check(int(n))
+            entries = np.zeros((max(n, 1), 3), np.int64)
+            n2 = L.evs_cache_exact_export(self._h, entries.ctypes.data, n, state.ctypes.data, st)
+        if n2 != n:
+            if n2 < 0:
+                _lib.check(int(n2))
+            raise _lib.EvsError(_lib.EVS_ESTATE, "export_exact_state: the cache changed between the count and the export")
+        return {"entries": entries[:n], "state": state, "n_rows": np.asarray(getattr(self, "_n_rows", []), np.int64)}
+
+    def save_exact_state(self, path):
+        """export_exact_state() into an .npz file (read back by load_exact_state with allow_pickle=False)"""
+        import numpy as np
+        with open(path, "wb") as f:
+            np.savez(f, **self.export_exact_state())
+
+    def load_exact_state(self, state_or_path, strict=True):
+        """Warm start of the exact path: the exported entries into this cache, which must be fresh with its backing set -- ONE
+        parallel launch builds the map, the entry records, the lists and the arena; no request is replayed.  state_or_path:
+        what export_exact_state returned (of a GpuCache or a HostCache), or the path of a save_exact_state file.
+        strict=True: the cache must have the exporter's policy, capacity, tables and EvLFU constants, and continues exactly
+        as the exporter would have; strict=False: any capacity >= n, 'state' may be None (scalars derived, counters 0)."""
+        entries, state, n_rows = read_exact_state(state_or_path)
+        check_exact_rows(n_rows, getattr(self, "_n_rows", None), strict)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().evs_cache_exact_load(self._h, int(entries.shape[0]), entries.ctypes.data if entries.shape[0] else None,
+                                                       None if state is None else state.ctypes.data, 1 if strict else 0,
+                                                       torch.cuda.current_stream(self.device).cuda_stream))
+        return self
 
     # ---- online row updates (include/evstore_hip.h: evs_cache_update_rows / evs_cache_refresh_rows) ----
     def _rows_call(self, keys, values, count, assume_distinct=False):

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gpu_cache import EVLFU_VARIANTS, POLICY
+from .gpu_cache import EVLFU_VARIANTS, POLICY, check_exact_rows, read_exact_state
 
 
 def _np(a, dtype):
@@ -56,6 +56,7 @@ class HostCache:
             ptrs.append(a.ctypes.data)
             rows.append(a.nbytes // rb)
         self._backing = keep
+        self._n_rows = rows
         _lib.check(_lib.lib().evs_hostcache_set_backing(self._h, (C.c_void_p * self.n_tables)(*ptrs), (C.c_int64 * self.n_tables)(*rows)))
         return self
 
@@ -104,6 +105,34 @@ class HostCache:
         out = np.zeros((max(n, 1), 3), np.int64)
         _lib.lib().evs_hostcache_dump(self._h, out.ctypes.data, n)
         return out[:n]
+
+
+    # ---- warm start (include/evstore_hip.h: evs_hostcache_export / evs_hostcache_load) ----
+    def export_exact_state(self):
+        """-> {'entries' (n, 3) int64 = dump() in list order, 'state' (20,) int64, 'n_rows' (T,) int64}: the format of
+        GpuCache.export_exact_state -- a state saved by one engine loads into the other."""
+        L = _lib.lib()
+        state = np.zeros(20, np.int64)
+        n = L.evs_hostcache_export(self._h, None, 0, None)
+        if n < 0:
+            _lib.check(int(n))
+        entries = np.zeros((max(n, 1), 3), np.int64)
+        n2 = L.evs_hostcache_export(self._h, entries.ctypes.data, n, state.ctypes.data)
+        if n2 < 0:
+            _lib.check(int(n2))
+        return {"entries": entries[:n], "state": state, "n_rows": np.asarray(getattr(self, "_n_rows", []), np.int64)}
+
+    def save_exact_state(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, **self.export_exact_state())
+
+    def load_exact_state(self, state_or_path, strict=True):
+        """the exported entries into this cache, which must be fresh with its backing set (GpuCache.load_exact_state's rules)"""
+        entries, state, n_rows = read_exact_state(state_or_path)
+        check_exact_rows(n_rows, getattr(self, "_n_rows", None), strict)
+        _lib.check(_lib.lib().evs_hostcache_load(self._h, int(entries.shape[0]), entries.ctypes.data if entries.shape[0] else None,
+                                                 None if state is None else state.ctypes.data, 1 if strict else 0))
+        return self
 
 
 class HostAltKeyTier:

@@ -7,6 +7,7 @@
                                                  the difference of consecutive stamps, so it includes the loader and
                                                  whatever the loop does with Z
   warm-up                                        dlrm_s_pytorch_C1.py:2224-2242  one full replay of the same workload
+                                                 (inference(..., warm_state=path) loads a saved cache state instead)
   calculate_and_write_cdf(dir, algo, stamps)     dlrm_s_pytorch_C1.py:299-326  sorted latencies thinned to ~1000 points,
                                                  CSV columns y, latency_ms
 
@@ -30,10 +31,24 @@ def dlrm_wrap(forward, X, lS_o, lS_i, use_gpu, device, non_blocking=False):
     return forward(X, lS_o, lS_i)
 
 
-def inference(test_ld, forward, use_gpu=True, device="cuda", consume=None, non_blocking=False):
+def _load_warm_state(warm_state, load_state):
+    """warm_state: the path of a state file a cache module's save_state wrote; load_state: what takes it (default: the
+    EvLFU_C1 module's load_state -- the reference's default cache, dlrm_s_pytorch_C1.py:227-275)"""
+    if load_state is None:
+        from .cache_algo import EvLFU_C1
+        load_state = EvLFU_C1.load_state
+    load_state(warm_state)
+
+
+def inference(test_ld, forward, use_gpu=True, device="cuda", consume=None, non_blocking=False, warm_state=None, load_state=None):
     """The timing loop of dlrm_s_pytorch_C1.py:inference(): stamps at the top of every request and one after the last.
     test_ld yields (X, lS_o, lS_i) host batches; consume(Z) stands for what the loop does with the result (the
-    reference copies Z to the host, :1025, unless --ev-lookup-only).  -> arr_time_start (len = requests + 1)."""
+    reference copies Z to the host, :1025, unless --ev-lookup-only).  -> arr_time_start (len = requests + 1).
+    warm_state (a path; default None: nothing changes): the cache tier is given that saved state before the first stamp --
+    load_state(warm_state), by default cache_algo.EvLFU_C1.load_state -- INSTEAD of the warm-up replay, which the reference
+    (and bench.py) make by calling this loop once untimed in front of the timed pass: with warm_state that first call goes."""
+    if warm_state is not None:
+        _load_warm_state(warm_state, load_state)
     arr_time_start = []
     for X, lS_o, lS_i in test_ld:
         arr_time_start.append(time.time())

@@ -632,7 +632,8 @@ EVS_API int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t max
  * The envelope is evs_cache_lookup_bags': a tier ALONE under batch policy 2, 8-way sets, tables in HBM; EvLFU, LRU or LFU;
  * codec 32 / 16 / 8 / 4; the two-copy arena or the single-copy one.  The host decides every placement (evs_cache_load_plan),
  * the device only places: one launch copies each entry's row from its backing table into the arena row its way owns and stores
- * the way word.  The exact batch-1 engines and the alt-key tier have no warm start.
+ * the way word.  The exact batch-1 engines have a warm start of their own (evs_cache_exact_export / evs_cache_exact_load, below;
+ * the two state formats are not converted into each other); the alt-key tier has none.
  *
  * evs_cache_batch_export first brings the cache to rest as evs_cache_batch_dump does (pending closes folded, an EvLFU flush the
  * last close asked for run), so an export never carries pending work, and returns the resident count (a negative error code
@@ -758,6 +759,56 @@ EVS_API int evs_cache_reset_counters(evs_cache *c, void *stream);
 /* Resident keys in list order as (bucket | frequency | 0, table_1based, row) triples (host);
  * returns the number of resident keys (or a negative error). */
 EVS_API int64_t evs_cache_dump(evs_cache *c, int64_t *triples, int64_t max_triples, void *stream);
+/* Warm start of the EXACT batch-1 engines -- this one and the host engine below (evs_hostcache_export / _load) share the format,
+ * so a state saved by one loads into the other.  The exact policies are deterministic: a fresh cache that loads the export of
+ * a cache cut anywhere in a request stream and continues the stream gives, bit for bit, the hit flags, rows, list order and
+ * counters of the uncut run (tests/test_exact_warm_host.py, tests/test_gpu_exact_warm.py on the reference's golden traces).
+ *   entries (host): n rows of 3 int64 = evs_cache_dump's triples in its order: (score, table_1based, row); score = the EvLFU
+ *     bucket 0 .. n_tables, the LFU frequency >= 1, 0 for LRU.  Array order IS list order: EvLFU buckets ascending and front to
+ *     back inside a bucket, LFU frequencies ascending and FIFO inside a frequency, LRU the recency list front to back.
+ *   state20 (host): [format version = 2, policy, capacity, n_tables, dim, codec, min_C1, n_perfect, least_freq, n_flush, n_evict,
+ *     n_requests, n_perfect_hits, n_hits, max_perfect, flush_n, perfect_mode, 0, 0, 0].  (Version 1 is the batched tier's state16;
+ *     neither loader accepts the other's state.)  Arena slot numbers, the free-stack order and the hash layout are not part of
+ *     the state: no entry point can observe them.
+ * evs_cache_exact_export = evs_cache_dump (a resident server is sent home first) plus the state; returns the resident count,
+ *   entries == NULL: the count only; state20 may be NULL.  EVS_ESTATE for a cache on the batched path.
+ * evs_cache_exact_load gives a state to a FRESH cache: backing set, never used through either path, no server running, not a
+ *   member of a tier server -- anything else is EVS_ESTATE and the cache stays usable, as for staged file-backed tables (the
+ *   exact path does not serve them; pinned-host tables and registered file-tier tables are accepted, the kernel reads their rows
+ *   over the bus as the exact engine's miss path does).  Everything is checked on the host before the device is touched, by
+ *   evs_exact_load_check (pure host code, callable without a GPU; both loaders run exactly this function), and a failure loads
+ *   nothing: EVS_EINVAL, the reason named, for a table outside 1 .. n_tables, a row outside its table, a duplicate key, a score
+ *   outside the policy's range (EvLFU 0 .. n_tables, LRU 0, LFU 1 .. max_freq - 2 with max_freq the device engine's 2^22; the
+ *   host engine passes 0 = unbounded), scores that are not non-decreasing along the array (the lists must be contiguous runs),
+ *   n > capacity (no shrinking: re-placement into a smaller tier is the batched tier's feature), a version other than 2, a state
+ *   of another policy, state scalars out of range (min_C1 outside 0 .. n_tables, least_freq < 1 or beyond max_freq - 1, a
+ *   negative counter).
+ *     strict = 1  state20 is required; its policy, capacity, n_tables, max_perfect, flush_n and perfect_mode must equal the
+ *                 cache's; min_C1, n_perfect, least_freq and the five counters are restored; dim and codec are reported, not
+ *                 compared (rows always come from the cache's own backing).  The cache then continues exactly as the exporter
+ *                 would have.
+ *     strict = 0  any capacity >= n and any constants; with state20 the scalars are taken from it -- range-checked and otherwise
+ *                 TRUSTED: min_C1, least_freq and n_perfect are not functions of the entries (the reference lets the first two
+ *                 rest on an empty list and recounts the third only at a perfect request or a flush), so they are not compared
+ *                 with the run lengths; a made-up value moves a flush or an eviction, or raises the policy's sticky error
+ *                 (EVS_ESTATE from evs_cache_stats), and corrupts nothing --, with state20 = NULL they are
+ *                 derived: min_C1 = the lowest non-empty bucket (0 when empty), n_perfect = the length of bucket n_tables,
+ *                 least_freq = the lowest frequency present (1 when empty), counters 0.
+ *   The device load is ONE parallel launch: entry i of the array becomes entry index i (arena row i); a lane group per entry
+ *   copies the row from the backing table, one lane writes the entry record and its list links and claims the key's slot of the
+ *   open-address map with a 64-bit compare-and-swap; the same launch writes the free stack and the LFU list heads.  No request
+ *   is replayed.  n = 0 is success without a launch; the call returns when the load has run.  On success the cache is an
+ *   exact-path cache: evs_cache_lookup_batch on it is refused (EVS_ESTATE) as for any exact-path cache.  Both map forms are
+ *   built: the packed one (capacity <= 2^25: key and entry in the one word the compare-and-swap installs) and the unpacked one
+ *   (larger caches: the key by compare-and-swap, the entry beside it in slot_entry[]).
+ *   (EVS_EHIP from the copies or the launch is the one error behind which the cache is no longer fresh.)
+ * A C1 + C2 pair is exported and loaded one cache at a time: without an alt-key tier the pair keeps no state outside its two
+ * caches.  OUT OF SCOPE: the alt-key tier (evs_aprx / evs_hostaprx: its pending-eviction queue is not dumpable), and converting
+ * between this format and the batched tier's. */
+EVS_API int64_t evs_cache_exact_export(evs_cache *c, int64_t *entries, int64_t max_entries, int64_t *state20, void *stream);
+EVS_API int evs_cache_exact_load(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state20, int strict, void *stream);
+EVS_API int evs_exact_load_check(int policy, int64_t capacity, int n_tables, const int64_t *n_rows, int64_t n, const int64_t *entries,
+                                 const int64_t *state20, int strict, int64_t max_freq);   /* pure host */
 
 /* ---------------------------------------------------------------------------
  * a6-a9, a12 at batch 1: the HOST engine of the exact policies (csrc/evs_hostcache.hip).
@@ -792,6 +843,11 @@ EVS_API int evs_hostcache_request_c1c2c3(evs_hostcache *c1, evs_hostcache *c2, e
 EVS_API int evs_hostcache_stats(evs_hostcache *c, int64_t *out8);
 EVS_API int evs_hostcache_reset_counters(evs_hostcache *c);
 EVS_API int64_t evs_hostcache_dump(evs_hostcache *c, int64_t *triples, int64_t max_triples);
+/* Warm start of the host engine: evs_cache_exact_export / evs_cache_exact_load's format, checks and strict / non-strict rules
+ * (above), in pure host code -- the load builds the tier from its own take / push_back primitives in array order, then sets the
+ * scalars.  The target must be fresh (backing set, no request served, nothing loaded): EVS_ESTATE otherwise. */
+EVS_API int64_t evs_hostcache_export(evs_hostcache *c, int64_t *entries, int64_t max_entries, int64_t *state20);
+EVS_API int evs_hostcache_load(evs_hostcache *c, int64_t n, const int64_t *entries, const int64_t *state20, int strict);
 EVS_API int evs_hostaprx_create(evs_hostaprx **out, int64_t capacity, int n_tables);
 EVS_API int evs_hostaprx_destroy(evs_hostaprx *p);
 EVS_API int evs_hostaprx_set_altkeys(evs_hostaprx *p, const uint32_t *const *alt_tables, const int64_t *n_rows);
@@ -880,6 +936,11 @@ EVS_API long long evs_manager_aprx_hit(void);             /* evlfu_8bit->aprx_ev
  * pinned: evs_cache_serve_request_to for one layer, evs_tiers_serve_request_to for two / three; the server is stopped at exit).
  * Reads the manager's fields only: callable without a GPU. */
 EVS_API int evs_manager_engine(void);
+/* Warm start of the manager's tiers: evs_cache_exact_export / evs_hostcache_export (and the strict loads) forwarded to tier 1 | 2
+ * of whichever engine ev_lookup runs; the manager is initialised first, as ev_lookup does.  A resident server is stopped first
+ * and started again by the next lookup.  n_caching_layer == 3 is refused (EVS_EINVAL): the alt-key tier has no export. */
+EVS_API int64_t evs_manager_export(int tier, int64_t *entries, int64_t max, int64_t *state20);
+EVS_API int evs_manager_load(int tier, int64_t n, const int64_t *entries, const int64_t *state20);
 EVS_API float *ev_lookup(int *arr);                      /* cache_manager.cpp:231 */
 EVS_API float *get_ev_values(int *arr);                  /* cache_manager.cpp:257 */
 EVS_API void print_perfect_hit(void);                    /* cache_manager.cpp:262 */

@@ -13,7 +13,15 @@ not bit-equal; the rates must lie within 0.01 of each other, the band tests/test
 sequential oracle).  Acceptance: load (plan included) is shorter than the replay, host clock against host clock, per policy.
 ONE JSON line, also written to --out.  Every tier runs the form bench.py runs: EvLFU its one-launch update, LRU / LFU the probe / consumer / insert chain.
 
-    python tools/warm_start_bench.py [--max-rows 200000 --batch 2048] [--out profiles/warm_start.json]"""
+    python tools/warm_start_bench.py [--max-rows 200000 --batch 2048] [--out profiles/warm_start.json]
+
+--exact runs the EXACT batch-1 engine's leg instead (recorded, not gated; profiles/exact_warm_start.json): for the same tier
+(10 % of the Criteo-Kaggle rows = 3 376 257 entries, fp32, d = 36) the wall time of evs_cache_exact_load -- the host checks, the
+host plan and upload + launch + wait separately, and the kernel alone by device events -- against the time evs_cache_request
+needs to replay, in ONE launch, the requests that put the same number of keys into the tier (n / 26 requests of new keys: the
+in-kernel replay the load replaces, at its cheapest -- a workload that has to reach a warm steady state replays many more).
+
+    python tools/warm_start_bench.py --exact [--max-rows 200000] [--out profiles/exact_warm_start.json]"""
 import argparse
 import ctypes as C
 import json
@@ -36,8 +44,99 @@ def ms_since(t0):
     return round((time.perf_counter() - t0) * 1e3, 3)
 
 
+def exact_leg(args):
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    x_load = C.CDLL(E._lib.LIB_PATH).evs_x_exact_load_timed   # evs_cache_exact_load's three steps with a clock between them
+    x_load.restype, x_load.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    ln = [min(n, args.max_rows) if args.max_rows else n for n in bench.KAGGLE_LN]
+    T, d = len(ln), args.dim
+    cap = int(args.frac * sum(ln))
+    ev = bench.make_tables(ln, d, seed=0, device=dev)
+    rs = np.random.RandomState(5)
+    # a state of `cap` distinct keys, every table holding its share (small tables whole), EvLFU buckets drawn and sorted
+    share = np.minimum(np.asarray(ln, np.int64), np.maximum(1, (np.asarray(ln, np.float64) / sum(ln) * cap).astype(np.int64)))
+    while share.sum() < cap:
+        room = np.asarray(ln, np.int64) - share
+        k = int(np.argmax(room))
+        share[k] += min(int(room[k]), cap - int(share.sum()))
+    keys = np.concatenate([np.stack([np.full(int(m), k + 1, np.int64), rs.permutation(ln[k])[:int(m)].astype(np.int64)], 1) for k, m in enumerate(share)])
+    keys = keys[rs.permutation(len(keys))][:cap]
+    n = len(keys)
+    entries = np.ascontiguousarray(np.concatenate([np.sort(rs.randint(0, T + 1, size=n)).astype(np.int64)[:, None], keys], 1))
+    n_req = (n + T - 1) // T
+    # the replay: n / T requests, request j asks table k for a row it has not asked for before (small tables wrap around)
+    reqs = torch.from_numpy(np.stack([(np.arange(n_req, dtype=np.int64) * 7919 + 13 * k) % ln[k] for k in range(T)], 1).astype(np.int32)).to(dev)
+    out = torch.empty((n_req, T, d), dtype=torch.float32, device=dev)
+    hit = torch.empty((n_req, T), dtype=torch.uint8, device=dev)
+
+    def fresh():
+        c = E.GpuCache("evlfu", cap, T, d, 32, "python", dev)
+        c.set_backing(ev)
+        return c
+
+    w = fresh()                                   # every kernel has run once before anything is timed
+    w.load_exact_state({"entries": entries[:1000], "state": None}, strict=False)
+    w.request(reqs[:8].contiguous(), out=out[:8], hit=hit[:8])
+    del w
+    torch.cuda.synchronize()
+    r = {"load_ms": [], "check_ms": [], "plan_ms": [], "upload_launch_wait_ms": [], "kernel_ms": [], "replay_ms": [], "replay_wall_ms": []}
+    for rnd in range(args.rounds):
+        c = fresh()
+        torch.cuda.synchronize()
+        t4 = (C.c_double * 4)()
+        t0 = time.perf_counter()
+        E._lib.check(x_load(c._h, n, entries.ctypes.data, None, 0, torch.cuda.current_stream(dev).cuda_stream, t4))
+        r["load_ms"].append(ms_since(t0))
+        for k, name in enumerate(("check_ms", "plan_ms", "upload_launch_wait_ms", "kernel_ms")):
+            r[name].append(round(float(t4[k]), 3))
+        if rnd == 0:   # what was loaded is what comes back, in order, and it is served from the arena
+            assert np.array_equal(c.dump(), entries)
+            probe = np.zeros((64, T), np.int32)
+            for k in range(T):
+                mine = entries[entries[:, 1] == k + 1][:, 2]
+                probe[:, k] = mine[np.arange(64) % len(mine)]
+            h, o = c.request(torch.from_numpy(probe).to(dev))
+            assert bool(h.all()) and all(torch.equal(o[:, k], ev.raw[k].view(torch.float32).view(-1, d)[torch.from_numpy(probe[:, k]).to(dev).long()]) for k in range(T))
+        del c
+        c = fresh()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        c.request(reqs, out=out, hit=hit)
+        e1.record()
+        torch.cuda.synchronize()
+        r["replay_wall_ms"].append(ms_since(t0))
+        r["replay_ms"].append(round(e0.elapsed_time(e1), 3))
+        r["replay_entries"] = c.stats()["size"]
+        del c
+    r["replay_us_per_request"] = round(min(r["replay_ms"]) * 1e3 / n_req, 3)
+    r["replay_ms_n_requests_extrapolated"] = round(r["replay_us_per_request"] * n / 1e3, 1)
+    r["replay_over_load"] = round(min(r["replay_wall_ms"]) / min(r["load_ms"]), 2)
+    line = json.dumps({"tool": "warm_start_bench --exact",
+                       "shape": {"rows": int(sum(ln)), "capacity": cap, "entries": n, "frac": args.frac, "dim": d, "codec": 32, "policy": "evlfu",
+                                 "replay_requests": n_req, "rounds": args.rounds},
+                       "what": {"load_ms": "host clock around the load (evs_cache_exact_load's steps: checks + plan + upload + one launch + wait)",
+                                "check_ms": "evs_exact_load_check inside it (host)", "plan_ms": "records, list heads, run list (host)",
+                                "upload_launch_wait_ms": "record upload, state copy, the launch, the synchronise (host clock)",
+                                "kernel_ms": "the load kernel alone, device events",
+                                "replay_ms": "evs_cache_request over replay_requests requests of new keys in ONE launch, device events",
+                                "replay_wall_ms": "host clock around it, ending in a synchronise",
+                                "replay_entries": "keys resident after the replay (small tables wrap around, so fewer than entries)",
+                                "replay_ms_n_requests_extrapolated": "replay_us_per_request x entries: what as many REQUESTS as the tier has entries would take (not run)",
+                                "replay_over_load": "min replay_wall_ms / min load_ms (recorded, not gated)"},
+                       "exact": r})
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--exact", action="store_true", help="the exact batch-1 engine's leg (evs_cache_exact_load against the in-kernel replay)")
     ap.add_argument("--frac", type=float, default=0.10)
     ap.add_argument("--batch", type=int, default=16384)
     ap.add_argument("--alpha", type=float, default=0.75)
@@ -46,9 +145,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="loads per policy, each into a fresh twin")
     ap.add_argument("--max-rows", type=int, default=0, help="clamp every table to this many rows (0: full size)")
     ap.add_argument("--dim", type=int, default=36)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "warm_start.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/warm_start.json (--exact: profiles/exact_warm_start.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exact_warm_start.json" if args.exact else "warm_start.json")
     assert torch.cuda.is_available(), "warm_start_bench measures on the GPU"
+    if args.exact:
+        return exact_leg(args)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     lib = E._lib.lib()
