@@ -3403,6 +3403,12 @@ struct evs_cache {
     //               to hand slot s out again waits for it on the host (the server overwrites the slot in host order).
     hipEvent_t exact_done = nullptr; bool exact_pending = false;
     std::vector<hipEvent_t> slot_done; std::vector<char> slot_busy;
+    // order of update and consumers on the set-associative batched path (evs_cache_set_miss_order): 0 "consume first", 1 "fetch
+    // first" (probe -> update -> sa_repoint -> consumers: every missing row is read once, by the update); the counters the
+    // repoint kernel adds into (device, 2 words, allocated at the first fetch-first call) and the calls that ran the chain
+    int miss_order = 0;
+    unsigned long long *fetch_cnt = nullptr;
+    long long fetch_calls = 0;
     int inline_mode = -1;          // the update inside the probe launch (evs_fused_rf.hip): -1 not decided (EVS_CACHE_INLINE, default on), 0 / 1
     evs_tier_server *tsrv = nullptr;   // the tier pair / triple server this cache belongs to (evs_tiers_serve_*)
 };
@@ -3545,7 +3551,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->bag_pool};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->bag_pool, c->fetch_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -3666,7 +3672,42 @@ extern "C" int evs_cache_set_inline_update(evs_cache *c, int on) {
     EVS_REQUIRE(c && (on == 0 || on == 1), "evs_cache_set_inline_update: bad argument");
     EVS_REQUIRE(on == 0 || c->host.policy == kEvLFU, "evs_cache_set_inline_update: the one-launch form is EvLFU's; an %s cache runs probe, consumer and insert as launches of their own",
                 policy_name(c->host.policy));
+    EVS_REQUIRE(on == 0 || c->miss_order == 0, "evs_cache_set_inline_update: this %s cache runs its batches fetch-first (evs_cache_set_miss_order): the update is a launch of its own "
+                "in front of the consumers, never inside the probe launch", policy_name(c->host.policy));
     c->inline_mode = on;
+    return EVS_OK;
+}
+
+// Which of the two runs first on the set-associative batched path, the consumers or the policy update (the contract:
+// include/evstore_hip.h).  0 "consume first": today's chains and refusals.  1 "fetch first": probe -> update -> sa_repoint ->
+// consumers, which is what lets the tier stand over host-memory tables.  Before the first batched call or load only.
+extern "C" int evs_cache_set_miss_order(evs_cache *c, int order) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_set_miss_order: NULL cache");
+    EVS_REQUIRE(order == 0 || order == 1, "evs_cache_set_miss_order: order %d on an %s cache (0 \"consume first\", 1 \"fetch first\")", order, policy_name(c->host.policy));
+    if (c->used == 2 || c->bs || c->sa.tags) {
+        set_error("evs_cache_set_miss_order: the batched path of this %s cache is already in use (the order is set before the first batched call or load)",
+                  policy_name(c->host.policy));
+        return EVS_ESTATE;
+    }
+    EVS_REQUIRE(order == 0 || c->inline_mode != 1, "evs_cache_set_miss_order: this %s cache was told to update inside the probe launch (evs_cache_set_inline_update(c, 1)); "
+                "fetch-first runs the update as a launch of its own in front of the consumers", policy_name(c->host.policy));
+    c->miss_order = order;
+    return EVS_OK;
+}
+
+// out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their table, 0]
+extern "C" int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_fetch_stats: NULL cache");
+    EVS_REQUIRE(out4, "evs_cache_fetch_stats: NULL out4");
+    unsigned long long h[2] = {0ull, 0ull};
+    if (c->fetch_cnt) {
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        EVS_HIP_CHECK(hipMemcpyAsync(h, c->fetch_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    out4[0] = c->fetch_calls; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = 0;
     return EVS_OK;
 }
 
@@ -4174,7 +4215,7 @@ static int batch_check(evs_cache *c, const char *who) {
     if (!c->has_backing) { set_error("%s: call evs_cache_set_backing first", who); return EVS_ESTATE; }
     if (c->host.policy != kEvLFU) {   // LRU / LFU: the set-associative form or nothing (evs_cache_policy.hip), refused before anything is allocated
         const char *pn = policy_name(c->host.policy);
-        if (c->host_backing || c->ft) {
+        if ((c->host_backing && c->miss_order == 0) || c->ft) {   // (fetch-first takes host memory the device can address: fetch_first_check)
             set_error("%s: the batched path of an %s cache reads its tables in place from HBM (no host-memory / file-backed tables)", who, pn);
             return EVS_ESTATE;
         }
@@ -4501,7 +4542,8 @@ static int resolved_batch_policy(evs_cache *c, bool single_tier) {
     if (c->batch_policy < 0 && c->host.policy != evs::kEvLFU) c->batch_policy = 2;   // LRU / LFU: set-associative (batch_prepare refuses what that form cannot take)
     if (c->batch_policy < 0) {
         const char *e = evs::env_switch("EVS_CACHE_POLICY");
-        const bool sa_ok = single_tier && !c->host_backing && !c->ft && sa_single_feasible(c);
+        // (a fetch-first cache, evs_cache_set_miss_order: the set-associative form wherever its tables live)
+        const bool sa_ok = single_tier && (!c->host_backing || c->miss_order == 1) && !c->ft && sa_single_feasible(c);
         if (e && e[0] == 'p') c->batch_policy = 0;
         else if (e && e[0] == 's' && e[1] == 'a') c->batch_policy = 1;
         else c->batch_policy = sa_ok ? 2 : 1;
@@ -4556,6 +4598,77 @@ static void sampled_flush_if_wanted(evs_cache *c, hipStream_t st) {
     hipLaunchKernelGGL(cache_batch_sampled_flush_finish_kernel, dim3(1), dim3(1), 0, st, c->bs, c->host.n_tables);
 }
 
+// ---- fetch-first order (evs_cache_set_miss_order(c, 1); the contract: include/evstore_hip.h) --------------------------------
+// What such a cache is held to, checked at every batched call behind batch_check and before anything is allocated: a tier alone,
+// batch policy 2 (given or resolved), sets of 8 ways, EvLFU over the two-copy arena, tables in HBM or in host memory the device
+// addresses.  A policy that was only resolved here is forgotten again on a refusal.  On success an inline setting that was never
+// given is 0 from here on.
+static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
+    using namespace evs;
+    const char *pn = policy_name(c->host.policy);
+    const bool evlfu = c->host.policy == kEvLFU;
+    if (c->ft) {
+        set_error("%s: a fetch-first %s cache reads its tables in place, from HBM or from host memory the device addresses (no file-backed tables: "
+                  "staged tables need the reader pool and the plan policy)", who, pn);
+        return EVS_ESTATE;
+    }
+    EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; fetch-first is a tier alone's", who, pn);
+    const int given = c->batch_policy;
+    const int bp = resolved_batch_policy(c);
+    if (bp != 2) {
+        c->batch_policy = given;
+        set_error("%s: fetch-first is the set-associative tier's order (batch policy 2); this %s cache's batch policy is %s", who, pn, bp == 0 ? "plan" : "sampled");
+        return EVS_EINVAL;
+    }
+    bool alone8 = true, dual = true;
+    if (c->sa.tags) { alone8 = c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u; dual = c->sa.dual != 0u; }
+    else if (evlfu) {
+        SaUniverse u; SaGeom g;
+        alone8 = sa_single_ways() == 8u;
+        if (sa_single_feasible(c, &u, &g)) dual = g.dual != 0u;   // (not feasible: batch_state says why)
+    }
+    if (!alone8) {
+        c->batch_policy = given;
+        set_error("%s: a fetch-first %s cache needs sets of 8 ways (EVS_SA_WAYS=16: the re-point kernel searches 8-way sets)", who, pn);
+        return EVS_EINVAL;
+    }
+    if (evlfu && !dual) {
+        c->batch_policy = given;
+        set_error("%s: a fetch-first %s cache needs the two-copy arena (EVS_SA_DUAL=0, or tags wider than 21 bits, leave one row per way): a way the batch "
+                  "hits can be the same batch's victim, and the consumers read behind the update", who, pn);
+        return EVS_EINVAL;
+    }
+    if (evlfu && bags) {
+        c->batch_policy = given;
+        set_error("%s: an %s cache has no fetch-first bag form: a sample's count exists only after the pooling walk, so the update cannot run in front of it", who, pn);
+        return EVS_EINVAL;
+    }
+    if (c->inline_mode < 0) c->inline_mode = 0;
+    return EVS_OK;
+}
+// the counter block of the re-point kernel (zeroed on st), at the first fetch-first call
+static int fetch_first_state(evs_cache *c, hipStream_t st, const char *who) {
+    if (c->fetch_cnt) return EVS_OK;
+    unsigned long long *p = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&p), 2 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemsetAsync(p, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        evs::set_error("%s: allocating the fetch-first counters failed", who);
+        return EVS_ENOMEM;
+    }
+    c->fetch_cnt = p;
+    return EVS_OK;
+}
+static evs::RepointArgs repoint_args(evs_cache *c, const unsigned char *hit, long long *row_ptrs, long long B) {
+    evs::RepointArgs ra{};
+    ra.sa = c->sa; ra.sau = c->sau;
+    for (int k = 0; k < 32; k++) ra.backing_rows[k] = k < c->host.n_tables ? c->backing_rows[k] : 0;
+    ra.hit = hit; ra.row_ptrs = row_ptrs; ra.arena = c->a.arena; ra.counters = c->fetch_cnt;
+    ra.B = B; ra.T = c->host.n_tables; ra.row_bytes = c->host.row_bytes;
+    return ra;
+}
+
 static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float *out, uint8_t *hit, const float *x,
                             int64_t x_stride, int itself, float *R, void *stream) {
     using namespace evs;
@@ -4563,6 +4676,13 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     EVS_REQUIRE(hit, "evs_cache_lookup_batch: NULL hit");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchArgs a;
+    // fetch-first (evs_cache_set_miss_order): probe -> update -> sa_repoint -> consumers, the set-associative tier over tables in
+    // HBM or in host memory -- every missing row crosses the bus once, inside the update
+    const bool ff = c && c->miss_order == 1;
+    if (ff) {
+        { const int rc = batch_check(c, "evs_cache_lookup_batch"); if (rc) return rc; }
+        { const int rc = fetch_first_check(c, "evs_cache_lookup_batch", false); if (rc) return rc; }
+    }
     const int prc = batch_prepare(c, B, rows, st, a, "evs_cache_lookup_batch");
     if (prc) return prc;
     const int T = c->host.n_tables;
@@ -4573,7 +4693,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     // that got an entry are re-pointed at their arena rows and only then do the consumers read -- every missing
     // row crosses the bus once (K5's de-duplicated fetch).  Miss tier in HBM: consumers first, as measured best.
     const bool host_tier = c->host_backing;
-    if (host_tier) {
+    if (host_tier && !ff) {
         if (!c->estamp) {
             EVS_HIP_CHECK(hipMalloc(&c->estamp, cap * 4));
             EVS_HIP_CHECK(hipMemsetAsync(c->estamp, 0, cap * 4, st));
@@ -4613,7 +4733,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     // The interaction alone as the consumer, tables in HBM, a shape the rows-in-registers kernel takes: K1 writes 4-byte
     // row ids (arena entry / table row) instead of 8-byte addresses and that kernel reads them (22.9 -> ~20 us at
     // B = 16 384).  The 8-byte address table is the (B,T) int64 buffer either way: the ids use its first half.
-    if (R && !out && !host_tier && !(c->ft && c->staged_mask) && c->host.codec == 32 && fused_row_ids_supported(B, T, c->host.dim)) {
+    if (R && !out && !host_tier && !ff && !(c->ft && c->staged_mask) && c->host.codec == 32 && fused_row_ids_supported(B, T, c->host.dim)) {
         bool small = true;
         for (int k = 0; k < T; k++) small = small && c->backing_rows[k] < (1ll << 30);
         if (small) a.row_ids = reinterpret_cast<int *>(c->row_ptrs);
@@ -4629,7 +4749,14 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     if (resolved_batch_policy(c) == 2) {
         // Set-associative policy (evs_hash.h): probe (one line per key) -> consumers -> ONE update kernel (one line, one
         // CAS and the row per new key) -> counters folded every kCloseEvery-th batch.  No hash, no tombstones, no sweeps.
-        if (host_tier || c->ft) { set_error("evs_cache_lookup_batch: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)"); return EVS_ESTATE; }
+        if ((host_tier && !ff) || c->ft) { set_error("evs_cache_lookup_batch: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)"); return EVS_ESTATE; }
+        RepointArgs ra{};
+        if (ff) {
+            { const int rc = fetch_first_state(c, st, "evs_cache_lookup_batch"); if (rc) return rc; }
+            ra = repoint_args(c, hit, c->row_ptrs, B);
+            ra.requests = rows; ra.n_pos = B * T;
+            c->fetch_calls++;
+        }
         if (c->host.policy != kEvLFU) {
             // LRU / LFU (evs_cache_policy.hip): probe + touch -> consumers -> insert, always as launches of their own; batch
             // number n = 1, 2, ... rides in the way words modulo 2^S
@@ -4646,8 +4773,14 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
             a.list_cap = pa.list_cap;
             policy_probe_launch(pa, a.g1, st);
-            const int rc = consumers(); if (rc) return rc;
-            policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
+            if (ff) {   // a way hit in this batch is touched, so never this batch's victim: its arena row is intact behind the insert
+                policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
+                sa_repoint_launch(ra, a.g1, st);
+                const int rc = consumers(); if (rc) return rc;
+            } else {
+                const int rc = consumers(); if (rc) return rc;
+                policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
+            }
             c->pending_batches++; c->pending_requests += B;
             if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
             EVS_HIP_CHECK(hipGetLastError());
@@ -4662,9 +4795,9 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         for (int k = 0; k < T; k++) small_tabs = small_tabs && c->backing_rows[k] < (1ll << 30);
         // a reduced-precision tier (the reference's one-layer 16 / 8 / 4-bit builds): the probe folded into ITS consumer too
         static const bool foldq_on = !(evs::env_switch("EVS_CACHE_FOLDQ") && evs::env_switch("EVS_CACHE_FOLDQ")[0] == '0');
-        const bool foldq = fold_on && foldq_on && c->host.codec != 32 && R && !out && c->sa.ways == 8 && c->sa.sub_shift == 0 && small_tabs &&
+        const bool foldq = !ff && fold_on && foldq_on && c->host.codec != 32 && R && !out && c->sa.ways == 8 && c->sa.sub_shift == 0 && small_tabs &&
                            (cap << c->sa.dual) < (1ll << 30) && fused_probe_codec_supported(B, T, c->host.dim, c->host.codec);
-        const bool fold = (fold_on && a.row_ids && R && !out && c->sa.ways == 8 && (cap << c->sa.dual) < (1ll << 30)) || foldq;   // (the folded probes are compiled for 8-way sets; tile entries carry an arena row in 30 bits)
+        const bool fold = (!ff && fold_on && a.row_ids && R && !out && c->sa.ways == 8 && (cap << c->sa.dual) < (1ll << 30)) || foldq;   // (the folded probes are compiled for 8-way sets; tile entries carry an arena row in 30 bits)
         // the update inside the probe launch too: fp32 rows, the folded fp32 launch, a two-copy arena (EVS_CACHE_INLINE=0: every
         // batch updated by a launch of its own behind it -- the round-4 chain, strict snapshot flags)
         if (c->inline_mode < 0) c->inline_mode = (evs::env_switch("EVS_CACHE_INLINE") && evs::env_switch("EVS_CACHE_INLINE")[0] == '0') ? 0 : 1;
@@ -4698,6 +4831,17 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
                 EVS_HIP_CHECK(hipGetLastError());
                 return EVS_OK;
             }
+        } else if (ff) {
+            // (a hit way can be this batch's victim: the replacement writes the other copy of the two-copy arena and flips the
+            //  select bit, so the address the probe computed from the old word stays valid until the consumers have read it)
+            hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
+            launch_sa_update(a, st);
+            sa_repoint_launch(ra, a.g1, st);
+            const int rc = consumers(); if (rc) return rc;
+            c->pending_batches++; c->pending_requests += B;
+            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+            EVS_HIP_CHECK(hipGetLastError());
+            return EVS_OK;
         } else {
             hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
             const int rc = consumers(); if (rc) return rc;
@@ -4914,6 +5058,8 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     // host-tier order -- probe (hits and served alt rows stamped), both tiers' updates (each missing row fetched ONCE into its
     // tier's arena: over the bus by the update kernel, or by the host's reader pool for staged tables), a patch kernel that
     // points every missed position at the arena / staged copy, and only then the consumers.
+    EVS_REQUIRE(c1->miss_order == 0 && c2->miss_order == 0, "evs_cache_lookup_batch_c1c2: an %s tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone; "
+                "the pair / triple runs its own chains", policy_name(c1->host.policy));
     const bool host2 = c1->host_backing || c2->host_backing;
     const bool file2 = (c1->ft && c1->staged_mask) || (c2->ft && c2->staged_mask);
     // a pair that was given no policy takes the set-associative form where both tiers can (tables in HBM, at least one full
@@ -5243,6 +5389,8 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule says what a request's hit count is over bags "
                 "(its priority counts a request's hit keys); lru / lfu caches take ragged bags as they are", who, policy_name(c->host.policy));
     { const int rc = batch_check(c, who); if (rc) return rc; }
+    const bool ff = c->miss_order == 1;   // fetch-first (evs_cache_set_miss_order): probe -> insert -> sa_repoint -> pooling
+    if (ff) { const int rc = fetch_first_check(c, who, true); if (rc) return rc; }
     if (evlfu) {   // the set-associative tier alone, 8 ways, tables in HBM: refused before anything is allocated
         const char *pn = policy_name(c->host.policy);
         if (c->host_backing || c->ft) {
@@ -5269,6 +5417,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         EVS_REQUIRE(reinterpret_cast<uintptr_t>(c->backing[k]) % piece_bytes == 0, "%s: table %d is not %d-byte aligned", who, k, piece_bytes);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    if (ff) { const int rc = fetch_first_state(c, st, who); if (rc) return rc; }
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
 
@@ -5342,8 +5491,20 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
     a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
     a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
+    a.pool_flags = ff ? pa.hit : nullptr;
 
     if (grid) bags_probe_launch(a, (int)grid, st);
+    if (ff) {   // (LRU / LFU: fetch_first_check) the insert in front of the pooling, the installed misses re-pointed at the arena
+        c->fetch_calls++;
+        if (grid) {
+            policy_insert_launch(pa, (int)grid, 128u, st);
+            RepointArgs ra = repoint_args(c, pa.hit, c->bag_ptrs, B);
+            for (int k = 0; k < 32; k++) ra.indices[k] = a.indices[k];
+            for (int k = 0; k < 33; k++) ra.pos0[k] = a.pos0[k];
+            ra.n_pos = n_pos; ra.iters = (int)iters;
+            sa_repoint_flat_launch(ra, (int)grid, st);
+        }
+    }
     bags_pool_launch(a, c->host.codec, st);
     if (interact) {
         const float *feats[EVS_MAX_FEATURES];
@@ -5365,7 +5526,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         u.part1 = c->part1; u.part2 = c->part2; u.host_tomb = c->host_tomb_dev;
         u.miss_rec = c->bag_rec; u.list_cnt = c->bag_list_cnt; u.list_cap = pa.list_cap; u.g1 = (int)grid;
         launch_sa_update(u, st);
-    } else if (grid) {
+    } else if (grid && !ff) {
         policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
     }
     c->pending_batches++; c->pending_requests += B;

@@ -93,6 +93,9 @@ struct BagArgs {
     uint4 *prov;                           // n_pos records: (row, table, set, bit 31 | hit way -- or tag + 1 of a miss -- or 0: no key)
     int *pos_sample;                       // n_pos words: the sample whose bag covers the position (-1: no valid bag does)
     int *agg;                              // B words: the sample's served bags (0 .. T)
+    // fetch-first order (evs_cache_set_miss_order): the update has re-pointed the installed misses at the arena before the
+    // pooling runs, so "this position was a hit" comes from the probe's flags (not NULL) instead of the address range
+    const unsigned char *pool_flags;
 };
 // probe over the flat position list: grid blocks of 256 threads, one lane per position.  LRU / LFU: probe + touch, writes miss
 // list j (records as above).  EvLFU: no way word is written; writes prov and presets pos_sample to -1
@@ -104,5 +107,28 @@ void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st);
 // sample) with the histogram moves into part1 columns 0 .. T, every miss into list j as (row, table | agg << 8, set, tag + 1),
 // the record cache_batch_sa_list_kernel (evs_cache.hip) reads
 void bags_raise_list_launch(const BagArgs &a, int grid, hipStream_t st);
+
+// Fetch-first order (evs_cache_set_miss_order(c, 1); the chain: evs_cache.hip, cache_batch_impl): behind the policy update, every
+// position the probe flagged 0 is searched again in its set -- the line the update touched a moment ago -- and, where the key
+// got a way, its slot of the pointer table is re-pointed from the table row at the arena row.  A key that was turned away
+// (its set took 8 new keys in this batch) keeps the table address the probe wrote.  An index out of range is no key.  Writes
+// no way word, reads no table.  counters: [0] positions re-pointed, [1] positions left on their table (one add per block each).
+struct RepointArgs {
+    SaGeom sa; SaUniverse sau;
+    const int *requests;                   // (B, T) form: int32 row ids ...
+    const long long *indices[32];          // ... flat form: per table its int64 row ids, the positions table-major from pos0[]
+    long long pos0[33];
+    long long backing_rows[32];
+    const unsigned char *hit;              // the probe's flags, one per position
+    long long *row_ptrs;                   // the pointer table, one slot per position
+    unsigned char *arena;
+    unsigned long long *counters;
+    long long B, n_pos;
+    int T, row_bytes, iters;
+};
+// (B, T) form: the probe's grid and walk (block j: requests 8 j, 8 (j + grid), ...; a half-wave per request, a lane per key)
+void sa_repoint_launch(const RepointArgs &a, int grid, hipStream_t st);
+// flat form: the bag probe's grid and walk (block j: positions 256 (j + i grid) + thread, i < iters)
+void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st);
 
 }  // namespace evs

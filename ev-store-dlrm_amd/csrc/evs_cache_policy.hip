@@ -230,6 +230,7 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
         const long long *__restrict__ off = args.offsets[t];
         const long long nnz = args.pos0[t + 1] - args.pos0[t];
         const long long *__restrict__ ptrs = args.p.row_ptrs + args.pos0[t];
+        const unsigned char *__restrict__ flags = args.pool_flags ? args.pool_flags + args.pos0[t] : nullptr;
 
         long long s[UNROLL], len[UNROLL];
         long long maxlen = 0;
@@ -268,7 +269,8 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
                 r[u] = nullptr;
                 if (j < len[u]) {
                     r[u] = reinterpret_cast<const unsigned char *>(ptrs[s[u] + j]);
-                    miss[u] = miss[u] || !(r[u] >= arena && r[u] < arena_end);
+                    // (fetch-first order: an installed miss points into the arena by now -- the probe's flag says what it was)
+                    miss[u] = miss[u] || (flags ? flags[s[u] + j] == 0 : !(r[u] >= arena && r[u] < arena_end));
                     if constexpr (EVLFU) {
                         if (piece == 0) args.pos_sample[args.pos0[t] + s[u] + j] = (int)(b0 + (long long)u * RPW + slot);
                     }
@@ -365,6 +367,76 @@ __global__ void __launch_bounds__(256) bags_raise_list_kernel(const BagArgs args
     if ((int)threadIdx.x <= T && s_delta[threadIdx.x])
         atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], s_delta[threadIdx.x]);
     if (threadIdx.x == 0) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
+}
+
+// Fetch-first order, behind the update launch: one lane per position.  A position the probe flagged 0 whose index is in range
+// is searched again in its set (the same (set, tag + 1) the probe computed; the line sits in L2 / Infinity Cache, the update
+// has just touched it) and re-pointed at the arena row of the way that holds its key now.  Re-probing instead of having the
+// insert write its way into the miss record: of the copies of a key only the compare-and-swap's winner knows the way, and
+// every copy has to be re-pointed.  Nothing writes a way word during this launch, so the plain line read is the tier as the
+// update left it.  FLAT: the bag probe's walk over the flat position list, else the (B, T) probe's half-wave per request.
+template <bool FLAT>
+__global__ void __launch_bounds__(256) sa_repoint_kernel(const RepointArgs args) {
+    __shared__ int s_cnt[2];   // positions re-pointed / left on their table
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32], s_pos0[32];
+    __shared__ const long long *s_idx[32];
+    const int T = args.T;
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        const bool tab = (int)threadIdx.x < T;
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = tab ? args.backing_rows[threadIdx.x] : 0;
+        if constexpr (FLAT) {
+            s_idx[threadIdx.x] = args.indices[threadIdx.x];
+            s_pos0[threadIdx.x] = tab ? args.pos0[threadIdx.x] : args.n_pos;
+        }
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63;
+    int n_in = 0, n_out = 0;   // this wave's totals, kept on lane 0
+    auto one = [&](bool on, long long p, int k, long long row) {
+        // (on: the position exists; a hit, a bad index and a lane without a position all read set 0 and store nothing)
+        const bool want = on && args.hit[p] == 0 && row >= 0 && row < s_rows[k];
+        unsigned set = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(args.sau, s_base[k] + (want ? (unsigned)row : 0u)), set, tag1);
+        if (!want) set = 0u;
+        SaLine line;
+        sa_load<8>(g, set, line);
+        const int way = sa_find<8>(g, line, tag1, w);
+        const bool found = want && way >= 0;
+        if (found) args.row_ptrs[p] = (long long)(args.arena + (long long)sa_entry(g, set, (unsigned)way, w) * args.row_bytes);
+        const unsigned long long fm = __ballot(found), wm = __ballot(want);
+        n_in += __popcll(fm); n_out += __popcll(wm & ~fm);
+    };
+    if constexpr (FLAT) {
+        for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots)
+            const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+            const bool on = p < args.n_pos;
+            int k = 0;
+#pragma unroll
+            for (int step = 16; step >= 1; step >>= 1) k += (on && s_pos0[k + step] <= p) ? step : 0;
+            const long long row = on ? s_idx[k][p - s_pos0[k]] : -1;
+            one(on, p, k, row);
+        }
+    } else {
+        const int half = lane >> 5, hl = lane & 31;
+        const long long req_stride = (long long)gridDim.x * 8;
+        for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+             req += req_stride) {
+            const bool on = req < args.B && hl < T;
+            const long long p = req * T + hl;
+            const long long row = on ? (long long)args.requests[p] : -1;
+            one(on, p, hl, row);
+        }
+    }
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
 struct NoTail {};
@@ -488,6 +560,14 @@ void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st) {
 
 void bags_raise_list_launch(const BagArgs &a, int grid, hipStream_t st) {
     hipLaunchKernelGGL(bags_raise_list_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void sa_repoint_launch(const RepointArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(sa_repoint_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(sa_repoint_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
 }
 
 template <int CODEC, int UNROLL>

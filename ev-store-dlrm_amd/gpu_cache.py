@@ -277,6 +277,26 @@ class GpuCache:
         self._inline_told = True
         return self
 
+    def set_miss_order(self, order):
+        """Which runs first on the set-associative batched path: 'consume-first' (the default: probe, consumers, update --
+        tables in HBM only) or 'fetch-first' (probe, update, a kernel that re-points the installed misses at the arena, then the
+        consumers: every missing row is read once, by the update, so the tables may live in pinned host memory as well as in
+        HBM).  Before the first batched call or load; 'fetch-first' against set_inline_update(True) raises EVS_EINVAL
+        (include/evstore_hip.h: evs_cache_set_miss_order)."""
+        if order not in ("consume-first", "fetch-first"):
+            raise ValueError("order must be 'consume-first' or 'fetch-first', got %r" % (order,))
+        _lib.check(_lib.lib().evs_cache_set_miss_order(self._h, 1 if order == "fetch-first" else 0))
+        self._fetch_first = order == "fetch-first"
+        return self
+
+    def fetch_stats(self):
+        """Counters of the fetch-first chain, cumulative since creation: 'calls' (batched calls that ran it), 'repointed'
+        (missed positions served from the arena row the update installed) and 'in_place' (missed positions served from their
+        table: the key's set took 8 new keys in that batch).  Synchronises."""
+        s = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().evs_cache_fetch_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
+        return {"calls": int(s[0]), "repointed": int(s[1]), "in_place": int(s[2])}
+
     def serve_stop(self):
         _lib.check(_lib.lib().evs_cache_serve_stop(self._h))
 
@@ -477,7 +497,8 @@ class GpuCache:
         if state is not None:
             if int(state[13]) == 1 and not getattr(self, "_bag_rule_told", False):
                 self.set_bag_rule("served-bags")
-            if int(state[14]) >= 0 and not getattr(self, "_inline_told", False) and (self.policy == "evlfu" or int(state[14]) == 0):
+            if int(state[14]) >= 0 and not getattr(self, "_inline_told", False) and (self.policy == "evlfu" or int(state[14]) == 0) \
+                    and not (getattr(self, "_fetch_first", False) and int(state[14]) == 1):   # (a fetch-first cache has the chain only)
                 self.set_inline_update(bool(state[14]))
         return {"placed": int(out4[0]), "turned_away": int(out4[1]), "batch": int(out4[3])}
 

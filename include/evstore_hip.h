@@ -622,6 +622,44 @@ EVS_API int evs_cache_set_bag_rule(evs_cache *c, int rule);
  * the default; the environment variable EVS_CACHE_INLINE=0 only changes the default of caches that were never told.  May be
  * called between batches.  LRU / LFU caches have the chain only: on = 1 is refused (EVS_EINVAL), on = 0 accepted. */
 EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
+/* Which runs first on the set-associative batched path of this cache, the consumers or the policy update.
+ *   0 "consume first" (the default): today's chains -- probe, consumers, update -- and today's refusals: the set-associative
+ *     tier reads its miss tier in place from HBM.
+ *   1 "fetch first": one stream, in this order -- (EvLFU: the flush an earlier close asked for,) the unfolded probe, which
+ *     writes 8-byte row addresses and the miss lists; the policy update; sa_repoint, which searches every position flagged 0
+ *     again in its set and, where the key got a way, re-points its slot of the address table at the arena row; the consumers;
+ *     the close bookkeeping.  Every missing row is read ONCE, by the update thread that installs it, so the tables may live in
+ *     HBM or in host memory the device addresses (evs_cache_set_backing over pinned memory).  Flags are strict residency at
+ *     arrival; the tier state after a call is what the order-0 chain leaves for the same batch (the update reads the same
+ *     words either way, and the consumers write nothing the update reads).  Why the reordering is safe: the inserts read
+ *     their source row through a plain global pointer; a way changes at most once per update launch and a way stamped by the
+ *     running batch is never a victim -- under LRU / LFU a way hit in batch n is touched, so its arena row is intact when the
+ *     consumers read it; under EvLFU a hit way CAN be that batch's victim, and the replacement writes the other copy of the
+ *     two-copy arena and flips the select bit, so the address the probe computed stays valid until the consumers have read it.
+ *     A key whose set took 8 new keys in the batch is turned away and served in place from its table.
+ * The envelope of an order-1 cache, resolved and checked at every batched call before anything is allocated (a policy that was
+ * only resolved there is forgotten again on a refusal; every message names the cache's policy):
+ *   tier       a tier alone; as a member of a C1 + C2 (+ C3) lookup it is refused at that call, EVS_EINVAL.
+ *   policy     batch policy 2, given or resolved: LRU / LFU as always; an EvLFU cache that was given no policy and no
+ *              EVS_CACHE_POLICY takes it wherever the geometry has a set-associative form, wherever its tables live (the one
+ *              resolution rule that differs from order 0).  plan / sampled, given or from the environment: EVS_EINVAL.
+ *   ways       8-way sets (EVS_SA_WAYS=16: EVS_EINVAL).  EvLFU needs the two-copy arena (EVS_SA_DUAL=0: EVS_EINVAL); LRU / LFU
+ *              run over either arena.
+ *   tables     HBM or device-addressable host memory.  File-backed tables: EVS_ESTATE.  Order 1 over HBM tables is legal and
+ *              gives the results of order 0.
+ *   served     evs_cache_lookup_batch (every codec); evs_cache_lookup_interact (fp32 rows; reduced precision with the tables in
+ *              HBM only); evs_cache_lookup_bags / _lookup_bags_interact for LRU / LFU.  EvLFU bags: EVS_EINVAL -- a sample's
+ *              count exists only after the pooling walk, so the update cannot run in front of it.  evs_cache_batch_stats,
+ *              _batch_dump, _update_rows and _refresh_rows work as before; the warm start over HBM tables too (over host
+ *              tables it keeps its EVS_ESTATE).  The inline setting of an order-1 cache that was never given one is 0.
+ * May be called only before the cache's first batched call or load: EVS_ESTATE afterwards.  EVS_EINVAL: a NULL cache, an order
+ * outside {0, 1}, order 1 on a cache that was told evs_cache_set_inline_update(c, 1) (and that call on an order-1 cache).
+ * The exact path ignores the setting. */
+EVS_API int evs_cache_set_miss_order(evs_cache *c, int order);
+/* out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their
+ * table, 0], cumulative since creation.  An index out of range is no key and is counted nowhere.  Synchronises the stream.
+ * EVS_EINVAL for a NULL cache or a NULL out4, before the device is touched. */
+EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
 /* out8: [size, n_free, n_tombstones, n_flush, n_evict, n_requests, n_perfect_hits, n_hits];
  * hist (may be NULL): n_tables+1 resident-entry counts per priority (LRU / LFU caches: hist[0] = size, the rest 0). */
 EVS_API int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist, void *stream);
