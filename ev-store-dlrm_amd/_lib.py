@@ -141,6 +141,9 @@ _PROTOS = {
     "evs_cache_batch_export": (_i64, [_vp, _vp, _i64, _vp, _vp]),
     "evs_cache_batch_load": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp]),
     "evs_cache_load_plan": (_int, [_int, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
+    "evs_cache_pair_export": (_i64, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "evs_cache_pair_load": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp]),
+    "evs_cache_pair_load_plan": (_int, [_i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
     "evs_cache_exact_export": (_i64, [_vp, _vp, _i64, _vp, _vp]),
     "evs_cache_exact_load": (_int, [_vp, _i64, _vp, _vp, _int, _vp]),
     "evs_exact_load_check": (_int, [_int, _i64, _int, _vp, _i64, _vp, _vp, _int, _i64]),

@@ -3493,19 +3493,23 @@ bool sa_single_feasible(const evs_cache *c, evs::SaUniverse *u_out = nullptr, ev
 // (the reference's 1 : 2 split, evlfu_8.cpp:63-78: C1 8 ways + C2 2 x 8, every probe an 8-way search of 32 bytes), else
 // min(cap2 / nset, 16) ways in one.  false: no such geometry (a tier would get fewer than 4 ways) -- each tier then keeps
 // records of its own (two line requests per key)
-bool sa_pair_geometry(const evs_cache *c1, const evs_cache *c2, evs::SaUniverse &u, evs::SaGeom &g1, evs::SaGeom &g2) {
-    static const bool on = !(evs::env_switch("EVS_SA_PAIR") && evs::env_switch("EVS_SA_PAIR")[0] == '0');
-    if (!on || !c1->has_backing || !c2->has_backing || c1->host.n_tables != c2->host.n_tables) return false;
-    const long long cap1 = c1->host.cap, cap2 = c2->host.cap;
+// (the formula over capacities and row counts alone: evs_cache_pair_load_plan plans for a pair that is not there)
+bool sa_pair_geometry_of(long long cap1, long long cap2, int T, const long long *rows1, const long long *rows2,
+                         evs::SaUniverse &u, evs::SaGeom &g1, evs::SaGeom &g2) {
     long long nset = std::max<long long>(std::max<long long>(cap1 / 8, (cap2 + 15) / 16), 1);
     const long long w1 = std::min<long long>(cap1 / nset, evs::kSaMaxWays);
     long long w2 = std::min<long long>(cap2 / nset, evs::kSaMaxWays);
     unsigned sub2 = 0;
     if (w2 == 16) { w2 = 8; sub2 = 1; }
     if (w1 < 4 || w2 < 4) return false;
-    if (!sa_make_universe(c1->backing_rows, c2->backing_rows, c1->host.n_tables, u)) return false;
+    if (!sa_make_universe(rows1, rows2, T, u)) return false;
     const unsigned off2 = (unsigned)((w1 + 3) / 4 * 4);
     return sa_make_geom(g1, (unsigned)nset, (unsigned)w1, 0, 32, u) && sa_make_geom(g2, (unsigned)nset, (unsigned)w2, off2, 32, u, sub2);
+}
+bool sa_pair_geometry(const evs_cache *c1, const evs_cache *c2, evs::SaUniverse &u, evs::SaGeom &g1, evs::SaGeom &g2) {
+    static const bool on = !(evs::env_switch("EVS_SA_PAIR") && evs::env_switch("EVS_SA_PAIR")[0] == '0');
+    if (!on || !c1->has_backing || !c2->has_backing || c1->host.n_tables != c2->host.n_tables) return false;
+    return sa_pair_geometry_of(c1->host.cap, c2->host.cap, c1->host.n_tables, c1->backing_rows, c2->backing_rows, u, g1, g2);
 }
 int sa_alloc(evs_cache *c, evs_cache *partner, hipStream_t st) {   // the set records of c (shared with partner), zeroed on st
     auto *m = new evs_cache::SaShared();
@@ -5040,6 +5044,55 @@ extern "C" int64_t evs_aprx_batch_dump(evs_aprx *p, int64_t *triples, int64_t ma
     return m;
 }
 
+// The batch policy both tiers of a pair take (no device call; evs_cache_pair_load asks before it plans and puts the tiers'
+// given policies back when it refuses)
+static int pair_resolve_policy(evs_cache *c1, evs_cache *c2, const char *who) {
+    using namespace evs;
+    const bool host2 = c1->host_backing || c2->host_backing;
+    const bool file2 = (c1->ft && c1->staged_mask) || (c2->ft && c2->staged_mask);
+    // a pair that was given no policy takes the set-associative form where both tiers can (tables in HBM, at least one full
+    // set each), the sampled update over host-memory tables, the plan-based one when a tier has STAGED tables (its reader
+    // pool works between plan and assign); a tier with a policy of its own decides for the other; one set-associative and
+    // one hashed tier: refused
+    {
+        const bool free1 = c1->batch_policy < 0, free2 = c2->batch_policy < 0;
+        const bool sa_ok = !host2 && !c1->ft && !c2->ft && (c1->sa.tags || sa_single_feasible(c1)) && (c2->sa.tags || sa_single_feasible(c2));
+        if (file2) {
+            if (free1) c1->batch_policy = 0;
+            if (free2) c2->batch_policy = 0;
+        } else if (free1 && free2 && !(evs::env_switch("EVS_CACHE_POLICY"))) c1->batch_policy = c2->batch_policy = sa_ok ? 2 : 1;
+        else if (free1 != free2) {
+            evs_cache *set = free1 ? c2 : c1, *unset = free1 ? c1 : c2;
+            unset->batch_policy = (set->batch_policy == 2 && !sa_ok) ? 1 : set->batch_policy;
+        }
+        const int p1 = resolved_batch_policy(c1, true), p2 = resolved_batch_policy(c2, true);
+        EVS_REQUIRE((p1 == 2) == (p2 == 2), "%s: both tiers take the set-associative batch policy, or neither (C1 %d, C2 %d)", who, p1, p2);
+        if (p1 == 2 && host2) { set_error("%s: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
+        EVS_REQUIRE(p1 != 2 || sa_ok, "%s: the set-associative batch policy needs both tiers' tables in HBM and at least %d entries each", who, (int)kSaSingleWays);
+        if (file2 && (p1 != 0 || p2 != 0)) { set_error("%s: a pair with staged file-backed tables takes the plan-based batch policy on both tiers (C1 %d, C2 %d)", who, p1, p2); return EVS_ESTATE; }
+        EVS_REQUIRE(!host2 || (p1 == p2), "%s: tiers over host-memory / file-backed tables take the same batch policy (C1 %d, C2 %d)", who, p1, p2);
+    }
+    return EVS_OK;
+}
+// How a C1 + C2 pair starts out, for the first lookup and for a warm start (evs_cache_pair_load) alike: the batch policy both
+// tiers take, then -- two set-associative tiers that start out together -- the shared set records, zeroed on st.  Calling it
+// again on a pair that has started changes nothing.
+static int pair_start(evs_cache *c1, evs_cache *c2, hipStream_t st, const char *who) {
+    using namespace evs;
+    { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return rc; }
+    // two set-associative tiers that start out together share their set records: ONE 128-byte record per set holds C1's and
+    // C2's ways, so a key's two probes are one line request (a tier that was used alone before keeps records of its own)
+    if (resolved_batch_policy(c1) == 2 && !c1->sa.tags && !c2->sa.tags && !c1->bs && !c2->bs) {
+        SaUniverse u; SaGeom g1, g2;
+        if (sa_pair_geometry(c1, c2, u, g1, g2)) {
+            c1->sau = u; c2->sau = u; c1->sa = g1; c2->sa = g2;
+            const int arc = sa_alloc(c1, c2, st);
+            if (arc) { c1->sa = SaGeom{}; c2->sa = SaGeom{}; set_error("%s: allocating the set records failed", who); return arc; }
+        }
+    }
+    return EVS_OK;
+}
+
 static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B, const int32_t *rows, float *out, uint8_t *tier,
                            int high_agghit_threshold, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
     using namespace evs;
@@ -5061,40 +5114,8 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     EVS_REQUIRE(c1->miss_order == 0 && c2->miss_order == 0, "evs_cache_lookup_batch_c1c2: an %s tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone; "
                 "the pair / triple runs its own chains", policy_name(c1->host.policy));
     const bool host2 = c1->host_backing || c2->host_backing;
-    const bool file2 = (c1->ft && c1->staged_mask) || (c2->ft && c2->staged_mask);
-    // a pair that was given no policy takes the set-associative form where both tiers can (tables in HBM, at least one full
-    // set each), the sampled update over host-memory tables, the plan-based one when a tier has STAGED tables (its reader
-    // pool works between plan and assign); a tier with a policy of its own decides for the other; one set-associative and
-    // one hashed tier: refused
-    {
-        const bool free1 = c1->batch_policy < 0, free2 = c2->batch_policy < 0;
-        const bool sa_ok = !host2 && !c1->ft && !c2->ft && (c1->sa.tags || sa_single_feasible(c1)) && (c2->sa.tags || sa_single_feasible(c2));
-        if (file2) {
-            if (free1) c1->batch_policy = 0;
-            if (free2) c2->batch_policy = 0;
-        } else if (free1 && free2 && !(evs::env_switch("EVS_CACHE_POLICY"))) c1->batch_policy = c2->batch_policy = sa_ok ? 2 : 1;
-        else if (free1 != free2) {
-            evs_cache *set = free1 ? c2 : c1, *unset = free1 ? c1 : c2;
-            unset->batch_policy = (set->batch_policy == 2 && !sa_ok) ? 1 : set->batch_policy;
-        }
-        const int p1 = resolved_batch_policy(c1, true), p2 = resolved_batch_policy(c2, true);
-        EVS_REQUIRE((p1 == 2) == (p2 == 2), "evs_cache_lookup_batch_c1c2: both tiers take the set-associative batch policy, or neither (C1 %d, C2 %d)", p1, p2);
-        if (p1 == 2 && host2) { set_error("evs_cache_lookup_batch_c1c2: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)"); return EVS_ESTATE; }
-        EVS_REQUIRE(p1 != 2 || sa_ok, "evs_cache_lookup_batch_c1c2: the set-associative batch policy needs both tiers' tables in HBM and at least %d entries each", (int)kSaSingleWays);
-        if (file2 && (p1 != 0 || p2 != 0)) { set_error("evs_cache_lookup_batch_c1c2: a pair with staged file-backed tables takes the plan-based batch policy on both tiers (C1 %d, C2 %d)", p1, p2); return EVS_ESTATE; }
-        EVS_REQUIRE(!host2 || (p1 == p2), "evs_cache_lookup_batch_c1c2: tiers over host-memory / file-backed tables take the same batch policy (C1 %d, C2 %d)", p1, p2);
-    }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // two set-associative tiers that start out together share their set records: ONE 128-byte record per set holds C1's and
-    // C2's ways, so a key's two probes are one line request (a tier that was used alone before keeps records of its own)
-    if (resolved_batch_policy(c1) == 2 && !c1->sa.tags && !c2->sa.tags && !c1->bs && !c2->bs) {
-        SaUniverse u; SaGeom g1, g2;
-        if (sa_pair_geometry(c1, c2, u, g1, g2)) {
-            c1->sau = u; c2->sau = u; c1->sa = g1; c2->sa = g2;
-            const int arc = sa_alloc(c1, c2, st);
-            if (arc) { c1->sa = SaGeom{}; c2->sa = SaGeom{}; set_error("evs_cache_lookup_batch_c1c2: allocating the set records failed"); return arc; }
-        }
-    }
+    { const int prc = pair_start(c1, c2, st, "evs_cache_lookup_batch_c1c2"); if (prc) return prc; }
     // (The pair's update folded into the probe launch as well -- the thread that routes a double miss claims a way of the
     //  destination tier, whose ways it has to read AGAIN once the request's agg_hit has decided the destination, a look at the
     //  other tier's set behind the claim so that a key routed both ways ends up in one tier, the rows copied table -> arena at
@@ -5706,6 +5727,19 @@ extern "C" __attribute__((visibility("default"))) int evs_x_warm_launch(const vo
     return hipGetLastError() == hipSuccess ? EVS_OK : EVS_EHIP;
 }
 
+// ... and the pair form's (tools/warm_start_bench.py --pair): geo = per tier [ways, word offset, log2 sub-sets, row bytes], the
+// record list C1's n1 records and then C2's n2, each sorted by slot; slots[2] = each tier's slot count
+extern "C" __attribute__((visibility("default"))) int evs_x_warm_pair_launch(const void *recs, long long n1, long long n2, unsigned *tags,
+                                                                             unsigned char *arena1, unsigned char *arena2, const int *geo,
+                                                                             const long long *slots, void *stream) {
+    evs::WarmPairArgs a{};
+    a.recs = reinterpret_cast<const evs::WarmRec *>(recs); a.n1 = n1; a.n2 = n2; a.tags = tags;
+    a.t1 = evs::WarmTier{arena1, geo[3], (unsigned)geo[0], (unsigned)geo[1], 32u, (unsigned)geo[2], slots[0]};
+    a.t2 = evs::WarmTier{arena2, geo[7], (unsigned)geo[4], (unsigned)geo[5], 32u, (unsigned)geo[6], slots[1]};
+    evs::warm_load_pair_launch(a, reinterpret_cast<hipStream_t>(stream));
+    return hipGetLastError() == hipSuccess ? EVS_OK : EVS_EHIP;
+}
+
 extern "C" int evs_cache_batch_load(evs_cache *c, int64_t n, const int64_t *entries, const int64_t *state16, int strict, int64_t *out4, void *stream) {
     using namespace evs;
     const char *who = "evs_cache_batch_load";
@@ -5771,6 +5805,237 @@ extern "C" int evs_cache_batch_load(evs_cache *c, int64_t n, const int64_t *entr
     c->pending_batches = 0; c->pending_requests = 0;
     c->used = 2;
     if (out4) for (int i = 0; i < 4; i++) out4[i] = o4[i];
+    return EVS_OK;
+}
+
+// ---- warm start of the C1 + C2 pair that shares its set records (evs_cache_warm.h: warm_plan_pair) -----------------------------
+// do the two caches run as a pair over ONE record per set index, c1 in front
+static bool pair_shares_records(const evs_cache *c1, const evs_cache *c2) {
+    return c1->sa.tags && c1->sa_mem && c1->sa_mem == c2->sa_mem && c1 != c2 && c1->sa.line_words == 32u && c2->sa.line_words == 32u &&
+           c1->sa.w_off == 0u && c2->sa.w_off >= c1->sa.ways;
+}
+
+extern "C" int evs_cache_pair_load_plan(int64_t cap1, int64_t cap2, int n_tables, const int64_t *n_rows1, const int64_t *n_rows2, int64_t n,
+                                        const int64_t *entries, const int64_t *state32, int strict, int64_t *dest_slot, uint32_t *words,
+                                        int64_t *out8) {
+    using namespace evs;
+    const char *who = "evs_cache_pair_load_plan";
+    EVS_REQUIRE(n_tables >= 1 && n_tables <= 32 && n_rows1 && n_rows2, "%s: n_tables %d (1 .. 32) or NULL n_rows", who, n_tables);
+    EVS_REQUIRE(cap1 >= 1 && cap1 < (1ll << 30) && cap2 >= 1 && cap2 < (1ll << 30), "%s: capacities %lld, %lld", who, (long long)cap1, (long long)cap2);
+    long long rows1[32], rows2[32];
+    for (int k = 0; k < n_tables; k++) {
+        EVS_REQUIRE(n_rows1[k] >= 0 && n_rows2[k] >= 0, "%s: n_rows[%d] = %lld, %lld", who, k, (long long)n_rows1[k], (long long)n_rows2[k]);
+        rows1[k] = n_rows1[k]; rows2[k] = n_rows2[k];
+    }
+    SaUniverse u; SaGeom g1, g2;
+    EVS_REQUIRE(sa_pair_geometry_of(cap1, cap2, n_tables, rows1, rows2, u, g1, g2),
+                "%s: capacities %lld + %lld have no shared set record (max(cap1 / 8, ceil(cap2 / 16)) records would leave a tier fewer than 4 ways, "
+                "or the tables hold 2^32 rows or more / tags that do not fit the way word)", who, (long long)cap1, (long long)cap2);
+    // planned into arrays of its own: a refusal leaves the caller's untouched
+    std::vector<int64_t> dest((size_t)std::max<int64_t>(n, 1));
+    std::vector<uint32_t> wd((size_t)std::max<int64_t>(n, 1));
+    int64_t o8[8];
+    EVS_REQUIRE(n <= 0 || (dest_slot && words), "%s: NULL dest_slot / words", who);
+    if (const char *why = warm_plan_pair(u, g1, g2, cap1, cap2, n_tables, n_rows1, n_rows2, n, entries, state32, strict, dest.data(), wd.data(), o8, nullptr)) {
+        set_error("%s: %s", who, why);
+        return EVS_EINVAL;
+    }
+    for (int64_t i = 0; i < n; i++) { dest_slot[i] = dest[(size_t)i]; words[i] = wd[(size_t)i]; }
+    if (out8) for (int i = 0; i < 8; i++) out8[i] = o8[i];
+    return EVS_OK;
+}
+
+// rows of (tier, table_1based, row, score, age, slot) sorted by (tier, slot) (host); returns the count
+extern "C" int64_t evs_cache_pair_export(evs_cache *c1, evs_cache *c2, int64_t *entries, int64_t max_entries, int64_t *state32, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_pair_export";
+    EVS_REQUIRE(c1 && c2, "%s: NULL cache", who);
+    EVS_REQUIRE(c1->bs && c2->bs && pair_shares_records(c1, c2),
+                "%s: these two caches are not a C1 + C2 pair that shares its set records (the batched pair lookup has not run on them in this "
+                "order, or each tier keeps records of its own)", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    sampled_close_pending2(c1, 0, c2, 0, st);
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    sampled_flush_if_wanted(c1, st);
+    sampled_flush_if_wanted(c2, st);
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<unsigned> tags((size_t)c1->sa.nset * c1->sa.line_words);   // the shared records, read once
+    EVS_HIP_CHECK(hipMemcpy(tags.data(), c1->sa.tags, tags.size() * 4, hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (int k = 0; k < 2; k++) {
+        const evs_cache *c = k ? c2 : c1;
+        const SaGeom &g = c->sa;
+        for (unsigned es = 0; es < (g.nset << g.sub_shift); es++)
+            for (unsigned w = 0; w < g.ways; w++) {
+                const unsigned word = tags[(size_t)(es >> g.sub_shift) * g.line_words + g.w_off + (es & ((1u << g.sub_shift) - 1u)) * g.ways + w];
+                if (!word) continue;
+                if (entries && n < max_entries) {
+                    const unsigned long long key = sa_key_of_host(c->sau, g, es, word);
+                    int64_t *e = entries + 6 * n;
+                    long long score, age;
+                    warm_word_fields(g, 0, c->stamp_counter, word, score, age);
+                    e[0] = k + 1; e[1] = (int64_t)(key >> 32); e[2] = (int64_t)(key & 0xffffffffull); e[3] = score; e[4] = age;
+                    e[5] = (int64_t)es * g.ways + w;
+                }
+                n++;
+            }
+    }
+    if (state32) {
+        for (int i = 0; i < 32; i++) state32[i] = 0;
+        state32[kWpVersion] = kWarmPairVersion; state32[kWpTables] = c1->host.n_tables; state32[kWpDim] = c1->host.dim; state32[kWpNset] = c1->sa.nset;
+        for (int k = 0; k < 2; k++) {
+            const evs_cache *c = k ? c2 : c1;
+            BatchState h;
+            EVS_HIP_CHECK(hipMemcpy(&h, c->bs, sizeof h, hipMemcpyDeviceToHost));
+            int64_t *b = state32 + kWpTier0 + k * kWpBlock;
+            b[kWpCap] = c->host.cap; b[kWpCodec] = c->host.codec; b[kWpWays] = c->sa.ways; b[kWpSubs] = 1ll << c->sa.sub_shift;
+            b[kWpStampBits] = (int64_t)warm_stamp_bits(c->sa, 0); b[kWpBatch] = c->stamp_counter; b[kWpFlush] = h.n_flush; b[kWpEvict] = h.n_evict;
+            b[kWpRequests] = h.n_requests; b[kWpPerfect] = h.n_perfect_hits; b[kWpHits] = h.n_hits;
+        }
+    }
+    return n;
+}
+
+// what evs_cache_pair_load refuses about the two caches (nothing is changed but a batch policy that was not given: the caller
+// puts it back)
+static int pair_warm_check(evs_cache *c1, evs_cache *c2, const char *who) {
+    using namespace evs;
+    EVS_REQUIRE(c1 && c2 && c1 != c2, "%s: NULL cache, or one cache twice", who);
+    EVS_REQUIRE(c1->host.policy == kEvLFU && c2->host.policy == kEvLFU, "%s: the tier pair is EvLFU's (C1 %s, C2 %s)", who,
+                policy_name(c1->host.policy), policy_name(c2->host.policy));
+    EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
+    for (evs_cache *c : {c1, c2}) {
+        { const int rc = batch_check(c, who); if (rc) return rc; }
+        if (c->host_backing || c->ft) { set_error("%s: the warm start reads the tables in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
+        if (c->serving || c->tsrv) { set_error("%s: a resident server is running on a tier (or the tiers belong to a tier server)", who); return EVS_ESTATE; }
+        EVS_REQUIRE(c->miss_order == 0, "%s: a tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone", who);
+        if (c->used != 0 || c->bs || c->sa.tags || c->exact_touched) {
+            set_error("%s: %s has served requests or holds state already; a load goes into two fresh caches", who, c == c1 ? "C1" : "C2");
+            return EVS_ESTATE;
+        }
+    }
+    { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return rc; }
+    const int p1 = resolved_batch_policy(c1), p2 = resolved_batch_policy(c2);
+    if (p1 != 2 || p2 != 2) {
+        set_error("%s: the warm start is the set-associative pair's (batch policy 2); the batch policy of these tiers is %s", who,
+                  (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
+        return EVS_EINVAL;
+    }
+    SaUniverse u; SaGeom g1, g2;
+    EVS_REQUIRE(sa_pair_geometry(c1, c2, u, g1, g2), "%s: capacities %lld + %lld give the pair no shared set record (a tier would get fewer than 4 ways, "
+                "or EVS_SA_PAIR=0); the shared record is the only geometry this call loads", who, (long long)c1->host.cap, (long long)c2->host.cap);
+    return EVS_OK;
+}
+// a start that did not get as far as the launch is taken back: both caches are fresh again
+static void pair_unstart(evs_cache *c1, evs_cache *c2, hipStream_t st) {
+    (void)hipStreamSynchronize(st);   // (the memsets of the start are on their way)
+    for (evs_cache *c : {c1, c2}) {
+        if (c->slab_batch) { (void)hipFree(c->slab_batch); c->slab_batch = nullptr; }
+        if (c->host_tomb) { (void)hipHostFree(c->host_tomb); c->host_tomb = nullptr; c->host_tomb_dev = nullptr; }
+        c->bs = nullptr; c->eslot = nullptr; c->bslots = nullptr; c->part1 = nullptr; c->part2 = nullptr;
+        sa_release(c);
+        c->sa = evs::SaGeom{};
+    }
+    (void)hipGetLastError();
+}
+
+extern "C" int evs_cache_pair_load(evs_cache *c1, evs_cache *c2, int64_t n, const int64_t *entries, const int64_t *state32, int strict,
+                                   int64_t *out8, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_pair_load";
+    EVS_REQUIRE(n >= 0 && (n == 0 || entries) && (strict == 0 || strict == 1), "%s: a negative count, NULL entries or strict outside {0, 1}", who);
+    EVS_REQUIRE(c1 && c2, "%s: NULL cache", who);
+    const int given1 = c1->batch_policy, given2 = c2->batch_policy;
+    auto refuse = [&](int rc) { c1->batch_policy = given1; c2->batch_policy = given2; return rc; };
+    { const int rc = pair_warm_check(c1, c2, who); if (rc) return refuse(rc); }
+    const int T = c1->host.n_tables;
+    evs_cache *cs[2] = {c1, c2};
+    // the plan: pure host code, the same function evs_cache_pair_load_plan exports
+    std::vector<int64_t> dest((size_t)std::max<int64_t>(n, 1));
+    std::vector<uint32_t> words((size_t)std::max<int64_t>(n, 1));
+    int64_t o8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rows1[32], rows2[32];
+    for (int k = 0; k < T; k++) { rows1[k] = c1->backing_rows[k]; rows2[k] = c2->backing_rows[k]; }
+    {
+        const int rc = evs_cache_pair_load_plan(c1->host.cap, c2->host.cap, T, rows1, rows2, n, entries, state32, strict, dest.data(), words.data(), o8);
+        if (rc) return refuse(rc);
+    }
+    if (strict && state32 && state32[kWpDim] != c1->host.dim) {
+        set_error("%s: a strict load needs the dim of the exporting pair (%lld, not %d)", who, (long long)state32[kWpDim], c1->host.dim);
+        return refuse(EVS_EINVAL);
+    }
+    // the packed list sorted by (tier, slot) (each tier's arena stores then run forward): slot -> entry per tier, then one sweep
+    std::vector<WarmRec> recs;
+    recs.reserve((size_t)(o8[0] + o8[3]));
+    BatchState h[2] = {};
+    long long n_recs[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+        const evs_cache *c = cs[k];
+        std::vector<int64_t> owner((size_t)c->host.cap, -1);   // (a tier's slots: effective sets x ways <= its capacity)
+        for (int64_t i = 0; i < n; i++)
+            if (entries[6 * i] == k + 1 && dest[(size_t)i] >= 0 && dest[(size_t)i] < (int64_t)owner.size()) owner[(size_t)dest[(size_t)i]] = i;
+        for (size_t slot = 0; slot < owner.size(); slot++) {
+            const int64_t i = owner[slot];
+            if (i < 0) continue;
+            const int64_t *e = entries + 6 * i;
+            recs.push_back(WarmRec{(unsigned long long)reinterpret_cast<uintptr_t>(c->backing[e[1] - 1]) + (unsigned long long)e[2] * (unsigned long long)c->host.row_bytes,
+                                   (unsigned)slot, words[(size_t)i]});
+            h[k].cnt[e[3]]++;
+            n_recs[k]++;
+        }
+    }
+    if (n_recs[0] != o8[0] || n_recs[1] != o8[3]) { set_error("%s: the plan names a slot outside a tier", who); return refuse(EVS_EINVAL); }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the record list goes up BEFORE the pair is started: a failure up to here leaves both caches fresh
+    WarmRec *dev = nullptr;
+    if (!recs.empty()) {
+        if (hipMalloc(reinterpret_cast<void **>(&dev), recs.size() * sizeof(WarmRec)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: allocating the list of %lld entries failed", who, (long long)recs.size());
+            return refuse(EVS_ENOMEM);
+        }
+        const hipError_t err = hipMemcpy(dev, recs.data(), recs.size() * sizeof(WarmRec), hipMemcpyHostToDevice);
+        if (err != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); set_error("%s: %s", who, hipGetErrorString(err)); return refuse(EVS_EHIP); }
+    }
+    // the pair starts as it does at its first lookup: the shared records (zeroed on st), then each tier's counters and replica rows
+    int rc = pair_start(c1, c2, st, who);
+    if (!rc && !pair_shares_records(c1, c2)) { set_error("%s: the pair did not take the shared set record", who); rc = EVS_EINVAL; }
+    if (!rc) rc = batch_state(c1, st, who);
+    if (!rc) rc = batch_state(c2, st, who);
+    if (rc) { pair_unstart(c1, c2, st); if (dev) (void)hipFree(dev); return refuse(rc); }
+    if (dev) {
+        WarmPairArgs a{};
+        a.recs = dev; a.n1 = n_recs[0]; a.n2 = n_recs[1]; a.tags = c1->sa.tags;
+        for (int k = 0; k < 2; k++) {
+            const evs_cache *c = cs[k];
+            WarmTier &t = k ? a.t2 : a.t1;
+            t.arena = c->a.arena; t.row_bytes = c->host.row_bytes; t.ways = c->sa.ways; t.w_off = c->sa.w_off; t.line_words = c->sa.line_words;
+            t.sub_shift = c->sa.sub_shift; t.n_slots = std::min<long long>(((long long)c->sa.nset << c->sa.sub_shift) * c->sa.ways, c->host.cap);
+        }
+        warm_load_pair_launch(a, st);
+        hipError_t err = hipGetLastError();
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        (void)hipFree(dev);
+        if (err != hipSuccess) { (void)hipGetLastError(); set_error("%s: %s", who, hipGetErrorString(err)); return EVS_EHIP; }
+    }
+    EVS_HIP_CHECK(hipStreamSynchronize(st));
+    // the counters: what was placed, and what the state carries
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = cs[k];
+        const long long cap = c->host.cap;
+        const int64_t *b = state32 ? state32 + kWpTier0 + k * kWpBlock : nullptr;
+        h[k].count = (int)n_recs[k]; h[k].n_free = (int)cap - h[k].count;
+        h[k].batch_id = b ? b[kWpBatch] : o8[6];
+        if (b) { h[k].n_flush = b[kWpFlush]; h[k].n_evict = b[kWpEvict]; h[k].n_requests = b[kWpRequests]; h[k].n_perfect_hits = b[kWpPerfect]; h[k].n_hits = b[kWpHits]; }
+        EVS_HIP_CHECK(hipMemcpy(c->bs, &h[k], sizeof h[k], hipMemcpyHostToDevice));
+        // the words a close leaves in mapped host memory (sampled_close_block): [1] the EvLFU flush is wanted, [3] "full"
+        c->host_tomb[0] = 0; c->host_tomb[2] = (int)h[k].batch_id;
+        c->host_tomb[1] = h[k].cnt[T] >= c->host.max_perfect ? 1 : 0;
+        c->host_tomb[3] = h[k].count >= cap - (cap > 65536 ? cap / 256 : 0) ? 1 : 0;
+        c->stamp_counter = h[k].batch_id;
+        c->pending_batches = 0; c->pending_requests = 0;
+        c->used = 2;
+    }
+    if (out8) for (int i = 0; i < 8; i++) out8[i] = o8[i];
     return EVS_OK;
 }
 

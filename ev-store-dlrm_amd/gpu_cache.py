@@ -631,6 +631,75 @@ def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
     return tier, out
 
 
+# ---- warm start of the pair (include/evstore_hip.h: evs_cache_pair_export / evs_cache_pair_load) ----
+def export_state_c1c2(c1, c2):
+    """What the batched C1 + C2 pair holds, at rest (pending closes folded, a wanted flush run on either tier) -> a dict of
+    numpy arrays: 'entries' (n, 6) int64 rows of (tier 1 | 2, table_1based, row, score, age, slot) sorted by (tier, slot),
+    'state' (32,) int64 (format version 3, n_tables, dim, nset, then per tier capacity, codec, ways, sub-sets, stamp bits S,
+    batch number, five counters, 0) and 'n_rows1' / 'n_rows2' (T,) int64, the rows of each tier's backing tables.  The pair
+    must share its set records (the default geometry of lookup_batch_c1c2 on two set-associative tiers)."""
+    import numpy as np
+    L, st = _lib.lib(), torch.cuda.current_stream(c1.device).cuda_stream
+    state = np.zeros(32, np.int64)
+    with torch.cuda.device(c1.device):
+        n = L.evs_cache_pair_export(c1._h, c2._h, None, 0, None, st)
+        if n < 0:
+            _lib.check(int(n))
+        entries = np.zeros((max(n, 1), 6), np.int64)
+        n2 = L.evs_cache_pair_export(c1._h, c2._h, entries.ctypes.data, n, state.ctypes.data, st)
+    if n2 != n:
+        if n2 < 0:
+            _lib.check(int(n2))
+        raise _lib.EvsError(_lib.EVS_ESTATE, "export_state_c1c2: the pair changed between the count and the export")
+    return {"entries": entries[:n], "state": state, "n_rows1": np.asarray(getattr(c1, "_n_rows", []), np.int64),
+            "n_rows2": np.asarray(getattr(c2, "_n_rows", []), np.int64)}
+
+
+def save_state_c1c2(c1, c2, path):
+    """export_state_c1c2() into an .npz file (np.savez; read back by load_state_c1c2 with allow_pickle=False)"""
+    import numpy as np
+    with open(path, "wb") as f:
+        np.savez(f, **export_state_c1c2(c1, c2))
+
+
+def load_state_c1c2(c1, c2, state_or_path, strict=True):
+    """Warm start of the pair: the exported entries into two caches that must BOTH be fresh with their backing set -- the pair
+    starts as its first lookup would start it, then one launch copies every entry's row from its tier's table into its tier's
+    arena and stores its way word; the host decides every placement.  state_or_path: what export_state_c1c2 returned, or the
+    path of a save_state_c1c2 file.  strict=True: the pair must have the exporter's capacities, tables and geometry, and
+    continues exactly as the exporter would have; strict=False: every key is placed anew in its own tier of this pair's
+    geometry (per effective set the highest scores, youngest first, the rest turned away); 'state' may then be None (batch
+    number = the largest age, counters 0).  An alt-key tier's membership is not carried.
+    -> {'placed': (p1, p2), 'turned_away': (t1, t2), 'batch'}"""
+    import numpy as np
+    if isinstance(state_or_path, dict):
+        d = state_or_path
+    else:
+        try:
+            with np.load(state_or_path, allow_pickle=False) as z:
+                d = {k: z[k] for k in z.files}
+        except Exception as e:
+            raise _lib.EvsError(_lib.EVS_EIO, "load_state_c1c2: %s is not a readable state file (%s)" % (state_or_path, e))
+    missing = [k for k in ("entries", "state") + (() if isinstance(state_or_path, dict) else ("n_rows1", "n_rows2")) if k not in d]
+    if missing:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "load_state_c1c2: the state lacks %s" % ", ".join(repr(k) for k in missing))
+    entries = np.ascontiguousarray(d["entries"], np.int64)
+    state = None if d["state"] is None else np.ascontiguousarray(d["state"], np.int64)
+    if entries.ndim != 2 or entries.shape[1] != 6 or (state is not None and state.shape != (32,)):
+        raise _lib.EvsError(_lib.EVS_EINVAL, "load_state_c1c2: 'entries' must be (n, 6) and 'state' (32,)")
+    if state is not None and int(state[0]) != 3:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "load_state_c1c2: unknown format version %d (the pair's state is version 3)" % int(state[0]))
+    for c, key in ((c1, "n_rows1"), (c2, "n_rows2")):
+        if strict and d.get(key) is not None and hasattr(c, "_n_rows") and list(np.asarray(d[key]).astype(np.int64)) != list(c._n_rows):
+            raise _lib.EvsError(_lib.EVS_EINVAL, "load_state_c1c2: a strict load needs backing tables of the exporter's row counts (%s)" % key)
+    out8 = np.zeros(8, np.int64)
+    with torch.cuda.device(c1.device):
+        _lib.check(_lib.lib().evs_cache_pair_load(c1._h, c2._h, int(entries.shape[0]), entries.ctypes.data if entries.shape[0] else None,
+                                                  None if state is None else state.ctypes.data, 1 if strict else 0, out8.ctypes.data,
+                                                  torch.cuda.current_stream(c1.device).cuda_stream))
+    return {"placed": (int(out8[0]), int(out8[3])), "turned_away": (int(out8[1]), int(out8[4])), "batch": int(out8[6])}
+
+
 def lookup_batch_c1c2c3(c1, c2, c3, rows, threshold=23, out=None, tier=None):
     return lookup_batch_c1c2(c1, c2, rows, threshold, out, tier, c3=c3)
 

@@ -715,6 +715,62 @@ EVS_API int evs_cache_batch_load(evs_cache *c, int64_t n, const int64_t *entries
                                  int64_t *out4, void *stream);
 EVS_API int evs_cache_load_plan(int policy, int64_t capacity, int n_tables, const int64_t *n_rows, int64_t n, const int64_t *entries,
                                 const int64_t *state16, int strict, int64_t *dest_slot, uint32_t *words, int64_t *out4);
+/* Warm start of the batched C1 + C2 pair (evs_cache_lookup_batch_c1c2 / _lookup_interact_c1c2 and their three-tier forms): both
+ * tiers of a pair that shares its set records -- one 128-byte record per set index holds C1's 4 .. 16 ways and then C2's, C2
+ * possibly as two 8-way sub-sets picked by a quotient bit -- exported together and given back together.  EvLFU tiers, tables in
+ * HBM, any two codecs.  The calls above keep refusing a tier of a pair; these refuse everything that is not such a pair.  An
+ * alt-key tier (evs_aprx) may be passed to the lookups that follow a load: its membership is NOT carried, it starts as it is.
+ *
+ * evs_cache_pair_export brings BOTH tiers to rest as evs_cache_batch_export does for one (the pair's pending closes folded, a
+ * flush the last close asked of either tier run), reads the shared records once and returns the entry count of both tiers (a
+ * negative error code otherwise; entries == NULL: the count only).  EVS_EINVAL for two caches that are not such a pair.
+ *   entries (host): rows of 6 int64 sorted by (tier, slot) -- (tier 1 | 2, table_1based, row, score, age, slot)
+ *     score  the EvLFU priority 0 .. n_tables
+ *     age    (stamp of batch n - the way's stamp) mod 2^S of its tier, S = 26 - tag bits of the tier's geometry (a pair keeps one
+ *            arena row per way: no copy-select bit); batch n is stamped (n mod 0x7ffffffe) + 1 mod 2^S
+ *     slot   effective set * ways + way = the tier's arena row; effective set = (set index << s) | sub-set, s = log2 of the
+ *            tier's sub-sets per record
+ *   state32 (host, may be NULL): [format version = 3, n_tables, dim, nset], then per tier a block of 12 -- [capacity, codec, ways,
+ *     sub-sets per record (1 | 2), S, batch number n, n_flush, n_evict, n_requests, n_perfect_hits, n_hits, 0] -- and zeros.
+ *     (Version 1 is the single tier's state16, version 2 the exact engines' state20: each call refuses the others' by version.)
+ *
+ * evs_cache_pair_load takes n such rows into two caches that are BOTH fresh -- backing set, nothing served on either path yet,
+ * no state loaded (anything else: EVS_ESTATE, both left as they were).  Everything is decided and checked on the host before
+ * the device is touched; a failure loads nothing and leaves both caches fresh (a batch policy that was only resolved here is
+ * forgotten again), so a lookup that follows starts a cold pair.  The pair is started exactly as its first lookup starts it
+ * (the shared records, each tier's counters), then ONE launch copies every entry's row from its tier's table into its tier's
+ * arena and stores its way word into the shared record.
+ *   strict = 1  state32 is required; its n_tables, nset, and per tier capacity, ways, sub-sets and S must be this pair's (and its
+ *               dim).  Every entry goes to its own slot of its own tier, which must lie in the key's effective set and hold one
+ *               entry; the words come back as exported; n and the five counters of each tier are restored.
+ *   strict = 0  re-placement into THIS pair's geometry: a key stays in the tier it was exported from (the tier is its precision;
+ *               nothing spills into the other), its effective set is computed anew, ages are clamped to 2^S' - 2, per effective
+ *               set the `ways` best of (score descending, age ascending, table, row) take ways 0 .. ways - 1 and the rest are
+ *               turned away.  state32 given: each tier's n and counters are its block's; NULL: n = the largest clamped age over
+ *               both tiers, the same for both, the counters 0.
+ *   EVS_EINVAL, the reason named: a tier outside {1, 2}, a table or row outside its tier's table, a score outside 0 .. n_tables, a
+ *   negative age, a key twice in one tier, a key in both tiers, a format version other than 3.
+ *   Size, free count and priority histogram of each tier are rebuilt from what was placed; a tier whose top bucket holds
+ *   max_perfect entries or more asks for its flush as a close does (it runs with the next pair call).
+ *   out8 (host, may be NULL) = [placed in C1, turned away from C1, S1, placed in C2, turned away from C2, S2, batch number after
+ *   the load, 0].  n = 0 is success without a launch.  The call returns when the load has run.  (EVS_EHIP from the launch itself
+ *   is the one error behind which the pair is no longer fresh.)
+ * Refused with the reason named and both caches left usable: a cache that is not EvLFU, tiers that disagree on n_tables or dim,
+ * a batch policy that is or resolves to plan / sampled on either tier, a cache set to fetch-first (evs_cache_set_miss_order),
+ * capacities for which the pair gets no shared record -- a tier would have fewer than 4 ways, or EVS_SA_PAIR=0: the shared
+ * record is the only geometry this call loads -- (EVS_EINVAL); host-memory or file-backed tables, a resident server running,
+ * a cache that is not fresh (EVS_ESTATE).
+ *
+ * evs_cache_pair_load_plan is the placement itself, pure host code without a GPU call -- evs_cache_pair_load runs exactly this
+ * function: for a pair of cap1 + cap2 entries over n_tables tables of n_rows1[k] / n_rows2[k] rows (the key universe is built
+ * from the larger of the two per table) it writes, per entry, dest_slot (its slot in its tier; -1: turned away) and the way
+ * word, and out8 as above.  EVS_EINVAL as listed and for capacities without a shared record; a refusal writes nothing. */
+EVS_API int64_t evs_cache_pair_export(evs_cache *c1, evs_cache *c2, int64_t *entries, int64_t max_entries, int64_t *state32, void *stream);
+EVS_API int evs_cache_pair_load(evs_cache *c1, evs_cache *c2, int64_t n, const int64_t *entries, const int64_t *state32, int strict,
+                                int64_t *out8, void *stream);
+EVS_API int evs_cache_pair_load_plan(int64_t cap1, int64_t cap2, int n_tables, const int64_t *n_rows1, const int64_t *n_rows2, int64_t n,
+                                     const int64_t *entries, const int64_t *state32, int strict, int64_t *dest_slot, uint32_t *words,
+                                     int64_t *out8);
 /* File-backed miss tier: the reference's mmap miss path (emb_storage/mmap_file_read.py:32-40,
  * reader pool mixed_precs_caching/evlfu_8.cpp:191-250) under the GPU cache.  evs_filetier_open maps every
  * ev-table-N.bin read-only (row r at byte row_bytes * r) and REGISTERS tables with the GPU (hipHostRegister, mapped:

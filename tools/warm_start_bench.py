@@ -21,7 +21,18 @@ host plan and upload + launch + wait separately, and the kernel alone by device 
 needs to replay, in ONE launch, the requests that put the same number of keys into the tier (n / 26 requests of new keys: the
 in-kernel replay the load replaces, at its cheapest -- a workload that has to reach a warm steady state replays many more).
 
-    python tools/warm_start_bench.py --exact [--max-rows 200000] [--out profiles/exact_warm_start.json]"""
+    python tools/warm_start_bench.py --exact [--max-rows 200000] [--out profiles/exact_warm_start.json]
+
+--pair runs the batched C1 + C2 pair's leg (recorded; profiles/warm_start_pair.json) at the bench's mixed-precision tier shape
+(Kaggle cardinalities, u8 + u4, d = 36, B = 16 384, the 48-48 split of 2 % of the rows): the replay fill bench.py runs before it
+measures, the export, evs_cache_pair_load_plan (host clock), the load into a fresh pair (host clock around evs_cache_pair_load:
+plan + upload + allocation + launch), the tool's own upload of the record list and allocation of records and arenas (host
+clock), the load's kernel alone over that list (developer entry evs_x_warm_pair_launch, device events) -- and the steady state:
+us per batch of the LOADED pair beside the replay-warmed pair it was exported from and beside a SECOND replay-warmed pair (the
+A/A twin), on the same batches in the same process, chunk by chunk in rotating order.  The one comparison with a margin: the
+loaded pair may be slower than its replay-warmed twin by no more than the two replay-warmed twins differ from each other.
+
+    python tools/warm_start_bench.py --pair [--max-rows 200000 --batch 2048] [--out profiles/warm_start_pair.json]"""
 import argparse
 import ctypes as C
 import json
@@ -134,8 +145,167 @@ def exact_leg(args):
     return 0
 
 
+def pair_leg(args):
+    from evstore_dlrm_amd import gpu_cache
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    lib = E._lib.lib()
+    x_launch = C.CDLL(E._lib.LIB_PATH).evs_x_warm_pair_launch
+    x_launch.restype = C.c_int
+    x_launch.argtypes = [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    ln = [min(n, args.max_rows) if args.max_rows else n for n in bench.KAGGLE_LN]
+    T, d, B = len(ln), args.dim, args.batch
+    fill, steps, chunks = args.pair_fill, args.pair_steps, args.pair_chunks
+    ev = bench.make_tables(ln, d, seed=0, device=dev)
+    ev8, ev4 = ev.encode(8), ev.encode(4)
+    del ev
+    budget = int(0.02 * sum(ln))
+    caps = (int(0.48 * budget) * 4, int(0.48 * budget) * 8)
+    row_bytes = (d, d // 2)
+    rq = [b[1].t().contiguous().to(torch.int32) for b in
+          bench.make_batches(ln, B, fill + steps * chunks, seed=21, device=dev, dist="zipf", alpha=args.alpha)]
+    x = torch.rand((B, d), device=dev)
+    tier = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    n_rows = np.asarray(ln, np.int64)
+    table_ptr = (np.array([t.data_ptr() for t in ev8.raw], np.uint64), np.array([t.data_ptr() for t in ev4.raw], np.uint64))
+
+    def fresh():
+        c1, c2 = E.GpuCache("evlfu", caps[0], T, d, 8, "cpp", dev), E.GpuCache("evlfu", caps[1], T, d, 4, "cpp", dev)
+        c1.set_backing(ev8)
+        c2.set_backing(ev4)
+        return c1, c2
+
+    def run(pair, lo, hi):
+        for r in rq[lo:hi]:
+            gpu_cache.lookup_interact_c1c2(pair[0], pair[1], r, x, tier=tier)
+
+    def timed(pair, lo, hi):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        run(pair, lo, hi)
+        e1.record()
+        torch.cuda.synchronize()
+        return ms_since(t0), e0.elapsed_time(e1)
+
+    w = fresh()                                   # every kernel has run once before anything is timed
+    run(w, 0, 2)
+    w2 = fresh()
+    gpu_cache.load_state_c1c2(w2[0], w2[1], gpu_cache.export_state_c1c2(*w))
+    run(w2, 2, 3)
+    del w, w2
+    torch.cuda.synchronize()
+
+    r = {}
+    a, a2 = fresh(), fresh()
+    r["replay_wall_ms"], r["replay_ms"] = [round(v, 3) for v in timed(a, 0, fill)]
+    r["replay_twin_wall_ms"], r["replay_twin_ms"] = [round(v, 3) for v in timed(a2, 0, fill)]
+    t0 = time.perf_counter()
+    s = gpu_cache.export_state_c1c2(*a)
+    r["export_ms"] = ms_since(t0)
+    n = len(s["entries"])
+    n1 = int((s["entries"][:, 0] == 1).sum())
+    dest, words, out8 = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint32), np.zeros(8, np.int64)
+    t0 = time.perf_counter()
+    E._lib.check(lib.evs_cache_pair_load_plan(caps[0], caps[1], T, n_rows.ctypes.data, n_rows.ctypes.data, n, s["entries"].ctypes.data,
+                                              s["state"].ctypes.data, 1, dest.ctypes.data, words.ctypes.data, out8.ctypes.data))
+    r["plan_ms"] = ms_since(t0)
+    r["load_ms"] = []
+    loaded = None
+    for rnd in range(args.rounds):
+        w = fresh()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = gpu_cache.load_state_c1c2(w[0], w[1], s)
+        r["load_ms"].append(ms_since(t0))
+        assert info["placed"] == (n1, n - n1) and info["turned_away"] == (0, 0) and info["batch"] == fill
+        if loaded is None:
+            loaded = w
+    # the launch alone: the record list the load builds, set records and arenas of the tool's own
+    st = s["state"]
+    geo = np.array([st[4 + 2], 0, 0, row_bytes[0], st[16 + 2], (st[4 + 2] + 3) // 4 * 4, int(st[16 + 3]).bit_length() - 1, row_bytes[1]], np.int32)
+    slots = np.array([caps[0], caps[1]], np.int64)
+    e = s["entries"]
+    recs = np.zeros(n, np.dtype([("src", "<u8"), ("slot", "<u4"), ("word", "<u4")]))
+    for k in (0, 1):
+        m = e[:, 0] == k + 1
+        recs["src"][m] = table_ptr[k][e[m, 1] - 1] + e[m, 2].astype(np.uint64) * np.uint64(row_bytes[k])
+    recs["slot"], recs["word"] = dest[:n], words[:n]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    recs_dev = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev)
+    tags = torch.zeros(int(st[3]) * 32, dtype=torch.int32, device=dev)
+    arenas = [torch.empty(caps[k] * row_bytes[k], dtype=torch.uint8, device=dev) for k in (0, 1)]
+    torch.cuda.synchronize()
+    r["upload_alloc_ms"] = ms_since(t0)
+    nbytes = n1 * row_bytes[0] + (n - n1) * row_bytes[1]
+    src, dst = torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    best = None
+    for rep_ in range(4):          # (the first one warms the buffers' pages; a copy in front of each pushes the rows out of the caches)
+        dst.copy_(src)
+        torch.cuda.synchronize()
+        e0.record()
+        assert x_launch(recs_dev.data_ptr(), n1, n - n1, tags.data_ptr(), arenas[0].data_ptr(), arenas[1].data_ptr(), geo.ctypes.data,
+                        slots.ctypes.data, torch.cuda.current_stream(dev).cuda_stream) == 0
+        e1.record()
+        torch.cuda.synchronize()
+        if rep_:
+            best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
+    r["load_launch_ms"] = round(best, 4)
+    assert int((tags != 0).sum()) == n, "the launch did not store every way word"
+    dst.copy_(src)
+    torch.cuda.synchronize()
+    e0.record()
+    dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize()
+    r["copy_ms"] = round(e0.elapsed_time(e1), 4)
+    del recs_dev, tags, arenas, src, dst
+    r.update(entries_c1=n1, entries_c2=n - n1, bytes_moved=nbytes)
+    # steady state: the loaded pair, its replay-warmed twin and the second replay-warmed pair on the same batches, chunk by chunk
+    pairs = {"twin": a, "twin_aa": a2, "loaded": loaded}
+    us = {k: [] for k in pairs}
+    names = list(pairs)
+    for c in range(chunks):
+        lo = fill + c * steps
+        for k in names[c % 3:] + names[:c % 3]:
+            us[k].append(round(timed(pairs[k], lo, lo + steps)[1] * 1e3 / steps, 3))
+    med = {k: float(np.median(v)) for k, v in us.items()}
+    spread = abs(med["twin_aa"] - med["twin"])
+    hits = {k: sum(c.batch_stats()["n_hits"] for c in p) for k, p in pairs.items()}
+    r.update(us_per_batch=us, loaded_us_per_batch=round(med["loaded"], 3), twin_us_per_batch=round(med["twin"], 3),
+             twin_aa_us_per_batch=round(med["twin_aa"], 3), aa_spread_us=round(spread, 3),
+             loaded_minus_twin_us=round(med["loaded"] - med["twin"], 3), n_hits=hits,
+             loaded_within_aa_spread=bool(med["loaded"] - med["twin"] <= spread),
+             load_shorter_than_replay=bool(min(r["load_ms"]) < r["replay_wall_ms"]))
+    line = json.dumps({"tool": "warm_start_bench --pair",
+                       "shape": {"rows": int(sum(ln)), "capacities": caps, "batch": B, "dim": d, "codecs": [8, 4], "zipf_alpha": args.alpha,
+                                 "replay_batches": fill, "steady_chunks": chunks, "batches_per_chunk": steps, "rounds": args.rounds},
+                       "what": {"replay_ms": "device events around the fill batches (lookup_interact_c1c2)", "replay_wall_ms": "host clock around them, ending in a synchronise",
+                                "export_ms": "host clock around export_state_c1c2", "plan_ms": "evs_cache_pair_load_plan, strict (host clock: pure host code)",
+                                "load_ms": "host clock around load_state_c1c2 into a fresh pair: plan + upload + allocation + launch, per round",
+                                "upload_alloc_ms": "host clock around the tool's own upload of the record list and allocation of records and arenas",
+                                "load_launch_ms": "device events around the load's kernel alone (evs_x_warm_pair_launch, best of 3)",
+                                "copy_ms": "device-to-device copy of bytes_moved",
+                                "loaded_us_per_batch / twin_us_per_batch / twin_aa_us_per_batch": "median over the chunks of device-event time per batch",
+                                "aa_spread_us": "|twin_aa - twin|: what two replay-warmed pairs differ by in this run",
+                                "loaded_within_aa_spread": "loaded - twin <= aa_spread_us (the verdict); load_shorter_than_replay is recorded, not gated"},
+                       "pair": r, "accepted": r["loaded_within_aa_spread"]})
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pair", action="store_true", help="the batched C1 + C2 pair's leg (evs_cache_pair_load against the replay fill; steady state beside replay-warmed twins)")
+    ap.add_argument("--pair-fill", type=int, default=180, help="--pair: fill batches (bench.py's mixed-tier fill)")
+    ap.add_argument("--pair-steps", type=int, default=20, help="--pair: batches per steady-state chunk")
+    ap.add_argument("--pair-chunks", type=int, default=9, help="--pair: steady-state chunks per pair")
     ap.add_argument("--exact", action="store_true", help="the exact batch-1 engine's leg (evs_cache_exact_load against the in-kernel replay)")
     ap.add_argument("--frac", type=float, default=0.10)
     ap.add_argument("--batch", type=int, default=16384)
@@ -148,10 +318,13 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/warm_start.json (--exact: profiles/exact_warm_start.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "exact_warm_start.json" if args.exact else "warm_start.json")
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "exact_warm_start.json" if args.exact else "warm_start_pair.json" if args.pair else "warm_start.json")
     assert torch.cuda.is_available(), "warm_start_bench measures on the GPU"
     if args.exact:
         return exact_leg(args)
+    if args.pair:
+        return pair_leg(args)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     lib = E._lib.lib()
