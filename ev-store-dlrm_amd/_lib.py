@@ -136,6 +136,8 @@ _PROTOS = {
     "evs_cache_lookup_interact": (_int, [_vp, _i64, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
     "evs_cache_lookup_bags": (_int, [_vp, _i64, _pp, _pp, _i64p, _vp, _i64, _i64, _vp, _vp]),
     "evs_cache_lookup_bags_interact": (_int, [_vp, _i64, _pp, _pp, _i64p, _vp, _i64, _int, _vp, _vp, _vp]),
+    "evs_cache_lookup_bags_c1c2": (_int, [_vp, _vp, _i64, _pp, _pp, _i64p, _vp, _i64, _i64, _vp, _int, _vp]),
+    "evs_cache_lookup_bags_interact_c1c2": (_int, [_vp, _vp, _i64, _pp, _pp, _i64p, _vp, _i64, _int, _vp, _vp, _int, _vp]),
     "evs_cache_batch_stats": (_int, [_vp, _i64p, _i64p, _vp]),
     "evs_cache_batch_dump": (_i64, [_vp, _vp, _i64, _vp]),
     "evs_cache_batch_export": (_i64, [_vp, _vp, _i64, _vp, _vp]),

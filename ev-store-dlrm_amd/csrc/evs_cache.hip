@@ -3346,8 +3346,17 @@ struct evs_cache {
     long long *bag_ptrs = nullptr; unsigned char *bag_hit = nullptr; uint4 *bag_rec = nullptr; int *bag_list_cnt = nullptr, *bag_sample = nullptr;
     // ... and for EvLFU under the "served bags" rule: the probe's record per position, the position -> sample map, a count per sample
     uint4 *bag_prov = nullptr; int *bag_pos_sample = nullptr, *bag_agg = nullptr;
+    bool had_c3 = false;        // a batched three-tier lookup has run on this cache: its evictions feed an alt-key tier (the pair's bag form refuses it)
     int bag_rule = 0;           // evs_cache_set_bag_rule: 0 none (an EvLFU cache has no bag form), 1 "served bags"
     float *bag_pool = nullptr; long long bag_pool_floats = 0;
+    // ragged bags through the C1 + C2 pair (evs_cache_lookup_bags_c1c2; held by C1, sized and grown like slab_bags): per position
+    // the tier code, the serve byte, the row address, the probe's record and the sample; both tiers' miss lists; per sample the
+    // hand-over word (zero between calls) and the count
+    void *slab_bags2 = nullptr;
+    long long bag2_max_pos = -1, bag2_max_b = 0;
+    unsigned char *bag2_code = nullptr, *bag2_serve = nullptr; long long *bag2_ptrs = nullptr; uint4 *bag2_prov = nullptr;
+    uint4 *bag2_rec[2] = {nullptr, nullptr}; int *bag2_list_cnt[2] = {nullptr, nullptr};
+    int *bag2_pos_sample = nullptr, *bag2_sample = nullptr, *bag2_agg = nullptr;
     int used = 0;  // 0 fresh, 1 exact path, 2 batched path
     bool exact_touched = false;   // an exact-path request or a resident server has run on the state, or a state was loaded (evs_cache_exact_load takes untouched caches only)
     int *estamp = nullptr;      // allocated when the backing tables live in host memory
@@ -3555,7 +3564,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->bag_pool, c->fetch_cnt};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -5092,6 +5101,21 @@ static int pair_start(evs_cache *c1, evs_cache *c2, hipStream_t st, const char *
     }
     return EVS_OK;
 }
+// What the (B, T) form and the bag form of the pair (cache_bags_c1c2_impl) share, so that calls of the two may alternate: the
+// route filter C1 holds, a tier's next batch stamp (never 0, distinct for consecutive batches), the batches the closes owe.
+constexpr unsigned kRouteWords = 1u << 20;
+static int pair_route_filter(evs_cache *c1, hipStream_t st) {
+    using namespace evs;
+    if (c1->route_filter) return EVS_OK;
+    EVS_HIP_CHECK(hipMalloc(&c1->route_filter, kRouteWords * 4));
+    EVS_HIP_CHECK(hipMemsetAsync(c1->route_filter, 0, kRouteWords * 4, st));
+    return EVS_OK;
+}
+static int pair_next_stamp(evs_cache *c) { return (int)(++c->stamp_counter % 0x7ffffffe) + 1; }
+static void pair_count_batch(evs_cache *c1, evs_cache *c2, int64_t B) {
+    c1->pending_batches++; c1->pending_requests += B;
+    c2->pending_batches++; c2->pending_requests += B;
+}
 
 static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B, const int32_t *rows, float *out, uint8_t *tier,
                            int high_agghit_threshold, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
@@ -5151,6 +5175,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         if (!c3->has_alt) { set_error("evs_cache_lookup_batch_c1c2c3: call evs_aprx_set_altkeys first"); return EVS_ESTATE; }
         if (c3->used == 1) { set_error("evs_cache_lookup_batch_c1c2c3: this alt-key tier is used through the exact path"); return EVS_ESTATE; }
         c3->used = 2;
+        c1->had_c3 = c2->had_c3 = true;
         for (evs_cache *c : {c1, c2})
             if (!c->evicted_keys) EVS_HIP_CHECK(hipMalloc(&c->evicted_keys, (long long)c->host.cap * 8));
         a1.evicted_keys = c1->evicted_keys; a2.evicted_keys = c2->evicted_keys;
@@ -5173,18 +5198,14 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         set_error("evs_cache_lookup_batch_c1c2: the tiers were built over different key universes (table row counts differ); make both over the same tables");
         return EVS_ESTATE;
     }
-    constexpr unsigned kRouteWords = 1u << 20;
     static const bool route_on_env = !(evs::env_switch("EVS_CACHE_ROUTEFILTER") && evs::env_switch("EVS_CACHE_ROUTEFILTER")[0] == '0');
     const bool route_on = route_on_env || sa2;   // (the set-associative update has no cross-tier hash look-up to fall back on)
-    if (sampled2 && route_on && !c1->route_filter) {
-        EVS_HIP_CHECK(hipMalloc(&c1->route_filter, kRouteWords * 4));
-        EVS_HIP_CHECK(hipMemsetAsync(c1->route_filter, 0, kRouteWords * 4, st));
-    }
+    if (sampled2 && route_on) { const int frc = pair_route_filter(c1, st); if (frc) return frc; }
     if (sampled2) {
         for (int k = 0; k < 2; k++) {
             evs_cache *c = k ? c2 : c1;
             BatchArgs &a = k ? a2 : a1;
-            if (!host2) a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;   // (host tiers: set above, with the hit stamps)
+            if (!host2) a.stamp = pair_next_stamp(c);   // (host tiers: set above, with the hit stamps)
             a.tomb_parity = sa2 ? -1 : (a.stamp & 1);
             sampled_flush_if_wanted(c, st);
             static const bool c3_inline_on = !(evs::env_switch("EVS_CACHE_C3INLINE") && evs::env_switch("EVS_CACHE_C3INLINE")[0] == '0');
@@ -5329,8 +5350,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         }
         }
         if (c3 && !a1.c3_tags) hipLaunchKernelGGL(c3_batch_insert_lists_kernel, dim3(2 * kReplicas * 8), dim3(256), 0, st, a1, a2, tt.c3);   // what the two tiers evicted
-        c1->pending_batches++; c1->pending_requests += B;
-        c2->pending_batches++; c2->pending_requests += B;
+        pair_count_batch(c1, c2, B);
         // The close only folds counters, and the one thing the next probe reads of them is "is C1 full" (the routing rule).
         // Once a close that ran after C1's last flush has reported it full -- nothing but a flush takes entries away -- the
         // counters are folded every kCloseEvery-th batch as in the single-tier path (5 us per batch become 0.6); while C1
@@ -5372,6 +5392,21 @@ extern "C" int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t 
     EVS_REQUIRE((x && R) || B == 0, "evs_cache_lookup_interact: NULL x / R");
     EVS_REQUIRE(x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "evs_cache_lookup_interact: x must be 16-byte aligned, stride % 4 == 0");
     return cache_batch_impl(c, B, rows, nullptr, hit, x, x_stride, itself, R, stream);
+}
+
+// What the set-associative update (sa_list_block, sa_insert_one) reads of a tier when the bag chains hand it their miss lists: one
+// filler for the single-tier EvLFU bag chain and for both tiers of the pair's, so that a field the update starts reading is set in
+// one place.  No alt-key tier (c3_tags stays NULL: the bag forms refuse a pair that has one).
+static evs::BatchArgs bag_update_args(evs_cache *c, int64_t B, int stamp, uint4 *rec, int *cnt, int list_cap, int grid) {
+    using namespace evs;
+    BatchArgs u{};
+    u.bs = c->bs; u.a = c->a; u.sa = c->sa; u.sau = c->sau; u.stamp = stamp; u.tomb_parity = -1;
+    for (int k = 0; k < kMaxTables; k++) { u.backing[k] = c->backing[k]; u.backing_rows[k] = c->backing_rows[k]; }
+    u.B = B; u.cap = (int)c->host.cap; u.T = c->host.n_tables; u.d = c->host.dim; u.codec = c->host.codec; u.row_bytes = c->host.row_bytes;
+    u.max_perfect = c->host.max_perfect; u.flush_n = c->host.flush_n;
+    u.part1 = c->part1; u.part2 = c->part2; u.host_tomb = c->host_tomb_dev;
+    u.miss_rec = rec; u.list_cnt = cnt; u.list_cap = list_cap; u.g1 = grid;
+    return u;
 }
 
 // ---- ragged bags through an LRU / LFU / EvLFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) ---------------
@@ -5539,13 +5574,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         // every sample's count is known: the hit ways go up, the misses are listed with their counts, and the (B, T) chain's
         // update inserts them -- priorities read after all raises, the launches in stream order
         bags_raise_list_launch(a, (int)grid, st);
-        BatchArgs u{};
-        u.bs = c->bs; u.a = c->a; u.sa = c->sa; u.sau = c->sau; u.stamp = stamp; u.tomb_parity = -1;
-        for (int k = 0; k < kMaxTables; k++) { u.backing[k] = c->backing[k]; u.backing_rows[k] = c->backing_rows[k]; }
-        u.B = B; u.cap = (int)c->host.cap; u.T = T; u.d = d; u.codec = c->host.codec; u.row_bytes = c->host.row_bytes;
-        u.max_perfect = c->host.max_perfect; u.flush_n = c->host.flush_n;
-        u.part1 = c->part1; u.part2 = c->part2; u.host_tomb = c->host_tomb_dev;
-        u.miss_rec = c->bag_rec; u.list_cnt = c->bag_list_cnt; u.list_cap = pa.list_cap; u.g1 = (int)grid;
+        const BatchArgs u = bag_update_args(c, B, stamp, c->bag_rec, c->bag_list_cnt, pa.list_cap, (int)grid);
         launch_sa_update(u, st);
     } else if (grid && !ff) {
         policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
@@ -5569,6 +5598,223 @@ extern "C" int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int
     using namespace evs;
     EVS_REQUIRE(B <= 0 || (x && R), "evs_cache_lookup_bags_interact: NULL x / R");
     return cache_bags_impl(c, B, indices, offsets, nnz, nullptr, 0, 0, x, x_stride, itself, R, hit, stream, "evs_cache_lookup_bags_interact");
+}
+
+// ---- ragged bags through the batched C1 + C2 pair (the rule: include/evstore_hip.h at evs_cache_lookup_bags_c1c2) -------------
+// One call is batch n of both tiers, as a (B, T) call of batch_c1c2_impl is: the same stamps, the same flush at entry, the same
+// route filter, update launch and closes.  Between them the bag chain of evs_cache_policy.hip:
+//   probe2 (one lane per position, both tiers' ways out of the shared record, no way word written)
+//   -> count (a lane per bag over the code bytes: agg per sample -- the table a miss is served from depends on it)
+//   -> route + raise + list  -> pool2 (every position decoded by its serving tier)  (-> dense interaction)  -> the pair's update.
+static bool pair_shares_records(const evs_cache *c1, const evs_cache *c2);
+static const char *bag_pair_codecs_ok(int c1, int c2) {   // the six pairs the reference builds (MGR_VARIANTS)
+    return (c1 == 32 && (c2 == 16 || c2 == 8 || c2 == 4)) || (c1 == 16 && (c2 == 8 || c2 == 4)) || (c1 == 8 && c2 == 4) ? nullptr
+           : "32-16, 32-8, 32-4, 16-8, 16-4, 8-4";
+}
+static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
+                                const int64_t *nnz, float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride,
+                                int itself, float *R, uint8_t *tier, int threshold, void *stream, const char *who) {
+    using namespace evs;
+    const bool interact = R != nullptr || x != nullptr;
+    // the argument checks of cache_bags_impl, in its order
+    EVS_REQUIRE(B >= 0, "%s: B = %lld", who, (long long)B);
+    if (B == 0) return EVS_OK;
+    EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
+    EVS_REQUIRE(indices && offsets && nnz, "%s: NULL indices / offsets / nnz", who);
+    EVS_REQUIRE(interact ? (x && R) : pooled != nullptr, "%s: NULL %s", who, interact ? "x / R" : "pooled");
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
+    EVS_REQUIRE(c1 && c2, "%s: NULL cache (%s)", who, !c1 ? "C1" : "C2");
+    EVS_REQUIRE(c1 != c2, "%s: one cache given as both tiers", who);
+    EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
+    const int T = c1->host.n_tables, d = c1->host.dim;
+    EVS_REQUIRE(T <= 32, "%s: at most 32 tables", who);
+    EVS_REQUIRE(B < (1ll << 31), "%s: B = %lld", who, (long long)B);
+    long long n_pos = 0;
+    for (int k = 0; k < T; k++) {
+        EVS_REQUIRE(nnz[k] >= 0, "%s: nnz[%d] = %lld", who, k, (long long)nnz[k]);
+        EVS_REQUIRE(indices[k] || nnz[k] == 0, "%s: indices[%d] is NULL", who, k);
+        EVS_REQUIRE(offsets[k], "%s: offsets[%d] is NULL", who, k);
+        n_pos += nnz[k];
+        EVS_REQUIRE(n_pos < (1ll << 31), "%s: 2^31 lookups or more in one call", who);
+    }
+    EVS_REQUIRE(d % 4 == 0 && d <= 256, "%s: the pooling takes a dim that is a multiple of 4 up to 256, not %d", who, d);
+    if (interact)
+        EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
+                    who, EVS_MAX_FEATURES, T, d);
+    // the envelope: refused before anything is allocated, the pair left as it was
+    evs_cache *cs[2] = {c1, c2};
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = cs[k];
+        const char *cn = k ? "C2" : "C1";
+        EVS_REQUIRE(c->host.policy == kEvLFU, "%s: the tier pair is EvLFU's; %s is an %s cache", who, cn, policy_name(c->host.policy));
+        EVS_REQUIRE(c->bag_rule == 1, "%s: %s has no bag rule: evs_cache_set_bag_rule(c, 1) says what a request's hit count is over bags, and the pair "
+                    "needs it told to both tiers", who, cn);
+        { const int rc = batch_check(c, who); if (rc) return rc; }
+        if (c->host_backing || c->ft) {
+            set_error("%s: the bag form of the pair reads its tables in place from HBM; %s sits over host-memory / file-backed tables", who, cn);
+            return EVS_ESTATE;
+        }
+        EVS_REQUIRE(c->miss_order == 0, "%s: %s runs fetch-first (evs_cache_set_miss_order): such a tier is a tier alone", who, cn);
+        EVS_REQUIRE(!(c->serving || c->tsrv), "%s: a resident server is running on %s", who, cn);
+        EVS_REQUIRE(!c->had_c3, "%s: %s has run as a tier of a triple (evs_cache_lookup_batch_c1c2c3): the bag form has no alt-key tier, and the "
+                    "pair's evictions would bypass it", who, cn);
+    }
+    {
+        const char *pairs = bag_pair_codecs_ok(c1->host.codec, c2->host.codec);
+        EVS_REQUIRE(!pairs, "%s: no pooling for a %d-bit C1 over a %d-bit C2; the pairs of precisions are %s", who, c1->host.codec, c2->host.codec, pairs);
+    }
+    const int given1 = c1->batch_policy, given2 = c2->batch_policy;
+    if (c1->sa.tags || c2->sa.tags || c1->bs || c2->bs) {   // a pair that has started: it must have started out together, over one record per set
+        EVS_REQUIRE(pair_shares_records(c1, c2), "%s: the bag form is the set-associative pair's that shares its set records (batch policy 2 on both tiers, "
+                    "started out together); these tiers %s", who,
+                    (c1->batch_policy == 0 || c1->batch_policy == 1 || c2->batch_policy == 0 || c2->batch_policy == 1)
+                        ? "run the plan-based or the sampled update" : "did not start out as such a pair (records of their own)");
+    } else {
+        auto refuse = [&](int rc) { c1->batch_policy = given1; c2->batch_policy = given2; return rc; };
+        { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return refuse(rc); }
+        const int p1 = resolved_batch_policy(c1), p2 = resolved_batch_policy(c2);
+        if (p1 != 2 || p2 != 2) {
+            set_error("%s: the bag form is the set-associative pair's (batch policy 2); the batch policy of these tiers is %s", who,
+                      (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
+            return refuse(EVS_EINVAL);
+        }
+        SaUniverse u; SaGeom g1, g2;
+        if (!sa_pair_geometry(c1, c2, u, g1, g2)) {
+            set_error("%s: capacities %lld + %lld give the pair no shared set record (a tier would get fewer than 4 ways, or EVS_SA_PAIR=0); the bag form "
+                      "needs it", who, (long long)c1->host.cap, (long long)c2->host.cap);
+            return refuse(EVS_EINVAL);
+        }
+    }
+    for (int k = 0; k < 2; k++) {
+        const int piece_bytes = cs[k]->host.codec / 2;   // what a lane reads of a row at once: 16 / 8 / 4 / 2 bytes
+        for (int t = 0; t < T; t++)
+            EVS_REQUIRE(reinterpret_cast<uintptr_t>(cs[k]->backing[t]) % piece_bytes == 0, "%s: table %d of %s is not %d-byte aligned", who, t, k ? "C2" : "C1", piece_bytes);
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = pair_start(c1, c2, st, who); if (rc) return rc; }
+    if (!pair_shares_records(c1, c2)) { set_error("%s: the pair did not get its shared set records", who); return EVS_ESTATE; }
+    for (evs_cache *c : cs) { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    int *err = index_error_flag();
+    if (!err) return EVS_EHIP;
+
+    // one lane per position, blocks of 256, looping past kProbeGridMax blocks; a miss list per block and tier
+    long long grid = (n_pos + 255) / 256; if (grid > kProbeGridMax) grid = kProbeGridMax;
+    const long long iters = grid ? (n_pos + 256 * grid - 1) / (256 * grid) : 0;
+    if (n_pos > c1->bag2_max_pos || B > c1->bag2_max_b) {   // grow: the new slab first, the old one goes only when the new one exists
+        const long long np = std::max<long long>(n_pos, c1->bag2_max_pos), nb = std::max<long long>(B, c1->bag2_max_b);
+        unsigned char *code = nullptr, *serve = nullptr; long long *ptrs = nullptr; uint4 *prov = nullptr, *rec1 = nullptr, *rec2 = nullptr;
+        int *cnt1 = nullptr, *cnt2 = nullptr, *pos_sample = nullptr, *sample = nullptr, *agg = nullptr;
+        void *slab = nullptr;
+        SlabPlan sp;
+        const long long n_rec = np <= 256ll * kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * kProbeGridMax;   // (as cache_bags_impl sizes its lists)
+        sp.add(&code, np); sp.add(&serve, np); sp.add(&ptrs, np * 8); sp.add(&prov, np * 16); sp.add(&pos_sample, np * 4);
+        sp.add(&rec1, n_rec * 16); sp.add(&rec2, n_rec * 16);
+        sp.add(&cnt1, (long long)kProbeGridMax * 4); sp.add(&cnt2, (long long)kProbeGridMax * 4);
+        sp.add(&sample, nb * 4); sp.add(&agg, nb * 4);
+        if (!sp.carve(&slab)) { set_error("%s: allocating the buffers of a call of %lld lookups failed", who, n_pos); return EVS_ENOMEM; }
+        if (c1->slab_bags2) {
+            EVS_HIP_CHECK(hipStreamSynchronize(st));
+            (void)hipFree(c1->slab_bags2);
+        }
+        c1->slab_bags2 = slab;
+        c1->bag2_code = code; c1->bag2_serve = serve; c1->bag2_ptrs = ptrs; c1->bag2_prov = prov; c1->bag2_pos_sample = pos_sample;
+        c1->bag2_rec[0] = rec1; c1->bag2_rec[1] = rec2; c1->bag2_list_cnt[0] = cnt1; c1->bag2_list_cnt[1] = cnt2;
+        c1->bag2_sample = sample; c1->bag2_agg = agg;
+        c1->bag2_max_pos = np; c1->bag2_max_b = nb;
+        EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
+    }
+    if (interact && (long long)T * B * d > c1->bag_pool_floats) {
+        float *pool = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&pool), (size_t)T * B * d * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: allocating the (T, B, d) block of %lld samples failed", who, (long long)B);
+            return EVS_ENOMEM;
+        }
+        if (c1->bag_pool) {
+            EVS_HIP_CHECK(hipStreamSynchronize(st));
+            (void)hipFree(c1->bag_pool);
+        }
+        c1->bag_pool = pool; c1->bag_pool_floats = (long long)T * B * d;
+    }
+    { const int rc = pair_route_filter(c1, st); if (rc) return rc; }
+    // batch n of both tiers: the (B, T) pair's stamps, and the flush the close of an earlier batch asked for, before the probe
+    int stamp[2];
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = cs[k];
+        c->used = 2;
+        c->batch_calls++;
+        stamp[k] = pair_next_stamp(c);
+        sampled_flush_if_wanted(c, st);
+    }
+
+    BagPairArgs a;
+    a.sa1 = c1->sa; a.sa2 = c2->sa; a.sau = c1->sau;
+    a.pos0[0] = 0;
+    for (int k = 0; k < 32; k++) {
+        a.indices[k] = k < T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
+        a.offsets[k] = k < T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
+        a.pos0[k + 1] = a.pos0[k] + (k < T ? nnz[k] : 0);
+        a.rows[k] = k < T ? std::min<long long>(c1->backing_rows[k], c2->backing_rows[k]) : 0;
+        a.backing1[k] = c1->backing[k]; a.backing2[k] = c2->backing[k];
+    }
+    a.arena1 = c1->a.arena; a.arena2 = c2->a.arena;
+    a.row_bytes1 = c1->host.row_bytes; a.row_bytes2 = c2->host.row_bytes;
+    a.n_pos = n_pos; a.B = B; a.iters = (int)iters; a.T = T; a.d = d; a.threshold = threshold;
+    a.err = err;
+    a.code = tier ? tier : c1->bag2_code; a.serve = c1->bag2_serve; a.row_ptrs = c1->bag2_ptrs; a.prov = c1->bag2_prov;
+    a.pos_sample = c1->bag2_pos_sample; a.agg = c1->bag2_agg; a.sample_cnt = c1->bag2_sample;
+    a.miss_rec1 = c1->bag2_rec[0]; a.miss_rec2 = c1->bag2_rec[1]; a.list_cnt1 = c1->bag2_list_cnt[0]; a.list_cnt2 = c1->bag2_list_cnt[1];
+    a.list_cap = (int)(iters * 256);
+    a.part1_1 = c1->part1; a.part1_2 = c2->part1;
+    a.route_filter = c1->route_filter; a.route_mask = kRouteWords - 1; a.route_stamp = (unsigned)stamp[0];
+    a.out = interact ? c1->bag_pool : pooled;
+    a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
+    a.chunks_per_table = 0;
+
+    if (grid) bags_probe2_launch(a, (int)grid, st);
+    bags_count2_launch(a, st);
+    if (grid) bags_route2_launch(a, (int)grid, st);   // (in front of the pooling: raises change priorities only, no key or arena row moves until the update)
+    if (!bags_pool2_launch(a, c1->host.codec, c2->host.codec, st)) { set_error("%s: no pooling kernel for the pair of precisions", who); return EVS_EINVAL; }
+    if (interact) {
+        const float *feats[EVS_MAX_FEATURES];
+        int64_t strides[EVS_MAX_FEATURES];
+        feats[0] = x; strides[0] = x_stride;
+        for (int k = 0; k < T; k++) { feats[k + 1] = c1->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
+        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+        if (rc) {   // nothing is inserted and the raises stand; the batch is counted, so the close folds its hits with its requests
+            pair_count_batch(c1, c2, B);
+            return rc;
+        }
+    }
+    if (grid) {
+        const BatchArgs u1 = bag_update_args(c1, B, stamp[0], a.miss_rec1, a.list_cnt1, a.list_cap, (int)grid);
+        BatchArgs u2 = bag_update_args(c2, B, stamp[1], a.miss_rec2, a.list_cnt2, a.list_cap, (int)grid);
+        u2.route_filter = c1->route_filter; u2.route_mask = kRouteWords - 1; u2.route_stamp = (unsigned)stamp[0];
+        if (!launch_sa_update_pair(u1, u2, st)) {
+            launch_sa_update(u1, st);
+            launch_sa_update(u2, st);
+        }
+    }
+    pair_count_batch(c1, c2, B);
+    if (c1->pending_batches >= kCloseEvery || c2->pending_batches >= kCloseEvery) sampled_close_pending2(c1, 0, c2, 0, st);
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+
+extern "C" int evs_cache_lookup_bags_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
+                                          const int64_t *nnz, float *pooled, int64_t out_table_stride, int64_t out_bag_stride,
+                                          uint8_t *tier, int high_agghit_threshold, void *stream) {
+    return cache_bags_c1c2_impl(c1, c2, B, indices, offsets, nnz, pooled, out_table_stride, out_bag_stride, nullptr, 0, 0, nullptr, tier,
+                                high_agghit_threshold, stream, "evs_cache_lookup_bags_c1c2");
+}
+
+extern "C" int evs_cache_lookup_bags_interact_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices,
+                                                   const int64_t *const *offsets, const int64_t *nnz, const float *x, int64_t x_stride,
+                                                   int itself, float *R, uint8_t *tier, int high_agghit_threshold, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(B <= 0 || (x && R), "evs_cache_lookup_bags_interact_c1c2: NULL x / R");
+    return cache_bags_c1c2_impl(c1, c2, B, indices, offsets, nnz, nullptr, 0, 0, x, x_stride, itself, R, tier, high_agghit_threshold, stream,
+                                "evs_cache_lookup_bags_interact_c1c2");
 }
 
 // out8 (host): [size, n_free, n_tomb, n_flush, n_evict, n_requests, n_perfect_hits, n_hits]; hist: n_tables+1 priority counts

@@ -108,6 +108,48 @@ void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st);
 // the record cache_batch_sa_list_kernel (evs_cache.hip) reads
 void bags_raise_list_launch(const BagArgs &a, int grid, hipStream_t st);
 
+// Ragged bags through the C1 + C2 pair that shares its set records (evs_cache_lookup_bags_c1c2; the rule: include/evstore_hip.h
+// there).  Positions are numbered as above.  Where a missed position is served from depends on its sample's agg_hit, and one bag
+// can mix rows of two precisions, so the chain is  probe2 -> count -> route + raise + list -> pool2 (-> dense interaction) -> the
+// pair's update:
+//   prov[p]   the probe's record of position p: x = row, y = table | hit way << 8 | tier code << 12 | "the key's C1 set has a free
+//             way" << 14 | "a key" << 15, z = the set index, w = the quotient -- (set, quotient) place the key in either tier
+//             (sa_place), so nothing is searched or divided twice
+//   code[p]   1 = resident in C1, 2 = in C2, 0 = neither (or no key)
+//   serve[p]  the tier whose codec decodes the row row_ptrs[p] names: the code of a hit, the destination of a miss, 0 = no row
+struct BagPairArgs {
+    SaGeom sa1, sa2; SaUniverse sau;
+    const long long *indices[32];
+    const long long *offsets[32];
+    long long pos0[33];
+    long long rows[32];                    // per table: min of the two tiers' row counts (an index past either is no key)
+    const unsigned char *backing1[32], *backing2[32];
+    unsigned char *arena1, *arena2;
+    int row_bytes1, row_bytes2;
+    long long n_pos, B;
+    int iters, T, d, threshold;
+    int *err;
+    unsigned char *code, *serve;
+    long long *row_ptrs;
+    uint4 *prov;
+    int *pos_sample, *agg, *sample_cnt;    // as BagArgs has them
+    uint4 *miss_rec1, *miss_rec2; int *list_cnt1, *list_cnt2; int list_cap;   // per route block and tier: (row, table | agg << 8, effective set, tag + 1)
+    int *part1_1, *part1_2;                // replica rows: columns 0 .. T histogram moves, 38 hits (per tier), 39 all-served samples (C1's)
+    unsigned *route_filter; unsigned route_mask, route_stamp;
+    float *out; long long out_tstride, out_bstride;
+    long long chunks_per_table;
+};
+// one lane per position (grid blocks of 256 threads, block j walks positions 256 (j + i grid) + thread, i < iters): one read of the
+// shared record finds both tiers' ways; writes code, serve and row_ptrs of the hits, prov, pos_sample = -1.  Writes no way word
+void bags_probe2_launch(const BagPairArgs &a, int grid, hipStream_t st);
+// one lane per bag over the code bytes alone: pos_sample, agg[b] = the sample's served bags, the all-served samples into column 39
+void bags_count2_launch(const BagPairArgs &a, hipStream_t st);
+// one lane per position (the probe's grid): a miss gets its destination tier, its table address and its serve byte, is stamped
+// into the route filter (odd tables routed to C1) and listed for its tier in list j; a hit way goes to max(old, agg)
+void bags_route2_launch(const BagPairArgs &a, int grid, hipStream_t st);
+// pooled[k][b]: bags_pool_launch's shape, every position decoded by the codec its serve byte names.  false: no kernel for the pair
+bool bags_pool2_launch(const BagPairArgs &a, int codec1, int codec2, hipStream_t st);
+
 // Fetch-first order (evs_cache_set_miss_order(c, 1); the chain: evs_cache.hip, cache_batch_impl): behind the policy update, every
 // position the probe flagged 0 is searched again in its set -- the line the update touched a moment ago -- and, where the key
 // got a way, its slot of the pointer table is re-pointed from the table row at the arena row.  A key that was turned away

@@ -14,6 +14,9 @@
 // EvLFU under the "served bags" rule runs  bags_probe (no touch) -> bags_pool (+ the samples' counts) (-> dense interaction) ->
 // bags_raise_list -> cache_batch_sa_list_kernel (evs_cache.hip): a sample's count exists only after the pooling has seen all
 // its bags, so the raises and the miss lists come from a launch of their own behind it.
+// The C1 + C2 pair over bags (evs_cache_lookup_bags_c1c2) runs  bags_probe2 -> bags_count2 -> bags_route2 -> bags_pool2 (-> dense
+// interaction) -> cache_batch_sa_list2_kernel (evs_cache.hip): the table a missed position is served from depends on its sample's
+// count, so the counts come from a pass over the code bytes IN FRONT of the pooling, and the pooling decodes per position.
 #include <type_traits>
 
 #include "evs_cache_policy.h"
@@ -369,6 +372,306 @@ __global__ void __launch_bounds__(256) bags_raise_list_kernel(const BagArgs args
     if (threadIdx.x == 0) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
 }
 
+// ---- ragged bags through the C1 + C2 pair (evs_cache_lookup_bags_c1c2; the records: evs_cache_policy.h, BagPairArgs) ----------
+// K1 of the pair over bags: bags_probe_kernel's walk, cache_batch_probe2_kernel's look at the shared record -- both tiers' ways of
+// the key's set in one line request, "C1 has room" = the key's own C1 set has a free way -- and no write to a way word: the
+// raises wait for the samples' counts (bags_route2_kernel).  An index out of range of either tier's table is no key.
+constexpr unsigned kProvWayShift = 8, kProvCodeShift = 12, kProvRoom = 1u << 14, kProvKey = 1u << 15;
+__global__ void __launch_bounds__(256) bags_probe2_kernel(const BagPairArgs args) {
+    __shared__ int s_hits[2];
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32], s_pos0[32];
+    __shared__ const long long *s_idx[32];
+    const int T = args.T;
+    if (threadIdx.x < 2) s_hits[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        const bool tab = (int)threadIdx.x < T;
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = tab ? args.rows[threadIdx.x] : 0;
+        s_idx[threadIdx.x] = args.indices[threadIdx.x];
+        s_pos0[threadIdx.x] = tab ? args.pos0[threadIdx.x] : args.n_pos;
+    }
+    __syncthreads();
+    const SaGeom &g1 = args.sa1, &g2 = args.sa2;
+    const bool w88 = g1.ways == 8u && g2.ways == 8u;   // (the reference's 1 : 2 pair: way counts known to the compiler)
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = p < args.n_pos;
+        int k = 0;
+#pragma unroll
+        for (int step = 16; step >= 1; step >>= 1) k += (on && s_pos0[k + step] <= p) ? step : 0;
+        const long long row = on ? s_idx[k][p - s_pos0[k]] : -1;
+        const bool ok = on && row >= 0 && row < s_rows[k];
+        bad = bad || (on && !ok);
+        unsigned set = 0u, q = 0u;
+        sa_divmod(g1, sa_perm(args.sau, s_base[k] + (ok ? (unsigned)row : 0u)), set, q);   // (the tiers share nset: one division)
+        if (!ok) { set = 0u; q = 0u; }
+        unsigned es1, tg1, es2, tg2, w1 = 0u, w2 = 0u;
+        sa_place(g1, set, q, es1, tg1);
+        sa_place(g2, set, q, es2, tg2);
+        SaLine l1, l2;
+        int y1, y2;
+        bool room;
+        if (w88) {
+            sa_load<8>(g1, es1, l1);
+            sa_load<8>(g2, es2, l2);
+            y1 = sa_find<8>(g1, l1, tg1, w1); y2 = sa_find<8>(g2, l2, tg2, w2);
+            room = sa_has_free<8>(g1, l1);
+        } else {
+            sa_load<0>(g1, es1, l1);
+            sa_load<0>(g2, es2, l2);
+            y1 = sa_find<0>(g1, l1, tg1, w1); y2 = sa_find<0>(g2, l2, tg2, w2);
+            room = sa_has_free<0>(g1, l1);
+        }
+        const unsigned code = (ok && y1 >= 0) ? 1u : ((ok && y2 >= 0) ? 2u : 0u);
+        if (on) {
+            const unsigned char *src = nullptr;
+            if (code == 1u) src = args.arena1 + (long long)sa_entry(g1, es1, (unsigned)y1, w1) * args.row_bytes1;
+            else if (code == 2u) src = args.arena2 + (long long)sa_entry(g2, es2, (unsigned)y2, w2) * args.row_bytes2;
+            args.code[p] = (unsigned char)code;
+            args.serve[p] = (unsigned char)code;
+            args.row_ptrs[p] = (long long)src;
+            const unsigned way = code == 1u ? (unsigned)y1 : (code == 2u ? (unsigned)y2 : 0u);
+            args.prov[p] = make_uint4((unsigned)row, (unsigned)k | (way << kProvWayShift) | (code << kProvCodeShift) | (room ? kProvRoom : 0u) | (ok ? kProvKey : 0u),
+                                      set, q);
+            args.pos_sample[p] = -1;
+        }
+        const unsigned long long h1 = __ballot(code == 1u), h2 = __ballot(code == 2u);
+        if (lane == 0) {
+            if (h1) atomicAdd(&s_hits[0], __popcll(h1));
+            if (h2) atomicAdd(&s_hits[1], __popcll(h2));
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_hits[0]) atomicAdd(&args.part1_1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38], s_hits[0]);
+        if (s_hits[1]) atomicAdd(&args.part1_2[(blockIdx.x % kPolReplicas) * kPolPartCols + 38], s_hits[1]);
+    }
+}
+
+// The count pass: a lane per bag walks the bag's code bytes -- no row is touched -- tells every position it covers which sample
+// it belongs to, and hands its verdict to the sample's word (bags_pool_kernel's sample_cnt hand-over): whoever brings a sample's
+// T-th bag writes agg[b] = the sample's served bags, counts an all-served sample with a lookup into column 39 and leaves the
+// word zero.  It runs before the pooling because the table a miss is served from depends on agg.  A bag whose offsets are
+// backwards or past nnz is empty (served) and raises the sticky flag.
+__global__ void __launch_bounds__(256) bags_count2_kernel(const BagPairArgs args) {
+    __shared__ int s_perfect;
+    __shared__ long long s_pos0[33];
+    __shared__ const long long *s_off[32];
+    if (threadIdx.x == 0) s_perfect = 0;
+    if (threadIdx.x < 33) s_pos0[threadIdx.x] = args.pos0[threadIdx.x];
+    if (threadIdx.x < 32) s_off[threadIdx.x] = args.offsets[threadIdx.x];
+    __syncthreads();
+    const int T = args.T;
+    const long long B = args.B, n_bags = (long long)T * B;
+    bool bad = false;
+    int n_perfect = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bags; i += (long long)gridDim.x * 256) {
+        const int t = (int)(i / B);
+        const long long b = i - (long long)t * B;
+        const long long nnz = s_pos0[t + 1] - s_pos0[t];
+        const long long *__restrict__ off = s_off[t];
+        long long st = off[b];
+        long long en = (b + 1 < B) ? off[b + 1] : nnz;
+        if (!(st >= 0 && en >= st && en <= nnz)) { bad = true; st = 0; en = 0; }
+        const unsigned char *__restrict__ code = args.code + s_pos0[t];
+        int *__restrict__ ps = args.pos_sample + s_pos0[t];
+        bool miss = false;
+        for (long long j = st; j < en; j++) {
+            miss = miss || code[j] == 0;
+            ps[j] = (int)b;
+        }
+        const int mine = 1 | (en > st ? 1 << 8 : 0) | (miss ? 1 << 16 : 0);
+        const int all = atomicAdd(&args.sample_cnt[b], mine) + mine;
+        if ((all & 0xff) == T) {   // the sample's last bag: nobody else writes the word any more
+            args.sample_cnt[b] = 0;
+            args.agg[b] = T - (all >> 16);
+            if (((all >> 8) & 0xff) != 0 && (all >> 16) == 0) n_perfect++;
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    if (n_perfect) atomicAdd(&s_perfect, n_perfect);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_perfect)
+        atomicAdd(&args.part1_1[(blockIdx.x % kPolReplicas) * kPolPartCols + 39], s_perfect);
+}
+
+// Route + raise + list: one lane per position, the probe's grid and walk.  a = agg of the position's sample (0 when no valid bag
+// covers it).  A hit way goes to max(old, a) in the tier that holds it (a plain read first, as bags_raise_list_kernel).  A miss is
+// routed on the snapshot (evlfu_8.cpp:570-601 as cache_batch_probe2_kernel evaluates it: the key's own C1 set has room -> C1;
+// else a < threshold -> C1 for an odd table index, C2 for an even one; else C2), gets the destination's table row and serve
+// byte, stamps the route filter (odd tables routed to C1) and goes into the block's list of its tier in the record
+// cache_batch_sa_list2_kernel reads.  Nothing but raises writes a way word during this launch.
+__global__ void __launch_bounds__(256) bags_route2_kernel(const BagPairArgs args) {
+    __shared__ int s_delta[2][64];
+    __shared__ int s_list_n[2];
+    __shared__ const unsigned char *s_tab[2][32];
+    const int T = args.T;
+    if (threadIdx.x < 128) s_delta[threadIdx.x >> 6][threadIdx.x & 63] = 0;
+    if (threadIdx.x < 2) s_list_n[threadIdx.x] = 0;
+    if (threadIdx.x < 32) { s_tab[0][threadIdx.x] = args.backing1[threadIdx.x]; s_tab[1][threadIdx.x] = args.backing2[threadIdx.x]; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = p < args.n_pos;
+        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+        int a = 0;
+        if (on) {
+            r = args.prov[p];
+            const int b = args.pos_sample[p];
+            if (b >= 0) a = args.agg[b];
+        }
+        const int k = (int)(r.y & 31u);
+        const unsigned code = (r.y >> kProvCodeShift) & 3u;
+        const bool is_miss = (r.y & kProvKey) != 0u && code == 0u;
+        int dest = 0;
+        if (code != 0u) dest = (int)code;
+        else if (is_miss) dest = (r.y & kProvRoom) ? 1 : (a < args.threshold ? ((k & 1) ? 1 : 2) : 2);
+        const SaGeom &g = dest == 2 ? args.sa2 : args.sa1;
+        unsigned es = 0u, tag1 = 0u;
+        sa_place(g, r.z, r.w, es, tag1);
+        if (code != 0u && a > 0) {
+            unsigned *wp = sa_ways_ptr(g, es) + ((r.y >> kProvWayShift) & 15u);
+            const unsigned w = *wp;
+            if (sa_prio(w) < a) {
+                const int old = sa_raise(g, wp, w, a);
+                if (old >= 0) { atomicSub(&s_delta[dest - 1][old], 1); atomicAdd(&s_delta[dest - 1][a], 1); }
+            }
+        }
+        if (is_miss) {
+            args.serve[p] = (unsigned char)dest;
+            args.row_ptrs[p] = (long long)(s_tab[dest - 1][k] + (long long)r.x * (dest == 1 ? args.row_bytes1 : args.row_bytes2));
+            if (args.route_filter && dest == 1 && (k & 1))
+                args.route_filter[mix64(((unsigned long long)(k + 1) << 32) | r.x) & args.route_mask] = args.route_stamp;
+        }
+#pragma unroll
+        for (int t = 0; t < 2; t++) {   // the wave's misses of each tier, packed, behind the block's earlier ones
+            const bool mine = is_miss && dest == t + 1;
+            const unsigned long long mm = __ballot(mine);
+            int base = 0;
+            if (lane == 0 && mm) base = atomicAdd(&s_list_n[t], __popcll(mm));
+            base = __shfl(base, 0, 64);
+            if (mine) {
+                const int at = base + __popcll(mm & ((1ull << lane) - 1ull));
+                if (at < args.list_cap)
+                    (t ? args.miss_rec2 : args.miss_rec1)[(long long)blockIdx.x * args.list_cap + at] = make_uint4(r.x, (unsigned)k | ((unsigned)a << 8), es, tag1);
+            }
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= T) {
+        const int v1 = s_delta[0][threadIdx.x], v2 = s_delta[1][threadIdx.x];
+        if (v1) atomicAdd(&args.part1_1[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], v1);
+        if (v2) atomicAdd(&args.part1_2[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], v2);
+    }
+    if (threadIdx.x == 0) {
+        args.list_cnt1[blockIdx.x] = s_list_n[0] < args.list_cap ? s_list_n[0] : args.list_cap;
+        args.list_cnt2[blockIdx.x] = s_list_n[1] < args.list_cap ? s_list_n[1] : args.list_cap;
+    }
+}
+
+// The pair's pooling: bags_pool_kernel's shape (d / 4 lanes per bag, UNROLL bags in flight per group, the table id wave-uniform,
+// index order, unfused fp32 adds from +0), both codecs' tables in LDS, and per position the decoder its serve byte names -- the
+// rows of a bag may come from two tiers, 16 / 8 / 4 / 2 bytes per piece.  The samples' counts are the count pass's; a bag whose
+// offsets are out of order pools nothing, as it counted nothing there.
+template <int CODEC1, int CODEC2, int UNROLL>
+__global__ void __launch_bounds__(256) bags_pool2_kernel(const BagPairArgs args) {
+    __shared__ float s_lut1[CodecLut<CODEC1>::kEntries], s_lut2[CodecLut<CODEC2>::kEntries];
+    if constexpr (CODEC1 != 32) codec_lut_init<CODEC1>(s_lut1);
+    codec_lut_init<CODEC2>(s_lut2);
+    __syncthreads();
+    const int T = args.T;
+    const int LPR = args.d / 4;
+    const int RPW = kWave / LPR;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int slot = lane / LPR;
+    const int piece = lane - slot * LPR;
+    const bool lane_on = slot < RPW;
+    const long long B = args.B;
+    const int bags_per_item = RPW * UNROLL;
+    const int64_t n_items = (int64_t)T * args.chunks_per_table;
+    const XcdRange xr = xcd_range(n_items, 4, wave);
+
+    for (int64_t item = xr.first; item < xr.end; item += xr.stride) {
+        const int t = __builtin_amdgcn_readfirstlane((int)(item / args.chunks_per_table));
+        const long long chunk = item - (long long)t * args.chunks_per_table;
+        const long long b0 = chunk * bags_per_item;
+        const long long *__restrict__ off = args.offsets[t];
+        const long long nnz = args.pos0[t + 1] - args.pos0[t];
+        const long long *__restrict__ ptrs = args.row_ptrs + args.pos0[t];
+        const unsigned char *__restrict__ serve = args.serve + args.pos0[t];
+
+        long long s[UNROLL], len[UNROLL];
+        long long maxlen = 0;
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const long long b = b0 + (long long)u * RPW + slot;
+            s[u] = 0;
+            len[u] = 0;
+            if (lane_on && b < B) {
+                const long long st = off[b];
+                const long long en = (b + 1 < B) ? off[b + 1] : nnz;
+                if (st >= 0 && en >= st && en <= nnz) {
+                    s[u] = st;
+                    len[u] = en - st;
+                }
+            }
+            maxlen = len[u] > maxlen ? len[u] : maxlen;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {   // wave-wide max bag length (all lanes run the same trip count)
+            const long long o = __shfl_xor(maxlen, m, kWave);
+            maxlen = o > maxlen ? o : maxlen;
+        }
+
+        float4 acc[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+        for (long long j = 0; j < maxlen; j++) {
+            const unsigned char *r[UNROLL];
+            int sv[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                r[u] = nullptr;
+                sv[u] = 0;
+                if (j < len[u]) {
+                    r[u] = reinterpret_cast<const unsigned char *>(ptrs[s[u] + j]);
+                    sv[u] = serve[s[u] + j];
+                }
+            }
+            float4 v[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (r[u] && sv[u] == 1) v[u] = RowPiece<CODEC1>::load(r[u], piece, s_lut1);
+                else if (r[u] && sv[u] == 2) v[u] = RowPiece<CODEC2>::load(r[u], piece, s_lut2);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                if (r[u] && sv[u] != 0) {
+                    acc[u].x = __fadd_rn(acc[u].x, v[u].x);
+                    acc[u].y = __fadd_rn(acc[u].y, v[u].y);
+                    acc[u].z = __fadd_rn(acc[u].z, v[u].z);
+                    acc[u].w = __fadd_rn(acc[u].w, v[u].w);
+                }
+            }
+        }
+
+        float *__restrict__ out = args.out + (long long)t * args.out_tstride + (long long)piece * 4;
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const long long b = b0 + (long long)u * RPW + slot;
+            if (lane_on && b < B) *reinterpret_cast<float4 *>(out + b * args.out_bstride) = acc[u];
+        }
+    }
+}
+
 // Fetch-first order, behind the update launch: one lane per position.  A position the probe flagged 0 whose index is in range
 // is searched again in its set (the same (set, tag + 1) the probe computed; the line sits in L2 / Infinity Cache, the update
 // has just touched it) and re-pointed at the arena row of the way that holds its key now.  Re-probing instead of having the
@@ -591,6 +894,45 @@ void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st) {
     case 8: bags_pool_launch_t<8, kUnroll>(args, (unsigned)blocks, st); break;
     default: bags_pool_launch_t<4, kUnroll>(args, (unsigned)blocks, st); break;
     }
+}
+
+void bags_probe2_launch(const BagPairArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_probe2_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_count2_launch(const BagPairArgs &a, hipStream_t st) {
+    long long blocks = ((long long)a.T * a.B + 255) / 256;
+    if (blocks > (long long)kNumCu * 8) blocks = (long long)kNumCu * 8;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(bags_count2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+}
+
+void bags_route2_launch(const BagPairArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_route2_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+// the six pairs of precisions the reference builds (MGR_VARIANTS)
+bool bags_pool2_launch(const BagPairArgs &a, int codec1, int codec2, hipStream_t st) {
+    constexpr int kUnroll = 4;
+    BagPairArgs args = a;
+    const int bags_per_item = (kWave / (a.d / 4)) * kUnroll;
+    args.chunks_per_table = (a.B + bags_per_item - 1) / bags_per_item;
+    const long long n_items = (long long)a.T * args.chunks_per_table;
+    long long blocks = (n_items + 3) / 4;
+    if (blocks > (long long)kNumCu * 8) blocks = (long long)kNumCu * 8;
+    blocks = round_up((int)blocks, kNumXcd);
+    const dim3 grid((unsigned)blocks), block(256);
+    const int pair = codec1 * 100 + codec2;
+    switch (pair) {
+    case 3216: hipLaunchKernelGGL((bags_pool2_kernel<32, 16, kUnroll>), grid, block, 0, st, args); break;
+    case 3208: hipLaunchKernelGGL((bags_pool2_kernel<32, 8, kUnroll>), grid, block, 0, st, args); break;
+    case 3204: hipLaunchKernelGGL((bags_pool2_kernel<32, 4, kUnroll>), grid, block, 0, st, args); break;
+    case 1608: hipLaunchKernelGGL((bags_pool2_kernel<16, 8, kUnroll>), grid, block, 0, st, args); break;
+    case 1604: hipLaunchKernelGGL((bags_pool2_kernel<16, 4, kUnroll>), grid, block, 0, st, args); break;
+    case 804: hipLaunchKernelGGL((bags_pool2_kernel<8, 4, kUnroll>), grid, block, 0, st, args); break;
+    default: return false;
+    }
+    return true;
 }
 
 // compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail)

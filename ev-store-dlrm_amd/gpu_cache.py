@@ -631,6 +631,54 @@ def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
     return tier, out
 
 
+# ---- ragged bags through the pair (include/evstore_hip.h: evs_cache_lookup_bags_c1c2) ----
+def _check_bag_pair(c1, c2):
+    if not (c1.n_tables == c2.n_tables and c1.dim == c2.dim):
+        raise ValueError("the tiers must agree on n_tables and dim")
+
+
+def lookup_bags_c1c2(c1, c2, lS_o, lS_i, threshold=23, out=None):
+    """Multi-hot lookup through the batched C1 + C2 pair (both 'evlfu' after set_bag_rule('served-bags'); the pair that shares its
+    set records): every position is probed against both tiers as they stand when the call starts (code 1 = in C1, 2 = in C2,
+    0 = neither), a sample's agg_hit is the number of its T bags without a missed position, every hit way is raised to it, a
+    missed position is routed by the reference's rule on the snapshot and served from its destination tier's table at that
+    tier's precision, every distinct missed key is inserted once; the bags pool the served rows in index order, each decoded at
+    the precision of the tier that serves it (include/evstore_hip.h: evs_cache_lookup_bags_c1c2).  lS_o / lS_i as
+    GpuCache.lookup_bags takes them.
+    -> (tiers: T uint8 tensors, one code per index, views of one flat array; ly: T (B, dim) fp32 tensors, views of one
+    (T, B, dim) block -- `out`, when given)."""
+    _check_bag_pair(c1, c2)
+    B, idx_c, off_c, nnz_c, flat, tiers, _keep = c1._bags_call(lS_o, lS_i)
+    T, d = c1.n_tables, c1.dim
+    if out is None:
+        out = torch.empty((T, B, d), dtype=torch.float32, device=c1.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, B, d)):
+        raise ValueError("out must be a contiguous (%d, %d, %d) fp32 device tensor" % (T, B, d))
+    _lib.check(_lib.lib().evs_cache_lookup_bags_c1c2(c1._h, c2._h, B, idx_c, off_c, nnz_c, out.data_ptr(), B * d, d, flat.data_ptr(),
+                                                     int(threshold), torch.cuda.current_stream(c1.device).cuda_stream))
+    return tiers, list(out.unbind(0))
+
+
+def lookup_bags_interact_c1c2(c1, c2, lS_o, lS_i, x, threshold=23, itself=False, out=None):
+    """R = interact_features(x, the T pooled bags of lookup_bags_c1c2): the same rule and codes, the pooling into a (T, B, dim)
+    block C1 owns, the dense interaction, then the pair's update (include/evstore_hip.h: evs_cache_lookup_bags_interact_c1c2).
+    -> (tiers as lookup_bags_c1c2 gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
+    _check_bag_pair(c1, c2)
+    B, idx_c, off_c, nnz_c, flat, tiers, _keep = c1._bags_call(lS_o, lS_i)
+    F = c1.n_tables + 1
+    P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
+    if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (B, c1.dim) and x.stride(1) == 1):
+        raise ValueError("x must be a (B, %d) fp32 device tensor with unit inner stride" % c1.dim)
+    if out is None:
+        out = torch.empty((B, c1.dim + P), dtype=torch.float32, device=c1.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * (c1.dim + P)):
+        raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * (c1.dim + P)))
+    _lib.check(_lib.lib().evs_cache_lookup_bags_interact_c1c2(
+        c1._h, c2._h, B, idx_c, off_c, nnz_c, x.data_ptr(), int(x.stride(0)) if B > 1 else c1.dim, int(bool(itself)),
+        out.data_ptr(), flat.data_ptr(), int(threshold), torch.cuda.current_stream(c1.device).cuda_stream))
+    return tiers, out
+
+
 # ---- warm start of the pair (include/evstore_hip.h: evs_cache_pair_export / evs_cache_pair_load) ----
 def export_state_c1c2(c1, c2):
     """What the batched C1 + C2 pair holds, at rest (pending closes folded, a wanted flush run on either tier) -> a dict of

@@ -506,7 +506,8 @@ EVS_API int evs_cache_set_batch_policy(evs_cache *c, int policy);
  * that holds it; a double miss is routed by the reference's rule (evlfu_8.cpp:570-601) evaluated on the snapshot
  * -- C1 not full: C1; C1 full and agg_hit < threshold: odd table index -> C1, even -> C2; else C2 -- served from
  * the destination tier's backing table at that tier's precision and inserted there once per batch.  out: (B,T,dim)
- * fp32; tier (B,T): 1 = C1 hit, 2 = C2 hit, 0 = miss.  Both caches take the batched path from then on.
+ * fp32; tier (B,T): 1 = C1 hit, 2 = C2 hit, 0 = miss.  Both caches take the batched path from then on.  One index per table
+ * and sample; ragged bags (multi-hot features) go through evs_cache_lookup_bags_c1c2 / _lookup_bags_interact_c1c2.
  * MISS TIERS OUTSIDE HBM (BASELINE configs[4] composed; the reference's tiers read their misses from files inside the
  * request: evlfu_8.cpp:380-414 get_from_file, reader pool :191-250, :603-625): either tier may sit over pinned host tables
  * (evs_cache_set_backing) or file-backed ones (evs_cache_set_file_backing).  The pair then runs: probe (this batch's hits
@@ -604,13 +605,62 @@ EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *ro
  * file-backed tables (EVS_ESTATE), a cache driven by the exact path (EVS_ESTATE), a capacity below 8 or 2^32 rows over all
  * tables (EVS_EINVAL, as evs_cache_lookup_batch refuses them); an EvLFU cache whose batch policy is or resolves to plan or
  * sampled (set explicitly, through EVS_CACHE_POLICY, or because the geometry has no set-associative form), and 16-way sets
- * (EVS_SA_WAYS=16) or a tier of a C1 + C2 pair (EVS_EINVAL). */
+ * (EVS_SA_WAYS=16) or a tier of a C1 + C2 pair (EVS_EINVAL: the pair's bag form is evs_cache_lookup_bags_c1c2, below). */
 EVS_API int evs_cache_lookup_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
                                   const int64_t *nnz, float *pooled, int64_t out_table_stride, int64_t out_bag_stride,
                                   uint8_t *hit, void *stream);
 EVS_API int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int64_t *const *indices,
                                            const int64_t *const *offsets, const int64_t *nnz, const float *x, int64_t x_stride,
                                            int itself, float *R, uint8_t *hit, void *stream);
+/* RAGGED BAGS THROUGH THE BATCHED C1 + C2 PAIR (the mixed-precision pair of evs_cache_lookup_batch_c1c2 behind multi-hot
+ * features; csrc/evs_cache_policy.hip).  Inputs exactly as evs_cache_lookup_bags takes them: host arrays of device pointers, B
+ * bag starts per table, the last bag runs to nnz[k].
+ * THE RULE.  One call is batch n of BOTH tiers.  It shares the batch number, the stamps, the counters, the closes and the pending
+ * EvLFU flush with evs_cache_lookup_batch_c1c2 / _lookup_interact_c1c2; calls of the two forms may alternate on one pair.
+ *   a lookup  is one POSITION of one index array; all sum(nnz) positions are probed, whether or not a bag covers them.  An
+ *             index outside [0, n_rows) of EITHER tier's table k (the (B, T) probe's check) is no key: code 0, it contributes
+ *             nothing, it is never inserted, and it raises the sticky flag evs_check_index_errors reads.
+ *   probe     (strict snapshot) tier[p] = 1 when the key is resident in C1 when the call starts, else 2 when in C2, else 0.  The
+ *             probe writes no way word.  All positions that name one key get one code.
+ *   served bag, agg_hit(b)  as the single-tier EvLFU rule above defines them: bag (b, k) is served when none of its positions
+ *             has code 0 or is out of range; an empty bag is served; a bag whose offsets are backwards or past nnz[k] is
+ *             empty (and raises the sticky flag), hence served.  agg_hit(b) is the number of sample b's T bags that are
+ *             served.  A position no valid bag covers counts as 0.  (Offsets that go back can make two valid bags of different
+ *             samples cover one position -- the sticky flag is raised by the bag in between; such a position counts for one of
+ *             them, which one is not specified, and with it its route, its serving tier and its share of pooled.  Codes are
+ *             unaffected.)
+ *   raise     every hit way named by a position of sample b goes to max(old, agg_hit(b)) in the tier that holds it; its stamp
+ *             stays.
+ *   route     of a missed position of sample b (evlfu_8.cpp:570-601 on the snapshot, as the (B, T) form evaluates it for
+ *             set-associative tiers): the key's own C1 set has a free way in the snapshot -> C1; else agg_hit(b) < threshold ->
+ *             C1 for an odd table index k, C2 for an even one; else C2.  The position is SERVED FROM THE DESTINATION TIER'S
+ *             BACKING TABLE AT THAT TIER'S PRECISION.
+ *   insert    every distinct missed key once, by the (B, T) form's update launch, unchanged, over the miss lists.  A key routed
+ *             both ways by different positions (odd tables only) goes to C1 (the route filter), as in the (B, T) form.  Its
+ *             priority is the maximum of agg_hit over the positions listed for the tier that takes it; victim choice, the
+ *             turn-away and the stamp are the update's own.
+ *   pooled    pooled[k][b] = sum over the bag's positions, in index order, of the served rows DECODED PER POSITION AT THE
+ *             PRECISION OF THE TIER THAT SERVES THAT POSITION (a bag may mix rows of both); fp32 adds, unfused, from +0.0f.
+ *             The output is a pure function of the snapshot and the input (positions two bags cover excepted, above): bit-exactly
+ *             predictable on contended batches too.
+ *   counters  (evs_cache_batch_stats, per tier) n_hits += the positions hit in that tier; n_requests += B; perfect requests
+ *             are the samples with at least one lookup and agg_hit = T, counted where the (B, T) probe counts them (C1).  With
+ *             one index per bag both tiers' counters equal what the (B, T) call leaves.
+ * tier: flat DEVICE uint8 array of sum(nnz) entries, table-major; may be NULL.  pooled / x / R as evs_cache_lookup_bags /
+ * _lookup_bags_interact take them; the interact form pools into a (T, B, d) block C1 owns and runs evs_interact_dot.
+ * THE ENVELOPE, checked before anything is allocated, the pair left usable: the argument checks are evs_cache_lookup_bags'
+ * (EVS_EINVAL; B == 0 is success); both caches EvLFU with evs_cache_set_bag_rule(c, 1) told to BOTH (EVS_EINVAL names the cache
+ * that lacks it); the pair shares its set record (evs_cache_pair_load's geometry: plan-based, sampled and EVS_SA_PAIR=0 pairs,
+ * tiers that did not start out together: EVS_EINVAL); both tiers' tables in HBM (host-memory / file-backed: EVS_ESTATE); miss
+ * order 0; no alt-key tier (a pair that has run evs_cache_lookup_batch_c1c2c3 / _interact_c1c2c3: EVS_EINVAL); the pairs of precisions the reference builds -- 32-16, 32-8, 32-4, 16-8, 16-4, 8-4 (others:
+ * EVS_EINVAL naming the codecs); dim a multiple of 4 up to 256, the interact form evs_fused_dim_supported(dim) and
+ * n_tables + 1 <= 32. */
+EVS_API int evs_cache_lookup_bags_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices,
+                                       const int64_t *const *offsets, const int64_t *nnz, float *pooled, int64_t out_table_stride,
+                                       int64_t out_bag_stride, uint8_t *tier, int high_agghit_threshold, void *stream);
+EVS_API int evs_cache_lookup_bags_interact_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices,
+                                                const int64_t *const *offsets, const int64_t *nnz, const float *x, int64_t x_stride,
+                                                int itself, float *R, uint8_t *tier, int high_agghit_threshold, void *stream);
 /* What a request's hit count is over ragged bags, for an EvLFU cache (the rule: evs_cache_lookup_bags, above): 0 none (the
  * default: the bag entry points refuse the cache), 1 "served bags".  May be called between calls.  EVS_EINVAL, with the policy
  * named: a rule outside {0, 1}; rule 1 on an LRU / LFU cache (their bag form needs none; rule 0 is accepted). */

@@ -15,6 +15,16 @@ The per-kernel split comes from a profiler run of its own:
     python tools/bags_cache_bench.py --kernel-stats 2048=DIR/.../..._kernel_stats.csv evlfu:16384=... --out profiles/bags_cache.json
 (--chain-only runs the warm-up and the chain alone, one --policy per profiler run; --kernel-stats folds the library's rows of
 those files into the JSON under kernel_split[policy], the policy named in front of the batch size, lru when it is left out.)
+
+--pair: the bag form of the mixed-precision C1 + C2 pair (lookup_bags_interact_c1c2: probe2 -> count -> route + raise + list ->
+pool2 -> dense interaction -> the pair's update) at the reference's flagship shape -- u8 C1 + u4 C2 at the 48-48-4 split of 2 %
+of the Kaggle rows (1 296 480 + 2 592 960 entries), d = 36, B = 16 384, Zipf 0.75, both pairs warmed until their sizes stop
+growing -- into profiles/bags_pair.json:
+  (a) one index per bag beside lookup_interact_c1c2(fused=False) on a twin pair: the same batches, alternating, one process;
+  (b) ragged bags of mean length --pair-mean-bag (0 .. 2 x mean indices) on the first pair.
+Its per-kernel times come from a profiler run of its own, as above:
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bags_cache_bench.py --pair --chain-only
+    python tools/bags_cache_bench.py --pair --pair-timing profiles/bags_pair.json --kernel-stats one_index_per_bag=DIR/.../..._kernel_stats.csv
 Needs a GPU."""
 import argparse
 import csv
@@ -105,6 +115,118 @@ def run(policy, B, ev, ln, dev, args):
             "uncached_apply_emb_interact_us_per_batch": {"mean": round(float(plain.mean()), 2), "median": round(float(np.median(plain)), 2)}}
 
 
+def make_pair_batch(ln, B, g, dev, mean_bag, alpha):
+    """-> (lS_o, lS_i, rq): bags of exactly one index (mean_bag == 1; rq = the (B, T) int32 rows of the same batch) or of
+    0 .. 2 * mean_bag indices (rq None); rows Zipf as make_batch draws them"""
+    lo, li = [], []
+    e = 1.0 - alpha
+    for n in ln:
+        if mean_bag == 1:
+            sizes = torch.ones((B,), dtype=torch.int64, device=dev)
+        else:
+            sizes = torch.randint(0, 2 * mean_bag + 1, (B,), device=dev, generator=g, dtype=torch.int64)
+        ends = torch.cumsum(sizes, 0)
+        nnz = int(ends[-1])
+        u = torch.rand((nnz,), device=dev, generator=g, dtype=torch.float64)
+        r = (((float(n) ** e - 1.0) * u + 1.0) ** (1.0 / e)).to(torch.int64).clamp_(1, n) - 1
+        lo.append((ends - sizes).contiguous())
+        li.append((r * 2654435761 % n).to(torch.int64))
+    rq = torch.stack(li, 1).to(torch.int32).contiguous() if mean_bag == 1 else None
+    return lo, li, rq
+
+
+def run_pair(ln, dev, args):
+    """the pair's bag form at the flagship shape -> the JSON's "pair" section (or, --chain-only, the profiled chain alone)"""
+    T, d, B = len(ln), args.dim, args.pair_batch
+    ev = bench.make_tables(ln, d, seed=0, device=dev)
+    ev8, ev4 = ev.encode(8), ev.encode(4)
+    budget = int(0.02 * sum(ln))
+    caps = (int(0.48 * budget) * 4, int(0.48 * budget) * 8)
+
+    def pair(rule):
+        c1, c2 = E.GpuCache("evlfu", caps[0], T, d, 8, "cpp", dev), E.GpuCache("evlfu", caps[1], T, d, 4, "cpp", dev)
+        c1.set_backing(ev8)
+        c2.set_backing(ev4)
+        if rule:
+            c1.set_bag_rule("served-bags")
+            c2.set_bag_rule("served-bags")
+        return c1, c2
+
+    g = torch.Generator(device=dev).manual_seed(7)
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    R = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+    a = pair(True)
+    b = None if args.chain_only else pair(False)
+    n_warm, last = 0, -1
+    while n_warm < args.max_warmup:                   # one index per bag on both pairs until the sizes stop growing
+        for _ in range(10):
+            lo, li, rq = make_pair_batch(ln, B, g, dev, 1, args.alpha)
+            E.lookup_bags_interact_c1c2(a[0], a[1], lo, li, x, out=R)
+            if b:
+                E.lookup_interact_c1c2(b[0], b[1], rq, x, fused=False)
+        n_warm += 10
+        size = a[0].batch_stats()["size"] + a[1].batch_stats()["size"]
+        if last >= 0 and size - last < 0.002 * (caps[0] + caps[1]):
+            break
+        last = size
+    one = [make_pair_batch(ln, B, g, dev, 1, args.alpha) for _ in range(args.steps)]
+    rag = [make_pair_batch(ln, B, g, dev, args.pair_mean_bag, args.alpha) for _ in range(args.steps)]
+    if args.chain_only:
+        for lo, li, _ in (rag if args.pair_profile == "ragged" else one):
+            E.lookup_bags_interact_c1c2(a[0], a[1], lo, li, x, out=R)
+        torch.cuda.synchronize()
+        return {"batch": B, "warmup_batches": n_warm, "batches": args.steps, "profiled": args.pair_profile}
+
+    def stats(p):
+        return [c.batch_stats() for c in p]
+
+    out = {"batch": B, "capacities": list(caps), "codecs": [8, 4], "dim": d, "warmup_batches": n_warm,
+           "sizes_after_warmup": [s["size"] for s in stats(a)], "timed_batches": args.steps}
+    # (a) one index per bag: the bag form on pair a, the (B, T) form + dense interaction on its twin, alternating
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)]
+    s0, t0 = stats(a), stats(b)
+    torch.cuda.synchronize()
+    for (lo, li, rq), e4 in zip(one, evs):
+        e4[0].record()
+        E.lookup_bags_interact_c1c2(a[0], a[1], lo, li, x, out=R)
+        e4[1].record()
+        e4[2].record()
+        E.lookup_interact_c1c2(b[0], b[1], rq, x, fused=False)
+        e4[3].record()
+    torch.cuda.synchronize()
+    s1, t1 = stats(a), stats(b)
+    bag = np.array([e4[0].elapsed_time(e4[1]) for e4 in evs]) * 1e3
+    bt = np.array([e4[2].elapsed_time(e4[3]) for e4 in evs]) * 1e3
+    n_pos = args.steps * B * T
+    out["one_index_per_bag"] = {
+        "bag_form_us_per_call": {"mean": round(float(bag.mean()), 2), "median": round(float(np.median(bag)), 2)},
+        "bt_form_unfused_us_per_call": {"mean": round(float(bt.mean()), 2), "median": round(float(np.median(bt)), 2)},
+        "ratio_bag_over_bt_median": round(float(np.median(bag) / np.median(bt)), 3),
+        "hit_rate_bag_form": round(sum(s1[k]["n_hits"] - s0[k]["n_hits"] for k in (0, 1)) / n_pos, 4),
+        "hit_rate_bt_form": round(sum(t1[k]["n_hits"] - t0[k]["n_hits"] for k in (0, 1)) / n_pos, 4)}
+    # (b) ragged bags on pair a
+    for lo, li, _ in rag[:10]:
+        E.lookup_bags_interact_c1c2(a[0], a[1], lo, li, x, out=R)
+    ev2 = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(args.steps)]
+    s0 = stats(a)
+    torch.cuda.synchronize()
+    for (lo, li, _), e2 in zip(rag, ev2):
+        e2[0].record()
+        E.lookup_bags_interact_c1c2(a[0], a[1], lo, li, x, out=R)
+        e2[1].record()
+    torch.cuda.synchronize()
+    s1 = stats(a)
+    t = np.array([e2[0].elapsed_time(e2[1]) for e2 in ev2]) * 1e3
+    n_pos = sum(int(v.numel()) for _, li, _ in rag for v in li)
+    out["ragged"] = {"mean_bag": args.pair_mean_bag, "lookups_per_call": round(n_pos / args.steps, 1),
+                     "bag_form_us_per_call": {"mean": round(float(t.mean()), 2), "median": round(float(np.median(t)), 2)},
+                     "hit_rate": round(sum(s1[k]["n_hits"] - s0[k]["n_hits"] for k in (0, 1)) / n_pos, 4),
+                     "all_served_samples": s1[0]["n_perfect_hits"] - s0[0]["n_perfect_hits"],
+                     "flushes": [s1[k]["n_flush"] - s0[k]["n_flush"] for k in (0, 1)]}
+    return out
+
+
 def kernel_split(path):
     """the library's rows of a rocprofv3 kernel_stats.csv: name, calls, average microseconds, share of the traced time"""
     rows = []
@@ -114,6 +236,20 @@ def kernel_split(path):
                 rows.append({"kernel": r["Name"][:160], "calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2),
                              "percent": float(r["Percentage"])})
     return rows
+
+
+def finish_pair(res, args):
+    """the --pair JSON: the profiler's rows folded in (--kernel-stats), written (not for --chain-only) and printed"""
+    if args.kernel_stats:
+        res["kernel_split"] = {"source": "rocprofv3 --kernel-trace --stats over a --pair --chain-only run (warm-up launches included in the averages)"}
+        for item in args.kernel_stats:
+            b, path = item.split("=", 1)
+            res["kernel_split"][b] = kernel_split(path)
+    line = json.dumps(res)
+    if not args.chain_only:
+        with open(args.out or os.path.join(ROOT, "profiles", "bags_pair.json"), "w") as f:
+            f.write(line + "\n")
+    print(line)
 
 
 def main():
@@ -129,13 +265,35 @@ def main():
     ap.add_argument("--dim", type=int, default=36)
     ap.add_argument("--chain-only", action="store_true", help="warm-up and the chain alone: the run a profiler wraps")
     ap.add_argument("--kernel-stats", nargs="*", default=[], metavar="[POLICY:]B=CSV", help="kernel_stats.csv of a --chain-only profiler run per batch size")
+    ap.add_argument("--pair", action="store_true", help="the bag form of the u8 + u4 pair at the flagship shape (see above)")
+    ap.add_argument("--pair-batch", type=int, default=16384)
+    ap.add_argument("--pair-mean-bag", type=int, default=4)
+    ap.add_argument("--pair-timing", default="", metavar="JSON", help="--pair --kernel-stats: fold the profiler's rows into this timing run's JSON "
+                    "instead of timing again (no GPU needed)")
+    ap.add_argument("--pair-profile", choices=["one", "ragged"], default="one", help="--pair --chain-only: which batches the profiled run draws")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.pair and args.pair_profile == "ragged" and args.pair_mean_bag < 2:
+        ap.error("--pair-profile ragged needs --pair-mean-bag of 2 or more")
+    if args.pair and args.pair_timing:                # fold the profiler's rows into an earlier timing run's JSON: no GPU needed
+        with open(args.pair_timing) as f:
+            finish_pair(json.load(f), args)
+        return
     if not torch.cuda.is_available():
         sys.exit("bags_cache_bench: needs a GPU")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     ln = [min(n, args.max_rows) if args.max_rows else n for n in bench.KAGGLE_LN]
+    if args.pair:
+        res = {"tool": "bags_cache_bench --pair",
+               "chain": "bags_probe2_kernel -> bags_count2_kernel -> bags_route2_kernel -> bags_pool2_kernel -> dense interaction -> "
+                        "cache_batch_sa_list2_kernel",
+               "device": torch.cuda.get_device_name(0),
+               "shape": {"rows": sum(ln), "dim": args.dim, "zipf_alpha": args.alpha},
+               "timing": "device events around every call, the two forms alternating batch by batch; dispatch gaps included",
+               "pair": run_pair(ln, dev, args)}
+        finish_pair(res, args)
+        return
     ev = bench.make_tables(ln, args.dim, seed=0, device=dev)
     runs = []
     for B in args.batch:
