@@ -118,6 +118,8 @@ _PROTOS = {
     "evs_cache_set_bag_rule": (_int, [_vp, _int]),
     "evs_cache_set_miss_order": (_int, [_vp, _int]),
     "evs_cache_fetch_stats": (_int, [_vp, _i64p, _vp]),
+    "evs_cache_set_batch_approx": (_int, [_vp, _int]),
+    "evs_cache_approx_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_serve_stop": (_int, [_vp]),
     "evs_tiers_serve_start": (_int, [C.POINTER(_vp), _vp, _vp, _vp, _int, _vp, _int, _i64]),
     "evs_tiers_serve_request": (_int, [_vp, _vp, _vp, C.POINTER(C.c_int)]),

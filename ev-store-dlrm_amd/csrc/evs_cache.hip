@@ -1844,6 +1844,94 @@ __global__ void __launch_bounds__(256) cache_batch_probe_gather_kernel(const Bat
     if (args.miss_rec && threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n;
 }
 
+// K1 with the approximate-embedding mode of the batched EvLFU rule (evs_cache_set_batch_approx; the rule: include/evstore_hip.h):
+// the set-associative probe above in list mode -- a 32-lane half-wave per request, agg_hit by ballot, the raise, the pointer
+// table, the block's packed miss list -- and, behind the ballot, the substitution: in a request whose agg_hit reaches the
+// threshold a missing lane is served the address the nearest HIT lane below it is served (one shuffle inside the half), the
+// codec's zero row when no lane below it hit, is flagged 2 and stays out of the miss list.  Sets of 8 ways only.
+struct ApproxArgs {
+    int thres;                        // 1 .. T
+    const unsigned char *zero_row;    // a row of the cache's codec that decodes to +0.0f (zero_page / zero_code_page)
+    unsigned long long *counters;     // kReplicas rows of [samples approximated, positions served an earlier hit's row, positions served the zero row]
+};
+constexpr int kApproxCntStride = 16;  // words between replica rows (128 bytes: a line each)
+
+__global__ void __launch_bounds__(256) cache_batch_probe_approx_kernel(const BatchArgs args, const ApproxArgs ap) {
+    __shared__ int s_delta[kMaxBuckets];
+    __shared__ int s_sum[5];   // hits / perfect requests / approximated samples / positions served a hit's row / the zero row, of this block
+    __shared__ int s_list_n;   // misses this block has listed so far
+    for (int i = threadIdx.x; i < kMaxBuckets; i += blockDim.x) s_delta[i] = 0;
+    if (threadIdx.x < 5) s_sum[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_list_n = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const int T = args.T;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool req_on = req < args.B;
+        const bool key_on = req_on && hl < T;
+        const int row = key_on ? args.requests[req * T + hl] : -1;
+        const bool ok = key_on && row >= 0 && row < args.backing_rows[hl < T ? hl : 0];
+        unsigned set = 0u, sa_tag1 = 0u, sa_w = 0u;
+        sa_split(args.sa, sa_perm(args.sau, args.sau.row_base[hl] + (ok ? (unsigned)row : 0u)), set, sa_tag1);
+        if (!ok) set = 0u;
+        SaLine line;
+        sa_load<8>(args.sa, set, line);
+        const int way = sa_find<8>(args.sa, line, sa_tag1, sa_w);
+        const int e = (ok && way >= 0) ? (int)sa_entry(args.sa, set, (unsigned)way, sa_w) : -1;
+        const unsigned long long hm = __ballot(e >= 0);
+        const unsigned hmask = (unsigned)(half ? (hm >> 32) : hm);
+        const int agg = __popc(hmask);   // true hits only: an approximated position never counts
+        if (e >= 0 && sa_prio(sa_w) < agg) {
+            const int old = sa_raise(args.sa, sa_ways_ptr(args.sa, set) + way, sa_w, agg);
+            if (old >= 0) { atomicSub(&s_delta[old], 1); atomicAdd(&s_delta[agg], 1); }
+        }
+        const unsigned char *src = nullptr;
+        if (e >= 0) src = args.a.arena + (long long)e * args.row_bytes;
+        else if (ok) src = args.backing[hl] + (long long)row * args.row_bytes;
+        // The substitution.  Every lane of the wave runs the shuffle (a lane that is off reads lane 0 of its half and drops
+        // the value); the select comes afterwards.  A hit lane's src is its arena address, which is what lane `prev` holds.
+        const bool approx = agg >= ap.thres;   // uniform over the half-wave
+        const unsigned below = hmask & ((1u << hl) - 1u);
+        const int prev = below ? 31 - __clz(below) : 0;
+        const long long src_prev = __shfl((long long)src, prev, 32);
+        const bool sub = approx && ok && e < 0;
+        if (sub) src = below ? reinterpret_cast<const unsigned char *>(src_prev) : ap.zero_row;
+        if (key_on) {
+            args.hit[req * T + hl] = e >= 0 ? 1 : (sub ? 2 : 0);
+            args.row_ptrs[req * T + hl] = (long long)src;
+        }
+        const bool is_miss = ok && e < 0 && !approx;   // an approximated position is no miss: not listed, hence never fetched or inserted
+        const unsigned long long mm = __ballot(is_miss);
+        const unsigned mh = (unsigned)(half ? (mm >> 32) : mm);
+        int base = 0;
+        if (hl == 0 && mh) base = atomicAdd(&s_list_n, __popc(mh));
+        base = __shfl(base, half * 32, 64);
+        if (is_miss) {
+            const int at = base + __popc(mh & ((1u << hl) - 1u));
+            args.miss_rec[(long long)blockIdx.x * args.list_cap + at] = make_uint4((unsigned)row, (unsigned)hl | ((unsigned)agg << 8), set, sa_tag1);
+        }
+        const unsigned long long sm = __ballot(sub), zm = __ballot(sub && !below);
+        const unsigned sh = (unsigned)(half ? (sm >> 32) : sm), zh = (unsigned)(half ? (zm >> 32) : zm);
+        if (req_on && hl == 0) {
+            atomicAdd(&s_sum[0], agg);
+            if (agg == T) atomicAdd(&s_sum[1], 1);
+            if (sh) { atomicAdd(&s_sum[2], 1); atomicAdd(&s_sum[3], __popc(sh & ~zh)); atomicAdd(&s_sum[4], __popc(zh)); }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < kPartCols) {
+        const int i = threadIdx.x;
+        const int v = i <= T ? s_delta[i] : i == 38 ? s_sum[0] : i == 39 ? s_sum[1] : 0;
+        if (v) atomicAdd(&args.part1[(blockIdx.x % kReplicas) * kPartCols + i], v);
+    }
+    // (replica rows for the reason part1 has them: 2 048 blocks adding into three words of one line serialise; evs_cache_approx_stats sums the rows)
+    if (threadIdx.x >= 64 && threadIdx.x < 67 && s_sum[threadIdx.x - 62])
+        atomicAdd(&ap.counters[(blockIdx.x % kReplicas) * kApproxCntStride + (threadIdx.x - 64)], (unsigned long long)s_sum[threadIdx.x - 62]);
+    if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n;
+}
+
 // rows (B,T,d) fp32 from the pointer table (only when the caller wants the pooled rows themselves)
 __global__ void __launch_bounds__(256) cache_rows_from_ptrs_kernel(const long long *row_ptrs, float *out, long long B,
                                                                    int T, int d, int codec) {
@@ -3418,7 +3506,12 @@ struct evs_cache {
     int miss_order = 0;
     unsigned long long *fetch_cnt = nullptr;
     long long fetch_calls = 0;
-    int inline_mode = -1;          // the update inside the probe launch (evs_fused_rf.hip): -1 not decided (EVS_CACHE_INLINE, default on), 0 / 1
+    // approximate-embedding mode of the batched EvLFU rule (evs_cache_set_batch_approx): the threshold (0 off), the replica rows
+    // of three counters its probe adds into (device, allocated at the first call with a threshold in force) and the calls that ran it
+    int batch_approx = 0;
+    unsigned long long *approx_cnt = nullptr;
+    long long approx_calls = 0;
+    int inline_mode = -1;         // the update inside the probe launch (evs_fused_rf.hip): -1 not decided (EVS_CACHE_INLINE, default on), 0 / 1
     evs_tier_server *tsrv = nullptr;   // the tier pair / triple server this cache belongs to (evs_tiers_serve_*)
 };
 // The tier pair / triple as a resident server (cache_c1c2_serve_kernel): the single-tier server's mailbox and ring rules, owned
@@ -3564,7 +3657,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -3721,6 +3814,45 @@ extern "C" int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream) 
         EVS_HIP_CHECK(hipStreamSynchronize(st));
     }
     out4[0] = c->fetch_calls; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = 0;
+    return EVS_OK;
+}
+
+// The approximate-embedding mode of the batched EvLFU rule (the contract: include/evstore_hip.h): thres <= 0 off (the default:
+// every chain launch for launch as without this call), 1 .. n_tables on -- a sample whose agg_hit reaches it has its missed
+// positions served the row of its nearest earlier hit (the zero row when there is none), flagged 2 and kept out of the miss
+// list.  May be set between batched calls; what a call with a threshold in force is held to: batch_approx_check.
+extern "C" int evs_cache_set_batch_approx(evs_cache *c, int thres) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_set_batch_approx: NULL cache");
+    if (thres <= 0) { c->batch_approx = 0; return EVS_OK; }
+    const char *pn = policy_name(c->host.policy);
+    EVS_REQUIRE(c->host.policy == kEvLFU, "evs_cache_set_batch_approx: threshold %d on an %s cache: the approximate mode is evlfu's (the reference's lru / lfu "
+                "have none); 0 is accepted", thres, pn);
+    EVS_REQUIRE(thres <= c->host.n_tables, "evs_cache_set_batch_approx: threshold %d on an %s cache of %d tables (a sample has at most %d hits; <= 0 is off)",
+                thres, pn, c->host.n_tables, c->host.n_tables);
+    const int zero_bytes = c->host.codec == 32 ? 4096 : 1024;
+    EVS_REQUIRE(c->host.row_bytes <= zero_bytes, "evs_cache_set_batch_approx: a row of this %s cache has %d bytes; the zero row a position without an earlier hit is "
+                "served has %d", pn, c->host.row_bytes, zero_bytes);
+    c->batch_approx = thres;
+    return EVS_OK;
+}
+
+// out4 (host), cumulative: [batched calls run with a threshold in force, samples at or above it with at least one miss, positions
+// served an earlier hit's row, positions served the zero row]
+extern "C" int evs_cache_approx_stats(evs_cache *c, int64_t *out4, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(out4, "evs_cache_approx_stats: NULL out4");
+    EVS_REQUIRE(c, "evs_cache_approx_stats: NULL cache");
+    unsigned long long h[3] = {0ull, 0ull, 0ull};
+    if (c->approx_cnt) {
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        unsigned long long rows[kReplicas * kApproxCntStride];
+        EVS_HIP_CHECK(hipMemcpyAsync(rows, c->approx_cnt, sizeof rows, hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int r = 0; r < kReplicas; r++)
+            for (int k = 0; k < 3; k++) h[k] += rows[r * kApproxCntStride + k];
+    }
+    out4[0] = c->approx_calls; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = (int64_t)h[2];
     return EVS_OK;
 }
 
@@ -4682,6 +4814,50 @@ static evs::RepointArgs repoint_args(evs_cache *c, const unsigned char *hit, lon
     return ra;
 }
 
+// ---- approximate-embedding mode (evs_cache_set_batch_approx(c, thres > 0); the contract: include/evstore_hip.h) -------------
+// What a (B, T) call with a threshold in force is held to, checked behind batch_check (and fetch_first_check) and before anything
+// is allocated: an EvLFU tier alone (the setter refuses the other policies), batch policy 2 given or resolved, sets of 8 ways,
+// tables the kernels read in place.  A policy that was only resolved here is forgotten again on a refusal.
+static int batch_approx_check(evs_cache *c, const char *who) {
+    using namespace evs;
+    const char *pn = policy_name(c->host.policy);
+    if (c->ft) {
+        set_error("%s: the approximate mode of an %s cache is the set-associative tier's, which reads its tables in place (no file-backed tables)", who, pn);
+        return EVS_ESTATE;
+    }
+    EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; the approximate mode "
+                "(evs_cache_set_batch_approx) is a tier alone's -- the pair has the alt-key tier for it", who, pn);
+    const int given = c->batch_policy;
+    const int bp = resolved_batch_policy(c);
+    if (bp != 2) {
+        c->batch_policy = given;
+        set_error("%s: the approximate mode (evs_cache_set_batch_approx) is the set-associative tier's (batch policy 2); this %s cache's batch policy is %s",
+                  who, pn, bp == 0 ? "plan" : "sampled");
+        return EVS_EINVAL;
+    }
+    const bool alone8 = c->sa.tags ? (c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u) : sa_single_ways() == 8u;
+    if (!alone8) {
+        c->batch_policy = given;
+        set_error("%s: the approximate mode of an %s cache needs sets of 8 ways (EVS_SA_WAYS=16: its probe is compiled for 8-way sets)", who, pn);
+        return EVS_EINVAL;
+    }
+    return EVS_OK;
+}
+// the counter block of the approximating probe (zeroed on st), at the first call with a threshold in force
+static int batch_approx_state(evs_cache *c, hipStream_t st, const char *who) {
+    if (c->approx_cnt) return EVS_OK;
+    unsigned long long *p = nullptr;
+    const size_t bytes = (size_t)evs::kReplicas * evs::kApproxCntStride * sizeof(unsigned long long);
+    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        evs::set_error("%s: allocating the approximate-mode counters failed", who);
+        return EVS_ENOMEM;
+    }
+    c->approx_cnt = p;
+    return EVS_OK;
+}
+
 static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float *out, uint8_t *hit, const float *x,
                             int64_t x_stride, int itself, float *R, void *stream) {
     using namespace evs;
@@ -4695,6 +4871,12 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     if (ff) {
         { const int rc = batch_check(c, "evs_cache_lookup_batch"); if (rc) return rc; }
         { const int rc = fetch_first_check(c, "evs_cache_lookup_batch", false); if (rc) return rc; }
+    }
+    // approximate-embedding mode (evs_cache_set_batch_approx): the unfolded chain in pointer mode behind a probe of its own
+    const bool apx = c && c->batch_approx > 0;
+    if (apx) {
+        { const int rc = batch_check(c, "evs_cache_lookup_batch"); if (rc) return rc; }
+        { const int rc = batch_approx_check(c, "evs_cache_lookup_batch"); if (rc) return rc; }
     }
     const int prc = batch_prepare(c, B, rows, st, a, "evs_cache_lookup_batch");
     if (prc) return prc;
@@ -4746,7 +4928,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     // The interaction alone as the consumer, tables in HBM, a shape the rows-in-registers kernel takes: K1 writes 4-byte
     // row ids (arena entry / table row) instead of 8-byte addresses and that kernel reads them (22.9 -> ~20 us at
     // B = 16 384).  The 8-byte address table is the (B,T) int64 buffer either way: the ids use its first half.
-    if (R && !out && !host_tier && !ff && !(c->ft && c->staged_mask) && c->host.codec == 32 && fused_row_ids_supported(B, T, c->host.dim)) {
+    if (R && !out && !host_tier && !ff && !apx && !(c->ft && c->staged_mask) && c->host.codec == 32 && fused_row_ids_supported(B, T, c->host.dim)) {
         bool small = true;
         for (int k = 0; k < T; k++) small = small && c->backing_rows[k] < (1ll << 30);
         if (small) a.row_ids = reinterpret_cast<int *>(c->row_ptrs);
@@ -4769,6 +4951,10 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             ra = repoint_args(c, hit, c->row_ptrs, B);
             ra.requests = rows; ra.n_pos = B * T;
             c->fetch_calls++;
+        }
+        if (apx) {
+            { const int rc = batch_approx_state(c, st, "evs_cache_lookup_batch"); if (rc) return rc; }
+            if (!(c->host.codec == 32 ? zero_page() : zero_code_page(c->host.codec))) return EVS_ENOMEM;
         }
         if (c->host.policy != kEvLFU) {
             // LRU / LFU (evs_cache_policy.hip): probe + touch -> consumers -> insert, always as launches of their own; batch
@@ -4803,6 +4989,31 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         sampled_flush_if_wanted(c, st);
         a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
         a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+        if (apx) {
+            // A threshold in force: always the unfolded chain in pointer mode.  An approximated position holds the address its
+            // nearest earlier HIT is served, and that address stays valid until the consumers have read it for the reason a
+            // hit's own does -- consume first: the update runs behind the consumers; fetch first: a hit way that is this
+            // batch's victim is replaced in the OTHER copy of the two-copy arena (the select bit flips), so the address the
+            // probe computed from the old word still names the old row.  The re-point kernel passes over flag 2, and the
+            // update never sees an approximated position: the probe lists none.
+            ApproxArgs ap;
+            ap.thres = c->batch_approx; ap.counters = c->approx_cnt;
+            ap.zero_row = reinterpret_cast<const unsigned char *>(c->host.codec == 32 ? zero_page() : zero_code_page(c->host.codec));
+            hipLaunchKernelGGL(cache_batch_probe_approx_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a, ap);
+            c->approx_calls++;
+            if (ff) {
+                launch_sa_update(a, st);
+                sa_repoint_launch(ra, a.g1, st);
+                const int rc = consumers(); if (rc) return rc;
+            } else {
+                const int rc = consumers(); if (rc) return rc;
+                launch_sa_update(a, st);
+            }
+            c->pending_batches++; c->pending_requests += B;
+            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+            EVS_HIP_CHECK(hipGetLastError());
+            return EVS_OK;
+        }
         static const bool fold_on = !(evs::env_switch("EVS_CACHE_FOLD") && evs::env_switch("EVS_CACHE_FOLD")[0] == '0');
         bool small_tabs = true;   // (tile entries carry a row id in 30 bits)
         for (int k = 0; k < T; k++) small_tabs = small_tabs && c->backing_rows[k] < (1ll << 30);
@@ -5137,6 +5348,8 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     // points every missed position at the arena / staged copy, and only then the consumers.
     EVS_REQUIRE(c1->miss_order == 0 && c2->miss_order == 0, "evs_cache_lookup_batch_c1c2: an %s tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone; "
                 "the pair / triple runs its own chains", policy_name(c1->host.policy));
+    EVS_REQUIRE(c1->batch_approx <= 0 && c2->batch_approx <= 0, "evs_cache_lookup_batch_c1c2: %s is an %s cache with an approximate threshold on (evs_cache_set_batch_approx): "
+                "that mode is a tier alone's; the pair / triple has the alt-key tier for it", c1->batch_approx > 0 ? "C1" : "C2", policy_name(c1->host.policy));
     const bool host2 = c1->host_backing || c2->host_backing;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     { const int prc = pair_start(c1, c2, st, "evs_cache_lookup_batch_c1c2"); if (prc) return prc; }
@@ -5655,6 +5868,8 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
             return EVS_ESTATE;
         }
         EVS_REQUIRE(c->miss_order == 0, "%s: %s runs fetch-first (evs_cache_set_miss_order): such a tier is a tier alone", who, cn);
+        EVS_REQUIRE(c->batch_approx <= 0, "%s: %s is an %s cache with an approximate threshold on (evs_cache_set_batch_approx): that mode is a tier alone's",
+                    who, cn, policy_name(c->host.policy));
         EVS_REQUIRE(!(c->serving || c->tsrv), "%s: a resident server is running on %s", who, cn);
         EVS_REQUIRE(!c->had_c3, "%s: %s has run as a tier of a triple (evs_cache_lookup_batch_c1c2c3): the bag form has no alt-key tier, and the "
                     "pair's evictions would bypass it", who, cn);

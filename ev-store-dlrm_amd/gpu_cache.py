@@ -297,6 +297,23 @@ class GpuCache:
         _lib.check(_lib.lib().evs_cache_fetch_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
         return {"calls": int(s[0]), "repointed": int(s[1]), "in_place": int(s[2])}
 
+    def set_batch_approx(self, thres):
+        """The approximate-embedding mode of lookup_batch / lookup_interact on an 'evlfu' set-associative tier: a sample with at
+        least `thres` of its T keys resident has every missed position served the row of its nearest earlier hit (a row of
+        +0.0 when there is none), flagged 2, and neither fetched nor inserted.  thres <= 0 (or None) switches it off, the
+        default; may be set between calls.  thres > n_tables, or thres > 0 on an 'lru' / 'lfu' cache, raises EVS_EINVAL
+        (include/evstore_hip.h: evs_cache_set_batch_approx).  The bag forms ignore it."""
+        _lib.check(_lib.lib().evs_cache_set_batch_approx(self._h, 0 if thres is None else int(thres)))
+        return self
+
+    def approx_stats(self):
+        """Counters of the approximate mode, cumulative since creation: 'calls' (batched calls run with a threshold in force),
+        'samples' (samples at or above it that had at least one miss), 'substituted' (positions served an earlier hit's row)
+        and 'zero_rows' (positions served the zero row).  Synchronises."""
+        s = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().evs_cache_approx_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
+        return {"calls": int(s[0]), "samples": int(s[1]), "substituted": int(s[2]), "zero_rows": int(s[3])}
+
     def serve_stop(self):
         _lib.check(_lib.lib().evs_cache_serve_stop(self._h))
 

@@ -710,6 +710,42 @@ EVS_API int evs_cache_set_miss_order(evs_cache *c, int order);
  * table, 0], cumulative since creation.  An index out of range is no key and is counted nowhere.  Synchronises the stream.
  * EVS_EINVAL for a NULL cache or a NULL out4, before the device is touched. */
 EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
+/* The approximate-embedding mode of the batched EvLFU rule (the reference: cache_algo/EvLFU_C1.py:122-125, :142-152 -- a request
+ * whose agg_hit reaches approx_emb_thres does not fetch its missing rows; each reuses the vector of the hit before it and is
+ * reported as a hit; nothing is inserted for it).  The exact batch-1 engines take it as evs_cache_request's approx_thres; this is
+ * the same mode for evs_cache_lookup_batch / evs_cache_lookup_interact on the set-associative tier.
+ *   thres <= 0            off, the default: every call behaves as without this function, launch for launch.
+ *   1 <= thres <= n_tables  on.  May be called between batched calls.
+ * With a threshold in force a call is still batch n of the batched EvLFU rule (evs_cache_set_batch_policy), and on the snapshot:
+ *   count       agg_hit(b) = the number of sample b's T keys resident at arrival, as ever: an approximated position never counts.
+ *               The raise of hit ways to agg_hit(b) is unchanged; n_hits counts true hits only, n_perfect_hits the samples with
+ *               agg_hit = T.
+ *   substitute  where agg_hit(b) >= thres every missed position (b, t) -- a valid key that is not resident -- is served the row
+ *               that sample b's nearest hit position t' < t is served: the arena row of key (t' + 1, rows[b, t']), in the cache's
+ *               codec, bit-equal to that key's table row.  With no hit below t it is served a row of exact +0.0f (what the exact
+ *               engine does; the reference draws a random vector there).
+ *   flag        hit[b, t] = 2: non-zero, as the reference reports a hit, and told from a true hit's 1.
+ *   no miss     an approximated position is in no miss list: not fetched, not inserted, not re-pointed by sa_repoint (which
+ *               passes over every flag but 0).  A key approximated for one sample and missed by a sample below the threshold is
+ *               inserted once, its priority the maximum agg_hit over the positions that were NOT approximated.
+ *   bad index   an index out of range stays what it is without the mode: no key, flag 0, a zero row, never approximated.
+ *   thres = T   a sample at the threshold has no miss, so nothing is approximated: flags, outputs, dump and counters are those
+ *               of the same calls with the mode off.
+ * The turn-away, the stamps, the EvLFU flush and the alternation with the bag forms hold as without the mode.  The bag forms
+ * (evs_cache_lookup_bags*) ignore the setting.  The setting is not part of the warm-start state: export and load are unchanged.
+ * The envelope of a call with a threshold in force, checked before anything is allocated (the cache stays usable, the message
+ * names the policy): an EvLFU tier alone; batch policy 2, given or resolved; 8-way sets; any codec; miss order 0 (tables in HBM)
+ * or 1 (HBM or pinned host tables).  The call always runs the unfolded chain in pointer mode -- no 4-byte row ids, no folded
+ * probe, no one-launch inline form: evs_cache_set_inline_update(c, 1) is not refused, it is not taken while a threshold is on.
+ * EVS_EINVAL: a plan or sampled policy; 16-way sets (EVS_SA_WAYS=16); a cache with a threshold on as a member of a C1 + C2 (+ C3)
+ * lookup or of a pair bag call (those have the alt-key tier for the purpose).  File-backed tables keep their EVS_ESTATE.
+ * The setter returns EVS_EINVAL, with the policy named, for a NULL cache, thres > n_tables, thres > 0 on an LRU / LFU cache
+ * (the reference's have no such mode; thres <= 0 is accepted) and a row larger than the zero row (4 KiB fp32, 1 KiB of codes). */
+EVS_API int evs_cache_set_batch_approx(evs_cache *c, int thres);
+/* out4 (host), cumulative since creation: [batched calls run with a threshold in force, samples at or above it that had at
+ * least one miss, positions served an earlier hit's row, positions served the zero row].  Synchronises the stream.  EVS_EINVAL
+ * for a NULL cache or a NULL out4, before the device is touched. */
+EVS_API int evs_cache_approx_stats(evs_cache *c, int64_t *out4, void *stream);
 /* out8: [size, n_free, n_tombstones, n_flush, n_evict, n_requests, n_perfect_hits, n_hits];
  * hist (may be NULL): n_tables+1 resident-entry counts per priority (LRU / LFU caches: hist[0] = size, the rest 0). */
 EVS_API int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist, void *stream);
