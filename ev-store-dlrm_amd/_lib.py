@@ -116,6 +116,7 @@ _PROTOS = {
     "evs_cache_serve_consumed": (_int, [_vp, _int, _vp]),
     "evs_cache_set_inline_update": (_int, [_vp, _int]),
     "evs_cache_set_bag_rule": (_int, [_vp, _int]),
+    "evs_cache_set_bag_count": (_int, [_vp, _int]),
     "evs_cache_set_miss_order": (_int, [_vp, _int]),
     "evs_cache_fetch_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_set_batch_approx": (_int, [_vp, _int]),

@@ -3436,6 +3436,7 @@ struct evs_cache {
     uint4 *bag_prov = nullptr; int *bag_pos_sample = nullptr, *bag_agg = nullptr;
     bool had_c3 = false;        // a batched three-tier lookup has run on this cache: its evictions feed an alt-key tier (the pair's bag form refuses it)
     int bag_rule = 0;           // evs_cache_set_bag_rule: 0 none (an EvLFU cache has no bag form), 1 "served bags"
+    int bag_count = 0;          // evs_cache_set_bag_count: 0 the counts come out of the pooling walk, 1 "count first" (a launch of its own)
     float *bag_pool = nullptr; long long bag_pool_floats = 0;
     // ragged bags through the C1 + C2 pair (evs_cache_lookup_bags_c1c2; held by C1, sized and grown like slab_bags): per position
     // the tier code, the serve byte, the row address, the probe's record and the sample; both tiers' miss lists; per sample the
@@ -3865,6 +3866,20 @@ extern "C" int evs_cache_set_bag_rule(evs_cache *c, int rule) {
     EVS_REQUIRE(rule == 0 || c->host.policy == kEvLFU, "evs_cache_set_bag_rule: an %s cache takes ragged bags as they are (one touch per way and batch); "
                 "the \"served bags\" count is the evlfu priority's", policy_name(c->host.policy));
     c->bag_rule = rule;
+    return EVS_OK;
+}
+
+// When an EvLFU bag call computes its samples' counts (the contract: include/evstore_hip.h): 0 "in the pooling walk" -- today's
+// chain and refusals --, 1 "count first": a launch of its own between the probe and everything that needs a count, which is what
+// lets the update run in front of the pooling (fetch-first order).  May be set between calls; not part of the warm-start state.
+extern "C" int evs_cache_set_bag_count(evs_cache *c, int when) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_set_bag_count: NULL cache");
+    EVS_REQUIRE(when == 0 || when == 1, "evs_cache_set_bag_count: when %d on an %s cache (0 \"in the pooling walk\", 1 \"count first\")", when,
+                policy_name(c->host.policy));
+    EVS_REQUIRE(when == 0 || c->host.policy == kEvLFU, "evs_cache_set_bag_count: an %s cache's bag form needs no count (one touch per way and batch); "
+                "\"count first\" is the evlfu bag chain's", policy_name(c->host.policy));
+    c->bag_count = when;
     return EVS_OK;
 }
 
@@ -4745,8 +4760,8 @@ static void sampled_flush_if_wanted(evs_cache *c, hipStream_t st) {
 
 // ---- fetch-first order (evs_cache_set_miss_order(c, 1); the contract: include/evstore_hip.h) --------------------------------
 // What such a cache is held to, checked at every batched call behind batch_check and before anything is allocated: a tier alone,
-// batch policy 2 (given or resolved), sets of 8 ways, EvLFU over the two-copy arena, tables in HBM or in host memory the device
-// addresses.  A policy that was only resolved here is forgotten again on a refusal.  On success an inline setting that was never
+// batch policy 2 (given or resolved), sets of 8 ways, EvLFU over the two-copy arena (its bag calls: count first,
+// evs_cache_set_bag_count), tables in HBM or in host memory the device addresses.  A policy that was only resolved here is forgotten again on a refusal.  On success an inline setting that was never
 // given is 0 from here on.
 static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
     using namespace evs;
@@ -4783,7 +4798,7 @@ static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
                   "hits can be the same batch's victim, and the consumers read behind the update", who, pn);
         return EVS_EINVAL;
     }
-    if (evlfu && bags) {
+    if (evlfu && bags && c->bag_count != 1) {   // ("count first", evs_cache_set_bag_count: the counts come from a pass over the flags in front of the update)
         c->batch_policy = given;
         set_error("%s: an %s cache has no fetch-first bag form: a sample's count exists only after the pooling walk, so the update cannot run in front of it", who, pn);
         return EVS_EINVAL;
@@ -5627,6 +5642,8 @@ static evs::BatchArgs bag_update_args(evs_cache *c, int64_t B, int stamp, uint4 
 // kernel of the (B, T) chain, unchanged, on one stream: the consumers read before the insert moves anything.
 // EvLFU ("served bags", evs_cache_set_bag_rule): probe without a touch -> pooling, which also counts every sample's served
 // bags -> (the dense interaction) -> raise + list -> the set-associative update of the (B, T) chain (cache_batch_sa_list_kernel).
+// "Count first" (evs_cache_set_bag_count(c, 1)): probe -> count -> pooling alone (-> interaction) -> raise + list -> update, and
+// in fetch-first order  probe -> count -> raise + list -> update -> sa_repoint -> pooling alone (-> interaction).
 static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
                            float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, int itself,
                            float *R, uint8_t *hit, void *stream, const char *who) {
@@ -5660,9 +5677,12 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     { const int rc = batch_check(c, who); if (rc) return rc; }
     const bool ff = c->miss_order == 1;   // fetch-first (evs_cache_set_miss_order): probe -> insert -> sa_repoint -> pooling
     if (ff) { const int rc = fetch_first_check(c, who, true); if (rc) return rc; }
-    if (evlfu) {   // the set-associative tier alone, 8 ways, tables in HBM: refused before anything is allocated
+    // "count first" (evs_cache_set_bag_count): the samples' counts from a launch of its own behind the probe.  With fetch-first order
+    // that puts raise + list, the update and sa_repoint in front of the pooling, so the tables may live in host memory
+    const bool cf = evlfu && c->bag_count == 1;
+    if (evlfu) {   // the set-associative tier alone, 8 ways, tables in HBM (fetch-first + count-first: or in host memory): refused before anything is allocated
         const char *pn = policy_name(c->host.policy);
-        if (c->host_backing || c->ft) {
+        if ((c->host_backing && !(ff && cf)) || c->ft) {
             set_error("%s: the bag form of an %s cache reads its tables in place from HBM (no host-memory / file-backed tables)", who, pn);
             return EVS_ESTATE;
         }
@@ -5761,12 +5781,23 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
     a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
     a.pool_flags = ff ? pa.hit : nullptr;
+    a.pool_only = cf ? 1 : 0;
 
     if (grid) bags_probe_launch(a, (int)grid, st);
-    if (ff) {   // (LRU / LFU: fetch_first_check) the insert in front of the pooling, the installed misses re-pointed at the arena
+    if (cf) bags_count_launch(a, st);   // every sample's count, the position -> sample map, column 39: nothing behind it judges a sample
+    if (ff) {   // the update in front of the pooling, the installed misses re-pointed at the arena
         c->fetch_calls++;
         if (grid) {
-            policy_insert_launch(pa, (int)grid, 128u, st);
+            if (evlfu) {
+                // (fetch_first_check: count first.)  The raises end before the update starts, and the update reads what it reads in
+                // order 0 -- the consumers write nothing of it.  A hit way that is this call's victim is replaced in the other copy
+                // of the two-copy arena, so the address the probe wrote names the old row until the pooling has read it.
+                bags_raise_list_launch(a, (int)grid, st);
+                const BatchArgs u = bag_update_args(c, B, stamp, c->bag_rec, c->bag_list_cnt, pa.list_cap, (int)grid);
+                launch_sa_update(u, st);
+            } else {
+                policy_insert_launch(pa, (int)grid, 128u, st);
+            }
             RepointArgs ra = repoint_args(c, pa.hit, c->bag_ptrs, B);
             for (int k = 0; k < 32; k++) ra.indices[k] = a.indices[k];
             for (int k = 0; k < 33; k++) ra.pos0[k] = a.pos0[k];
@@ -5783,7 +5814,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
         if (rc) return rc;   // (nothing is inserted: the touches stand, as after any launch failure behind the probe)
     }
-    if (grid && evlfu) {
+    if (grid && evlfu && !ff) {
         // every sample's count is known: the hit ways go up, the misses are listed with their counts, and the (B, T) chain's
         // update inserts them -- priorities read after all raises, the launches in stream order
         bags_raise_list_launch(a, (int)grid, st);

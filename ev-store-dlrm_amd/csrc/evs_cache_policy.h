@@ -96,13 +96,20 @@ struct BagArgs {
     // fetch-first order (evs_cache_set_miss_order): the update has re-pointed the installed misses at the arena before the
     // pooling runs, so "this position was a hit" comes from the probe's flags (not NULL) instead of the address range
     const unsigned char *pool_flags;
+    // EvLFU "count first" (evs_cache_set_bag_count(c, 1)): bags_count_launch has judged every sample in front of the pooling,
+    // which then only pools -- no sample_cnt hand-over, no agg / pos_sample write, no column-39 add, no look at a flag
+    int pool_only;
 };
 // probe over the flat position list: grid blocks of 256 threads, one lane per position.  LRU / LFU: probe + touch, writes miss
 // list j (records as above).  EvLFU: no way word is written; writes prov and presets pos_sample to -1
 void bags_probe_launch(const BagArgs &a, int grid, hipStream_t st);
 // pooled[k][b] = sum over the bag's positions of the rows the probe's pointer table names (d % 4 == 0, d <= 256); counts the
-// all-hit samples into column 39.  EvLFU: also agg and pos_sample
+// all-hit samples into column 39.  EvLFU: also agg and pos_sample.  pool_only: the pooled rows and the sticky flag, nothing else
 void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st);
+// EvLFU "count first", between the probe and whatever needs a sample's count: a group of 1 / 4 / 16 lanes per bag (by the call's
+// mean bag length) walks the bag's flag bytes (p.hit, as the probe wrote them) -- no row is touched -- and writes pos_sample,
+// agg[b] = the sample's served bags and the all-served samples with a lookup into column 39; sample_cnt is zero again behind it
+void bags_count_launch(const BagArgs &a, hipStream_t st);
 // EvLFU, behind the pooling: one lane per position (the probe's grid) -- every hit way to max(old, agg of the position's
 // sample) with the histogram moves into part1 columns 0 .. T, every miss into list j as (row, table | agg << 8, set, tag + 1),
 // the record cache_batch_sa_list_kernel (evs_cache.hip) reads

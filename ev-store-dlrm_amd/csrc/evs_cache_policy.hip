@@ -13,7 +13,9 @@
 // list of index positions and a pooling kernel as the consumer:  bags_probe -> bags_pool (-> dense interaction) -> insert.
 // EvLFU under the "served bags" rule runs  bags_probe (no touch) -> bags_pool (+ the samples' counts) (-> dense interaction) ->
 // bags_raise_list -> cache_batch_sa_list_kernel (evs_cache.hip): a sample's count exists only after the pooling has seen all
-// its bags, so the raises and the miss lists come from a launch of their own behind it.
+// its bags, so the raises and the miss lists come from a launch of their own behind it.  "Count first" (evs_cache_set_bag_count)
+// takes the counts out of the pooling:  bags_probe -> bags_count (a pass over the flag bytes) -> bags_pool (pooling alone) -> ... ,
+// and in fetch-first order  bags_probe -> bags_count -> bags_raise_list -> update -> sa_repoint -> bags_pool (pooling alone).
 // The C1 + C2 pair over bags (evs_cache_lookup_bags_c1c2) runs  bags_probe2 -> bags_count2 -> bags_route2 -> bags_pool2 (-> dense
 // interaction) -> cache_batch_sa_list2_kernel (evs_cache.hip): the table a missed position is served from depends on its sample's
 // count, so the counts come from a pass over the code bytes IN FRONT of the pooling, and the pooling decodes per position.
@@ -203,12 +205,14 @@ __global__ void __launch_bounds__(256) bags_probe_kernel(const BagArgs args) {
 // EVLFU ("served bags"): the judge also writes agg[b] = T - the sample's bags with a miss, and the piece-0 lane of a group tells
 // every position its bag covers which sample it belongs to (pos_sample; the probe preset -1).  The map comes from this walk
 // and not from a search over the offsets: a bag the bounds check calls empty covers nothing, exactly as it pools nothing.
-template <int CODEC, int UNROLL, bool EVLFU>
+// COUNT = false (EvLFU "count first": bags_count_kernel has judged the samples in front of this launch): the pooling alone -- no
+// flag is read, no sample word, agg, pos_sample or column 39 written; the bounds check and its sticky flag stay.
+template <int CODEC, int UNROLL, bool EVLFU, bool COUNT = true>
 __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
     __shared__ float s_lut[CodecLut<CODEC>::kEntries];
     __shared__ int s_perfect;
     if constexpr (CODEC != 32) codec_lut_init<CODEC>(s_lut);
-    if (threadIdx.x == 0) s_perfect = 0;
+    if (COUNT && threadIdx.x == 0) s_perfect = 0;
     __syncthreads();
     const int T = args.p.T;
     const int LPR = args.d / 4;
@@ -273,8 +277,8 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
                 if (j < len[u]) {
                     r[u] = reinterpret_cast<const unsigned char *>(ptrs[s[u] + j]);
                     // (fetch-first order: an installed miss points into the arena by now -- the probe's flag says what it was)
-                    miss[u] = miss[u] || (flags ? flags[s[u] + j] == 0 : !(r[u] >= arena && r[u] < arena_end));
-                    if constexpr (EVLFU) {
+                    if constexpr (COUNT) miss[u] = miss[u] || (flags ? flags[s[u] + j] == 0 : !(r[u] >= arena && r[u] < arena_end));
+                    if constexpr (EVLFU && COUNT) {
                         if (piece == 0) args.pos_sample[args.pos0[t] + s[u] + j] = (int)(b0 + (long long)u * RPW + slot);
                     }
                 }
@@ -302,7 +306,7 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
             const long long b = b0 + (long long)u * RPW + slot;
             if (lane_on && b < B) {
                 *reinterpret_cast<float4 *>(out + b * args.out_bstride) = acc[u];
-                if (piece == 0) {
+                if (COUNT && piece == 0) {
                     const int mine = 1 | (len[u] > 0 ? 1 << 8 : 0) | (miss[u] ? 1 << 16 : 0);
                     const int all = atomicAdd(&args.sample_cnt[b], mine) + mine;
                     if ((all & 0xff) == T) {   // the sample's last bag: nobody else writes the word any more
@@ -311,6 +315,77 @@ __global__ void __launch_bounds__(256) bags_pool_kernel(const BagArgs args) {
                         if constexpr (EVLFU) args.agg[b] = T - (all >> 16);
                     }
                 }
+            }
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    if constexpr (COUNT) {
+        if (n_perfect) atomicAdd(&s_perfect, n_perfect);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_perfect)
+            atomicAdd(&args.p.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 39], s_perfect);
+    }
+}
+
+// The count pass of the single tier (EvLFU "count first", evs_cache_set_bag_count(c, 1)): agg_hit(b) is a function of the probe's
+// flags and the offsets alone, so it needs no row -- bags_count2_kernel's walk and hand-over over the flag bytes the probe wrote
+// (args.p.hit: the caller's array when one was given).  A group of G lanes owns a bag: lane g of the group reads flags
+// st + g, st + g + G, ... and tells those positions their sample (pos_sample; the probe preset -1), the group's verdict is one
+// ballot, and lane 0 hands it to the sample's word: whoever brings a sample's T-th bag writes agg[b] = T - (bags with a miss),
+// counts the all-served sample with a lookup into column 39 and leaves the word zero.  A bag whose offsets are backwards or past
+// nnz is empty (served) and raises the sticky flag; an index out of range has flag 0 and makes its bag unserved.
+// G = 1 is the pair's lane per bag: neighbouring lanes walk neighbouring bags, whose flags are one contiguous run, so short bags
+// coalesce by themselves.  At 100 indices per bag a lane per bag reads bytes 100 apart and stores pos_sample words 400 bytes
+// apart -- one line per lane and step; G = 16 makes every step of a group one 16-byte read and one 64-byte store.  The bag of a
+// group is wave-uniform in trip count only per group, so the ballot stands behind the walk, where the wave has reconverged.
+template <int G>
+__global__ void __launch_bounds__(256) bags_count_kernel(const BagArgs args) {
+    __shared__ int s_perfect;
+    __shared__ long long s_pos0[33];
+    __shared__ const long long *s_off[32];
+    if (threadIdx.x == 0) s_perfect = 0;
+    if (threadIdx.x < 33) s_pos0[threadIdx.x] = args.pos0[threadIdx.x];
+    if (threadIdx.x < 32) s_off[threadIdx.x] = args.offsets[threadIdx.x];
+    __syncthreads();
+    const int T = args.p.T;
+    const long long B = args.p.B, n_bags = (long long)T * B;
+    constexpr int kBagsPerBlock = 256 / G;
+    const int g = threadIdx.x & (G - 1);
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    int n_perfect = 0;
+    // (block-uniform trip count: every lane of a wave reaches the ballot)
+    for (long long i0 = (long long)blockIdx.x * kBagsPerBlock; i0 < n_bags; i0 += (long long)gridDim.x * kBagsPerBlock) {
+        const long long i = i0 + threadIdx.x / G;
+        const bool on = i < n_bags;
+        const int t = on ? (int)(i / B) : 0;
+        const long long b = on ? i - (long long)t * B : 0;
+        const long long nnz = s_pos0[t + 1] - s_pos0[t];
+        long long st = 0, en = 0;
+        if (on) {
+            const long long *__restrict__ off = s_off[t];
+            st = off[b];
+            en = (b + 1 < B) ? off[b + 1] : nnz;
+            if (!(st >= 0 && en >= st && en <= nnz)) { bad = true; st = 0; en = 0; }
+        }
+        const unsigned char *__restrict__ flags = args.p.hit + s_pos0[t];
+        int *__restrict__ ps = args.pos_sample + s_pos0[t];
+        bool miss = false;
+        for (long long j = st + g; j < en; j += G) {
+            miss = miss || flags[j] == 0;
+            ps[j] = (int)b;
+        }
+        if constexpr (G > 1) {
+            const unsigned long long mm = __ballot(miss);
+            miss = ((mm >> (lane & ~(G - 1))) & ((1ull << G) - 1ull)) != 0ull;
+        }
+        if (on && g == 0) {
+            const int mine = 1 | (en > st ? 1 << 8 : 0) | (miss ? 1 << 16 : 0);
+            const int all = atomicAdd(&args.sample_cnt[b], mine) + mine;
+            if ((all & 0xff) == T) {   // the sample's last bag: nobody else writes the word any more
+                args.sample_cnt[b] = 0;
+                args.agg[b] = T - (all >> 16);
+                if (((all >> 8) & 0xff) != 0 && (all >> 16) == 0) n_perfect++;
             }
         }
     }
@@ -875,7 +950,8 @@ void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st) {
 
 template <int CODEC, int UNROLL>
 static void bags_pool_launch_t(const BagArgs &args, unsigned blocks, hipStream_t st) {
-    if (args.evlfu) hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, true>), dim3(blocks), dim3(256), 0, st, args);
+    if (args.pool_only) hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, false, false>), dim3(blocks), dim3(256), 0, st, args);
+    else if (args.evlfu) hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, true>), dim3(blocks), dim3(256), 0, st, args);
     else hipLaunchKernelGGL((bags_pool_kernel<CODEC, UNROLL, false>), dim3(blocks), dim3(256), 0, st, args);
 }
 
@@ -893,6 +969,21 @@ void bags_pool_launch(const BagArgs &a, int codec, hipStream_t st) {
     case 16: bags_pool_launch_t<16, kUnroll>(args, (unsigned)blocks, st); break;
     case 8: bags_pool_launch_t<8, kUnroll>(args, (unsigned)blocks, st); break;
     default: bags_pool_launch_t<4, kUnroll>(args, (unsigned)blocks, st); break;
+    }
+}
+
+// the lanes per bag follow the call's mean bag length: up to 4 indices a lane per bag (the pair's walk), up to 16 a group of 4,
+// beyond that a group of 16
+void bags_count_launch(const BagArgs &a, hipStream_t st) {
+    const long long n_bags = (long long)a.p.T * a.p.B;
+    const int G = a.n_pos <= 4 * n_bags ? 1 : (a.n_pos <= 16 * n_bags ? 4 : 16);
+    long long blocks = (n_bags * G + 255) / 256;
+    if (blocks > (long long)kNumCu * 8) blocks = (long long)kNumCu * 8;
+    if (blocks < 1) blocks = 1;
+    switch (G) {
+    case 1: hipLaunchKernelGGL(bags_count_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    case 4: hipLaunchKernelGGL(bags_count_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(bags_count_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
     }
 }
 

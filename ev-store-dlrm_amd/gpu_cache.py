@@ -367,6 +367,20 @@ class GpuCache:
         self._bag_rule_told = True
         return self
 
+    def set_bag_count(self, when):
+        """When an 'evlfu' bag call computes its samples' served-bag counts: 'pooling-walk' (the default: the pooling kernel
+        judges every sample as a by-product -- today's chain and refusals, tables in HBM only) or 'count-first' (a launch of its
+        own between the probe and everything that needs a count; the pooling then only pools).  The rule and every result are
+        the same.  On a 'consume-first' cache 'count-first' is the twin of the default chain; on a 'fetch-first' cache
+        (set_miss_order) it is what gives 'evlfu' a bag form at all: probe, count, raise + list, update, re-point, pooling -- every
+        missing row is read once, by the update, so the tables may live in pinned host memory as well as in HBM.  May be set
+        between calls.  'count-first' on an 'lru' / 'lfu' cache raises EVS_EINVAL (their bag form needs no count),
+        'pooling-walk' is accepted (include/evstore_hip.h: evs_cache_set_bag_count)."""
+        if when not in ("count-first", "pooling-walk"):
+            raise ValueError("when must be 'count-first' or 'pooling-walk', got %r" % (when,))
+        _lib.check(_lib.lib().evs_cache_set_bag_count(self._h, 1 if when == "count-first" else 0))
+        return self
+
     def _bags_call(self, lS_o, lS_i):
         """lS_o / lS_i as apply_emb takes them -- a (T, B) int64 tensor or a list of T 1-D int64 tensors, on the device ->
         (B, the C arrays of the call, the flat flag tensor and its per-table views, what must stay alive)"""

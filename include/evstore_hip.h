@@ -602,7 +602,8 @@ EVS_API int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t *ro
  * pooled / x / R, indices[k] with nnz[k] > 0, offsets[k]), nnz[k] < 0, sum(nnz) >= 2^31, a dim the pooling (interact form:
  * the interaction, evs_fused_dim_supported) does not take, n_tables + 1 > 32 features; B == 0 is success.  Refused with a
  * message that names the policy and the cache left usable: an EvLFU cache without a bag rule (EVS_EINVAL), host-memory or
- * file-backed tables (EVS_ESTATE), a cache driven by the exact path (EVS_ESTATE), a capacity below 8 or 2^32 rows over all
+ * file-backed tables (EVS_ESTATE; host memory is served in fetch-first order -- evs_cache_set_miss_order, for EvLFU with
+ * evs_cache_set_bag_count(c, 1)), a cache driven by the exact path (EVS_ESTATE), a capacity below 8 or 2^32 rows over all
  * tables (EVS_EINVAL, as evs_cache_lookup_batch refuses them); an EvLFU cache whose batch policy is or resolves to plan or
  * sampled (set explicitly, through EVS_CACHE_POLICY, or because the geometry has no set-associative form), and 16-way sets
  * (EVS_SA_WAYS=16) or a tier of a C1 + C2 pair (EVS_EINVAL: the pair's bag form is evs_cache_lookup_bags_c1c2, below). */
@@ -665,6 +666,35 @@ EVS_API int evs_cache_lookup_bags_interact_c1c2(evs_cache *c1, evs_cache *c2, in
  * default: the bag entry points refuse the cache), 1 "served bags".  May be called between calls.  EVS_EINVAL, with the policy
  * named: a rule outside {0, 1}; rule 1 on an LRU / LFU cache (their bag form needs none; rule 0 is accepted). */
 EVS_API int evs_cache_set_bag_rule(evs_cache *c, int rule);
+/* WHEN an EvLFU bag call (evs_cache_lookup_bags / _lookup_bags_interact) computes its samples' counts.  agg_hit(b) is a function
+ * of the probe's flags and the offsets alone; where it is computed decides what may run in front of the pooling.
+ *   0 "in the pooling walk" (the default): the chain above -- probe, pooling (which judges every sample as a by-product),
+ *     (interaction,) raise + list, update -- launch for launch, and every refusal as it was: an order-1 EvLFU cache
+ *     (evs_cache_set_miss_order) has no bag form, and the bag form reads its tables from HBM.
+ *   1 "count first": a launch of its own between the probe and everything that needs a count walks the flag bytes of every
+ *     bag (the caller's hit array when one was given, else the cache's), tells each covered position its sample, writes
+ *     agg_hit(b) and counts the all-served samples with a lookup; the pooling then only pools.  THE RULE IS UNCHANGED:
+ *     probe, served bag, agg_hit, raise, insert, uncovered, counters, flush and mixing hold as written at
+ *     evs_cache_lookup_bags; only the launch order moves.
+ *       order 0 (consume first):  (flush,) probe, count, pooling, (interaction,) raise + list, update.  Every observable result
+ *         -- flags, pooled bits, R bits, evs_cache_batch_dump, evs_cache_batch_stats with hist and n_perfect_hits, the exported
+ *         state -- equals what setting 0 gives for the same calls.  Over either arena (EVS_SA_DUAL=0 too); tables in HBM.
+ *       order 1 (fetch first):  (flush,) probe, count, raise + list, update, sa_repoint, pooling, (interaction,) the close
+ *         bookkeeping.  The tier state after a call is what the order-0 chain leaves for it: the raises end before the update
+ *         starts in both orders, the update reads the same words, the consumers write nothing it reads.  A hit way that is
+ *         this call's victim is read from the copy of the two-copy arena the update left alone (as in the (B, T) form).  A key
+ *         whose set took 8 new keys in the call is pooled in place from its table.  evs_cache_fetch_stats counts the call and
+ *         its re-pointed / in-place positions.  The envelope is an order-1 cache's (evs_cache_set_miss_order: a tier alone,
+ *         batch policy 2 given or resolved, 8-way sets, the two-copy arena), checked before anything is allocated, a policy
+ *         that was only resolved there forgotten on a refusal; tables in HBM or in device-addressable host memory -- the one
+ *         combination in which an EvLFU bag call reads host tables; file-backed tables stay EVS_ESTATE; all four codecs; a
+ *         call without a bag rule keeps its EVS_EINVAL.
+ * An all-served sample with a lookup is counted once per call whichever launch judges it, and the cache's sample words are zero
+ * again when a call ends, so the setting may change between calls (like evs_cache_set_bag_rule).  It is not part of the
+ * warm-start state: export and load are unchanged.  The pair's bag form (evs_cache_lookup_bags_c1c2*) has its own count pass
+ * and ignores the setting, as do the (B, T) forms.  EVS_EINVAL, with the policy named: a NULL cache; `when` outside {0, 1};
+ * when = 1 on an LRU / LFU cache (their bag form needs no count; when = 0 is accepted). */
+EVS_API int evs_cache_set_bag_count(evs_cache *c, int when);
 /* The one-launch form of a set-associative tier (round 5: the policy update runs INSIDE evs_cache_lookup_interact's probe +
  * interaction launch; a hit flag then says "served from the cache": 1 => resident at arrival, 0 => not resident OR retired
  * by one of this batch's own inserts OR resident in a way filled k 2^S batches ago, see evs_cache_set_batch_policy) is the default wherever its conditions hold (a tier alone, 8 ways, two-copy arena, at
@@ -698,7 +728,8 @@ EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
  *   tables     HBM or device-addressable host memory.  File-backed tables: EVS_ESTATE.  Order 1 over HBM tables is legal and
  *              gives the results of order 0.
  *   served     evs_cache_lookup_batch (every codec); evs_cache_lookup_interact (fp32 rows; reduced precision with the tables in
- *              HBM only); evs_cache_lookup_bags / _lookup_bags_interact for LRU / LFU.  EvLFU bags: EVS_EINVAL -- a sample's
+ *              HBM only); evs_cache_lookup_bags / _lookup_bags_interact for LRU / LFU, and for EvLFU once
+ *              evs_cache_set_bag_count(c, 1) ("count first") has been told; without it EvLFU bags are EVS_EINVAL -- a sample's
  *              count exists only after the pooling walk, so the update cannot run in front of it.  evs_cache_batch_stats,
  *              _batch_dump, _update_rows and _refresh_rows work as before; the warm start over HBM tables too (over host
  *              tables it keeps its EVS_ESTATE).  The inline setting of an order-1 cache that was never given one is 0.

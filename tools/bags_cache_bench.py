@@ -25,6 +25,19 @@ growing -- into profiles/bags_pair.json:
 Its per-kernel times come from a profiler run of its own, as above:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bags_cache_bench.py --pair --chain-only
     python tools/bags_cache_bench.py --pair --pair-timing profiles/bags_pair.json --kernel-stats one_index_per_bag=DIR/.../..._kernel_stats.csv
+
+--host-tables: the count-first EvLFU bag chain (GpuCache.set_bag_count("count-first")) at this tool's shape, into
+profiles/bags_count_first.json -- (a) EvLFU bags, order 0, the default chain, HBM tables: today's form; (b) the same count-first;
+(c) EvLFU bags, count-first, fetch-first, PINNED host tables; (d) LRU and LFU bags, fetch-first, pinned tables.  Per
+configuration: median / p95 us per call, hit rate, and the bytes that crossed the bus per call as tools/host_setassoc_bench.py
+accounts them.  The five alternate on the same batches in one process.  (a) as the PARENT commit runs it on the same machine is
+b's yardstick: this file run from the parent commit's tree with --host-configs a (a needs nothing new), beside b alone from this
+tree, folded in by --yardstick:
+    python tools/bags_cache_bench.py --host-tables --host-configs a --out PARENT_A.json        (the parent commit's library)
+    python tools/bags_cache_bench.py --host-tables --host-configs b --out B.json
+    python tools/bags_cache_bench.py --host-tables --batch 2048 16384 --yardstick parent_a=PARENT_A.json b=B.json
+Where the count pass's time goes comes from profiler runs of single configurations (--kernel-stats NAME=CSV folds them in):
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bags_cache_bench.py --host-tables --host-configs b --chain-only --batch 16384
 Needs a GPU."""
 import argparse
 import csv
@@ -227,6 +240,97 @@ def run_pair(ln, dev, args):
     return out
 
 
+HOST_CONFIGS = {   # name -> (policy, tables, how the cache is told)
+    "a_evlfu_default_hbm": ("evlfu", "hbm", lambda c: c.set_bag_rule("served-bags")),
+    "b_evlfu_count_first_hbm": ("evlfu", "hbm", lambda c: c.set_bag_rule("served-bags").set_bag_count("count-first")),
+    "c_evlfu_count_first_fetch_first_pinned": ("evlfu", "pinned", lambda c: c.set_miss_order("fetch-first").set_bag_rule("served-bags")
+                                               .set_bag_count("count-first")),
+    "d_lru_fetch_first_pinned": ("lru", "pinned", lambda c: c.set_miss_order("fetch-first")),
+    "d_lfu_fetch_first_pinned": ("lfu", "pinned", lambda c: c.set_miss_order("fetch-first")),
+}
+
+
+def run_host(ln, dev, args):
+    """--host-tables: the EvLFU bag chain count-first, over HBM and over pinned tables in fetch-first order, beside today's chain
+    and beside the LRU / LFU fetch-first bag chains -> the JSON's "host_tables" section, one entry per batch size.  Every
+    configuration is warmed on the same warm-up batches until its size stops growing; the timed batches are the same for all,
+    the configurations alternating call by call.  If the machine refuses the pinned memory every table is halved until it fits
+    (tools/host_setassoc_bench.py's rule) and the factor is recorded."""
+    d, T = args.dim, len(ln)
+    scale = 1.0
+    while True:
+        lns = [max(1, int(n * scale)) for n in ln]
+        ev = bench.make_tables(lns, d, seed=0, device=dev)
+        try:
+            pinned = [ev.fp32_view(k).cpu().pin_memory() for k in range(T)]
+            break
+        except RuntimeError as e:
+            print("bags_cache_bench: pinning %.2f GB failed (%s); halving every table" % (sum(lns) * d * 4 / 1e9, e), file=sys.stderr, flush=True)
+            del ev
+            scale *= 0.5
+    cap = int(args.frac * sum(lns))
+    rb = d * 4
+    out = {"rows": sum(lns), "table_scale": scale, "capacity": cap, "row_bytes": rb, "pinned_bytes": sum(lns) * rb, "batches": {}}
+    F = T + 1
+    for B in args.batch:
+        x = torch.rand((B, d), device=dev)
+        R = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+        caches, warmed = {}, {}
+        for name, (policy, where, tell) in HOST_CONFIGS.items():
+            if not name.startswith(tuple(args.host_configs)):
+                continue
+            c = E.GpuCache(policy, cap, T, d, 32, "python", dev)
+            tell(c)
+            c.set_backing(pinned if where == "pinned" else ev)
+            caches[name] = c
+            warmed[name] = warm(c, lns, B, torch.Generator(device=dev).manual_seed(7), dev, x, args)
+        g = torch.Generator(device=dev).manual_seed(11)
+        batches = [make_batch(lns, B, g, dev, args.max_bag, args.alpha) for _ in range(args.steps)]
+        n_pos = sum(int(t.numel()) for _, li in batches for t in li)
+        if args.chain_only:                          # the run a profiler wraps: the selected chains alone, untimed
+            for lo, li in batches:
+                for c in caches.values():
+                    c.lookup_bags_interact(lo, li, x, out=R)
+            torch.cuda.synchronize()
+            out["batches"]["B=%d" % B] = {"chain_only": list(caches), "warmup_batches": warmed, "batches": args.steps}
+            continue
+        for lo, li in batches[:10]:                  # settle: every configuration on the timed draw before the clock starts
+            for c in caches.values():
+                c.lookup_bags_interact(lo, li, x, out=R)
+        s0 = {n: (c.batch_stats(), c.fetch_stats()) for n, c in caches.items()}
+        events = {n: [] for n in caches}
+        torch.cuda.synchronize()
+        for lo, li in batches:
+            for n, c in caches.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                c.lookup_bags_interact(lo, li, x, out=R)
+                e1.record()
+                events[n].append((e0, e1))
+        torch.cuda.synchronize()
+        res = {}
+        for n, c in caches.items():
+            us = np.array([a.elapsed_time(b) * 1e3 for a, b in events[n]])
+            s1, f1 = c.batch_stats(), c.fetch_stats()
+            fd = {k: f1[k] - s0[n][1][k] for k in f1}
+            fetched = s1["size"] - s0[n][0]["size"] + s1["n_evict"] - s0[n][0]["n_evict"]
+            res[n] = {"median_us": round(float(np.median(us)), 2), "p95_us": round(float(np.percentile(us, 95)), 2),
+                      "hit_rate": round((s1["n_hits"] - s0[n][0]["n_hits"]) / n_pos, 4), "size": s1["size"], "warmup_batches": warmed[n],
+                      "flushes": s1["n_flush"] - s0[n][0]["n_flush"], "fetch_stats_delta": fd,
+                      "bus_bytes_per_call": None if HOST_CONFIGS[n][1] == "hbm" else round((fetched + fd["in_place"]) * rb / args.steps)}
+            print("bags_cache_bench: B=%d %s %s" % (B, n, res[n]), file=sys.stderr, flush=True)
+        entry = {"lookups_per_call": round(n_pos / args.steps, 1), "timed_batches": args.steps, "configs": res}
+        med = {k[0]: v["median_us"] for k, v in res.items() if k[0] in "abc"}
+        if "a" in med and "b" in med:
+            entry["b_over_a"] = round(med["b"] / med["a"], 3)
+        for k in ("d_lru_fetch_first_pinned", "d_lfu_fetch_first_pinned"):
+            if "c" in med and k in res:
+                entry["c_over_" + k[:5]] = round(med["c"] / res[k]["median_us"], 3)
+        out["batches"]["B=%d" % B] = entry
+        del caches
+    return out
+
+
 def kernel_split(path):
     """the library's rows of a rocprofv3 kernel_stats.csv: name, calls, average microseconds, share of the traced time"""
     rows = []
@@ -271,6 +375,11 @@ def main():
     ap.add_argument("--pair-timing", default="", metavar="JSON", help="--pair --kernel-stats: fold the profiler's rows into this timing run's JSON "
                     "instead of timing again (no GPU needed)")
     ap.add_argument("--pair-profile", choices=["one", "ragged"], default="one", help="--pair --chain-only: which batches the profiled run draws")
+    ap.add_argument("--host-tables", action="store_true", help="the count-first EvLFU bag chain over HBM and pinned host tables (see above)")
+    ap.add_argument("--host-configs", nargs="+", default=["a", "b", "c", "d"], metavar="PREFIX", help="--host-tables: only the configurations whose "
+                    "names start so (a configuration alone in its process: the form the parent-commit yardstick is taken in)")
+    ap.add_argument("--yardstick", nargs="*", default=[], metavar="NAME=JSON", help="--host-tables: JSON files of `--host-tables --host-configs X` "
+                    "runs on the same machine (this tool run from the parent commit's tree for configuration a), folded in under alone[NAME]")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.pair and args.pair_profile == "ragged" and args.pair_mean_bag < 2:
@@ -293,6 +402,39 @@ def main():
                "timing": "device events around every call, the two forms alternating batch by batch; dispatch gaps included",
                "pair": run_pair(ln, dev, args)}
         finish_pair(res, args)
+        return
+    if args.host_tables:
+        res = {"tool": "bags_cache_bench --host-tables", "device": torch.cuda.get_device_name(0),
+               "chains": {"a": "bags_probe_kernel -> bags_pool_kernel (+ counts) -> dense interaction -> bags_raise_list_kernel -> cache_batch_sa_list_kernel",
+                          "b": "bags_probe_kernel -> bags_count_kernel -> bags_pool_kernel (pooling alone) -> dense interaction -> bags_raise_list_kernel -> "
+                               "cache_batch_sa_list_kernel",
+                          "c": "bags_probe_kernel -> bags_count_kernel -> bags_raise_list_kernel -> cache_batch_sa_list_kernel -> sa_repoint_kernel -> "
+                               "bags_pool_kernel (pooling alone) -> dense interaction",
+                          "d": "bags_probe_kernel -> policy_insert_kernel -> sa_repoint_kernel -> bags_pool_kernel -> dense interaction"},
+               "shape": {"frac": args.frac, "dim": args.dim, "zipf_alpha": args.alpha, "bags": "1 .. %d" % args.max_bag},
+               "timing": "one pair of device events around every call (dispatch gaps included); the configurations alternate on the same batches "
+                         "in one process; bus bytes per call = (size delta + eviction delta + positions served in place) x row bytes",
+               "host_tables": run_host(ln, dev, args)}
+        for path in args.yardstick:                 # runs of single configurations, each alone in its process: NAME=JSON
+            name, path = path.split("=", 1)
+            with open(path) as f:
+                alone = json.load(f)
+            res.setdefault("alone", {})[name] = {k: {c: {m: r[m] for m in ("median_us", "p95_us", "hit_rate")} for c, r in v["configs"].items()}
+                                                 for k, v in alone["host_tables"]["batches"].items()}
+        if args.kernel_stats:                       # rocprofv3 --kernel-trace --stats over `--host-tables --host-configs X --chain-only` runs: NAME=CSV
+            res["kernel_split"] = {"source": "rocprofv3 --kernel-trace --stats over --host-tables --host-configs X --chain-only --batch B runs, one "
+                                             "configuration and batch size per run (warm-up launches included in the averages)"}
+            for item in args.kernel_stats:
+                name, path = item.split("=", 1)
+                res["kernel_split"][name] = kernel_split(path)
+        if args.chain_only:
+            print(json.dumps(res["host_tables"]["batches"]))
+            return
+        with open(args.out or os.path.join(ROOT, "profiles", "bags_count_first.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"tool": res["tool"], "batches": {k: {r: v[r] for r in v if r.startswith(("b_over", "c_over"))}
+                                                            for k, v in res["host_tables"]["batches"].items()}, "alone": res.get("alone")}))
         return
     ev = bench.make_tables(ln, args.dim, seed=0, device=dev)
     runs = []
