@@ -3803,18 +3803,22 @@ extern "C" int evs_cache_set_miss_order(evs_cache *c, int order) {
     return EVS_OK;
 }
 
-// out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their table, 0]
+// out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their table, 0];
+// C1 of a fetch-first pair: the pair's calls and re-point totals, [3] = hit positions whose way the call's own update took
 extern "C" int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream) {
     using namespace evs;
     EVS_REQUIRE(c, "evs_cache_fetch_stats: NULL cache");
     EVS_REQUIRE(out4, "evs_cache_fetch_stats: NULL out4");
-    unsigned long long h[2] = {0ull, 0ull};
+    unsigned long long h[3] = {0ull, 0ull, 0ull};
     if (c->fetch_cnt) {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        EVS_HIP_CHECK(hipMemcpyAsync(h, c->fetch_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+        unsigned long long rows[kFetchReplicas * kFetchRowWords];
+        EVS_HIP_CHECK(hipMemcpyAsync(rows, c->fetch_cnt, sizeof rows, hipMemcpyDeviceToHost, st));
         EVS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int r = 0; r < kFetchReplicas; r++)
+            for (int k = 0; k < 3; k++) h[k] += rows[r * kFetchRowWords + k];
     }
-    out4[0] = c->fetch_calls; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = 0;
+    out4[0] = c->fetch_calls; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = (int64_t)h[2];
     return EVS_OK;
 }
 
@@ -4806,12 +4810,14 @@ static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
     if (c->inline_mode < 0) c->inline_mode = 0;
     return EVS_OK;
 }
-// the counter block of the re-point kernel (zeroed on st), at the first fetch-first call
+// the counter block of the re-point kernels (zeroed on st), at the first fetch-first call: replica rows (evs_cache_policy.h:
+// kFetchReplicas x kFetchRowWords) of [0] re-pointed, [1] left in place, [2] the pair's hit positions whose way the update took (a
+// tier alone adds into row 0 and never writes [2]); evs_cache_fetch_stats sums the rows
 static int fetch_first_state(evs_cache *c, hipStream_t st, const char *who) {
     if (c->fetch_cnt) return EVS_OK;
     unsigned long long *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), 2 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemsetAsync(p, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) {
+    constexpr size_t bytes = (size_t)evs::kFetchReplicas * evs::kFetchRowWords * sizeof(unsigned long long);
+    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
         (void)hipGetLastError();
         if (p) (void)hipFree(p);
         evs::set_error("%s: allocating the fetch-first counters failed", who);
@@ -5288,10 +5294,12 @@ static int pair_resolve_policy(evs_cache *c1, evs_cache *c2, const char *who) {
     // a pair that was given no policy takes the set-associative form where both tiers can (tables in HBM, at least one full
     // set each), the sampled update over host-memory tables, the plan-based one when a tier has STAGED tables (its reader
     // pool works between plan and assign); a tier with a policy of its own decides for the other; one set-associative and
-    // one hashed tier: refused
+    // one hashed tier: refused.  A fetch-first pair (both tiers at evs_cache_set_miss_order(c, 1): its update runs in front of the
+    // consumers, so no table is read twice) takes the set-associative form wherever its tables live, as such a tier alone does
     {
+        const bool ff2 = c1->miss_order == 1 && c2->miss_order == 1;
         const bool free1 = c1->batch_policy < 0, free2 = c2->batch_policy < 0;
-        const bool sa_ok = !host2 && !c1->ft && !c2->ft && (c1->sa.tags || sa_single_feasible(c1)) && (c2->sa.tags || sa_single_feasible(c2));
+        const bool sa_ok = (!host2 || ff2) && !c1->ft && !c2->ft && (c1->sa.tags || sa_single_feasible(c1)) && (c2->sa.tags || sa_single_feasible(c2));
         if (file2) {
             if (free1) c1->batch_policy = 0;
             if (free2) c2->batch_policy = 0;
@@ -5302,7 +5310,7 @@ static int pair_resolve_policy(evs_cache *c1, evs_cache *c2, const char *who) {
         }
         const int p1 = resolved_batch_policy(c1, true), p2 = resolved_batch_policy(c2, true);
         EVS_REQUIRE((p1 == 2) == (p2 == 2), "%s: both tiers take the set-associative batch policy, or neither (C1 %d, C2 %d)", who, p1, p2);
-        if (p1 == 2 && host2) { set_error("%s: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
+        if (p1 == 2 && host2 && !ff2) { set_error("%s: the set-associative batch policy reads its miss tier in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
         EVS_REQUIRE(p1 != 2 || sa_ok, "%s: the set-associative batch policy needs both tiers' tables in HBM and at least %d entries each", who, (int)kSaSingleWays);
         if (file2 && (p1 != 0 || p2 != 0)) { set_error("%s: a pair with staged file-backed tables takes the plan-based batch policy on both tiers (C1 %d, C2 %d)", who, p1, p2); return EVS_ESTATE; }
         EVS_REQUIRE(!host2 || (p1 == p2), "%s: tiers over host-memory / file-backed tables take the same batch policy (C1 %d, C2 %d)", who, p1, p2);
@@ -5327,6 +5335,42 @@ static int pair_start(evs_cache *c1, evs_cache *c2, hipStream_t st, const char *
     }
     return EVS_OK;
 }
+// ---- fetch-first order of the pair (both tiers at evs_cache_set_miss_order(c, 1); the contract: include/evstore_hip.h) ------
+// What such a pair is held to, checked at every (B, T) call before anything is allocated: no alt-key tier, tables in HBM or in
+// host memory the device addresses, batch policy 2 on both tiers (given or resolved), the shared 128-byte set record -- the
+// re-point kernel searches a position's tier in ONE line.  A policy that was only resolved here is forgotten again on a refusal.
+static int pair_fetch_first_check(evs_cache *c1, evs_cache *c2, evs_aprx *c3, const char *who) {
+    using namespace evs;
+    const char *pn = policy_name(c1->host.policy);
+    EVS_REQUIRE(!c3, "%s: a fetch-first %s pair has no alt-key tier (the triple runs its own chains, consume first)", who, pn);
+    for (evs_cache *c : {c1, c2}) { const int rc = batch_check(c, who); if (rc) return rc; }
+    if (c1->ft || c2->ft) {
+        set_error("%s: a fetch-first %s pair reads its tables in place, from HBM or from host memory the device addresses (no file-backed tables: "
+                  "staged tables need the reader pool and the plan policy)", who, pn);
+        return EVS_ESTATE;
+    }
+    const int given1 = c1->batch_policy, given2 = c2->batch_policy;
+    auto refuse = [&](int rc) { c1->batch_policy = given1; c2->batch_policy = given2; return rc; };
+    { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return refuse(rc); }
+    const int p1 = resolved_batch_policy(c1), p2 = resolved_batch_policy(c2);
+    if (p1 != 2 || p2 != 2) {
+        set_error("%s: fetch-first is the set-associative pair's order (batch policy 2); the batch policy of these %s tiers is %s", who, pn,
+                  (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
+        return refuse(EVS_EINVAL);
+    }
+    bool shared = c1->sa.tags && c1->sa.tags == c2->sa.tags && c1->sa.line_words == 32u && c2->sa.line_words == 32u;
+    if (!shared && !c1->sa.tags && !c2->sa.tags && !c1->bs && !c2->bs) {   // (not started: what pair_start would give them)
+        SaUniverse u; SaGeom g1, g2;
+        shared = sa_pair_geometry(c1, c2, u, g1, g2);
+    }
+    if (!shared) {
+        set_error("%s: a fetch-first %s pair needs the shared set record (two fresh tiers that start out together, at least 4 ways each; not "
+                  "EVS_SA_PAIR=0): the re-point kernel finds a position's tier in one line", who, pn);
+        return refuse(EVS_EINVAL);
+    }
+    return EVS_OK;
+}
+
 // What the (B, T) form and the bag form of the pair (cache_bags_c1c2_impl) share, so that calls of the two may alternate: the
 // route filter C1 holds, a tier's next batch stamp (never 0, distinct for consecutive batches), the batches the closes owe.
 constexpr unsigned kRouteWords = 1u << 20;
@@ -5361,11 +5405,17 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     // host-tier order -- probe (hits and served alt rows stamped), both tiers' updates (each missing row fetched ONCE into its
     // tier's arena: over the bus by the update kernel, or by the host's reader pool for staged tables), a patch kernel that
     // points every missed position at the arena / staged copy, and only then the consumers.
-    EVS_REQUIRE(c1->miss_order == 0 && c2->miss_order == 0, "evs_cache_lookup_batch_c1c2: an %s tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone; "
+    // Both tiers at evs_cache_set_miss_order(c, 1): the fetch-first pair -- the set-associative form over the shared record
+    // wherever the tables live:  flush -> probe (unfolded) -> the pair's update -> sa_repoint2 -> consumers -> close, every
+    // missing row crossing the bus once, inside the update.  No hit is stamped (the tier state is order 0's): the re-point
+    // launch makes every position's address true again from the record as the update left it.
+    const bool ff2 = c1->miss_order == 1 && c2->miss_order == 1;
+    EVS_REQUIRE(ff2 || (c1->miss_order == 0 && c2->miss_order == 0), "evs_cache_lookup_batch_c1c2: an %s tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone; "
                 "the pair / triple runs its own chains", policy_name(c1->host.policy));
     EVS_REQUIRE(c1->batch_approx <= 0 && c2->batch_approx <= 0, "evs_cache_lookup_batch_c1c2: %s is an %s cache with an approximate threshold on (evs_cache_set_batch_approx): "
                 "that mode is a tier alone's; the pair / triple has the alt-key tier for it", c1->batch_approx > 0 ? "C1" : "C2", policy_name(c1->host.policy));
-    const bool host2 = c1->host_backing || c2->host_backing;
+    if (ff2) { const int rc = pair_fetch_first_check(c1, c2, c3, "evs_cache_lookup_batch_c1c2"); if (rc) return rc; }
+    const bool host2 = !ff2 && (c1->host_backing || c2->host_backing);   // the hashed host-tier order below
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     { const int prc = pair_start(c1, c2, st, "evs_cache_lookup_batch_c1c2"); if (prc) return prc; }
     // (The pair's update folded into the probe launch as well -- the thread that routes a double miss claims a way of the
@@ -5381,6 +5431,25 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     if (rc) return rc;
     const int T = c1->host.n_tables;
     const int wide = kNumCu * 8;
+    int *err = nullptr;   // (the re-point launch sees every position: it reports an index out of range through the sticky flag)
+    if (ff2) {
+        rc = fetch_first_state(c1, st, "evs_cache_lookup_batch_c1c2");   // (the pair's counters are C1's)
+        if (rc) return rc;
+        err = index_error_flag();
+        if (!err) return EVS_EHIP;
+    }
+    // the consumers through the pointer table, every row decoded by the codec its serve byte names
+    auto consumers = [&](bool interact) -> int {
+        if (out) {
+            long long nb = (B * T * (long long)c1->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
+            hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c1->row_ptrs, c1->row_tier, out,
+                               (long long)B, T, c1->host.dim, c1->host.codec, c2->host.codec);
+        }
+        if (R && interact)
+            return interact_from_mixed_rows(B, T, c1->host.dim, x, x_stride, c1->row_ptrs, c1->row_tier, c1->host.codec, c2->host.codec,
+                                            itself, R, st);
+        return EVS_OK;
+    };
     if (host2) {
         for (int k = 0; k < 2; k++) {
             evs_cache *c = k ? c2 : c1;
@@ -5475,7 +5544,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         a2.route_filter = c1->route_filter; a2.route_mask = kRouteWords - 1; a2.route_stamp = (unsigned)a1.stamp;
     }
     static const bool fold2_on = !(evs::env_switch("EVS_CACHE_FOLD2") && evs::env_switch("EVS_CACHE_FOLD2")[0] == '0');
-    const bool fold2 = fold2_on && sampled2 && !host2 && a1.miss_rec && R && !out && B <= 65536 && T <= 32 &&
+    const bool fold2 = fold2_on && sampled2 && !host2 && !ff2 && a1.miss_rec && R && !out && B <= 65536 && T <= 32 &&
                        (!sa2 || (c1->sa.ways == 8 && c2->sa.ways == 8 && (c1->host.cap << c1->sa.dual) < (1ll << 30) && (c2->host.cap << c2->sa.dual) < (1ll << 30))) &&   // (the folded probe is compiled for 8-way sets)
                        mixed84_supported(T, c1->host.dim, c1->host.codec, c2->host.codec);
     if (fold2) {
@@ -5524,16 +5593,8 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
             }
         }
         hipLaunchKernelGGL(cache_batch_patch_ptrs2_kernel, dim3((unsigned)a1.g2), dim3(256), 0, st, a1, a2, c1->row_tier);
-        if (out) {
-            long long nb = (B * T * (long long)c1->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
-            hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c1->row_ptrs, c1->row_tier, out,
-                               (long long)B, T, c1->host.dim, c1->host.codec, c2->host.codec);
-        }
-        if (R) {
-            rc = interact_from_mixed_rows(B, T, c1->host.dim, x, x_stride, c1->row_ptrs, c1->row_tier, c1->host.codec, c2->host.codec,
-                                          itself, R, st);
-            if (rc) return rc;
-        }
+        rc = consumers(true);
+        if (rc) return rc;
         if (sampled2) {
             c1->pending_batches++; c1->pending_requests += B;
             c2->pending_batches++; c2->pending_requests += B;
@@ -5552,16 +5613,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         EVS_HIP_CHECK(hipGetLastError());
         return EVS_OK;
     }
-    if (out) {
-        long long nb = (B * T * (long long)c1->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
-        hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c1->row_ptrs, c1->row_tier, out,
-                           (long long)B, T, c1->host.dim, c1->host.codec, c2->host.codec);
-    }
-    if (R && !fold2) {
-        rc = interact_from_mixed_rows(B, T, c1->host.dim, x, x_stride, c1->row_ptrs, c1->row_tier, c1->host.codec, c2->host.codec,
-                                      itself, R, st);
-        if (rc) return rc;
-    }
+    if (!ff2) { rc = consumers(!fold2); if (rc) return rc; }
     if (sampled2) {
         // one update kernel per tier (per-position form: the probe wrote a record per (request, table) and tier); the
         // routing reads each tier's entry count, so the counters are folded every batch here
@@ -5569,6 +5621,21 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
             if (!launch_sa_update_pair(a1, a2, st)) {
                 launch_sa_update(a1, st);
                 launch_sa_update(a2, st);
+            }
+            if (ff2) {   // the update reads the same words in either order; the consumers write nothing it reads
+                Repoint2Args ra{};
+                ra.sa1 = c1->sa; ra.sa2 = c2->sa; ra.sau = c1->sau;
+                ra.requests = rows; ra.code = tier; ra.serve = c1->row_tier; ra.row_ptrs = c1->row_ptrs;
+                for (int k = 0; k < 32; k++) {
+                    ra.rows[k] = k < T ? std::min(c1->backing_rows[k], c2->backing_rows[k]) : 0;
+                    ra.backing1[k] = k < T ? c1->backing[k] : nullptr; ra.backing2[k] = k < T ? c2->backing[k] : nullptr;
+                }
+                ra.arena1 = c1->a.arena; ra.arena2 = c2->a.arena; ra.counters = c1->fetch_cnt; ra.err = err;
+                ra.B = B; ra.T = T; ra.row_bytes1 = c1->host.row_bytes; ra.row_bytes2 = c2->host.row_bytes;
+                sa_repoint2_launch(ra, a1.g1, st);
+                c1->fetch_calls++;
+                rc = consumers(true);
+                if (rc) return rc;
             }
         } else {
         if (!a2.route_filter) { a2.other_slots = c1->bslots; a2.other_mask = (unsigned long long)(c1->bnslot - 1); }   // a key C1 just took is not inserted in C2 too
@@ -6345,6 +6412,8 @@ extern "C" int64_t evs_cache_pair_export(evs_cache *c1, evs_cache *c2, int64_t *
     EVS_REQUIRE(c1->bs && c2->bs && pair_shares_records(c1, c2),
                 "%s: these two caches are not a C1 + C2 pair that shares its set records (the batched pair lookup has not run on them in this "
                 "order, or each tier keeps records of its own)", who);
+    // (a fetch-first pair can share its records over host-memory tables; the warm start is the HBM pair's, export and load alike)
+    if (c1->host_backing || c2->host_backing) { set_error("%s: the warm start reads the tables in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     sampled_close_pending2(c1, 0, c2, 0, st);
     EVS_HIP_CHECK(hipStreamSynchronize(st));
@@ -6400,7 +6469,8 @@ static int pair_warm_check(evs_cache *c1, evs_cache *c2, const char *who) {
         { const int rc = batch_check(c, who); if (rc) return rc; }
         if (c->host_backing || c->ft) { set_error("%s: the warm start reads the tables in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
         if (c->serving || c->tsrv) { set_error("%s: a resident server is running on a tier (or the tiers belong to a tier server)", who); return EVS_ESTATE; }
-        EVS_REQUIRE(c->miss_order == 0, "%s: a tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone", who);
+        // (both tiers fetch-first: the pair's own order, over HBM tables here -- the load launch does not depend on it)
+        EVS_REQUIRE(c->miss_order == 0 || (c1->miss_order == 1 && c2->miss_order == 1), "%s: a tier that runs fetch-first (evs_cache_set_miss_order) is a tier alone", who);
         if (c->used != 0 || c->bs || c->sa.tags || c->exact_touched) {
             set_error("%s: %s has served requests or holds state already; a load goes into two fresh caches", who, c == c1 ? "C1" : "C2");
             return EVS_ESTATE;

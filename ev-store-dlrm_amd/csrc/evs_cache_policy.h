@@ -180,4 +180,37 @@ void sa_repoint_launch(const RepointArgs &a, int grid, hipStream_t st);
 // flat form: the bag probe's grid and walk (block j: positions 256 (j + i grid) + thread, i < iters)
 void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st);
 
+// Fetch-first order of the C1 + C2 pair that shares its set records (both tiers at evs_cache_set_miss_order(c, 1); the chain:
+// evs_cache.hip, batch_c1c2_impl; the rule: include/evstore_hip.h at evs_cache_lookup_batch_c1c2).  The pair has no two-copy
+// arena, so behind the pair's update a way the batch HIT may hold another key.  Every position is searched again in the ways of
+// the tier its serve byte d names, and only there -- the two tiers' ways are one 128-byte record, one line request per position:
+//   code 0, index in range   found: the slot is re-pointed at tier d's arena row; not found (the key was turned away, or the
+//                            route filter gave it to C1 while this position was routed to C2): it keeps tier d's table row
+//   code 1 / 2               found: nothing is stored; not found (this call's update took the way): the slot is pointed at
+//                            tier d's table row, whose bytes are those the arena held
+//   bad index / serve byte 0 untouched
+// Writes no way word, does no atomic on a record, reads no table.  counters (one add per block each): [0] miss positions
+// re-pointed at an arena, [1] miss positions left in place, [2] hit positions whose way the call's own update took.
+// (Same-address device atomics serialise at about 10 ns each: 2 048 blocks adding two or three totals into ONE counter block were 22
+//  of this launch's 30 us at B = 16 384.  The pair's totals therefore go into replica rows, a 128-byte line each, which
+//  evs_cache_fetch_stats sums; a tier alone keeps adding into row 0.)
+constexpr int kFetchReplicas = 32, kFetchRowWords = 16;
+struct Repoint2Args {
+    SaGeom sa1, sa2; SaUniverse sau;
+    const int *requests;                   // (B, T) int32 row ids
+    long long rows[32];                    // per table: min of the two tiers' row counts (an index past either is no key)
+    const unsigned char *backing1[32], *backing2[32];
+    const unsigned char *code;             // (B, T) the probe's tier codes (1 / 2 a hit there, 0 a miss)
+    const unsigned char *serve;            // (B, T) the probe's serve bytes (row_tier)
+    long long *row_ptrs;                   // (B, T) the pointer table
+    unsigned char *arena1, *arena2;
+    unsigned long long *counters;          // kFetchReplicas rows of kFetchRowWords words, block j adds into row j % kFetchReplicas, words 0 .. 2
+    int *err;                              // the sticky index-error flag: raised for an index out of range (counted nowhere)
+    long long B;
+    int T, row_bytes1, row_bytes2;
+};
+// the (B, T) probe's grid and walk (block j: requests 8 j, 8 (j + grid), ...; a half-wave per request, a lane per key); the 8 + 8
+// pair has its way counts compiled in, every other shared-record geometry takes the general form
+void sa_repoint2_launch(const Repoint2Args &a, int grid, hipStream_t st);
+
 }  // namespace evs

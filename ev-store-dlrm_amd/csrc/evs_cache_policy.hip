@@ -817,6 +817,80 @@ __global__ void __launch_bounds__(256) sa_repoint_kernel(const RepointArgs args)
     if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
+// ... of the C1 + C2 pair that shares its set records (the rule: evs_cache_policy.h at Repoint2Args).  The pair keeps one arena
+// row per way, so a way this batch hit can have been this batch's victim: a hit position is searched again too, and one whose
+// key is gone is pointed at the table row of its tier -- the same bytes.  A position looks at the ways of the tier its serve byte
+// names and at no other: the tier's view of the record is picked per lane (the fields the tiers share stay wave-uniform), then
+// sa_split / sa_load / sa_find as everywhere.  W: both tiers' way count when the launcher knows it (8: the reference's 1 : 2
+// pair), 0: any shared-record geometry.
+__device__ __forceinline__ SaGeom sa_geom_of(const SaGeom &g1, const SaGeom &g2, bool second) {
+    // (values, not references, on both sides of every choice: a conditional over two lvalues is an lvalue, and reading it is a
+    //  per-lane load through the chosen address -- seven vector loads and a round trip in front of the set line)
+    auto pick = [second](unsigned a, unsigned b) { return second ? b : a; };
+    SaGeom g = g1;   // (tags, nset, the divider and line_words are the pair's)
+    g.tag_mask = pick(g1.tag_mask, g2.tag_mask); g.tag_bits = pick(g1.tag_bits, g2.tag_bits);
+    g.w_off = pick(g1.w_off, g2.w_off); g.ways = pick(g1.ways, g2.ways);
+    g.sub_shift = pick(g1.sub_shift, g2.sub_shift); g.dual = pick(g1.dual, g2.dual);
+    g.stamp_mask = pick(g1.stamp_mask, g2.stamp_mask);
+    return g;
+}
+template <int W>
+__global__ void __launch_bounds__(256) sa_repoint2_kernel(const Repoint2Args args) {
+    __shared__ int s_cnt[3];   // misses re-pointed / misses left on their table / hits whose way the update took
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    __shared__ const unsigned char *s_tab1[32], *s_tab2[32];
+    const int T = args.T;
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.rows[threadIdx.x] : 0;
+        s_tab1[threadIdx.x] = args.backing1[threadIdx.x];
+        s_tab2[threadIdx.x] = args.backing2[threadIdx.x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    int n_in = 0, n_out = 0, n_took = 0;   // this wave's totals, kept on lane 0
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {   // block-uniform trip count (the ballots)
+        const bool on = req < args.B && hl < T;
+        const long long p = on ? req * T + hl : 0;
+        // (the three loads go out together, position 0 for a lane without one: no branch and no wait between them)
+        const int row_ld = args.requests[p];
+        const int d_ld = args.serve[p], code_ld = args.code[p];
+        const long long row = on ? (long long)row_ld : -1;
+        const int d = on ? d_ld : 0, code = on ? code_ld : 0;
+        // (a bad index, serve byte 0 and a lane without a position all read set 0 of C1's ways and store nothing)
+        const bool want = (d == 1 || d == 2) && code <= 2 && row >= 0 && row < s_rows[hl];
+        if (on && !(row >= 0 && row < s_rows[hl])) atomicOr(args.err, 1);   // (rare: the one atomic of the launch besides the totals)
+        const bool second = want && d == 2;
+        const SaGeom g = sa_geom_of(args.sa1, args.sa2, second);
+        unsigned es = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(args.sau, s_base[hl] + (want ? (unsigned)row : 0u)), es, tag1);
+        if (!want) es = 0u;
+        SaLine line;
+        sa_load<W>(g, es, line);
+        const int way = sa_find<W>(g, line, tag1, w);
+        const bool hit = code != 0;
+        const bool in = want && !hit && way >= 0, out = want && !hit && way < 0, took = want && hit && way < 0;
+        const int rb1 = args.row_bytes1, rb2 = args.row_bytes2;
+        unsigned char *const ar1 = args.arena1, *const ar2 = args.arena2;
+        const long long rb = second ? rb2 : rb1;
+        if (in) args.row_ptrs[p] = (long long)((second ? ar2 : ar1) + (long long)sa_entry(g, es, (unsigned)way, w) * rb);
+        if (took) args.row_ptrs[p] = (long long)((second ? s_tab2[hl] : s_tab1[hl]) + row * rb);
+        n_in += __popcll(__ballot(in)); n_out += __popcll(__ballot(out)); n_took += __popcll(__ballot(took));
+    }
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+        if (n_took) atomicAdd(&s_cnt[2], n_took);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x])
+        atomicAdd(&args.counters[(blockIdx.x % kFetchReplicas) * kFetchRowWords + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
 struct NoTail {};
 // the piece types of a row as compiler vector types (loads through an address-space-1 pointer want non-class types)
 template <typename U> struct Native { using type = U; };
@@ -946,6 +1020,11 @@ void sa_repoint_launch(const RepointArgs &a, int grid, hipStream_t st) {
 
 void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st) {
     hipLaunchKernelGGL(sa_repoint_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void sa_repoint2_launch(const Repoint2Args &a, int grid, hipStream_t st) {
+    if (a.sa1.ways == 8u && a.sa2.ways == 8u) hipLaunchKernelGGL(sa_repoint2_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(sa_repoint2_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
 }
 
 template <int CODEC, int UNROLL>

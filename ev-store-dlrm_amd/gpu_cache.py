@@ -292,10 +292,17 @@ class GpuCache:
     def fetch_stats(self):
         """Counters of the fetch-first chain, cumulative since creation: 'calls' (batched calls that ran it), 'repointed'
         (missed positions served from the arena row the update installed) and 'in_place' (missed positions served from their
-        table: the key's set took 8 new keys in that batch).  Synchronises."""
+        table: the key's set took 8 new keys in that batch).  On C1 of a fetch-first C1 + C2 pair (both tiers set to
+        'fetch-first') they count the pair's calls -- 'in_place' then includes a key routed both ways that C1 took -- and
+        'victim_hits' counts the hit positions whose way the call's own update took (served from their table row, the same
+        bytes).  That key exists only on a cache that has run as C1 of such a pair: a tier alone has no such position.
+        Synchronises."""
         s = (C.c_int64 * 4)()
         _lib.check(_lib.lib().evs_cache_fetch_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
-        return {"calls": int(s[0]), "repointed": int(s[1]), "in_place": int(s[2])}
+        d = {"calls": int(s[0]), "repointed": int(s[1]), "in_place": int(s[2])}
+        if getattr(self, "_pair_fetch_first", False):
+            d["victim_hits"] = int(s[3])
+        return d
 
     def set_batch_approx(self, thres):
         """The approximate-embedding mode of lookup_batch / lookup_interact on an 'evlfu' set-associative tier: a sample with at
@@ -646,7 +653,10 @@ def request_c1c2(c1, c2, rows, threshold=23, out=None, tier=None):
 def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
     """Batched two-tier lookup with snapshot semantics (include/evstore_hip.h: evs_cache_lookup_batch_c1c2): the
     throughput form of request_c1c2.  Returns (tier (B,T) uint8: 1 = C1 hit, 2 = C2 hit, 0 = miss; out (B,T,dim) fp32).
-    c3 (GpuAltKeyTier): the three-tier form (evs_cache_lookup_batch_c1c2c3) -- tier code 3 = the alt row was served."""
+    c3 (GpuAltKeyTier): the three-tier form (evs_cache_lookup_batch_c1c2c3) -- tier code 3 = the alt row was served.
+    Both tiers set_miss_order('fetch-first'): the fetch-first pair -- the set-associative tiers over the shared set record with
+    the update in front of the consumers, so either tier's tables may be pinned host tensors; same results as the default
+    order (c1.fetch_stats() counts its re-point launch).  No c3 there."""
     B = _check_batch(c1, rows, out, tier)
     if out is None:
         out = torch.empty((B, c1.n_tables, c1.dim), dtype=torch.float32, device=c1.device)
@@ -659,7 +669,14 @@ def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
     else:
         _lib.check(_lib.lib().evs_cache_lookup_batch_c1c2c3(c1._h, c2._h, c3._h, B, rows.data_ptr(), out.data_ptr(),
                                                             tier.data_ptr(), int(threshold), st))
+    _ran_pair(c1, c2)
     return tier, out
+
+
+def _ran_pair(c1, c2):
+    """a pair call went through: C1 of a fetch-first pair reports the pair's fourth counter from here on (fetch_stats)"""
+    if getattr(c1, "_fetch_first", False) and getattr(c2, "_fetch_first", False):
+        c1._pair_fetch_first = True
 
 
 # ---- ragged bags through the pair (include/evstore_hip.h: evs_cache_lookup_bags_c1c2) ----
@@ -812,6 +829,7 @@ def lookup_interact_c1c2(c1, c2, rows, x, threshold=23, itself=False, out=None, 
         _lib.check(_lib.lib().evs_cache_lookup_interact_c1c2c3(
             c1._h, c2._h, c3._h, B, rows.data_ptr(), x.data_ptr(), xs, int(bool(itself)), R.data_ptr(), tier.data_ptr(),
             int(threshold), st))
+    _ran_pair(c1, c2)
     return tier, R
 
 

@@ -515,7 +515,43 @@ EVS_API int evs_cache_set_batch_policy(evs_cache *c, int policy);
  * tier's arena (over the bus by the thread that inserts it; staged tables: by the host's reader pool, de-duplicated) ->
  * every missed position re-pointed at the arena / staged copy -> the consumers.  Policies: "sampled" over device-visible
  * tables (pinned, registered), "plan" on BOTH tiers as soon as one has staged tables; "setassoc": EVS_ESTATE.  A position
- * whose key another request of the batch routed to C1 (odd tables only) is served C1's copy at C1's precision. */
+ * whose key another request of the batch routed to C1 (odd tables only) is served C1's copy at C1's precision.
+ * THE FETCH-FIRST PAIR.  A pair whose BOTH tiers were told evs_cache_set_miss_order(c, 1) before their first batched call runs
+ * this call and evs_cache_lookup_interact_c1c2 as the set-associative pair over the shared 128-byte set record wherever the
+ * tables of either tier live -- HBM or device-addressable host memory -- on one stream, in this order:
+ *   1. the EvLFU flush an earlier close asked for;
+ *   2. the unfolded probe: 8-byte row addresses, the serve byte, the tier codes, the per-tier miss lists, hit ways raised;
+ *   3. the route filter and the pair's update launch (every missing row crosses the bus once, here);
+ *   4. sa_repoint2 (below);
+ *   5. the consumers through the pointer table;
+ *   6. the close bookkeeping.
+ * The folded probe is not taken.  Observable results equal what order 0 gives for the same calls: tier codes (strict snapshot),
+ * the bits of out, both tiers' evs_cache_batch_dump and evs_cache_batch_stats with hist, the exported state -- the update reads
+ * the same words in either order, the consumers write nothing it reads.  (R comes from the unfolded consumer: the usual
+ * float64-scaled bound, not order 0's folded kernel bit for bit.)
+ * The pair keeps ONE arena row per way, so a way the batch hit can be that batch's victim and hold another key's row by the time
+ * the consumers run.  Hits are NOT stamped against that (the tier state would differ from order 0's).  Instead step 4 makes every
+ * position's address true again from the set record as the update left it; with d the position's serve byte (1 or 2) it searches
+ * tier d's ways of the key's set, and only tier d's (C2's sub-set included; both tiers' ways are one line):
+ *   code 0, index in range   found: the address becomes tier d's arena row.  Not found -- the key was turned away, or, on an odd
+ *                            table, routed both ways and given to C1 while this position was routed to C2 --: it stays tier d's
+ *                            table row, read in place.  Either way the bytes are tier d's table row in tier d's codec.
+ *   code 1 / 2               found: nothing is stored.  Not found (this call's update took the way): the address becomes tier
+ *                            d's backing-table row -- served rows are exactly the table rows, so the bytes are those the arena held.
+ *   bad index / serve byte 0 untouched: code 0, a zero row, counted nowhere; the launch raises the sticky index-error flag
+ *                            (evs_check_index_errors) for it, which the order-0 (B, T) chains do not.
+ * The kernel writes no way word, does no atomic on a record and reads no table.  evs_cache_fetch_stats(c1, ...) reports its totals.
+ * The envelope, checked before anything is allocated, the pair left usable, the message naming the policy (a policy that was
+ * only resolved there is forgotten again):
+ *   order      both tiers at order 1; one of them: EVS_EINVAL ("a tier alone").
+ *   policy     batch policy 2 on both, given or resolved -- a pair that was given none takes it wherever its tables live;
+ *              plan / sampled, given or from EVS_CACHE_POLICY: EVS_EINVAL.
+ *   record     the shared set record: two fresh tiers that start out together with at least 4 ways each.  EVS_SA_PAIR=0, a tier
+ *              that was used alone before, capacities without such a record: EVS_EINVAL.
+ *   tables     file-backed: EVS_ESTATE.
+ *   tiers      no alt-key tier (the _c1c2c3 forms: EVS_EINVAL); an approximate threshold on a tier keeps its EVS_EINVAL.
+ * evs_cache_pair_export / evs_cache_pair_load take such a pair over HBM tables (state version 3, unchanged; over host tables:
+ * EVS_ESTATE); evs_cache_lookup_bags_c1c2 keeps its refusal of order-1 tiers. */
 EVS_API int evs_cache_lookup_batch_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int32_t *rows, float *out,
                                         uint8_t *tier, int high_agghit_threshold, void *stream);
 /* The same two-tier snapshot lookup with the interaction as its consumer (BASELINE configs[4] end to end):
@@ -719,7 +755,10 @@ EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
  *     A key whose set took 8 new keys in the batch is turned away and served in place from its table.
  * The envelope of an order-1 cache, resolved and checked at every batched call before anything is allocated (a policy that was
  * only resolved there is forgotten again on a refusal; every message names the cache's policy):
- *   tier       a tier alone; as a member of a C1 + C2 (+ C3) lookup it is refused at that call, EVS_EINVAL.
+ *   tier       a tier alone, or -- BOTH tiers at order 1 -- the C1 + C2 pair of evs_cache_lookup_batch_c1c2 / _lookup_interact_c1c2
+ *              ("THE FETCH-FIRST PAIR" there: its own envelope and its own re-point kernel).  One tier of a pair at order 1, the
+ *              triple, the pair's bag form: refused at that call, EVS_EINVAL.  A member of a pair stays refused by the
+ *              single-tier calls.
  *   policy     batch policy 2, given or resolved: LRU / LFU as always; an EvLFU cache that was given no policy and no
  *              EVS_CACHE_POLICY takes it wherever the geometry has a set-associative form, wherever its tables live (the one
  *              resolution rule that differs from order 0).  plan / sampled, given or from the environment: EVS_EINVAL.
@@ -739,6 +778,9 @@ EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
 EVS_API int evs_cache_set_miss_order(evs_cache *c, int order);
 /* out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their
  * table, 0], cumulative since creation.  An index out of range is no key and is counted nowhere.  Synchronises the stream.
+ * C1 of a fetch-first pair counts the pair: [pair calls run fetch-first, miss positions re-pointed at an arena (of either
+ * tier), miss positions left in place, hit positions whose way the call's own update took]; C2's own counters are not used.
+ * The fourth word stays 0 for a tier alone.
  * EVS_EINVAL for a NULL cache or a NULL out4, before the device is touched. */
 EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
 /* The approximate-embedding mode of the batched EvLFU rule (the reference: cache_algo/EvLFU_C1.py:122-125, :142-152 -- a request
