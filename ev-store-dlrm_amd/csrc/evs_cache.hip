@@ -5917,6 +5917,8 @@ extern "C" int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int
 //   probe2 (one lane per position, both tiers' ways out of the shared record, no way word written)
 //   -> count (a lane per bag over the code bytes: agg per sample -- the table a miss is served from depends on it)
 //   -> route + raise + list  -> pool2 (every position decoded by its serving tier)  (-> dense interaction)  -> the pair's update.
+// Both tiers at order 1 and "count first" (the fetch-first bag chain; tables in HBM or in device-addressable host memory):
+//   probe2 -> count -> route + raise + list -> the pair's update -> bags_repoint2 -> pool2 (-> dense interaction) -> the closes.
 static bool pair_shares_records(const evs_cache *c1, const evs_cache *c2);
 static const char *bag_pair_codecs_ok(int c1, int c2) {   // the six pairs the reference builds (MGR_VARIANTS)
     return (c1 == 32 && (c2 == 16 || c2 == 8 || c2 == 4)) || (c1 == 16 && (c2 == 8 || c2 == 4)) || (c1 == 8 && c2 == 4) ? nullptr
@@ -5953,6 +5955,10 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
                     who, EVS_MAX_FEATURES, T, d);
     // the envelope: refused before anything is allocated, the pair left as it was
+    // Both tiers at order 1 AND told "count first" (evs_cache_set_bag_count: the counts may be computed in front of everything, which
+    // is what lets the update run before the pooling): the fetch-first bag chain, over tables in HBM or in device-addressable host
+    // memory.  An order-0 pair ignores the count setting; an order-1 pair without it on both tiers keeps its refusal.
+    const bool ff2 = c1->miss_order == 1 && c2->miss_order == 1 && c1->bag_count == 1 && c2->bag_count == 1;
     evs_cache *cs[2] = {c1, c2};
     for (int k = 0; k < 2; k++) {
         evs_cache *c = cs[k];
@@ -5961,11 +5967,21 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         EVS_REQUIRE(c->bag_rule == 1, "%s: %s has no bag rule: evs_cache_set_bag_rule(c, 1) says what a request's hit count is over bags, and the pair "
                     "needs it told to both tiers", who, cn);
         { const int rc = batch_check(c, who); if (rc) return rc; }
-        if (c->host_backing || c->ft) {
+        // (in front of the table refusals: a pair meant to run fetch-first over host tables that lacks count-first is told so)
+        EVS_REQUIRE(ff2 || !(c1->miss_order == 1 && c2->miss_order == 1), "%s: the fetch-first bag form of an %s pair runs the update in front of the "
+                    "pooling, so it needs the samples' counts first: tell evs_cache_set_bag_count(c, 1) to both tiers (%s was not told)", who,
+                    policy_name(c->host.policy), c1->bag_count == 1 ? "C2" : "C1");
+        if (ff2 && c->ft) {
+            set_error("%s: the fetch-first bag form of an %s pair reads its tables in place, from HBM or from host memory the device addresses; %s sits "
+                      "over file-backed tables", who, policy_name(c->host.policy), cn);
+            return EVS_ESTATE;
+        }
+        if (!ff2 && (c->host_backing || c->ft)) {
             set_error("%s: the bag form of the pair reads its tables in place from HBM; %s sits over host-memory / file-backed tables", who, cn);
             return EVS_ESTATE;
         }
-        EVS_REQUIRE(c->miss_order == 0, "%s: %s runs fetch-first (evs_cache_set_miss_order): such a tier is a tier alone", who, cn);
+        EVS_REQUIRE(ff2 || c->miss_order == 0, "%s: %s runs fetch-first (evs_cache_set_miss_order): such an %s tier is a tier alone, or -- both tiers "
+                    "fetch-first and count-first -- a tier of the fetch-first pair", who, cn, policy_name(c->host.policy));
         EVS_REQUIRE(c->batch_approx <= 0, "%s: %s is an %s cache with an approximate threshold on (evs_cache_set_batch_approx): that mode is a tier alone's",
                     who, cn, policy_name(c->host.policy));
         EVS_REQUIRE(!(c->serving || c->tsrv), "%s: a resident server is running on %s", who, cn);
@@ -5977,6 +5993,9 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         EVS_REQUIRE(!pairs, "%s: no pooling for a %d-bit C1 over a %d-bit C2; the pairs of precisions are %s", who, c1->host.codec, c2->host.codec, pairs);
     }
     const int given1 = c1->batch_policy, given2 = c2->batch_policy;
+    // (the fetch-first pair's own envelope -- policy 2 given or resolved wherever the tables live, the shared record, no file-backed
+    //  tables -- in the words of the (B, T) form; it forgets a policy it only resolved when it refuses)
+    if (ff2) { const int rc = pair_fetch_first_check(c1, c2, nullptr, who); if (rc) return rc; }
     if (c1->sa.tags || c2->sa.tags || c1->bs || c2->bs) {   // a pair that has started: it must have started out together, over one record per set
         EVS_REQUIRE(pair_shares_records(c1, c2), "%s: the bag form is the set-associative pair's that shares its set records (batch policy 2 on both tiers, "
                     "started out together); these tiers %s", who,
@@ -6007,6 +6026,7 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
     { const int rc = pair_start(c1, c2, st, who); if (rc) return rc; }
     if (!pair_shares_records(c1, c2)) { set_error("%s: the pair did not get its shared set records", who); return EVS_ESTATE; }
     for (evs_cache *c : cs) { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    if (ff2) { const int rc = fetch_first_state(c1, st, who); if (rc) return rc; }   // (the pair's counters are C1's, shared with the (B, T) form)
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
 
@@ -6087,19 +6107,7 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
     if (grid) bags_probe2_launch(a, (int)grid, st);
     bags_count2_launch(a, st);
     if (grid) bags_route2_launch(a, (int)grid, st);   // (in front of the pooling: raises change priorities only, no key or arena row moves until the update)
-    if (!bags_pool2_launch(a, c1->host.codec, c2->host.codec, st)) { set_error("%s: no pooling kernel for the pair of precisions", who); return EVS_EINVAL; }
-    if (interact) {
-        const float *feats[EVS_MAX_FEATURES];
-        int64_t strides[EVS_MAX_FEATURES];
-        feats[0] = x; strides[0] = x_stride;
-        for (int k = 0; k < T; k++) { feats[k + 1] = c1->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
-        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
-        if (rc) {   // nothing is inserted and the raises stand; the batch is counted, so the close folds its hits with its requests
-            pair_count_batch(c1, c2, B);
-            return rc;
-        }
-    }
-    if (grid) {
+    auto update = [&]() {   // the (B, T) form's update launch over the route launch's lists
         const BatchArgs u1 = bag_update_args(c1, B, stamp[0], a.miss_rec1, a.list_cnt1, a.list_cap, (int)grid);
         BatchArgs u2 = bag_update_args(c2, B, stamp[1], a.miss_rec2, a.list_cnt2, a.list_cap, (int)grid);
         u2.route_filter = c1->route_filter; u2.route_mask = kRouteWords - 1; u2.route_stamp = (unsigned)stamp[0];
@@ -6107,7 +6115,36 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
             launch_sa_update(u1, st);
             launch_sa_update(u2, st);
         }
+    };
+    if (ff2) {
+        // fetch first: the raises and the lists are complete, so the update runs here -- every missing row crosses the bus once,
+        // inside it -- and the re-point launch makes every position's address true again from the record as the update left it.
+        // The update reads the same lists and way words in either order; neither the re-point nor the pooling writes one of them.
+        if (grid) {
+            update();
+            BagRepoint2Args ra{};
+            ra.sa1 = c1->sa; ra.sa2 = c2->sa;
+            for (int k = 0; k < 32; k++) { ra.backing1[k] = k < T ? c1->backing[k] : nullptr; ra.backing2[k] = k < T ? c2->backing[k] : nullptr; }
+            ra.prov = a.prov; ra.serve = a.serve; ra.row_ptrs = a.row_ptrs;
+            ra.arena1 = c1->a.arena; ra.arena2 = c2->a.arena; ra.counters = c1->fetch_cnt;
+            ra.n_pos = n_pos; ra.iters = (int)iters; ra.row_bytes1 = c1->host.row_bytes; ra.row_bytes2 = c2->host.row_bytes;
+            bags_repoint2_launch(ra, (int)grid, st);
+        }
+        c1->fetch_calls++;
     }
+    if (!bags_pool2_launch(a, c1->host.codec, c2->host.codec, st)) { set_error("%s: no pooling kernel for the pair of precisions", who); return EVS_EINVAL; }
+    if (interact) {
+        const float *feats[EVS_MAX_FEATURES];
+        int64_t strides[EVS_MAX_FEATURES];
+        feats[0] = x; strides[0] = x_stride;
+        for (int k = 0; k < T; k++) { feats[k + 1] = c1->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
+        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+        if (rc) {   // order 0: nothing is inserted and the raises stand (order 1: the batch is already inserted); the batch is counted, so the close folds its hits with its requests
+            pair_count_batch(c1, c2, B);
+            return rc;
+        }
+    }
+    if (grid && !ff2) update();
     pair_count_batch(c1, c2, B);
     if (c1->pending_batches >= kCloseEvery || c2->pending_batches >= kCloseEvery) sampled_close_pending2(c1, 0, c2, 0, st);
     EVS_HIP_CHECK(hipGetLastError());

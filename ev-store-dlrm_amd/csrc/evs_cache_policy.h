@@ -213,4 +213,26 @@ struct Repoint2Args {
 // pair has its way counts compiled in, every other shared-record geometry takes the general form
 void sa_repoint2_launch(const Repoint2Args &a, int grid, hipStream_t st);
 
+// ... and of the pair's bag form (evs_cache_lookup_bags_c1c2 with both tiers at order 1 and "count first"; the chain: evs_cache.hip,
+// cache_bags_c1c2_impl): behind the pair's update and in front of bags_pool2.  The rule per position is Repoint2Args' above, read
+// from what the bag probe and the route launch left -- prov[p] holds row, table, tier code, the key bit and (set, quotient), serve[p]
+// the serving tier -- so no index is loaded and nothing is divided or permuted again.  Every position with a key is searched,
+// whether or not a bag covers it; serve byte 0 (a bad index: the probe has raised the sticky flag) is untouched and counted
+// nowhere.  Writes no way word, does no atomic on a record, reads no table.  counters: the (B, T) form's replica rows and words
+// (the two forms may alternate on one pair).
+struct BagRepoint2Args {
+    SaGeom sa1, sa2;
+    const unsigned char *backing1[32], *backing2[32];
+    const uint4 *prov;                     // n_pos records as bags_probe2 wrote them (BagPairArgs)
+    const unsigned char *serve;            // n_pos serve bytes: the code of a hit, the destination bags_route2 gave a miss
+    long long *row_ptrs;                   // n_pos slots of the pointer table
+    unsigned char *arena1, *arena2;
+    unsigned long long *counters;          // kFetchReplicas rows of kFetchRowWords words, block j adds into row j % kFetchReplicas, words 0 .. 2
+    long long n_pos;
+    int iters, row_bytes1, row_bytes2;
+};
+// the bag probe's grid and walk (block j: positions 256 (j + i grid) + thread, i < iters); the 8 + 8 pair has its way counts
+// compiled in, every other shared-record geometry takes the general form
+void bags_repoint2_launch(const BagRepoint2Args &a, int grid, hipStream_t st);
+
 }  // namespace evs

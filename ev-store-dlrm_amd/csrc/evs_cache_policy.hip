@@ -19,6 +19,8 @@
 // The C1 + C2 pair over bags (evs_cache_lookup_bags_c1c2) runs  bags_probe2 -> bags_count2 -> bags_route2 -> bags_pool2 (-> dense
 // interaction) -> cache_batch_sa_list2_kernel (evs_cache.hip): the table a missed position is served from depends on its sample's
 // count, so the counts come from a pass over the code bytes IN FRONT of the pooling, and the pooling decodes per position.
+// Both tiers at order 1 and "count first":  bags_probe2 -> bags_count2 -> bags_route2 -> cache_batch_sa_list2_kernel ->
+// bags_repoint2 -> bags_pool2 (-> dense interaction), every missing row read once, by the update.
 #include <type_traits>
 
 #include "evs_cache_policy.h"
@@ -891,6 +893,58 @@ __global__ void __launch_bounds__(256) sa_repoint2_kernel(const Repoint2Args arg
         atomicAdd(&args.counters[(blockIdx.x % kFetchReplicas) * kFetchRowWords + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
+// ... and of the pair's bag form (the rule: evs_cache_policy.h at BagRepoint2Args): sa_repoint2_kernel over the flat position
+// list, the bag probe's grid and walk.  The probe left (row, table, code, key bit, set, quotient) in prov[p] and the route launch
+// the serving tier in serve[p], so a position costs two loads, sa_place in its tier's view of the record and one line request.
+template <int W>
+__global__ void __launch_bounds__(256) bags_repoint2_kernel(const BagRepoint2Args args) {
+    __shared__ int s_cnt[3];   // misses re-pointed / misses left on their table / hits whose way the update took
+    __shared__ const unsigned char *s_tab1[32], *s_tab2[32];
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        s_tab1[threadIdx.x] = args.backing1[threadIdx.x];
+        s_tab2[threadIdx.x] = args.backing2[threadIdx.x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    int n_in = 0, n_out = 0, n_took = 0;   // this wave's totals, kept on lane 0
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots)
+        const long long at = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = at < args.n_pos;
+        const long long p = on ? at : 0;
+        // (the two loads go out together, position 0 for a lane without one: no branch and no wait between them)
+        const uint4 r = args.prov[p];
+        const int d_ld = args.serve[p];
+        const int d = on ? d_ld : 0;
+        const int k = (int)(r.y & 31u);
+        const bool hit = ((r.y >> kProvCodeShift) & 3u) != 0u;
+        // (a bad index, serve byte 0 and a lane without a position all read set 0 of C1's ways and store nothing)
+        const bool want = (d == 1 || d == 2) && (r.y & kProvKey) != 0u;
+        const bool second = want && d == 2;
+        const SaGeom g = sa_geom_of(args.sa1, args.sa2, second);
+        unsigned es = 0u, tag1 = 0u, w = 0u;
+        sa_place(g, want ? r.z : 0u, want ? r.w : 0u, es, tag1);
+        SaLine line;
+        sa_load<W>(g, es, line);
+        const int way = sa_find<W>(g, line, tag1, w);
+        const bool in = want && !hit && way >= 0, out = want && !hit && way < 0, took = want && hit && way < 0;
+        const int rb1 = args.row_bytes1, rb2 = args.row_bytes2;
+        unsigned char *const ar1 = args.arena1, *const ar2 = args.arena2;
+        const long long rb = second ? rb2 : rb1;
+        if (in) args.row_ptrs[p] = (long long)((second ? ar2 : ar1) + (long long)sa_entry(g, es, (unsigned)way, w) * rb);
+        if (took) args.row_ptrs[p] = (long long)((second ? s_tab2[k] : s_tab1[k]) + (long long)r.x * rb);
+        n_in += __popcll(__ballot(in)); n_out += __popcll(__ballot(out)); n_took += __popcll(__ballot(took));
+    }
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+        if (n_took) atomicAdd(&s_cnt[2], n_took);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x])
+        atomicAdd(&args.counters[(blockIdx.x % kFetchReplicas) * kFetchRowWords + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
 struct NoTail {};
 // the piece types of a row as compiler vector types (loads through an address-space-1 pointer want non-class types)
 template <typename U> struct Native { using type = U; };
@@ -1025,6 +1079,11 @@ void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st) {
 void sa_repoint2_launch(const Repoint2Args &a, int grid, hipStream_t st) {
     if (a.sa1.ways == 8u && a.sa2.ways == 8u) hipLaunchKernelGGL(sa_repoint2_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(sa_repoint2_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_repoint2_launch(const BagRepoint2Args &a, int grid, hipStream_t st) {
+    if (a.sa1.ways == 8u && a.sa2.ways == 8u) hipLaunchKernelGGL(bags_repoint2_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bags_repoint2_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
 }
 
 template <int CODEC, int UNROLL>

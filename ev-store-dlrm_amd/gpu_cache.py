@@ -293,7 +293,7 @@ class GpuCache:
         """Counters of the fetch-first chain, cumulative since creation: 'calls' (batched calls that ran it), 'repointed'
         (missed positions served from the arena row the update installed) and 'in_place' (missed positions served from their
         table: the key's set took 8 new keys in that batch).  On C1 of a fetch-first C1 + C2 pair (both tiers set to
-        'fetch-first') they count the pair's calls -- 'in_place' then includes a key routed both ways that C1 took -- and
+        'fetch-first') they count the pair's calls, (B, T) and bag form alike -- 'in_place' then includes a key routed both ways that C1 took -- and
         'victim_hits' counts the hit positions whose way the call's own update took (served from their table row, the same
         bytes).  That key exists only on a cache that has run as C1 of such a pair: a tier alone has no such position.
         Synchronises."""
@@ -380,7 +380,10 @@ class GpuCache:
         own between the probe and everything that needs a count; the pooling then only pools).  The rule and every result are
         the same.  On a 'consume-first' cache 'count-first' is the twin of the default chain; on a 'fetch-first' cache
         (set_miss_order) it is what gives 'evlfu' a bag form at all: probe, count, raise + list, update, re-point, pooling -- every
-        missing row is read once, by the update, so the tables may live in pinned host memory as well as in HBM.  May be set
+        missing row is read once, by the update, so the tables may live in pinned host memory as well as in HBM.  The C1 + C2
+        pair's bag form (lookup_bags_c1c2 / lookup_bags_interact_c1c2) always counts first; there the setting is a statement: told
+        to BOTH tiers of a pair whose tiers are both 'fetch-first', it lets the pair's update run in front of the pooling (the
+        fetch-first bag chain, tables in HBM or pinned); a 'consume-first' pair ignores it.  May be set
         between calls.  'count-first' on an 'lru' / 'lfu' cache raises EVS_EINVAL (their bag form needs no count),
         'pooling-walk' is accepted (include/evstore_hip.h: evs_cache_set_bag_count)."""
         if when not in ("count-first", "pooling-walk"):
@@ -693,6 +696,12 @@ def lookup_bags_c1c2(c1, c2, lS_o, lS_i, threshold=23, out=None):
     tier's precision, every distinct missed key is inserted once; the bags pool the served rows in index order, each decoded at
     the precision of the tier that serves it (include/evstore_hip.h: evs_cache_lookup_bags_c1c2).  lS_o / lS_i as
     GpuCache.lookup_bags takes them.
+    Both tiers set_miss_order('fetch-first') AND set_bag_count('count-first'): the fetch-first bag chain -- probe, count, route +
+    raise + list, the pair's update, a kernel that re-points every position at where its row is now, then the pooling -- so every
+    distinct missing row is read once, by the update, and either tier's tables may be pinned host tensors.  Codes, pooled bits
+    and the tier state equal the default order's; c1.fetch_stats() counts the call and its 'repointed' / 'in_place' /
+    'victim_hits' positions.  Both at 'fetch-first' without 'count-first' on both, or one tier alone at 'fetch-first': EVS_EINVAL;
+    a 'consume-first' pair over pinned tables: EVS_ESTATE, as before.
     -> (tiers: T uint8 tensors, one code per index, views of one flat array; ly: T (B, dim) fp32 tensors, views of one
     (T, B, dim) block -- `out`, when given)."""
     _check_bag_pair(c1, c2)
@@ -704,12 +713,16 @@ def lookup_bags_c1c2(c1, c2, lS_o, lS_i, threshold=23, out=None):
         raise ValueError("out must be a contiguous (%d, %d, %d) fp32 device tensor" % (T, B, d))
     _lib.check(_lib.lib().evs_cache_lookup_bags_c1c2(c1._h, c2._h, B, idx_c, off_c, nnz_c, out.data_ptr(), B * d, d, flat.data_ptr(),
                                                      int(threshold), torch.cuda.current_stream(c1.device).cuda_stream))
+    _ran_pair(c1, c2)
     return tiers, list(out.unbind(0))
 
 
 def lookup_bags_interact_c1c2(c1, c2, lS_o, lS_i, x, threshold=23, itself=False, out=None):
     """R = interact_features(x, the T pooled bags of lookup_bags_c1c2): the same rule and codes, the pooling into a (T, B, dim)
     block C1 owns, the dense interaction, then the pair's update (include/evstore_hip.h: evs_cache_lookup_bags_interact_c1c2).
+    A pair with both tiers at 'fetch-first' and 'count-first' runs the fetch-first bag chain of lookup_bags_c1c2 (update and
+    re-point in front of the pooling; tables in HBM or pinned host memory; same codes, R bits and tier state).  There the batch is
+    already inserted when the interaction refuses its arguments; in the default order nothing is inserted then.
     -> (tiers as lookup_bags_c1c2 gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
     _check_bag_pair(c1, c2)
     B, idx_c, off_c, nnz_c, flat, tiers, _keep = c1._bags_call(lS_o, lS_i)
@@ -724,6 +737,7 @@ def lookup_bags_interact_c1c2(c1, c2, lS_o, lS_i, x, threshold=23, itself=False,
     _lib.check(_lib.lib().evs_cache_lookup_bags_interact_c1c2(
         c1._h, c2._h, B, idx_c, off_c, nnz_c, x.data_ptr(), int(x.stride(0)) if B > 1 else c1.dim, int(bool(itself)),
         out.data_ptr(), flat.data_ptr(), int(threshold), torch.cuda.current_stream(c1.device).cuda_stream))
+    _ran_pair(c1, c2)
     return tiers, out
 
 

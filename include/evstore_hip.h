@@ -551,7 +551,10 @@ EVS_API int evs_cache_set_batch_policy(evs_cache *c, int policy);
  *   tables     file-backed: EVS_ESTATE.
  *   tiers      no alt-key tier (the _c1c2c3 forms: EVS_EINVAL); an approximate threshold on a tier keeps its EVS_EINVAL.
  * evs_cache_pair_export / evs_cache_pair_load take such a pair over HBM tables (state version 3, unchanged; over host tables:
- * EVS_ESTATE); evs_cache_lookup_bags_c1c2 keeps its refusal of order-1 tiers. */
+ * EVS_ESTATE).
+ * THE FETCH-FIRST PAIR OVER BAGS.  evs_cache_lookup_bags_c1c2 / _lookup_bags_interact_c1c2 take such a pair once BOTH tiers have also
+ * been told evs_cache_set_bag_count(c, 1) ("count first"): the rule, the chain and the envelope are written at
+ * evs_cache_lookup_bags_c1c2 ("THE FETCH-FIRST BAG CHAIN").  Without count-first on both tiers the bag form keeps its EVS_EINVAL. */
 EVS_API int evs_cache_lookup_batch_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int32_t *rows, float *out,
                                         uint8_t *tier, int high_agghit_threshold, void *stream);
 /* The same two-tier snapshot lookup with the interaction as its consumer (BASELINE configs[4] end to end):
@@ -689,9 +692,48 @@ EVS_API int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int64_
  * (EVS_EINVAL; B == 0 is success); both caches EvLFU with evs_cache_set_bag_rule(c, 1) told to BOTH (EVS_EINVAL names the cache
  * that lacks it); the pair shares its set record (evs_cache_pair_load's geometry: plan-based, sampled and EVS_SA_PAIR=0 pairs,
  * tiers that did not start out together: EVS_EINVAL); both tiers' tables in HBM (host-memory / file-backed: EVS_ESTATE); miss
- * order 0; no alt-key tier (a pair that has run evs_cache_lookup_batch_c1c2c3 / _interact_c1c2c3: EVS_EINVAL); the pairs of precisions the reference builds -- 32-16, 32-8, 32-4, 16-8, 16-4, 8-4 (others:
+ * order 0, or the fetch-first bag chain below; no alt-key tier (a pair that has run evs_cache_lookup_batch_c1c2c3 / _interact_c1c2c3: EVS_EINVAL); the pairs of precisions the reference builds -- 32-16, 32-8, 32-4, 16-8, 16-4, 8-4 (others:
  * EVS_EINVAL naming the codecs); dim a multiple of 4 up to 256, the interact form evs_fused_dim_supported(dim) and
- * n_tables + 1 <= 32. */
+ * n_tables + 1 <= 32.
+ * THE FETCH-FIRST BAG CHAIN (the bag form of "THE FETCH-FIRST PAIR" at evs_cache_lookup_batch_c1c2) is taken only when ALL of these
+ * hold: both tiers are at evs_cache_set_miss_order(c, 1); both tiers have been told evs_cache_set_bag_count(c, 1) -- "count first" is
+ * the statement that the samples' counts may be computed in front of everything, which is exactly what lets the update run before
+ * the pooling --; both tiers have the bag rule.  The call then runs, on one stream:
+ *   (flush) -> bags_probe2 -> bags_count2 -> bags_route2 -> the pair's update launch -> bags_repoint2 -> bags_pool2
+ *           -> (dense interaction) -> the close bookkeeping.
+ * NOTHING OF THE RULE ABOVE CHANGES: tier codes (strict snapshot), served bag, agg_hit, raise, route, insert, counters, flush and
+ * mixing hold as written.  The tier state after a call is what the order-0 chain leaves for that call: the raises end before the
+ * update in both orders, the update reads the same lists and the same way words, and neither the re-point nor the pooling writes
+ * anything the update reads.  Codes, pooled bits, R bits, both tiers' evs_cache_batch_dump, evs_cache_batch_stats with hist and
+ * n_perfect_hits and the exported state equal order 0's on every call whose outcome does not depend on timing.
+ * RE-POINT (bags_repoint2).  Every position with a key -- serve byte 1 or 2, whether or not a bag covers it -- is searched again in
+ * the ways of the tier its serve byte names, in the one shared 128-byte record, and only there:
+ *   code 0, key now resident in that tier   that tier's arena row (counted `repointed`);
+ *   code 0, key not there                   turned away, or routed both ways and given to C1 by the route filter while this position
+ *                                           was routed to C2: it keeps the table row the route launch wrote (counted `in_place`);
+ *   code 1 / 2, way still holds the key     nothing is stored;
+ *   code 1 / 2, the update took the way     (the pair has one arena row per way) the tier's table row, the same bytes (counted
+ *                                           `victim_hits`);
+ *   serve byte 0 (a bad index)              untouched and counted nowhere; the probe has raised the sticky flag.
+ * The kernel writes no way word, does no atomic on a record and reads no table.  Over host tables every distinct missing row
+ * crosses the bus once, inside the update; only `in_place` and `victim_hits` positions are read from host memory by the pooling.
+ * evs_cache_fetch_stats(c1, ...) counts the pair's bag calls and the three totals in the words the (B, T) fetch-first pair uses;
+ * calls of the two forms may alternate on one pair.
+ * A FAILING INTERACTION.  The interaction's argument checks (dim, feature count, x / R) are made up front, before the device is
+ * touched.  Should evs_interact_dot still fail, an order-1 call leaves an already-inserted batch (the update ran in front of it);
+ * in order 0 nothing is inserted, as before.  Either way the batch is counted.
+ * ITS ENVELOPE, checked before anything is allocated, the pair left usable, a policy that was only resolved there forgotten again:
+ * the fetch-first pair's (batch policy 2 given or resolved wherever the tables live -- plan / sampled, given or from
+ * EVS_CACHE_POLICY: EVS_EINVAL; the shared set record -- EVS_SA_PAIR=0, capacities without one, tiers that started alone:
+ * EVS_EINVAL; file-backed tables: EVS_ESTATE; messages name the policy) plus the bag form's own (bag rule on both, the six pairs of
+ * precisions, no alt-key history, no resident server, no approximate threshold).  What the caller sees: a tier on which
+ * evs_cache_serve_start was called belongs to the exact path, so the batched path's own check speaks first -- EVS_ESTATE, "this
+ * evlfu cache is used through the exact path"; an order-1 pair cannot have alt-key history (the _c1c2c3 forms refuse it, EVS_EINVAL);
+ * both tiers at order 1 without count-first on both is refused (EVS_EINVAL naming evs_cache_set_bag_count) BEFORE the tables are
+ * looked at, so a pair over host-memory tables that forgot the setting is told so, not that its tables must be in HBM.  Each tier's tables may be in HBM or in
+ * device-addressable host memory, independently; the alignment check applies to host tables too.  One tier at order 1: EVS_EINVAL
+ * ("a tier alone").  Both at order 1 with count-first on none or one tier: EVS_EINVAL naming "fetch-first".  An order-0 pair
+ * ignores evs_cache_set_bag_count, runs the chain at the top launch for launch and keeps EVS_ESTATE over host-memory tables. */
 EVS_API int evs_cache_lookup_bags_c1c2(evs_cache *c1, evs_cache *c2, int64_t B, const int64_t *const *indices,
                                        const int64_t *const *offsets, const int64_t *nnz, float *pooled, int64_t out_table_stride,
                                        int64_t out_bag_stride, uint8_t *tier, int high_agghit_threshold, void *stream);
@@ -728,7 +770,9 @@ EVS_API int evs_cache_set_bag_rule(evs_cache *c, int rule);
  * An all-served sample with a lookup is counted once per call whichever launch judges it, and the cache's sample words are zero
  * again when a call ends, so the setting may change between calls (like evs_cache_set_bag_rule).  It is not part of the
  * warm-start state: export and load are unchanged.  The pair's bag form (evs_cache_lookup_bags_c1c2*) has its own count pass
- * and ignores the setting, as do the (B, T) forms.  EVS_EINVAL, with the policy named: a NULL cache; `when` outside {0, 1};
+ * in front of the pooling whatever the setting; an order-0 pair ignores it, as do the (B, T) forms.  On a pair with BOTH tiers at
+ * order 1 the setting, told to both tiers, is what admits the fetch-first bag chain ("THE FETCH-FIRST BAG CHAIN" at
+ * evs_cache_lookup_bags_c1c2); told to none or one of them, the call keeps its EVS_EINVAL.  EVS_EINVAL, with the policy named: a NULL cache; `when` outside {0, 1};
  * when = 1 on an LRU / LFU cache (their bag form needs no count; when = 0 is accepted). */
 EVS_API int evs_cache_set_bag_count(evs_cache *c, int when);
 /* The one-launch form of a set-associative tier (round 5: the policy update runs INSIDE evs_cache_lookup_interact's probe +
@@ -756,9 +800,10 @@ EVS_API int evs_cache_set_inline_update(evs_cache *c, int on);
  * The envelope of an order-1 cache, resolved and checked at every batched call before anything is allocated (a policy that was
  * only resolved there is forgotten again on a refusal; every message names the cache's policy):
  *   tier       a tier alone, or -- BOTH tiers at order 1 -- the C1 + C2 pair of evs_cache_lookup_batch_c1c2 / _lookup_interact_c1c2
- *              ("THE FETCH-FIRST PAIR" there: its own envelope and its own re-point kernel).  One tier of a pair at order 1, the
- *              triple, the pair's bag form: refused at that call, EVS_EINVAL.  A member of a pair stays refused by the
- *              single-tier calls.
+ *              ("THE FETCH-FIRST PAIR" there: its own envelope and its own re-point kernel) and, once both tiers were also told
+ *              evs_cache_set_bag_count(c, 1), of evs_cache_lookup_bags_c1c2 / _lookup_bags_interact_c1c2.  One tier of a pair at
+ *              order 1, the triple, the pair's bag form without count-first on both tiers: refused at that call, EVS_EINVAL.  A
+ *              member of a pair stays refused by the single-tier calls.
  *   policy     batch policy 2, given or resolved: LRU / LFU as always; an EvLFU cache that was given no policy and no
  *              EVS_CACHE_POLICY takes it wherever the geometry has a set-associative form, wherever its tables live (the one
  *              resolution rule that differs from order 0).  plan / sampled, given or from the environment: EVS_EINVAL.

@@ -26,6 +26,15 @@ Its per-kernel times come from a profiler run of its own, as above:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bags_cache_bench.py --pair --chain-only
     python tools/bags_cache_bench.py --pair --pair-timing profiles/bags_pair.json --kernel-stats one_index_per_bag=DIR/.../..._kernel_stats.csv
 
+--pair --fetch-first [--host-tables]: the pair's fetch-first bag chain (both tiers set_miss_order("fetch-first") and
+set_bag_count("count-first"): probe2 -> count -> route + raise + list -> the pair's update -> bags_repoint2 -> pool2 -> dense
+interaction) at the --pair shape, into profiles/bag_pair_fetch_first.json.  Without --host-tables: over HBM, alternating with the
+order-0 chain on a twin pair (section "hbm").  With it: both tiers' tables in pinned host memory, alternating -- one index per bag
+-- with the (B, T) fetch-first pair on a twin (section "pinned"), with the rows fetched, the positions read in place and the bus
+bytes per call.  --chain-only runs the fetch-first chain alone for a profiler, as above (--pair-profile one | ragged), and
+    python tools/bags_cache_bench.py --pair --fetch-first --pair-timing profiles/bag_pair_fetch_first.json --kernel-stats NAME=CSV
+folds the profiler's rows into the JSON under kernel_split[NAME] (no GPU needed).
+
 --host-tables: the count-first EvLFU bag chain (GpuCache.set_bag_count("count-first")) at this tool's shape, into
 profiles/bags_count_first.json -- (a) EvLFU bags, order 0, the default chain, HBM tables: today's form; (b) the same count-first;
 (c) EvLFU bags, count-first, fetch-first, PINNED host tables; (d) LRU and LFU bags, fetch-first, pinned tables.  Per
@@ -240,6 +249,110 @@ def run_pair(ln, dev, args):
     return out
 
 
+def run_pair_fetch(ln, dev, args):
+    """--pair --fetch-first: the pair's fetch-first bag chain (both tiers set_miss_order("fetch-first") + set_bag_count("count-first"))
+    at the --pair shape -> the JSON's "hbm" section, or, with --host-tables, its "pinned" section.  Over HBM it alternates with the order-0 chain on a twin pair;
+    with --host-tables both tiers' tables are pinned host tensors and it alternates, one index per bag, with the (B, T) fetch-first
+    pair (lookup_interact_c1c2(fused=False)) on a twin.  All pairs see the same batches, call by call, in one process."""
+    T, d, B = len(ln), args.dim, args.pair_batch
+    ev = bench.make_tables(ln, d, seed=0, device=dev)
+    ev8, ev4 = ev.encode(8), ev.encode(4)
+    del ev
+    rbs = (d, d // 2)                                 # row bytes of the u8 and the u4 tier
+    tabs = ([t.cpu().pin_memory() for t in ev8.raw], [t.cpu().pin_memory() for t in ev4.raw]) if args.host_tables else (ev8, ev4)
+    budget = int(0.02 * sum(ln))
+    caps = (int(0.48 * budget) * 4, int(0.48 * budget) * 8)
+
+    def pair(order):
+        p = E.GpuCache("evlfu", caps[0], T, d, 8, "cpp", dev), E.GpuCache("evlfu", caps[1], T, d, 4, "cpp", dev)
+        for c, tab in zip(p, tabs):
+            if order:
+                c.set_miss_order("fetch-first").set_bag_count("count-first")
+            c.set_bag_rule("served-bags").set_backing(tab)
+        return p
+
+    g = torch.Generator(device=dev).manual_seed(7)
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    R = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+    bags = lambda p: (lambda lo, li, rq: E.lookup_bags_interact_c1c2(p[0], p[1], lo, li, x, out=R))
+    bt = lambda p: (lambda lo, li, rq: E.lookup_interact_c1c2(p[0], p[1], rq, x, fused=False))
+    if args.chain_only:
+        pairs = {"fetch_first": pair(1)}
+        calls = {"fetch_first": bags(pairs["fetch_first"])}
+    elif args.host_tables:
+        pairs = {"fetch_first_pinned": pair(1), "bt_fetch_first_pinned": pair(1)}
+        calls = {"fetch_first_pinned": bags(pairs["fetch_first_pinned"]), "bt_fetch_first_pinned": bt(pairs["bt_fetch_first_pinned"])}
+    else:
+        pairs = {"order0_hbm": pair(0), "fetch_first_hbm": pair(1)}
+        calls = {n: bags(p) for n, p in pairs.items()}
+    first = next(iter(pairs.values()))
+    n_warm, last = 0, -1
+    while n_warm < args.max_warmup:                   # one index per bag on every pair until the sizes stop growing
+        for _ in range(10):
+            batch = make_pair_batch(ln, B, g, dev, 1, args.alpha)
+            for call in calls.values():
+                call(*batch)
+        n_warm += 10
+        size = first[0].batch_stats()["size"] + first[1].batch_stats()["size"]
+        if last >= 0 and size - last < 0.002 * (caps[0] + caps[1]):
+            break
+        last = size
+    draws = {"one_index_per_bag": [make_pair_batch(ln, B, g, dev, 1, args.alpha) for _ in range(args.steps)],
+             "ragged": [make_pair_batch(ln, B, g, dev, args.pair_mean_bag, args.alpha) for _ in range(args.steps)]}
+    if args.chain_only:
+        for batch in draws["ragged" if args.pair_profile == "ragged" else "one_index_per_bag"]:
+            calls["fetch_first"](*batch)
+        torch.cuda.synchronize()
+        return {"batch": B, "warmup_batches": n_warm, "batches": args.steps, "profiled": args.pair_profile}
+    out = {"batch": B, "capacities": list(caps), "codecs": [8, 4], "dim": d, "tables": "pinned host memory" if args.host_tables else "HBM",
+           "warmup_batches": n_warm, "sizes_after_warmup": [c.batch_stats()["size"] for c in first], "timed_batches": args.steps}
+
+    def snap(p):
+        return [c.batch_stats() for c in p], p[0].fetch_stats()
+
+    for section, batches in draws.items():
+        names = [n for n in calls if section == "one_index_per_bag" or not n.startswith("bt_")]
+        for batch in batches[:10]:                    # settle on the timed draw before the clock starts
+            for n in names:
+                calls[n](*batch)
+        s0 = {n: snap(pairs[n]) for n in names}
+        events = {n: [] for n in names}
+        torch.cuda.synchronize()
+        for batch in batches:
+            for n in names:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                calls[n](*batch)
+                e1.record()
+                events[n].append((e0, e1))
+        torch.cuda.synchronize()
+        n_pos = sum(int(v.numel()) for _, li, _ in batches for v in li)
+        res = {}
+        for n in names:
+            us = np.array([a.elapsed_time(b) * 1e3 for a, b in events[n]])
+            (st0, f0), (st1, f1) = s0[n], snap(pairs[n])
+            hits = sum(st1[k]["n_hits"] - st0[k]["n_hits"] for k in (0, 1))
+            fetched = [st1[k]["size"] - st0[k]["size"] + st1[k]["n_evict"] - st0[k]["n_evict"] for k in (0, 1)]
+            fd = {k: f1[k] - f0.get(k, 0) for k in f1}
+            res[n] = {"median_us": round(float(np.median(us)), 2), "p95_us": round(float(np.percentile(us, 95)), 2),
+                      "hit_rate": round(hits / n_pos, 4), "miss_positions_per_call": round((n_pos - hits) / args.steps, 1),
+                      "rows_fetched_per_call": [round(f / args.steps, 1) for f in fetched], "fetch_stats_delta": fd,
+                      "flushes": [st1[k]["n_flush"] - st0[k]["n_flush"] for k in (0, 1)]}
+            if args.host_tables:                      # the update's fetches, plus the positions the pooling reads in place (their tier is not
+                rest = fd.get("in_place", 0) + fd.get("victim_hits", 0)   # counted: bounded by the u4 and the u8 row)
+                res[n]["bus_bytes_per_call"] = [round((fetched[0] * rbs[0] + fetched[1] * rbs[1] + rest * rb) / args.steps) for rb in (rbs[1], rbs[0])]
+                res[n]["positions_read_from_host_by_the_consumer_per_call"] = round(rest / args.steps, 1)
+            print("bags_cache_bench: %s %s %s" % (section, n, res[n]), file=sys.stderr, flush=True)
+        entry = {"lookups_per_call": round(n_pos / args.steps, 1), "configs": res}
+        if "order0_hbm" in res:
+            entry["fetch_first_over_order0_median"] = round(res["fetch_first_hbm"]["median_us"] / res["order0_hbm"]["median_us"], 3)
+        if "bt_fetch_first_pinned" in res:
+            entry["bag_form_over_bt_form_median"] = round(res["fetch_first_pinned"]["median_us"] / res["bt_fetch_first_pinned"]["median_us"], 3)
+        out[section] = entry
+    return out
+
+
 HOST_CONFIGS = {   # name -> (policy, tables, how the cache is told)
     "a_evlfu_default_hbm": ("evlfu", "hbm", lambda c: c.set_bag_rule("served-bags")),
     "b_evlfu_count_first_hbm": ("evlfu", "hbm", lambda c: c.set_bag_rule("served-bags").set_bag_count("count-first")),
@@ -375,6 +488,8 @@ def main():
     ap.add_argument("--pair-timing", default="", metavar="JSON", help="--pair --kernel-stats: fold the profiler's rows into this timing run's JSON "
                     "instead of timing again (no GPU needed)")
     ap.add_argument("--pair-profile", choices=["one", "ragged"], default="one", help="--pair --chain-only: which batches the profiled run draws")
+    ap.add_argument("--fetch-first", action="store_true", help="--pair: the pair's fetch-first bag chain beside the order-0 chain over HBM, or "
+                    "(with --host-tables) over pinned host tables beside the (B, T) fetch-first pair (see above)")
     ap.add_argument("--host-tables", action="store_true", help="the count-first EvLFU bag chain over HBM and pinned host tables (see above)")
     ap.add_argument("--host-configs", nargs="+", default=["a", "b", "c", "d"], metavar="PREFIX", help="--host-tables: only the configurations whose "
                     "names start so (a configuration alone in its process: the form the parent-commit yardstick is taken in)")
@@ -382,8 +497,21 @@ def main():
                     "runs on the same machine (this tool run from the parent commit's tree for configuration a), folded in under alone[NAME]")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.fetch_first and not args.pair:
+        ap.error("--fetch-first is the pair's bag chain: give --pair with it (--host-tables alone is the single-tier bench)")
     if args.pair and args.pair_profile == "ragged" and args.pair_mean_bag < 2:
         ap.error("--pair-profile ragged needs --pair-mean-bag of 2 or more")
+    if args.pair and args.fetch_first and args.pair_timing:   # ... of --pair --fetch-first: --kernel-stats NAME=CSV into kernel_split[NAME]
+        with open(args.pair_timing) as f:
+            res = json.load(f)
+        res.setdefault("kernel_split", {"source": "rocprofv3 --kernel-trace --stats over --pair --fetch-first --chain-only runs (warm-up launches "
+                                                  "included in the averages)"})
+        for item in args.kernel_stats:
+            name, path = item.split("=", 1)
+            res["kernel_split"][name] = kernel_split(path)
+        with open(args.out or args.pair_timing, "w") as f:
+            f.write(json.dumps(res) + "\n")
+        return
     if args.pair and args.pair_timing:                # fold the profiler's rows into an earlier timing run's JSON: no GPU needed
         with open(args.pair_timing) as f:
             finish_pair(json.load(f), args)
@@ -393,6 +521,27 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     ln = [min(n, args.max_rows) if args.max_rows else n for n in bench.KAGGLE_LN]
+    if args.pair and args.fetch_first:
+        path = args.out or os.path.join(ROOT, "profiles", "bag_pair_fetch_first.json")
+        res = {}
+        if not args.chain_only and os.path.exists(path):   # the HBM run and the --host-tables run share one file
+            with open(path) as f:
+                res = json.load(f)
+        res.update({"tool": "bags_cache_bench --pair --fetch-first [--host-tables]",
+                    "chain": "bags_probe2_kernel -> bags_count2_kernel -> bags_route2_kernel -> cache_batch_sa_list2_kernel -> "
+                             "bags_repoint2_kernel -> bags_pool2_kernel -> dense interaction",
+                    "device": torch.cuda.get_device_name(0),
+                    "shape": {"rows": sum(ln), "dim": args.dim, "zipf_alpha": args.alpha},
+                    "timing": "one pair of device events around every call (dispatch gaps included); the compared pairs alternate on the same "
+                              "batches in one process; rows fetched = size delta + eviction delta per tier; bus bytes per call = rows fetched x "
+                              "the tier's row bytes + (in_place + victim_hits) x [u4, u8] row bytes (lower and upper figure)"})
+        res["pinned" if args.host_tables else "hbm"] = run_pair_fetch(ln, dev, args)
+        line = json.dumps(res)
+        if not args.chain_only:
+            with open(path, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     if args.pair:
         res = {"tool": "bags_cache_bench --pair",
                "chain": "bags_probe2_kernel -> bags_count2_kernel -> bags_route2_kernel -> bags_pool2_kernel -> dense interaction -> "
