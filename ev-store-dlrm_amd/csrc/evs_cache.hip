@@ -3465,10 +3465,6 @@ struct evs_cache {
     int *slot_stage = nullptr;
     long long staging_rows = 0;
     long long n_staged_rows = 0;   // rows the reader pool has fetched so far (statistics)
-    // fork / join of one batch: the hash part of the policy update (K2, K4) on a side stream under the consumer
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int fork_mode = -1;            // -1: not decided yet (EVS_CACHE_FORK, default off), 0 / 1
     long long batch_calls = 0, last_sweep_call = -100, last_hk_call = 0, last_flush_call = 0;
     int pending_batches = 0; long long pending_requests = 0;   // sampled update: batches whose counters the close has not folded yet
     unsigned long long *evicted_keys = nullptr;   // batched three-tier lookup: what K4 evicted, for the alt-key tier
@@ -3577,7 +3573,7 @@ unsigned sa_single_ways() {
 }
 // a tier alone keeps two arena rows per way (evs_hash.h: the two-copy arena; EVS_SA_DUAL=0: one, developer A/B)
 unsigned sa_single_dual() {
-    static const unsigned dual_on = (evs::env_switch("EVS_SA_DUAL") && evs::env_switch("EVS_SA_DUAL")[0] == '0') ? 0u : 1u;
+    static const unsigned dual_on = evs::env_switch_on("EVS_SA_DUAL") ? 1u : 0u;
     return dual_on;
 }
 // can this cache take the set-associative form on its own (universe below 2^32 keys, tags that fit the word)
@@ -3610,7 +3606,7 @@ bool sa_pair_geometry_of(long long cap1, long long cap2, int T, const long long 
     return sa_make_geom(g1, (unsigned)nset, (unsigned)w1, 0, 32, u) && sa_make_geom(g2, (unsigned)nset, (unsigned)w2, off2, 32, u, sub2);
 }
 bool sa_pair_geometry(const evs_cache *c1, const evs_cache *c2, evs::SaUniverse &u, evs::SaGeom &g1, evs::SaGeom &g2) {
-    static const bool on = !(evs::env_switch("EVS_SA_PAIR") && evs::env_switch("EVS_SA_PAIR")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_SA_PAIR");
     if (!on || !c1->has_backing || !c2->has_backing || c1->host.n_tables != c2->host.n_tables) return false;
     return sa_pair_geometry_of(c1->host.cap, c2->host.cap, c1->host.n_tables, c1->backing_rows, c2->backing_rows, u, g1, g2);
 }
@@ -3664,9 +3660,6 @@ extern "C" int evs_cache_destroy(evs_cache *c) {
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
     if (c->new_keys_host) (void)hipHostFree(c->new_keys_host);
     if (c->staging) (void)hipHostFree(c->staging);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->side) (void)hipStreamDestroy(c->side);
     if (c->mbox) {
         c->req_host[32] = 1u;   // stop
         __atomic_thread_fence(__ATOMIC_SEQ_CST);
@@ -4619,55 +4612,48 @@ static unsigned sampled_list_threads(const evs::BatchArgs &a) {
     if (w >= 1) return 64u * (unsigned)w;
     return a.list_cap > 8 * a.T ? 128u : 64u;
 }
-// the sampled update, compiled per row size (row_bytes = PIECES pieces of 16 / 8 / 4 / 2 bytes, at most 16 of them)
-template <int PIECES, typename U, typename TAIL = evs::NoTail>
-static void launch_sampled_update_t(const evs::BatchArgs &a, hipStream_t st) {
-    using namespace evs;
-    // K1 listed the misses: one wave per list (two when the lists are those of the folded probe's 16-sample blocks: twice as long)
-    if (a.miss_rec) hipLaunchKernelGGL((cache_batch_sampled_list_kernel<PIECES, U, TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a);
-    else hipLaunchKernelGGL((cache_batch_sampled_kernel<PIECES, U, TAIL>), dim3((unsigned)a.g2), dim3(256), 0, st, a);
+// The row shapes the update kernels are compiled for: row_bytes = PIECES pieces of U (16 / 8 bytes, at most 16 of them) and a
+// TAIL of 8 / 4 / 2 bytes; every other row size takes the generic PIECES = 0 form.  f gets the shape as a tag.
+template <int P, typename U_, typename TAIL_ = evs::NoTail>
+struct RowShape { static constexpr int PIECES = P; using U = U_; using TAIL = TAIL_; };
+template <typename F>
+static void with_row_shape(int row_bytes, F &&f) {
+    switch (row_bytes) {
+    case 144: f(RowShape<9, float4>{}); break;     // d = 36 fp32
+    case 256: f(RowShape<16, float4>{}); break;    // d = 64 fp32
+    case 128: f(RowShape<8, float4>{}); break;     // d = 32 fp32, d = 64 u16
+    case 64: f(RowShape<4, float4>{}); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
+    case 32: f(RowShape<2, float4>{}); break;
+    case 16: f(RowShape<1, float4>{}); break;
+    case 72: f(RowShape<4, float4, uint2>{}); break;            // d = 36 u16: 4 x 16 + 8
+    case 36: f(RowShape<2, float4, unsigned>{}); break;         // d = 36 u8: 2 x 16 + 4
+    case 18: f(RowShape<1, float4, unsigned short>{}); break;   // d = 36 u4: 16 + 2
+    case 8: f(RowShape<1, uint2>{}); break;
+    default: f(RowShape<0, float4>{}); break;
+    }
 }
+// the sampled update
 static void launch_sampled_update(const evs::BatchArgs &a, hipStream_t st) {
-    switch (a.row_bytes) {
-    case 144: launch_sampled_update_t<9, float4>(a, st); break;     // d = 36 fp32
-    case 256: launch_sampled_update_t<16, float4>(a, st); break;    // d = 64 fp32
-    case 128: launch_sampled_update_t<8, float4>(a, st); break;     // d = 32 fp32, d = 64 u16
-    case 64: launch_sampled_update_t<4, float4>(a, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
-    case 32: launch_sampled_update_t<2, float4>(a, st); break;
-    case 16: launch_sampled_update_t<1, float4>(a, st); break;
-    case 72: launch_sampled_update_t<4, float4, uint2>(a, st); break;            // d = 36 u16: 4 x 16 + 8
-    case 36: launch_sampled_update_t<2, float4, unsigned>(a, st); break;         // d = 36 u8: 2 x 16 + 4
-    case 18: launch_sampled_update_t<1, float4, unsigned short>(a, st); break;   // d = 36 u4: 16 + 2
-    case 8: launch_sampled_update_t<1, uint2>(a, st); break;
-    default: launch_sampled_update_t<0, float4>(a, st); break;
-    }
+    using namespace evs;
+    with_row_shape(a.row_bytes, [&](auto s) {
+        using S = decltype(s);
+        // K1 listed the misses: one wave per list (two when the lists are those of the folded probe's 16-sample blocks: twice as long)
+        if (a.miss_rec) hipLaunchKernelGGL((cache_batch_sampled_list_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a);
+        else hipLaunchKernelGGL((cache_batch_sampled_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g2), dim3(256), 0, st, a);
+    });
 }
-
-// the set-associative policy's update (always the list form), compiled per row size like the sampled one
-template <int PIECES, typename U, typename TAIL = evs::NoTail>
-static void launch_sa_update_t(const evs::BatchArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL((evs::cache_batch_sa_list_kernel<PIECES, U, TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a);
-}
+// the set-associative policy's update (always the list form)
 static void launch_sa_update(const evs::BatchArgs &a, hipStream_t st) {
-    switch (a.row_bytes) {
-    case 144: launch_sa_update_t<9, float4>(a, st); break;
-    case 256: launch_sa_update_t<16, float4>(a, st); break;
-    case 128: launch_sa_update_t<8, float4>(a, st); break;
-    case 64: launch_sa_update_t<4, float4>(a, st); break;
-    case 32: launch_sa_update_t<2, float4>(a, st); break;
-    case 16: launch_sa_update_t<1, float4>(a, st); break;
-    case 72: launch_sa_update_t<4, float4, uint2>(a, st); break;
-    case 36: launch_sa_update_t<2, float4, unsigned>(a, st); break;
-    case 18: launch_sa_update_t<1, float4, unsigned short>(a, st); break;
-    case 8: launch_sa_update_t<1, uint2>(a, st); break;
-    default: launch_sa_update_t<0, float4>(a, st); break;
-    }
+    with_row_shape(a.row_bytes, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((evs::cache_batch_sa_list_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a);
+    });
 }
 
 // ... and of a set-associative pair
 static bool launch_sa_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs &a2, hipStream_t st) {
     using namespace evs;
-    static const bool on = !(evs::env_switch("EVS_CACHE_PAIR") && evs::env_switch("EVS_CACHE_PAIR")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_CACHE_PAIR");
     if (!on || a1.g1 != a2.g1 || sampled_list_threads(a1) != sampled_list_threads(a2)) return false;
     const dim3 grid((unsigned)(2 * a1.g1)), block(sampled_list_threads(a1));
     if (a1.row_bytes == 36 && a2.row_bytes == 18)
@@ -4685,7 +4671,7 @@ static bool launch_sa_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs
 // both tiers' list updates as one launch (the pairs of row sizes a u8 C1 + u4 C2 make); false: no merged kernel for the pair
 static bool launch_sampled_update_pair(const evs::BatchArgs &a1, const evs::BatchArgs &a2, hipStream_t st) {
     using namespace evs;
-    static const bool on = !(evs::env_switch("EVS_CACHE_PAIR") && evs::env_switch("EVS_CACHE_PAIR")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_CACHE_PAIR");
     if (!on || !a1.miss_rec || !a2.miss_rec || a1.g1 != a2.g1 || sampled_list_threads(a1) != sampled_list_threads(a2)) return false;
     const dim3 grid((unsigned)(2 * a1.g1)), block(sampled_list_threads(a1));
     if (a1.row_bytes == 36 && a2.row_bytes == 18)
@@ -4762,10 +4748,61 @@ static void sampled_flush_if_wanted(evs_cache *c, hipStream_t st) {
     hipLaunchKernelGGL(cache_batch_sampled_flush_finish_kernel, dim3(1), dim3(1), 0, st, c->bs, c->host.n_tables);
 }
 
+// ---- the envelope of a set-associative tier alone ----------------------------------------------------------------------------
+// A check that refuses leaves the cache as it was: a batch policy that was only resolved (none was given -- other tables may
+// resolve differently) is forgotten again.  The guard remembers what one cache, or both tiers of a pair, were given and puts it
+// back when it goes out of scope, unless keep() has said that the call goes on.
+struct GivenPolicy {
+    evs_cache *const c1, *const c2;
+    const int given1, given2;
+    bool kept = false;
+    explicit GivenPolicy(evs_cache *a, evs_cache *b = nullptr) : c1(a), c2(b), given1(a->batch_policy), given2(b ? b->batch_policy : -1) {}
+    GivenPolicy(const GivenPolicy &) = delete;
+    GivenPolicy &operator=(const GivenPolicy &) = delete;
+    ~GivenPolicy() {
+        if (kept) return;
+        c1->batch_policy = given1;
+        if (c2) c2->batch_policy = given2;
+    }
+    void keep() { kept = true; }
+};
+// What the fetch-first order, the approximate mode and the EvLFU bag form ask about a cache (each words its own refusals): the
+// batch policy, resolved here where none was given (behind a GivenPolicy); whether its sets are the 8-way sets of a tier alone;
+// whether a way has two arena rows; whether it is a tier of a C1 + C2 (+ C3) lookup.  A cache without set records yet: what
+// batch_state will give it (LRU / LFU: always 8 ways; no feasible geometry: batch_state says why).
+struct AloneFacts { int policy; bool alone8, dual, of_pair; };
+static AloneFacts tier_alone_facts(evs_cache *c) {
+    using namespace evs;
+    AloneFacts f;
+    f.of_pair = c->tsrv || (c->sa.tags && c->sa.line_words == 32u);
+    f.policy = resolved_batch_policy(c);
+    f.alone8 = true; f.dual = true;
+    if (c->sa.tags) { f.alone8 = c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u; f.dual = c->sa.dual != 0u; }
+    else if (c->host.policy == kEvLFU) {
+        SaUniverse u; SaGeom g;
+        f.alone8 = sa_single_ways() == 8u;
+        if (sa_single_feasible(c, &u, &g)) f.dual = g.dual != 0u;
+    }
+    return f;
+}
+// a block of device counters (zeroed on st) at its first use; `what` names it in the refusal
+static int ensure_counters(unsigned long long **slot, size_t bytes, hipStream_t st, const char *who, const char *what) {
+    if (*slot) return EVS_OK;
+    unsigned long long *p = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        evs::set_error("%s: allocating the %s counters failed", who, what);
+        return EVS_ENOMEM;
+    }
+    *slot = p;
+    return EVS_OK;
+}
+
 // ---- fetch-first order (evs_cache_set_miss_order(c, 1); the contract: include/evstore_hip.h) --------------------------------
 // What such a cache is held to, checked at every batched call behind batch_check and before anything is allocated: a tier alone,
 // batch policy 2 (given or resolved), sets of 8 ways, EvLFU over the two-copy arena (its bag calls: count first,
-// evs_cache_set_bag_count), tables in HBM or in host memory the device addresses.  A policy that was only resolved here is forgotten again on a refusal.  On success an inline setting that was never
+// evs_cache_set_bag_count), tables in HBM or in host memory the device addresses.  On success an inline setting that was never
 // given is 0 from here on.
 static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
     using namespace evs;
@@ -4776,55 +4813,26 @@ static int fetch_first_check(evs_cache *c, const char *who, bool bags) {
                   "staged tables need the reader pool and the plan policy)", who, pn);
         return EVS_ESTATE;
     }
-    EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; fetch-first is a tier alone's", who, pn);
-    const int given = c->batch_policy;
-    const int bp = resolved_batch_policy(c);
-    if (bp != 2) {
-        c->batch_policy = given;
-        set_error("%s: fetch-first is the set-associative tier's order (batch policy 2); this %s cache's batch policy is %s", who, pn, bp == 0 ? "plan" : "sampled");
-        return EVS_EINVAL;
-    }
-    bool alone8 = true, dual = true;
-    if (c->sa.tags) { alone8 = c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u; dual = c->sa.dual != 0u; }
-    else if (evlfu) {
-        SaUniverse u; SaGeom g;
-        alone8 = sa_single_ways() == 8u;
-        if (sa_single_feasible(c, &u, &g)) dual = g.dual != 0u;   // (not feasible: batch_state says why)
-    }
-    if (!alone8) {
-        c->batch_policy = given;
-        set_error("%s: a fetch-first %s cache needs sets of 8 ways (EVS_SA_WAYS=16: the re-point kernel searches 8-way sets)", who, pn);
-        return EVS_EINVAL;
-    }
-    if (evlfu && !dual) {
-        c->batch_policy = given;
-        set_error("%s: a fetch-first %s cache needs the two-copy arena (EVS_SA_DUAL=0, or tags wider than 21 bits, leave one row per way): a way the batch "
-                  "hits can be the same batch's victim, and the consumers read behind the update", who, pn);
-        return EVS_EINVAL;
-    }
-    if (evlfu && bags && c->bag_count != 1) {   // ("count first", evs_cache_set_bag_count: the counts come from a pass over the flags in front of the update)
-        c->batch_policy = given;
-        set_error("%s: an %s cache has no fetch-first bag form: a sample's count exists only after the pooling walk, so the update cannot run in front of it", who, pn);
-        return EVS_EINVAL;
-    }
+    GivenPolicy given(c);
+    const AloneFacts f = tier_alone_facts(c);
+    EVS_REQUIRE(!f.of_pair, "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; fetch-first is a tier alone's", who, pn);
+    EVS_REQUIRE(f.policy == 2, "%s: fetch-first is the set-associative tier's order (batch policy 2); this %s cache's batch policy is %s", who, pn,
+                f.policy == 0 ? "plan" : "sampled");
+    EVS_REQUIRE(f.alone8, "%s: a fetch-first %s cache needs sets of 8 ways (EVS_SA_WAYS=16: the re-point kernel searches 8-way sets)", who, pn);
+    EVS_REQUIRE(!evlfu || f.dual, "%s: a fetch-first %s cache needs the two-copy arena (EVS_SA_DUAL=0, or tags wider than 21 bits, leave one row per way): a way the batch "
+                "hits can be the same batch's victim, and the consumers read behind the update", who, pn);
+    // ("count first", evs_cache_set_bag_count: the counts come from a pass over the flags in front of the update)
+    EVS_REQUIRE(!(evlfu && bags) || c->bag_count == 1, "%s: an %s cache has no fetch-first bag form: a sample's count exists only after the pooling walk, so the "
+                "update cannot run in front of it", who, pn);
     if (c->inline_mode < 0) c->inline_mode = 0;
+    given.keep();
     return EVS_OK;
 }
-// the counter block of the re-point kernels (zeroed on st), at the first fetch-first call: replica rows (evs_cache_policy.h:
-// kFetchReplicas x kFetchRowWords) of [0] re-pointed, [1] left in place, [2] the pair's hit positions whose way the update took (a
-// tier alone adds into row 0 and never writes [2]); evs_cache_fetch_stats sums the rows
+// the counter block of the re-point kernels, at the first fetch-first call: replica rows (evs_cache_policy.h: kFetchReplicas x
+// kFetchRowWords) of [0] re-pointed, [1] left in place, [2] the pair's hit positions whose way the update took (a tier alone adds
+// into row 0 and never writes [2]); evs_cache_fetch_stats sums the rows
 static int fetch_first_state(evs_cache *c, hipStream_t st, const char *who) {
-    if (c->fetch_cnt) return EVS_OK;
-    unsigned long long *p = nullptr;
-    constexpr size_t bytes = (size_t)evs::kFetchReplicas * evs::kFetchRowWords * sizeof(unsigned long long);
-    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
-        (void)hipGetLastError();
-        if (p) (void)hipFree(p);
-        evs::set_error("%s: allocating the fetch-first counters failed", who);
-        return EVS_ENOMEM;
-    }
-    c->fetch_cnt = p;
-    return EVS_OK;
+    return ensure_counters(&c->fetch_cnt, (size_t)evs::kFetchReplicas * evs::kFetchRowWords * sizeof(unsigned long long), st, who, "fetch-first");
 }
 static evs::RepointArgs repoint_args(evs_cache *c, const unsigned char *hit, long long *row_ptrs, long long B) {
     evs::RepointArgs ra{};
@@ -4838,7 +4846,7 @@ static evs::RepointArgs repoint_args(evs_cache *c, const unsigned char *hit, lon
 // ---- approximate-embedding mode (evs_cache_set_batch_approx(c, thres > 0); the contract: include/evstore_hip.h) -------------
 // What a (B, T) call with a threshold in force is held to, checked behind batch_check (and fetch_first_check) and before anything
 // is allocated: an EvLFU tier alone (the setter refuses the other policies), batch policy 2 given or resolved, sets of 8 ways,
-// tables the kernels read in place.  A policy that was only resolved here is forgotten again on a refusal.
+// tables the kernels read in place.
 static int batch_approx_check(evs_cache *c, const char *who) {
     using namespace evs;
     const char *pn = policy_name(c->host.policy);
@@ -4846,38 +4854,29 @@ static int batch_approx_check(evs_cache *c, const char *who) {
         set_error("%s: the approximate mode of an %s cache is the set-associative tier's, which reads its tables in place (no file-backed tables)", who, pn);
         return EVS_ESTATE;
     }
-    EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; the approximate mode "
+    GivenPolicy given(c);
+    const AloneFacts f = tier_alone_facts(c);
+    EVS_REQUIRE(!f.of_pair, "%s: this %s cache is a tier of a C1 + C2 (+ C3) lookup; the approximate mode "
                 "(evs_cache_set_batch_approx) is a tier alone's -- the pair has the alt-key tier for it", who, pn);
-    const int given = c->batch_policy;
-    const int bp = resolved_batch_policy(c);
-    if (bp != 2) {
-        c->batch_policy = given;
-        set_error("%s: the approximate mode (evs_cache_set_batch_approx) is the set-associative tier's (batch policy 2); this %s cache's batch policy is %s",
-                  who, pn, bp == 0 ? "plan" : "sampled");
-        return EVS_EINVAL;
-    }
-    const bool alone8 = c->sa.tags ? (c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u) : sa_single_ways() == 8u;
-    if (!alone8) {
-        c->batch_policy = given;
-        set_error("%s: the approximate mode of an %s cache needs sets of 8 ways (EVS_SA_WAYS=16: its probe is compiled for 8-way sets)", who, pn);
-        return EVS_EINVAL;
-    }
+    EVS_REQUIRE(f.policy == 2, "%s: the approximate mode (evs_cache_set_batch_approx) is the set-associative tier's (batch policy 2); this %s cache's batch policy is %s",
+                who, pn, f.policy == 0 ? "plan" : "sampled");
+    EVS_REQUIRE(f.alone8, "%s: the approximate mode of an %s cache needs sets of 8 ways (EVS_SA_WAYS=16: its probe is compiled for 8-way sets)", who, pn);
+    given.keep();
     return EVS_OK;
 }
-// the counter block of the approximating probe (zeroed on st), at the first call with a threshold in force
-static int batch_approx_state(evs_cache *c, hipStream_t st, const char *who) {
-    if (c->approx_cnt) return EVS_OK;
-    unsigned long long *p = nullptr;
-    const size_t bytes = (size_t)evs::kReplicas * evs::kApproxCntStride * sizeof(unsigned long long);
-    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
-        (void)hipGetLastError();
-        if (p) (void)hipFree(p);
-        evs::set_error("%s: allocating the approximate-mode counters failed", who);
-        return EVS_ENOMEM;
-    }
-    c->approx_cnt = p;
+
+// ---- what every batched chain does to a tier's host-side state ----
+// a tier's next batch stamp: never 0, distinct for consecutive batches
+static int next_batch_stamp(evs_cache *c) { return (int)(++c->stamp_counter % 0x7ffffffe) + 1; }
+// the hit stamps of a chain that updates in front of its consumers over hashed entries (BatchArgs::estamp), zeroed on st at first use
+static int ensure_estamp(evs_cache *c, hipStream_t st) {
+    if (c->estamp) return EVS_OK;
+    EVS_HIP_CHECK(hipMalloc(&c->estamp, (long long)c->host.cap * 4));
+    EVS_HIP_CHECK(hipMemsetAsync(c->estamp, 0, (long long)c->host.cap * 4, st));
     return EVS_OK;
 }
+// one more batch of B requests whose counters the close has not folded yet
+static void count_batch(evs_cache *c, int64_t B) { c->pending_batches++; c->pending_requests += B; }
 
 static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float *out, uint8_t *hit, const float *x,
                             int64_t x_stride, int itself, float *R, void *stream) {
@@ -4910,12 +4909,9 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     // row crosses the bus once (K5's de-duplicated fetch).  Miss tier in HBM: consumers first, as measured best.
     const bool host_tier = c->host_backing;
     if (host_tier && !ff) {
-        if (!c->estamp) {
-            EVS_HIP_CHECK(hipMalloc(&c->estamp, cap * 4));
-            EVS_HIP_CHECK(hipMemsetAsync(c->estamp, 0, cap * 4, st));
-        }
+        { const int rc = ensure_estamp(c, st); if (rc) return rc; }
         a.estamp = c->estamp; a.stamp_hits = 1;
-        a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;   // never 0, distinct for consecutive batches
+        a.stamp = next_batch_stamp(c);
     }
     auto consumers = [&]() -> int {
         if (out) {
@@ -4973,10 +4969,27 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             ra.requests = rows; ra.n_pos = B * T;
             c->fetch_calls++;
         }
-        if (apx) {
-            { const int rc = batch_approx_state(c, st, "evs_cache_lookup_batch"); if (rc) return rc; }
+        if (apx) {   // the counter block of the approximating probe, at the first call with a threshold in force
+            { const int rc = ensure_counters(&c->approx_cnt, (size_t)kReplicas * kApproxCntStride * sizeof(unsigned long long), st,
+                                             "evs_cache_lookup_batch", "approximate-mode"); if (rc) return rc; }
             if (!(c->host.codec == 32 ? zero_page() : zero_code_page(c->host.codec))) return EVS_ENOMEM;
         }
+        // The legs below differ in their probe and their update; the order around the consumers is the tier's -- fetch first:
+        // update -> re-point -> consumers; else consumers -> update -- and so is the tail: the batch is counted, its counters
+        // folded every kCloseEvery-th batch.  (A consumer that refuses ends the call there: the batch is not counted.)
+        auto chain = [&](auto &&update) -> int {
+            if (ff) { update(); sa_repoint_launch(ra, a.g1, st); }
+            { const int rc = consumers(); if (rc) return rc; }
+            if (!ff) update();
+            return EVS_OK;
+        };
+        auto done = [&]() -> int {
+            count_batch(c, B);
+            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+            EVS_HIP_CHECK(hipGetLastError());
+            return EVS_OK;
+        };
+        const auto sa_update = [&] { launch_sa_update(a, st); };
         if (c->host.policy != kEvLFU) {
             // LRU / LFU (evs_cache_policy.hip): probe + touch -> consumers -> insert, always as launches of their own; batch
             // number n = 1, 2, ... rides in the way words modulo 2^S
@@ -4993,20 +5006,11 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
             a.list_cap = pa.list_cap;
             policy_probe_launch(pa, a.g1, st);
-            if (ff) {   // a way hit in this batch is touched, so never this batch's victim: its arena row is intact behind the insert
-                policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
-                sa_repoint_launch(ra, a.g1, st);
-                const int rc = consumers(); if (rc) return rc;
-            } else {
-                const int rc = consumers(); if (rc) return rc;
-                policy_insert_launch(pa, a.g1, sampled_list_threads(a), st);
-            }
-            c->pending_batches++; c->pending_requests += B;
-            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-            EVS_HIP_CHECK(hipGetLastError());
-            return EVS_OK;
+            // (fetch first: a way hit in this batch is touched, so never this batch's victim: its arena row is intact behind the insert)
+            { const int rc = chain([&] { policy_insert_launch(pa, a.g1, sampled_list_threads(a), st); }); if (rc) return rc; }
+            return done();
         }
-        a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;
+        a.stamp = next_batch_stamp(c);
         sampled_flush_if_wanted(c, st);
         a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
         a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
@@ -5022,30 +5026,20 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             ap.zero_row = reinterpret_cast<const unsigned char *>(c->host.codec == 32 ? zero_page() : zero_code_page(c->host.codec));
             hipLaunchKernelGGL(cache_batch_probe_approx_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a, ap);
             c->approx_calls++;
-            if (ff) {
-                launch_sa_update(a, st);
-                sa_repoint_launch(ra, a.g1, st);
-                const int rc = consumers(); if (rc) return rc;
-            } else {
-                const int rc = consumers(); if (rc) return rc;
-                launch_sa_update(a, st);
-            }
-            c->pending_batches++; c->pending_requests += B;
-            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-            EVS_HIP_CHECK(hipGetLastError());
-            return EVS_OK;
+            { const int rc = chain(sa_update); if (rc) return rc; }
+            return done();
         }
-        static const bool fold_on = !(evs::env_switch("EVS_CACHE_FOLD") && evs::env_switch("EVS_CACHE_FOLD")[0] == '0');
+        static const bool fold_on = evs::env_switch_on("EVS_CACHE_FOLD");
         bool small_tabs = true;   // (tile entries carry a row id in 30 bits)
         for (int k = 0; k < T; k++) small_tabs = small_tabs && c->backing_rows[k] < (1ll << 30);
         // a reduced-precision tier (the reference's one-layer 16 / 8 / 4-bit builds): the probe folded into ITS consumer too
-        static const bool foldq_on = !(evs::env_switch("EVS_CACHE_FOLDQ") && evs::env_switch("EVS_CACHE_FOLDQ")[0] == '0');
+        static const bool foldq_on = evs::env_switch_on("EVS_CACHE_FOLDQ");
         const bool foldq = !ff && fold_on && foldq_on && c->host.codec != 32 && R && !out && c->sa.ways == 8 && c->sa.sub_shift == 0 && small_tabs &&
                            (cap << c->sa.dual) < (1ll << 30) && fused_probe_codec_supported(B, T, c->host.dim, c->host.codec);
         const bool fold = (!ff && fold_on && a.row_ids && R && !out && c->sa.ways == 8 && (cap << c->sa.dual) < (1ll << 30)) || foldq;   // (the folded probes are compiled for 8-way sets; tile entries carry an arena row in 30 bits)
         // the update inside the probe launch too: fp32 rows, the folded fp32 launch, a two-copy arena (EVS_CACHE_INLINE=0: every
         // batch updated by a launch of its own behind it -- the round-4 chain, strict snapshot flags)
-        if (c->inline_mode < 0) c->inline_mode = (evs::env_switch("EVS_CACHE_INLINE") && evs::env_switch("EVS_CACHE_INLINE")[0] == '0') ? 0 : 1;
+        if (c->inline_mode < 0) c->inline_mode = evs::env_switch_on("EVS_CACHE_INLINE") ? 1 : 0;
         // (a reduced-precision tier takes the same form in its own consumer: evs_fused_rfq.hip, PROBE)
         // (a way stamped by the RUNNING batch is hidden from this launch's probers; the stamp is the batch number modulo
         //  2^stamp_bits, so an entry last touched exactly k * 2^stamp_bits batches ago is hidden too -- a miss served from its
@@ -5070,67 +5064,29 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             const int rc = fused_probe_interact(B, T, c->host.dim, x, x_stride, pa, c->a.arena,
                                                 reinterpret_cast<const void *const *>(c->backing), c->backing_rows, itself, R, st, c->host.codec);
             if (rc) return rc;
-            if (inl) {   // nothing is left to do behind the launch
-                c->pending_batches++; c->pending_requests += B;
-                if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-                EVS_HIP_CHECK(hipGetLastError());
-                return EVS_OK;
-            }
-        } else if (ff) {
-            // (a hit way can be this batch's victim: the replacement writes the other copy of the two-copy arena and flips the
-            //  select bit, so the address the probe computed from the old word stays valid until the consumers have read it)
-            hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
-            launch_sa_update(a, st);
-            sa_repoint_launch(ra, a.g1, st);
-            const int rc = consumers(); if (rc) return rc;
-            c->pending_batches++; c->pending_requests += B;
-            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-            EVS_HIP_CHECK(hipGetLastError());
-            return EVS_OK;
-        } else {
-            hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
-            const int rc = consumers(); if (rc) return rc;
+            if (!inl) sa_update();   // (inline: nothing is left to do behind the launch)
+            return done();
         }
-        launch_sa_update(a, st);
-        c->pending_batches++; c->pending_requests += B;
-        if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-        EVS_HIP_CHECK(hipGetLastError());
-        return EVS_OK;
+        // (fetch first: a hit way can be this batch's victim: the replacement writes the other copy of the two-copy arena and flips
+        //  the select bit, so the address the probe computed from the old word stays valid until the consumers have read it)
+        hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
+        { const int rc = chain(sa_update); if (rc) return rc; }
+        return done();
     }
     if (resolved_batch_policy(c) == 1 && !file_mode) {
         // Sampled policy update: probe -> consumers -> ONE update kernel -> close.  (Host-memory miss tier: the update
         // first -- it fetches each missing row once -- then the re-pointed consumers.)
-        if (!host_tier) a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;   // (host tier: set above, with the hit stamps)
+        if (!host_tier) a.stamp = next_batch_stamp(c);   // (host tier: set above, with the hit stamps)
         a.tomb_parity = a.stamp & 1;
         sampled_flush_if_wanted(c, st);   // EvLFU flush the close of an earlier batch asked for: before this batch's probe
         if (!host_tier) {   // K1 lists the misses itself (the patch kernel of the host tier reads the per-position records)
             a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
             a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
         }
-        if (c->fork_mode < 0) {
-            const char *e = evs::env_switch("EVS_CACHE_FORK");
-            c->fork_mode = (e && e[0] == '1') ? 1 : 0;
-        }
-        // EVS_CACHE_FORK=1: the update runs on a side stream UNDER the consumer.  What makes that legal: with the hits of
-        // the batch stamped (K1) the update never takes an entry the consumer reads, and the consumer reads nothing
-        // else the update writes.
-        const bool fork = c->fork_mode == 1 && !host_tier && (R || out);
-        if (fork) {
-            if (!c->estamp) {
-                EVS_HIP_CHECK(hipMalloc(&c->estamp, cap * 4));
-                EVS_HIP_CHECK(hipMemsetAsync(c->estamp, 0, cap * 4, st));
-            }
-            a.estamp = c->estamp; a.stamp_hits = 1;
-            if (!c->side) {
-                EVS_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-                EVS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                EVS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-            }
-        }
         // the probe inside the consumer: one launch instead of two when the consumer is the rows-in-registers kernel
         // (EVS_CACHE_FOLD=0: the two-launch form)
-        static const bool fold_on = !(evs::env_switch("EVS_CACHE_FOLD") && evs::env_switch("EVS_CACHE_FOLD")[0] == '0');
-        const bool fold = fold_on && a.row_ids && a.miss_rec && !fork && R && !out;
+        static const bool fold_on = evs::env_switch_on("EVS_CACHE_FOLD");
+        const bool fold = fold_on && a.row_ids && a.miss_rec && R && !out;
         if (fold) {
             ProbeArgs pa;
             pa.slots = a.slots; pa.mask = a.mask; pa.reusable_tomb = a.tomb_parity ? kTomb : kTomb1;
@@ -5143,65 +5099,22 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             const int rc = fused_probe_interact(B, T, c->host.dim, x, x_stride, pa, c->a.arena,
                                                 reinterpret_cast<const void *const *>(c->backing), c->backing_rows, itself, R, st);
             if (rc) return rc;
-        } else
-        hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
-        hipStream_t su = st;
-        if (fold) {
-        } else if (fork) {
-            EVS_HIP_CHECK(hipEventRecord(c->ev_fork, st));
-            EVS_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-            su = c->side;
-        } else if (!host_tier) { const int rc = consumers(); if (rc) return rc; }
-        launch_sampled_update(a, su);
-        if (fork) {
-            EVS_HIP_CHECK(hipEventRecord(c->ev_join, c->side));
-            const int rc = consumers(); if (rc) return rc;
-            EVS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0));
+        } else {
+            hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
+            if (!host_tier) { const int rc = consumers(); if (rc) return rc; }
         }
+        launch_sampled_update(a, st);
         if (host_tier) {
             hipLaunchKernelGGL(cache_batch_patch_ptrs_kernel, dim3((unsigned)a.g2), dim3(256), 0, st, a);
             const int rc = consumers(); if (rc) return rc;
         }
-        c->pending_batches++; c->pending_requests += B;
+        count_batch(c, B);
         if (c->pending_batches >= kCloseEvery || a.rebuild) sampled_close_pending(c, a.rebuild, st);
         batch_housekeeping(c, a, st);
         EVS_HIP_CHECK(hipGetLastError());
         return EVS_OK;
     }
     hipLaunchKernelGGL(cache_batch_probe_gather_kernel, dim3((unsigned)a.g1), dim3(256), 0, st, a);
-    if (c->fork_mode < 0) {
-        const char *e = evs::env_switch("EVS_CACHE_FORK");
-        c->fork_mode = (e && e[0] == '1') ? 1 : 0;
-    }
-    // Fork / join inside the batch (EVS_CACHE_FORK=1, off by default): K2, K3 and K4 only touch the hash, the
-    // priorities and the free stack -- nothing the consumer reads (row addresses, arena and backing rows) -- so they
-    // can run on a side stream UNDER the consumer, K5 (which overwrites arena rows) joining behind both.  Same
-    // snapshot semantics, same results -- and slower on this stack: 148 us per batch against 125 (300 unseen batches,
-    // B = 16 384): both sides slow down when they overlap (consumer 22 -> 25 us, K2 27 -> 37) and the two
-    // cross-stream event waits cost more than the overlap returns.
-    const bool fork = c->fork_mode == 1 && !host_tier && !file_mode && (R || out);
-    if (fork) {
-        if (!c->side) {
-            EVS_HIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-            EVS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            EVS_HIP_CHECK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
-        EVS_HIP_CHECK(hipEventRecord(c->ev_fork, st));
-        EVS_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        batch_policy_a(c, a, c->side);
-        {
-            const int widef = kNumCu * 8;
-            long long ne = ((long long)a.cap + 255) / 256; if (ne > widef) ne = widef;
-            hipLaunchKernelGGL(cache_batch_evict_kernel, dim3((unsigned)ne), dim3(256), 0, c->side, a);
-        }
-        EVS_HIP_CHECK(hipEventRecord(c->ev_join, c->side));
-        const int rc = consumers(); if (rc) return rc;
-        EVS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0));
-        hipLaunchKernelGGL(cache_batch_assign_kernel, dim3((unsigned)a.g2), dim3(256), 0, st, a);
-        batch_close(c, a, st);
-        EVS_HIP_CHECK(hipGetLastError());
-        return EVS_OK;
-    }
     if (!host_tier) { const int rc = consumers(); if (rc) return rc; }
     if (file_mode) { const int rc = batch_stage_prepare(c, a, st); if (rc) return rc; }
     batch_policy_a(c, a, st);
@@ -5349,30 +5262,24 @@ static int pair_fetch_first_check(evs_cache *c1, evs_cache *c2, evs_aprx *c3, co
                   "staged tables need the reader pool and the plan policy)", who, pn);
         return EVS_ESTATE;
     }
-    const int given1 = c1->batch_policy, given2 = c2->batch_policy;
-    auto refuse = [&](int rc) { c1->batch_policy = given1; c2->batch_policy = given2; return rc; };
-    { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return refuse(rc); }
+    GivenPolicy given(c1, c2);
+    { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return rc; }
     const int p1 = resolved_batch_policy(c1), p2 = resolved_batch_policy(c2);
-    if (p1 != 2 || p2 != 2) {
-        set_error("%s: fetch-first is the set-associative pair's order (batch policy 2); the batch policy of these %s tiers is %s", who, pn,
-                  (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
-        return refuse(EVS_EINVAL);
-    }
+    EVS_REQUIRE(p1 == 2 && p2 == 2, "%s: fetch-first is the set-associative pair's order (batch policy 2); the batch policy of these %s tiers is %s", who, pn,
+                (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
     bool shared = c1->sa.tags && c1->sa.tags == c2->sa.tags && c1->sa.line_words == 32u && c2->sa.line_words == 32u;
     if (!shared && !c1->sa.tags && !c2->sa.tags && !c1->bs && !c2->bs) {   // (not started: what pair_start would give them)
         SaUniverse u; SaGeom g1, g2;
         shared = sa_pair_geometry(c1, c2, u, g1, g2);
     }
-    if (!shared) {
-        set_error("%s: a fetch-first %s pair needs the shared set record (two fresh tiers that start out together, at least 4 ways each; not "
-                  "EVS_SA_PAIR=0): the re-point kernel finds a position's tier in one line", who, pn);
-        return refuse(EVS_EINVAL);
-    }
+    EVS_REQUIRE(shared, "%s: a fetch-first %s pair needs the shared set record (two fresh tiers that start out together, at least 4 ways each; not "
+                "EVS_SA_PAIR=0): the re-point kernel finds a position's tier in one line", who, pn);
+    given.keep();
     return EVS_OK;
 }
 
 // What the (B, T) form and the bag form of the pair (cache_bags_c1c2_impl) share, so that calls of the two may alternate: the
-// route filter C1 holds, a tier's next batch stamp (never 0, distinct for consecutive batches), the batches the closes owe.
+// route filter C1 holds, the batches the closes owe (and next_batch_stamp of either tier).
 constexpr unsigned kRouteWords = 1u << 20;
 static int pair_route_filter(evs_cache *c1, hipStream_t st) {
     using namespace evs;
@@ -5381,11 +5288,7 @@ static int pair_route_filter(evs_cache *c1, hipStream_t st) {
     EVS_HIP_CHECK(hipMemsetAsync(c1->route_filter, 0, kRouteWords * 4, st));
     return EVS_OK;
 }
-static int pair_next_stamp(evs_cache *c) { return (int)(++c->stamp_counter % 0x7ffffffe) + 1; }
-static void pair_count_batch(evs_cache *c1, evs_cache *c2, int64_t B) {
-    c1->pending_batches++; c1->pending_requests += B;
-    c2->pending_batches++; c2->pending_requests += B;
-}
+static void pair_count_batch(evs_cache *c1, evs_cache *c2, int64_t B) { count_batch(c1, B); count_batch(c2, B); }
 
 static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B, const int32_t *rows, float *out, uint8_t *tier,
                            int high_agghit_threshold, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
@@ -5454,12 +5357,10 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         for (int k = 0; k < 2; k++) {
             evs_cache *c = k ? c2 : c1;
             BatchArgs &a = k ? a2 : a1;
-            if (!c->estamp) {
-                EVS_HIP_CHECK(hipMalloc(&c->estamp, (long long)c->host.cap * 4));
-                EVS_HIP_CHECK(hipMemsetAsync(c->estamp, 0, (long long)c->host.cap * 4, st));
-            }
+            rc = ensure_estamp(c, st);
+            if (rc) return rc;
             a.estamp = c->estamp; a.stamp_hits = 1;
-            a.stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;   // never 0, distinct for consecutive batches
+            a.stamp = next_batch_stamp(c);
         }
     }
     TwoTierArgs tt;
@@ -5495,17 +5396,17 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         set_error("evs_cache_lookup_batch_c1c2: the tiers were built over different key universes (table row counts differ); make both over the same tables");
         return EVS_ESTATE;
     }
-    static const bool route_on_env = !(evs::env_switch("EVS_CACHE_ROUTEFILTER") && evs::env_switch("EVS_CACHE_ROUTEFILTER")[0] == '0');
+    static const bool route_on_env = evs::env_switch_on("EVS_CACHE_ROUTEFILTER");
     const bool route_on = route_on_env || sa2;   // (the set-associative update has no cross-tier hash look-up to fall back on)
     if (sampled2 && route_on) { const int frc = pair_route_filter(c1, st); if (frc) return frc; }
     if (sampled2) {
         for (int k = 0; k < 2; k++) {
             evs_cache *c = k ? c2 : c1;
             BatchArgs &a = k ? a2 : a1;
-            if (!host2) a.stamp = pair_next_stamp(c);   // (host tiers: set above, with the hit stamps)
+            if (!host2) a.stamp = next_batch_stamp(c);   // (host tiers: set above, with the hit stamps)
             a.tomb_parity = sa2 ? -1 : (a.stamp & 1);
             sampled_flush_if_wanted(c, st);
-            static const bool c3_inline_on = !(evs::env_switch("EVS_CACHE_C3INLINE") && evs::env_switch("EVS_CACHE_C3INLINE")[0] == '0');
+            static const bool c3_inline_on = evs::env_switch_on("EVS_CACHE_C3INLINE");
             if (c3 && (c3_inline_on || sa2)) {   // the evicting thread inserts its victim into the alt-key set itself
                 a.c3_tags = c3->tags; a.c3_nset = c3->nset; a.c3_stat = c3->bstat;
             } else
@@ -5531,7 +5432,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         // the probe lists each tier's misses per block (as K1 does for one tier); with the alt-key tier attached a list
         // kernel block stages its victims in LDS: lists of at most kListVictMax records
         const long long lc = (B + 8 * (long long)a1.g1 - 1) / (8 * (long long)a1.g1) * 8 * T;
-        static const bool list_on = !(evs::env_switch("EVS_CACHE_LIST2") && evs::env_switch("EVS_CACHE_LIST2")[0] == '0');
+        static const bool list_on = evs::env_switch_on("EVS_CACHE_LIST2");
         if (sa2 || (list_on && !host2 && a1.g1 == a2.g1 && (!c3 || lc <= kListVictMax))) {   // (host tiers: the patch kernel reads the per-position records)
             a1.miss_rec = c1->miss_rec; a1.list_cnt = c1->list_cnt; a1.list_cap = (int)lc;
             a2.miss_rec = c2->miss_rec; a2.list_cnt = c2->list_cnt; a2.list_cap = (int)lc;
@@ -5543,7 +5444,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         tt.route_filter = c1->route_filter; tt.route_mask = kRouteWords - 1; tt.route_stamp = (unsigned)a1.stamp;
         a2.route_filter = c1->route_filter; a2.route_mask = kRouteWords - 1; a2.route_stamp = (unsigned)a1.stamp;
     }
-    static const bool fold2_on = !(evs::env_switch("EVS_CACHE_FOLD2") && evs::env_switch("EVS_CACHE_FOLD2")[0] == '0');
+    static const bool fold2_on = evs::env_switch_on("EVS_CACHE_FOLD2");
     const bool fold2 = fold2_on && sampled2 && !host2 && !ff2 && a1.miss_rec && R && !out && B <= 65536 && T <= 32 &&
                        (!sa2 || (c1->sa.ways == 8 && c2->sa.ways == 8 && (c1->host.cap << c1->sa.dual) < (1ll << 30) && (c2->host.cap << c2->sa.dual) < (1ll << 30))) &&   // (the folded probe is compiled for 8-way sets)
                        mixed84_supported(T, c1->host.dim, c1->host.codec, c2->host.codec);
@@ -5596,8 +5497,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         rc = consumers(true);
         if (rc) return rc;
         if (sampled2) {
-            c1->pending_batches++; c1->pending_requests += B;
-            c2->pending_batches++; c2->pending_requests += B;
+            pair_count_batch(c1, c2, B);
             volatile int *rep1 = reinterpret_cast<volatile int *>(c1->host_tomb);
             const bool c1_known_full = rep1 && rep1[3] == 1 && (long long)rep1[2] >= c1->last_flush_call && c1->last_flush_call < c1->batch_calls;
             if (!c1_known_full || c1->pending_batches >= kCloseEvery || c2->pending_batches >= kCloseEvery || a1.rebuild || a2.rebuild)
@@ -5650,7 +5550,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         // Once a close that ran after C1's last flush has reported it full -- nothing but a flush takes entries away -- the
         // counters are folded every kCloseEvery-th batch as in the single-tier path (5 us per batch become 0.6); while C1
         // fills, every batch.  (EVS_CACHE_LAZY2=0: every batch.)
-        static const bool lazy2_on = !(evs::env_switch("EVS_CACHE_LAZY2") && evs::env_switch("EVS_CACHE_LAZY2")[0] == '0');
+        static const bool lazy2_on = evs::env_switch_on("EVS_CACHE_LAZY2");
         volatile int *rep1 = reinterpret_cast<volatile int *>(c1->host_tomb);
         // (set-associative tiers: the routing reads the key's own set, not the entry count -- lazy from the first batch)
         const bool c1_known_full = sa2 || (lazy2_on && rep1 && rep1[3] == 1 && (long long)rep1[2] >= c1->last_flush_call && c1->last_flush_call < c1->batch_calls);
@@ -5704,26 +5604,29 @@ static evs::BatchArgs bag_update_args(evs_cache *c, int64_t B, int stamp, uint4 
     return u;
 }
 
-// ---- ragged bags through an LRU / LFU / EvLFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) ---------------
-// probe + touch over the flat position list -> pooling through the pointer table (-> the dense interaction) -> the insert
-// kernel of the (B, T) chain, unchanged, on one stream: the consumers read before the insert moves anything.
-// EvLFU ("served bags", evs_cache_set_bag_rule): probe without a touch -> pooling, which also counts every sample's served
-// bags -> (the dense interaction) -> raise + list -> the set-associative update of the (B, T) chain (cache_batch_sa_list_kernel).
-// "Count first" (evs_cache_set_bag_count(c, 1)): probe -> count -> pooling alone (-> interaction) -> raise + list -> update, and
-// in fetch-first order  probe -> count -> raise + list -> update -> sa_repoint -> pooling alone (-> interaction).
-static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
-                           float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, int itself,
-                           float *R, uint8_t *hit, void *stream, const char *who) {
+// ---- what the bag form of a tier alone and of the pair share in front of their chains -----------------------------------------
+// The argument checks, in one order for both forms, and what both then compute.  `tiers` stands where the form's own checks of
+// its cache(s) stand -- their wording differs -- and hands back the tables and the dim.  nothing: B = 0, the call is over.
+struct BagCall {
+    bool nothing = false, interact = false;
+    int T = 0, d = 0;
+    long long n_pos = 0;
+    long long grid = 0, iters = 0;   // the probe's grid: one lane per position, blocks of 256, looping past kProbeGridMax blocks
+};
+template <typename Tiers>
+static int bag_call_check(const char *who, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
+                          const float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, const float *R,
+                          Tiers &&tiers, BagCall &bc) {
     using namespace evs;
-    const bool interact = R != nullptr || x != nullptr;
+    const bool interact = bc.interact = R != nullptr || x != nullptr;
     EVS_REQUIRE(B >= 0, "%s: B = %lld", who, (long long)B);
-    if (B == 0) return EVS_OK;
+    if (B == 0) { bc.nothing = true; return EVS_OK; }
     EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
     EVS_REQUIRE(indices && offsets && nnz, "%s: NULL indices / offsets / nnz", who);
     EVS_REQUIRE(interact ? (x && R) : pooled != nullptr, "%s: NULL %s", who, interact ? "x / R" : "pooled");
     EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
-    EVS_REQUIRE(c, "%s: NULL cache", who);
-    const int T = c->host.n_tables, d = c->host.dim;
+    { const int rc = tiers(bc.T, bc.d); if (rc) return rc; }
+    const int T = bc.T, d = bc.d;
     EVS_REQUIRE(T <= 32, "%s: at most 32 tables", who);
     EVS_REQUIRE(B < (1ll << 31), "%s: B = %lld", who, (long long)B);
     long long n_pos = 0;
@@ -5738,6 +5641,65 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     if (interact)
         EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
                     who, EVS_MAX_FEATURES, T, d);
+    bc.n_pos = n_pos;
+    bc.grid = std::min<long long>((n_pos + 255) / 256, kProbeGridMax);
+    bc.iters = bc.grid ? (n_pos + 256 * bc.grid - 1) / (256 * bc.grid) : 0;
+    return EVS_OK;
+}
+// the miss-list records of calls of up to np positions: a call of n <= np positions lists grid * iters * 256 records -- n rounded
+// up to 256 while one pass does, else < n + 256 * kProbeGridMax
+static long long bag_list_records(long long np) {
+    return np <= 256ll * evs::kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * evs::kProbeGridMax;
+}
+// the (T, B, d) block the pooling fills for the dense interaction, held by c (C1 of a pair): the new block first, the old one
+// goes only when the new one exists
+static int bag_pool_grow(evs_cache *c, int T, int64_t B, int d, hipStream_t st, const char *who) {
+    if ((long long)T * B * d <= c->bag_pool_floats) return EVS_OK;
+    float *pool = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&pool), (size_t)T * B * d * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        evs::set_error("%s: allocating the (T, B, d) block of %lld samples failed", who, (long long)B);
+        return EVS_ENOMEM;
+    }
+    if (c->bag_pool) {
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        (void)hipFree(c->bag_pool);
+    }
+    c->bag_pool = pool; c->bag_pool_floats = (long long)T * B * d;
+    return EVS_OK;
+}
+// R = the dense interaction of x and the T pooled tables of that block
+static int bag_pool_interact(const float *pool, int T, int64_t B, int d, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
+    const float *feats[EVS_MAX_FEATURES];
+    int64_t strides[EVS_MAX_FEATURES];
+    feats[0] = x; strides[0] = x_stride;
+    for (int k = 0; k < T; k++) { feats[k + 1] = pool + (long long)k * B * d; strides[k + 1] = d; }
+    return evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+}
+
+// ---- ragged bags through an LRU / LFU / EvLFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) ---------------
+// probe + touch over the flat position list -> pooling through the pointer table (-> the dense interaction) -> the insert
+// kernel of the (B, T) chain, unchanged, on one stream: the consumers read before the insert moves anything.
+// EvLFU ("served bags", evs_cache_set_bag_rule): probe without a touch -> pooling, which also counts every sample's served
+// bags -> (the dense interaction) -> raise + list -> the set-associative update of the (B, T) chain (cache_batch_sa_list_kernel).
+// "Count first" (evs_cache_set_bag_count(c, 1)): probe -> count -> pooling alone (-> interaction) -> raise + list -> update, and
+// in fetch-first order  probe -> count -> raise + list -> update -> sa_repoint -> pooling alone (-> interaction).
+static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
+                           float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride, int itself,
+                           float *R, uint8_t *hit, void *stream, const char *who) {
+    using namespace evs;
+    BagCall bc;
+    {
+        const int rc = bag_call_check(who, B, indices, offsets, nnz, pooled, out_tstride, out_bstride, x, x_stride, R, [&](int &T, int &d) -> int {
+            EVS_REQUIRE(c, "%s: NULL cache", who);
+            T = c->host.n_tables; d = c->host.dim;
+            return EVS_OK;
+        }, bc);
+        if (rc || bc.nothing) return rc;
+    }
+    const bool interact = bc.interact;
+    const int T = bc.T, d = bc.d;
+    const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
     const bool evlfu = c->host.policy == kEvLFU;
     EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule says what a request's hit count is over bags "
                 "(its priority counts a request's hit keys); lru / lfu caches take ragged bags as they are", who, policy_name(c->host.policy));
@@ -5753,20 +5715,12 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
             set_error("%s: the bag form of an %s cache reads its tables in place from HBM (no host-memory / file-backed tables)", who, pn);
             return EVS_ESTATE;
         }
-        // (a refusal leaves the cache as it was: a policy that was only resolved here, not given, is forgotten again -- other
-        //  tables may resolve differently)
-        const int given = c->batch_policy;
-        const int bp = resolved_batch_policy(c);
-        const bool alone8 = c->sa.tags ? (c->sa.ways == 8u && c->sa.sub_shift == 0u && c->sa.line_words == 8u) : sa_single_ways() == 8u;
-        if (bp != 2 || !alone8) {
-            c->batch_policy = given;
-            if (bp != 2)
-                set_error("%s: the bag form of an %s cache is the set-associative tier's (batch policy 2); this cache's batch policy is %s", who, pn,
-                          bp == 0 ? "plan" : "sampled");
-            else
-                set_error("%s: the bag form of an %s cache needs a tier alone with sets of 8 ways", who, pn);
-            return EVS_EINVAL;
-        }
+        GivenPolicy given(c);
+        const AloneFacts f = tier_alone_facts(c);
+        EVS_REQUIRE(f.policy == 2, "%s: the bag form of an %s cache is the set-associative tier's (batch policy 2); this cache's batch policy is %s", who, pn,
+                    f.policy == 0 ? "plan" : "sampled");
+        EVS_REQUIRE(f.alone8, "%s: the bag form of an %s cache needs a tier alone with sets of 8 ways", who, pn);
+        given.keep();
     }
     const int piece_bytes = c->host.codec / 2;   // what a lane reads of a row at once: 16 / 8 / 4 / 2 bytes
     for (int k = 0; k < T; k++)
@@ -5777,17 +5731,13 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
 
-    // the probe's grid: one lane per position, blocks of 256, looping past kProbeGridMax blocks; a miss list per block
-    long long grid = (n_pos + 255) / 256; if (grid > kProbeGridMax) grid = kProbeGridMax;
-    const long long iters = grid ? (n_pos + 256 * grid - 1) / (256 * grid) : 0;
+    // (a miss list per block of the probe's grid)
     if (n_pos > c->bag_max_pos || B > c->bag_max_b) {   // grow: the new slab first, the old one goes only when the new one exists
         const long long np = std::max<long long>(n_pos, c->bag_max_pos), nb = std::max<long long>(B, c->bag_max_b);
         long long *ptrs = nullptr; unsigned char *flags = nullptr; uint4 *rec = nullptr; int *cnt = nullptr, *sample = nullptr;
         void *slab = nullptr;
         SlabPlan sp;
-        // (a call of n <= np positions lists grid * iters * 256 records: n rounded up to 256 while one pass does, else < n + 256 * kProbeGridMax)
-        const long long n_rec = np <= 256ll * kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * kProbeGridMax;
-        sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, n_rec * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
+        sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, bag_list_records(np) * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
         sp.add(&sample, nb * 4);
         uint4 *prov = nullptr; int *pos_sample = nullptr, *agg = nullptr;
         if (evlfu) { sp.add(&prov, np * 16); sp.add(&pos_sample, np * 4); sp.add(&agg, nb * 4); }
@@ -5802,19 +5752,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         c->bag_max_pos = np; c->bag_max_b = nb;
         EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
     }
-    if (interact && (long long)T * B * d > c->bag_pool_floats) {
-        float *pool = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&pool), (size_t)T * B * d * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("%s: allocating the (T, B, d) block of %lld samples failed", who, (long long)B);
-            return EVS_ENOMEM;
-        }
-        if (c->bag_pool) {
-            EVS_HIP_CHECK(hipStreamSynchronize(st));
-            (void)hipFree(c->bag_pool);
-        }
-        c->bag_pool = pool; c->bag_pool_floats = (long long)T * B * d;
-    }
+    if (interact) { const int rc = bag_pool_grow(c, T, B, d, st, who); if (rc) return rc; }
     c->used = 2;
     c->batch_calls++;
 
@@ -5824,7 +5762,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     pa.lay = PolLayout{}; pa.cur = 0u;
     int stamp = 0;
     if (evlfu) {   // the (B, T) chain's batch stamp, and the flush the close of an earlier batch asked for: before this batch's probe
-        stamp = (int)(++c->stamp_counter % 0x7ffffffe) + 1;
+        stamp = next_batch_stamp(c);
         sampled_flush_if_wanted(c, st);
     } else {
         pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
@@ -5852,19 +5790,24 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
 
     if (grid) bags_probe_launch(a, (int)grid, st);
     if (cf) bags_count_launch(a, st);   // every sample's count, the position -> sample map, column 39: nothing behind it judges a sample
+    auto update = [&] {
+        if (evlfu) {
+            // every sample's count is known: the hit ways go up, the misses are listed with their counts, and the (B, T) chain's
+            // update inserts them -- priorities read after all raises, the launches in stream order
+            bags_raise_list_launch(a, (int)grid, st);
+            const BatchArgs u = bag_update_args(c, B, stamp, c->bag_rec, c->bag_list_cnt, pa.list_cap, (int)grid);
+            launch_sa_update(u, st);
+        } else {
+            policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
+        }
+    };
     if (ff) {   // the update in front of the pooling, the installed misses re-pointed at the arena
         c->fetch_calls++;
         if (grid) {
-            if (evlfu) {
-                // (fetch_first_check: count first.)  The raises end before the update starts, and the update reads what it reads in
-                // order 0 -- the consumers write nothing of it.  A hit way that is this call's victim is replaced in the other copy
-                // of the two-copy arena, so the address the probe wrote names the old row until the pooling has read it.
-                bags_raise_list_launch(a, (int)grid, st);
-                const BatchArgs u = bag_update_args(c, B, stamp, c->bag_rec, c->bag_list_cnt, pa.list_cap, (int)grid);
-                launch_sa_update(u, st);
-            } else {
-                policy_insert_launch(pa, (int)grid, 128u, st);
-            }
+            // (EvLFU -- fetch_first_check: count first.)  The raises end before the update starts, and the update reads what it reads
+            // in order 0 -- the consumers write nothing of it.  A hit way that is this call's victim is replaced in the other copy
+            // of the two-copy arena, so the address the probe wrote names the old row until the pooling has read it.
+            update();
             RepointArgs ra = repoint_args(c, pa.hit, c->bag_ptrs, B);
             for (int k = 0; k < 32; k++) ra.indices[k] = a.indices[k];
             for (int k = 0; k < 33; k++) ra.pos0[k] = a.pos0[k];
@@ -5874,23 +5817,11 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     }
     bags_pool_launch(a, c->host.codec, st);
     if (interact) {
-        const float *feats[EVS_MAX_FEATURES];
-        int64_t strides[EVS_MAX_FEATURES];
-        feats[0] = x; strides[0] = x_stride;
-        for (int k = 0; k < T; k++) { feats[k + 1] = c->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
-        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+        const int rc = bag_pool_interact(c->bag_pool, T, B, d, x, x_stride, itself, R, stream);
         if (rc) return rc;   // (nothing is inserted: the touches stand, as after any launch failure behind the probe)
     }
-    if (grid && evlfu && !ff) {
-        // every sample's count is known: the hit ways go up, the misses are listed with their counts, and the (B, T) chain's
-        // update inserts them -- priorities read after all raises, the launches in stream order
-        bags_raise_list_launch(a, (int)grid, st);
-        const BatchArgs u = bag_update_args(c, B, stamp, c->bag_rec, c->bag_list_cnt, pa.list_cap, (int)grid);
-        launch_sa_update(u, st);
-    } else if (grid && !ff) {
-        policy_insert_launch(pa, (int)grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
-    }
-    c->pending_batches++; c->pending_requests += B;
+    if (grid && !ff) update();
+    count_batch(c, B);
     if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
     EVS_HIP_CHECK(hipGetLastError());
     return EVS_OK;
@@ -5928,32 +5859,20 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
                                 const int64_t *nnz, float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x, int64_t x_stride,
                                 int itself, float *R, uint8_t *tier, int threshold, void *stream, const char *who) {
     using namespace evs;
-    const bool interact = R != nullptr || x != nullptr;
-    // the argument checks of cache_bags_impl, in its order
-    EVS_REQUIRE(B >= 0, "%s: B = %lld", who, (long long)B);
-    if (B == 0) return EVS_OK;
-    EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
-    EVS_REQUIRE(indices && offsets && nnz, "%s: NULL indices / offsets / nnz", who);
-    EVS_REQUIRE(interact ? (x && R) : pooled != nullptr, "%s: NULL %s", who, interact ? "x / R" : "pooled");
-    EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
-    EVS_REQUIRE(c1 && c2, "%s: NULL cache (%s)", who, !c1 ? "C1" : "C2");
-    EVS_REQUIRE(c1 != c2, "%s: one cache given as both tiers", who);
-    EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
-    const int T = c1->host.n_tables, d = c1->host.dim;
-    EVS_REQUIRE(T <= 32, "%s: at most 32 tables", who);
-    EVS_REQUIRE(B < (1ll << 31), "%s: B = %lld", who, (long long)B);
-    long long n_pos = 0;
-    for (int k = 0; k < T; k++) {
-        EVS_REQUIRE(nnz[k] >= 0, "%s: nnz[%d] = %lld", who, k, (long long)nnz[k]);
-        EVS_REQUIRE(indices[k] || nnz[k] == 0, "%s: indices[%d] is NULL", who, k);
-        EVS_REQUIRE(offsets[k], "%s: offsets[%d] is NULL", who, k);
-        n_pos += nnz[k];
-        EVS_REQUIRE(n_pos < (1ll << 31), "%s: 2^31 lookups or more in one call", who);
+    BagCall bc;
+    {
+        const int rc = bag_call_check(who, B, indices, offsets, nnz, pooled, out_tstride, out_bstride, x, x_stride, R, [&](int &T, int &d) -> int {
+            EVS_REQUIRE(c1 && c2, "%s: NULL cache (%s)", who, !c1 ? "C1" : "C2");
+            EVS_REQUIRE(c1 != c2, "%s: one cache given as both tiers", who);
+            EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
+            T = c1->host.n_tables; d = c1->host.dim;
+            return EVS_OK;
+        }, bc);
+        if (rc || bc.nothing) return rc;
     }
-    EVS_REQUIRE(d % 4 == 0 && d <= 256, "%s: the pooling takes a dim that is a multiple of 4 up to 256, not %d", who, d);
-    if (interact)
-        EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
-                    who, EVS_MAX_FEATURES, T, d);
+    const bool interact = bc.interact;
+    const int T = bc.T, d = bc.d;
+    const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
     // the envelope: refused before anything is allocated, the pair left as it was
     // Both tiers at order 1 AND told "count first" (evs_cache_set_bag_count: the counts may be computed in front of everything, which
     // is what lets the update run before the pooling): the fetch-first bag chain, over tables in HBM or in device-addressable host
@@ -5992,7 +5911,6 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         const char *pairs = bag_pair_codecs_ok(c1->host.codec, c2->host.codec);
         EVS_REQUIRE(!pairs, "%s: no pooling for a %d-bit C1 over a %d-bit C2; the pairs of precisions are %s", who, c1->host.codec, c2->host.codec, pairs);
     }
-    const int given1 = c1->batch_policy, given2 = c2->batch_policy;
     // (the fetch-first pair's own envelope -- policy 2 given or resolved wherever the tables live, the shared record, no file-backed
     //  tables -- in the words of the (B, T) form; it forgets a policy it only resolved when it refuses)
     if (ff2) { const int rc = pair_fetch_first_check(c1, c2, nullptr, who); if (rc) return rc; }
@@ -6002,20 +5920,15 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
                     (c1->batch_policy == 0 || c1->batch_policy == 1 || c2->batch_policy == 0 || c2->batch_policy == 1)
                         ? "run the plan-based or the sampled update" : "did not start out as such a pair (records of their own)");
     } else {
-        auto refuse = [&](int rc) { c1->batch_policy = given1; c2->batch_policy = given2; return rc; };
-        { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return refuse(rc); }
+        GivenPolicy given(c1, c2);
+        { const int rc = pair_resolve_policy(c1, c2, who); if (rc) return rc; }
         const int p1 = resolved_batch_policy(c1), p2 = resolved_batch_policy(c2);
-        if (p1 != 2 || p2 != 2) {
-            set_error("%s: the bag form is the set-associative pair's (batch policy 2); the batch policy of these tiers is %s", who,
-                      (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
-            return refuse(EVS_EINVAL);
-        }
+        EVS_REQUIRE(p1 == 2 && p2 == 2, "%s: the bag form is the set-associative pair's (batch policy 2); the batch policy of these tiers is %s", who,
+                    (p1 != 2 ? p1 : p2) == 0 ? "plan" : "sampled");
         SaUniverse u; SaGeom g1, g2;
-        if (!sa_pair_geometry(c1, c2, u, g1, g2)) {
-            set_error("%s: capacities %lld + %lld give the pair no shared set record (a tier would get fewer than 4 ways, or EVS_SA_PAIR=0); the bag form "
-                      "needs it", who, (long long)c1->host.cap, (long long)c2->host.cap);
-            return refuse(EVS_EINVAL);
-        }
+        EVS_REQUIRE(sa_pair_geometry(c1, c2, u, g1, g2), "%s: capacities %lld + %lld give the pair no shared set record (a tier would get fewer than 4 ways, or "
+                    "EVS_SA_PAIR=0); the bag form needs it", who, (long long)c1->host.cap, (long long)c2->host.cap);
+        given.keep();
     }
     for (int k = 0; k < 2; k++) {
         const int piece_bytes = cs[k]->host.codec / 2;   // what a lane reads of a row at once: 16 / 8 / 4 / 2 bytes
@@ -6030,16 +5943,14 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
 
-    // one lane per position, blocks of 256, looping past kProbeGridMax blocks; a miss list per block and tier
-    long long grid = (n_pos + 255) / 256; if (grid > kProbeGridMax) grid = kProbeGridMax;
-    const long long iters = grid ? (n_pos + 256 * grid - 1) / (256 * grid) : 0;
+    // (a miss list per block of the probe's grid and tier)
     if (n_pos > c1->bag2_max_pos || B > c1->bag2_max_b) {   // grow: the new slab first, the old one goes only when the new one exists
         const long long np = std::max<long long>(n_pos, c1->bag2_max_pos), nb = std::max<long long>(B, c1->bag2_max_b);
         unsigned char *code = nullptr, *serve = nullptr; long long *ptrs = nullptr; uint4 *prov = nullptr, *rec1 = nullptr, *rec2 = nullptr;
         int *cnt1 = nullptr, *cnt2 = nullptr, *pos_sample = nullptr, *sample = nullptr, *agg = nullptr;
         void *slab = nullptr;
         SlabPlan sp;
-        const long long n_rec = np <= 256ll * kProbeGridMax ? (np + 255) / 256 * 256 : np + 256ll * kProbeGridMax;   // (as cache_bags_impl sizes its lists)
+        const long long n_rec = bag_list_records(np);
         sp.add(&code, np); sp.add(&serve, np); sp.add(&ptrs, np * 8); sp.add(&prov, np * 16); sp.add(&pos_sample, np * 4);
         sp.add(&rec1, n_rec * 16); sp.add(&rec2, n_rec * 16);
         sp.add(&cnt1, (long long)kProbeGridMax * 4); sp.add(&cnt2, (long long)kProbeGridMax * 4);
@@ -6056,19 +5967,7 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         c1->bag2_max_pos = np; c1->bag2_max_b = nb;
         EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
     }
-    if (interact && (long long)T * B * d > c1->bag_pool_floats) {
-        float *pool = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&pool), (size_t)T * B * d * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("%s: allocating the (T, B, d) block of %lld samples failed", who, (long long)B);
-            return EVS_ENOMEM;
-        }
-        if (c1->bag_pool) {
-            EVS_HIP_CHECK(hipStreamSynchronize(st));
-            (void)hipFree(c1->bag_pool);
-        }
-        c1->bag_pool = pool; c1->bag_pool_floats = (long long)T * B * d;
-    }
+    if (interact) { const int rc = bag_pool_grow(c1, T, B, d, st, who); if (rc) return rc; }
     { const int rc = pair_route_filter(c1, st); if (rc) return rc; }
     // batch n of both tiers: the (B, T) pair's stamps, and the flush the close of an earlier batch asked for, before the probe
     int stamp[2];
@@ -6076,7 +5975,7 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
         evs_cache *c = cs[k];
         c->used = 2;
         c->batch_calls++;
-        stamp[k] = pair_next_stamp(c);
+        stamp[k] = next_batch_stamp(c);
         sampled_flush_if_wanted(c, st);
     }
 
@@ -6134,11 +6033,7 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
     }
     if (!bags_pool2_launch(a, c1->host.codec, c2->host.codec, st)) { set_error("%s: no pooling kernel for the pair of precisions", who); return EVS_EINVAL; }
     if (interact) {
-        const float *feats[EVS_MAX_FEATURES];
-        int64_t strides[EVS_MAX_FEATURES];
-        feats[0] = x; strides[0] = x_stride;
-        for (int k = 0; k < T; k++) { feats[k + 1] = c1->bag_pool + (long long)k * B * d; strides[k + 1] = d; }
-        const int rc = evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
+        const int rc = bag_pool_interact(c1->bag_pool, T, B, d, x, x_stride, itself, R, stream);
         if (rc) {   // order 0: nothing is inserted and the raises stand (order 1: the batch is already inserted); the batch is counted, so the close folds its hits with its requests
             pair_count_batch(c1, c2, B);
             return rc;

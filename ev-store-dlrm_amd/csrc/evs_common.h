@@ -17,6 +17,8 @@ void set_error(const char *fmt, ...);
 // the library's one way to read an EVS_* switch from the environment (evs_api.hip): the first read of a name is recorded with whether it was set, for
 // evs_env_switches_seen().  Every read in csrc/ goes through here; the callers cache the answer in a static as before.
 const char *env_switch(const char *name);
+// a switch that is on unless its value starts with '0'
+inline bool env_switch_on(const char *name) { const char *e = env_switch(name); return !(e && e[0] == '0'); }
 // a numeric switch outside [lo, hi] falls back to its default, with one warning line on stderr
 long long env_switch_range(const char *name, long long dflt, long long lo, long long hi);
 

@@ -1257,7 +1257,7 @@ static void launch_nt(const FusedArgs &a, hipStream_t st) {
                 // every feature is dense -- the rows-in-registers kernel takes dense features as rows addressed by the sample
                 // number (it does so for x and for the sharded step's received vectors), with no index round trip at all.
                 // Needs 16-byte aligned rows (EVS_INTERACT_RF=0: the LDS-DMA loop).
-                static const bool dense_rf = !(evs::env_switch("EVS_INTERACT_RF") && evs::env_switch("EVS_INTERACT_RF")[0] == '0');
+                static const bool dense_rf = evs::env_switch_on("EVS_INTERACT_RF");
                 bool ok = dense_rf && tile_eligible(a, CODEC);
                 for (int f = 0; f < a.F && ok; f++)
                     ok = (reinterpret_cast<uintptr_t>(a.src[f]) & 15) == 0 && ((a.stride[f] * 4) & 15) == 0;
@@ -1490,7 +1490,7 @@ extern "C" int evs_emb_interact_dot(int64_t B, int F, int d, int codec, const ev
     // the rows-in-registers kernel then computes every feature's index / offsets address itself and asks for them before it
     // reads its feature table out of the kernel arguments (FusedArgs::stk)
     a.stk = 0;
-    static const bool stk_on = !(evs::env_switch("EVS_FUSED_STK") && evs::env_switch("EVS_FUSED_STK")[0] == '0');   // developer A/B
+    static const bool stk_on = evs::env_switch_on("EVS_FUSED_STK");   // developer A/B
     if (stk_on && indirect && !weighted && codec == 32 && F >= 2 && !feats[0].indices && (a.bag1 == 1 || a.bag1 == 3)) {
         bool yes = feats[1].indices != nullptr;
         const int64_t si = F > 2 && feats[2].indices ? feats[2].indices - feats[1].indices : 0;
@@ -1568,7 +1568,7 @@ extern "C" int evs_emb_interact_dot_stacked_multi(int K, int64_t B, int T, int d
     for (int k = 0; k < K; k++)
         EVS_REQUIRE(x[k] && indices_base[k] && R[k] && (!offsets_base || offsets_base[k]), "evs_emb_interact_dot_stacked_multi: batch %d has a NULL pointer", k);
     const int F = T + 1;
-    static const bool one_launch = !(evs::env_switch("EVS_FUSED_MULTI") && evs::env_switch("EVS_FUSED_MULTI")[0] == '0');
+    static const bool one_launch = evs::env_switch_on("EVS_FUSED_MULTI");
     // the one-launch form: fp32 tables, whole batches (nnz == B: what makes lS_o checkable per block), aligned operands
     bool fast = one_launch && K > 1 && codec == 32 && T >= 1 && nnz_per_table == B && B < (1ll << 31) && rf_multi_supported(B, F, d) &&
                 x_stride % 4 == 0 && x_stride >= 0 && x_stride < (1ll << 31) && optimistic_enabled();

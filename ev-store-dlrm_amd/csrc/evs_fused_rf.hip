@@ -159,7 +159,7 @@ bool launch_rf_probe(const FusedArgs &a, hipStream_t st) {
 // per sample, 135 VGPRs (three blocks per CU).  Same box, B = 16 384: one index per bag declared 30.4 -> 25.6 us (0.59 -> 0.70 of
 // peak), lS_o given 33.2 -> 27.5 us; B = 65 536: 91.5 -> 89.5 us.
 static bool rf_d64() {
-    static const bool on = !(evs::env_switch("EVS_FUSED_RF_D64") && evs::env_switch("EVS_FUSED_RF_D64")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_FUSED_RF_D64");
     return on;
 }
 
@@ -170,7 +170,7 @@ static bool rf_lean_shape(const FusedArgs &a) {
 }
 
 bool launch_rf_check(const FusedArgs &a, hipStream_t st) {
-    static const bool on = !(evs::env_switch("EVS_FUSED_RF_CHECK") && evs::env_switch("EVS_FUSED_RF_CHECK")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_FUSED_RF_CHECK");
     if (!on || !rf_mode() || a.F > kTileMaxF || a.bag1 != 3 || a.B > rf_max_batch()) return false;
     if (rf_lean_shape(a) && launch_rf_lean(a, rf_tile_per(), st)) return true;   // the stacked call: scalar arguments + model descriptor
     const bool nt2 = a.F > 16;

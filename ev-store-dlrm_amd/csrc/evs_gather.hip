@@ -670,7 +670,7 @@ __global__ void __launch_bounds__(256) bag_sum_flat_kernel(const GatherArgs args
 }
 
 static bool launch_bag_sum_flat(const GatherArgs &a, bool vec_ok, hipStream_t stream) {
-    static const bool on = !(evs::env_switch("EVS_GATHER_FLAT") && evs::env_switch("EVS_GATHER_FLAT")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_GATHER_FLAT");
     if (!on || !vec_ok || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64)) return false;
     int64_t nnz = 0;
     for (int k = 0; k < a.T; k++) { if (a.row_w[k] || !a.offsets[k]) return false; nnz += a.nnz[k]; }
@@ -780,7 +780,7 @@ __global__ void __launch_bounds__(256) bag_sum_long_kernel(const GatherArgs args
 }
 
 static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t stream) {
-    static const bool on = !(evs::env_switch("EVS_GATHER_LONG") && evs::env_switch("EVS_GATHER_LONG")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_GATHER_LONG");
     if (!on || !vec_ok || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64 || a.d == 128) || !zero_page()) return false;
     int64_t nnz = 0;
     for (int k = 0; k < a.T; k++) {
@@ -810,7 +810,7 @@ static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t st
 // is there a rows-in-registers gather for the launch, and launch it
 template <int CODEC>
 static bool launch_gather_rows(const GatherArgs &a, bool vec_ok, hipStream_t stream, bool bag1) {
-    static const bool on = !(evs::env_switch("EVS_GATHER_RF") && evs::env_switch("EVS_GATHER_RF")[0] == '0');
+    static const bool on = evs::env_switch_on("EVS_GATHER_RF");
     const void *zp = CODEC == 32 ? zero_page() : zero_code_page(CODEC);
     if (!on || !vec_ok || a.T > 32 || !(a.d == 16 || a.d == 32 || a.d == 36 || a.d == 64) || !zp) return false;
     for (int k = 0; k < a.T; k++) {

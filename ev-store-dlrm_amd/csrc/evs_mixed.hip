@@ -745,7 +745,7 @@ static void launch_mixed84(const Mixed84Args &a, bool probe, hipStream_t st) {
 
 // is there a (u8, u4) rows-in-registers kernel for the shape (the two-tier lookup folds its probe into it)
 bool mixed84_supported(int T, int d, int codec1, int codec2) {
-    static const bool rfq_on = !(evs::env_switch("EVS_MIXED_RFQ") && evs::env_switch("EVS_MIXED_RFQ")[0] == '0');
+    static const bool rfq_on = evs::env_switch_on("EVS_MIXED_RFQ");
     return rfq_on && codec1 == 8 && codec2 == 4 && T + 1 <= 28 && (d == 16 || d == 32 || d == 36);
 }
 // the two-tier probe and the interaction over the rows it finds, one launch (evs_cache.hip fills `probe`)

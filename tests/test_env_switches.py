@@ -1,6 +1,6 @@
 """CPU: the names of the EVS_* switches cannot drift.  Three lists are held to each other --
 
-  code      every EVS_* literal the library (csrc/*.hip, *.h, *.cpp: getenv / env_switch / env_switch_range), the package's
+  code      every EVS_* literal the library (csrc/*.hip, *.h, *.cpp: getenv / env_switch / env_switch_on / env_switch_range), the package's
             *.py and bench.py (os.environ, os.getenv) read, plus the EVS_* build flags the README documents (#if / #ifndef in csrc/)
   README    the first column of the "Environment switches" table
   SWITCHES  the entries of tests/test_gpu_switches.py (one child process per switch setting), or EXEMPT below with a reason
@@ -25,7 +25,7 @@ def _csrc_files():
 def names_read_by_the_code():
     names = set()
     for f in _csrc_files():
-        names |= set(re.findall(r'(?:getenv|env_switch|env_switch_range)\(\s*"(%s)"' % NAME, open(f).read()))
+        names |= set(re.findall(r'(?:getenv|env_switch|env_switch_on|env_switch_range)\(\s*"(%s)"' % NAME, open(f).read()))
     py = [os.path.join(dp, f) for dp, _, fs in os.walk(PKG) for f in fs if f.endswith(".py")] + [os.path.join(ROOT, "bench.py")]
     for f in py:
         text = open(f).read()
@@ -67,7 +67,7 @@ NEVER_SET_BEFORE = """EVS_FUSED_RF EVS_FUSED_RF_CHECK EVS_FUSED_RF_MAX_B EVS_FUS
     EVS_FUSED_RFQ_CHECK_MIN_B EVS_FUSED_TILE EVS_FUSED_TILE_MIN_B EVS_FUSED_TILE_ALIGN EVS_FUSED_LDS EVS_FUSED_OPTIMISTIC EVS_FUSED_MULTI
     EVS_INTERACT_RF EVS_GATHER_RF EVS_GATHER_FLAT EVS_GATHER_FLAT_MAXAVG EVS_GATHER_LONG EVS_GATHER_LONG_MINAVG EVS_GATHER_BLOCKS_PER_CU
     EVS_MIXED_RFQ EVS_SA_DUAL EVS_SA_PAIR EVS_CACHE_FOLD EVS_CACHE_FOLDQ EVS_CACHE_FOLD2 EVS_CACHE_PAIR EVS_CACHE_ROUTEFILTER
-    EVS_CACHE_LAZY2 EVS_CACHE_C3INLINE EVS_CACHE_LIST2 EVS_CACHE_LIST_WAVES EVS_CACHE_FORK EVS_CACHE_HASH_SCALE EVS_CACHE_POLICY
+    EVS_CACHE_LAZY2 EVS_CACHE_C3INLINE EVS_CACHE_LIST2 EVS_CACHE_LIST_WAVES EVS_CACHE_HASH_SCALE EVS_CACHE_POLICY
     EVS_DEFER_POOLING EVS_REQUIRE_EXT EVS_P2P_SPINS""".split()
 
 

@@ -155,7 +155,6 @@ SWITCHES = [
     _e("EVS_CACHE_FOLDQ", 0, TIER1 + TIER1_SA[-2:], "tier1"),
     _e("EVS_SA_DUAL", 0, TIER1_SA, "tier1"),
     _e("EVS_SA_PAD_MB", 2, TIER1_SA, "tier1"),
-    _e("EVS_CACHE_FORK", 1, TIER1, "tier1"),
     _e("EVS_CACHE_HASH_SCALE", 1, TIER1, "tier1"),
     _e("EVS_CACHE_LIST_WAVES", 1, TIER1_LIST, "tier1"),
     _e("EVS_CACHE_LIST_WAVES", 2, TIER1_LIST, "tier1"),
