@@ -119,6 +119,12 @@ _PROTOS = {
     "evs_cache_set_bag_count": (_int, [_vp, _int]),
     "evs_cache_set_miss_order": (_int, [_vp, _int]),
     "evs_cache_fetch_stats": (_int, [_vp, _i64p, _vp]),
+    "evs_cache_set_fed_backing": (_int, [_vp, _pp, _i64p]),
+    "evs_cache_fed_begin": (_int, [_vp, _i64, _vp, _vp, _vp, _i64p, _vp]),
+    "evs_cache_fed_finish": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "evs_cache_fed_finish_interact": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "evs_cache_fed_abort": (_int, [_vp]),
+    "evs_cache_fed_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_set_batch_approx": (_int, [_vp, _int]),
     "evs_cache_approx_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_serve_stop": (_int, [_vp]),

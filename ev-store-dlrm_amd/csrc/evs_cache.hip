@@ -2853,8 +2853,11 @@ template <> struct SaNative<NoTail> { using type = int; };
 // it -- the key itself (fold the priority, done) or another key of this batch (that way is out, next best).  The line
 // is read plainly: what a plain read can return is a word as it stood at the start of the launch or one written in it,
 // and a way changes at most once per launch (old -> stamped), which is all the argument needs (docs/HISTORY.md 3.4).
-template <int PIECES, typename U, typename TAIL = NoTail, int W = 0>
-__device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsigned char *table, int t, unsigned row, int agg, unsigned set, unsigned tag1, int *s_delta, int *s_stat) {
+// FED (a cache with fed tables, evs_cache_policy.h at FedSrc): fsrc, when not NULL, is the key's row in the caller's fed block and
+// is read instead of the table row.
+template <int PIECES, typename U, typename TAIL = NoTail, int W = 0, bool FED = false>
+__device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsigned char *table, int t, unsigned row, int agg, unsigned set, unsigned tag1, int *s_delta, int *s_stat,
+                                              const unsigned char *fsrc = nullptr) {
     constexpr int NW = W > 0 ? W : kSaMaxWays;   // ways the scans below walk (W = 0: any geometry, masked by args.sa.ways)
     const unsigned long long key = ((unsigned long long)(t + 1) << 32) | row;
     // two tiers: the other tier took this key in this very batch (only an odd table index can be routed both ways by two
@@ -2869,7 +2872,7 @@ __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsig
     SaLine line;
     sa_load<W>(args.sa, set, line);
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned char *srow = table + (long long)row * args.row_bytes;
+    const unsigned char *srow = (FED && fsrc) ? fsrc : table + (long long)row * args.row_bytes;
     using NU = typename SaNative<U>::type;
     using NT = typename SaNative<TAIL>::type;
     typedef const __attribute__((address_space(1))) NU *gsrc_t;
@@ -3008,8 +3011,8 @@ __global__ void __launch_bounds__(256) cache_batch_sampled_list_kernel(const Bat
 // the set-associative policy's update: the same lists, sa_insert_one per record.  The list's length, the lane's first
 // record and the table base addresses (into LDS: a per-lane index into the kernel arguments is a memory access) are
 // asked for together -- three dependent round trips per record: those, {set line, source row}, the CAS.
-template <int PIECES, typename U, typename TAIL>
-__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid);
+template <int PIECES, typename U, typename TAIL, bool FED = false>
+__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs = nullptr);
 template <int PIECES, typename U, typename TAIL = NoTail>
 __global__ void __launch_bounds__(256) cache_batch_sa_list_kernel(const BatchArgs args) { sa_list_block<PIECES, U, TAIL>(args, (int)blockIdx.x); }
 // both tiers of a two- / three-tier lookup in one launch: blocks [0, g1) take C1's lists, [g1, 2 g1) C2's (the route filter
@@ -3019,8 +3022,12 @@ __global__ void __launch_bounds__(256) cache_batch_sa_list2_kernel(const BatchAr
     if ((int)blockIdx.x < args1.g1) sa_list_block<P1, U1, T1>(args1, (int)blockIdx.x);
     else sa_list_block<P2, U2, T2>(args2, (int)blockIdx.x - args1.g1);
 }
-template <int PIECES, typename U, typename TAIL>
-__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid) {
+// ... of a cache with fed tables (evs_cache_set_fed_backing; evs_cache_policy.h at FedSrc): a record whose table is fed carries a
+// slot of the scratch table beside it, and its row is read from the caller's fed block at the index that slot names
+template <int PIECES, typename U, typename TAIL = NoTail>
+__global__ void __launch_bounds__(256) cache_batch_sa_list_fed_kernel(const BatchArgs args, const FedSrc fs) { sa_list_block<PIECES, U, TAIL, true>(args, (int)blockIdx.x, &fs); }
+template <int PIECES, typename U, typename TAIL, bool FED>
+__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs) {
     __shared__ int s_delta[kMaxBuckets];
     __shared__ int s_stat[3];
     __shared__ const unsigned char *s_table[32];
@@ -3039,6 +3046,11 @@ __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid) {
         for (int i = i0; i < n; i += 64 * nw) {
             if (i != i0) r = rec[i];
             const int t = (int)(r.y & 0xffu);
+            if constexpr (FED) {
+                const int slot = fs->rec_slot[(long long)bid * args.list_cap + i];
+                const unsigned char *fsrc = slot >= 0 ? fs->fed + (long long)fs->slot_index[slot] * fs->stride : nullptr;
+                sa_insert_one<PIECES, U, TAIL, W, true>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat, fsrc);
+            } else
             sa_insert_one<PIECES, U, TAIL, W>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat);
         }
     };
@@ -3510,6 +3522,25 @@ struct evs_cache {
     long long approx_calls = 0;
     int inline_mode = -1;         // the update inside the probe launch (evs_fused_rf.hip): -1 not decided (EVS_CACHE_INLINE, default on), 0 / 1
     evs_tier_server *tsrv = nullptr;   // the tier pair / triple server this cache belongs to (evs_tiers_serve_*)
+    // fed backing (evs_cache_set_fed_backing; the contract: include/evstore_hip.h at evs_cache_fed_begin): bit t of fed_mask = table t
+    // has rows and no address -- its missing rows come from the caller between evs_cache_fed_begin and evs_cache_fed_finish.
+    // The scratch of the list kernel (evs_cache_policy.h at FedSrc), grown with the largest call; what an open call has to
+    // remember until its finish; the counters of evs_cache_fed_stats ([0] missed positions of fed tables, [1] served from the block).
+    unsigned fed_mask = 0;
+    void *slab_fed = nullptr;
+    long long fed_max_pos = 0;
+    unsigned long long *fed_slot_key = nullptr; int *fed_slot_index = nullptr, *fed_rec_slot = nullptr, *fed_n = nullptr;
+    unsigned long long *fed_cnt = nullptr;
+    int *fed_part1 = nullptr;   // the replica rows an open call's probe adds into (behind fed_cnt; zero between calls): fed_part_fold_kernel
+    long long fed_calls = 0, fed_keys = 0;
+    struct FedOpen {
+        bool open = false;
+        evs::BatchArgs a; evs::PolicyArgs pa;
+        int64_t B = 0; const int32_t *rows = nullptr; uint8_t *hit = nullptr;
+        long long n_keys = 0;
+        unsigned slot_mask = 0;
+        long long stamp_counter0 = 0;   // what evs_cache_fed_abort puts back
+    } fedc;
 };
 // The tier pair / triple as a resident server (cache_c1c2_serve_kernel): the single-tier server's mailbox and ring rules, owned
 // by an object of its own because the state it mutates belongs to two or three handles.  Every entry point that reads or
@@ -3654,7 +3685,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt, c->slab_fed, c->fed_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -3882,15 +3913,36 @@ extern "C" int evs_cache_set_bag_count(evs_cache *c, int when) {
 
 static int serve_pause(evs_cache *c);
 static int exact_launched(evs_cache *c, hipStream_t st);
-extern "C" int evs_cache_set_backing(evs_cache *c, const void *const *tables, const int64_t *n_rows) {
+// a begin without its finish (evs_cache_fed_begin): everything that would read or move the state the open call stands on is refused
+static int fed_open_refuse(evs_cache *c, const char *who) {
+    if (!c || !c->fedc.open) return EVS_OK;
+    evs::set_error("%s: a fed call is open on this %s cache (evs_cache_fed_begin without evs_cache_fed_finish / evs_cache_fed_abort)", who, policy_name(c->host.policy));
+    return EVS_ESTATE;
+}
+// a cache with fed tables outside its own calls: its rows have no address, so everything that would read a table in place says so
+static int fed_refuse(evs_cache *c, const char *who, int code, const char *why) {
+    if (!c || !c->fed_mask) return EVS_OK;
+    evs::set_error("%s: this %s cache has fed tables (evs_cache_set_fed_backing): %s", who, policy_name(c->host.policy), why);
+    return code;
+}
+// evs_cache_set_backing; fed: a NULL table with rows is a fed table (evs_cache_set_fed_backing)
+static int set_backing_impl(evs_cache *c, const void *const *tables, const int64_t *n_rows, bool fed, const char *who) {
     using namespace evs;
-    EVS_REQUIRE(c && tables && n_rows, "evs_cache_set_backing: NULL argument");
+    EVS_REQUIRE(c && tables && n_rows, "%s: NULL argument", who);
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    if (fed) {
+        EVS_REQUIRE(c->host.n_tables <= 32, "%s: at most 32 tables", who);
+        for (int k = 0; k < c->host.n_tables; k++) EVS_REQUIRE(n_rows[k] >= 0, "%s: n_rows[%d] = %lld", who, k, (long long)n_rows[k]);
+    }
     { const int prc = serve_pause(c); if (prc) return prc; }   // (a server inside its idle window holds the OLD table pointers)
+    unsigned fed_mask = 0;
     for (int k = 0; k < c->host.n_tables; k++) {
-        EVS_REQUIRE(tables[k] || n_rows[k] == 0, "evs_cache_set_backing: table %d is NULL", k);
+        EVS_REQUIRE(fed || tables[k] || n_rows[k] == 0, "%s: table %d is NULL", who, k);
+        if (!tables[k] && n_rows[k] > 0) fed_mask |= 1u << k;
         c->backing[k] = reinterpret_cast<const unsigned char *>(tables[k]);
         c->backing_rows[k] = n_rows[k];
     }
+    c->fed_mask = fed_mask;
     c->has_backing = true;
     // where the miss tier lives decides the order of the batched pipeline (see cache_batch_impl)
     c->host_backing = false;
@@ -3902,12 +3954,21 @@ extern "C" int evs_cache_set_backing(evs_cache *c, const void *const *tables, co
     }
     return EVS_OK;
 }
+extern "C" int evs_cache_set_backing(evs_cache *c, const void *const *tables, const int64_t *n_rows) {
+    return set_backing_impl(c, tables, n_rows, false, "evs_cache_set_backing");
+}
+// ... where tables[k] may be NULL for a table with rows: a fed table, whose missing rows the caller supplies between
+// evs_cache_fed_begin and evs_cache_fed_finish (the contract: include/evstore_hip.h)
+extern "C" int evs_cache_set_fed_backing(evs_cache *c, const void *const *tables, const int64_t *n_rows) {
+    return set_backing_impl(c, tables, n_rows, true, "evs_cache_set_fed_backing");
+}
 
 // The miss tier is a set of ev-table-N.bin files (evs_filetier_open): registered tables are read by the kernels over the
 // bus like pinned host tables; the others ("staged") are served through the host's reader pool -- batched lookups only.
 extern "C" int evs_cache_set_file_backing(evs_cache *c, evs_filetier *ft) {
     using namespace evs;
     EVS_REQUIRE(c && ft, "evs_cache_set_file_backing: NULL argument");
+    { const int rc = fed_open_refuse(c, "evs_cache_set_file_backing"); if (rc) return rc; }
     { const int prc = serve_pause(c); if (prc) return prc; }
     EVS_REQUIRE(filetier_tables(ft) == c->host.n_tables, "evs_cache_set_file_backing: the tier has %d tables, the cache %d",
                 filetier_tables(ft), c->host.n_tables);
@@ -3920,6 +3981,7 @@ extern "C" int evs_cache_set_file_backing(evs_cache *c, evs_filetier *ft) {
         if (!c->backing[k] && c->backing_rows[k] > 0) c->staged_mask |= 1u << k;
     }
     c->ft = ft;
+    c->fed_mask = 0;
     c->has_backing = true;
     c->host_backing = true;
     return EVS_OK;
@@ -3943,6 +4005,8 @@ extern "C" int evs_cache_request(evs_cache *c, int64_t B, const int32_t *rows, f
                                  int approx_thres, void *stream) {
     using namespace evs;
     EVS_REQUIRE(c, "evs_cache_request: NULL cache");
+    { const int rc = fed_open_refuse(c, "evs_cache_request"); if (rc) return rc; }
+    { const int rc = fed_refuse(c, "evs_cache_request", EVS_ESTATE, "the exact path reads a missing row from its table; a fed cache serves evs_cache_fed_begin / evs_cache_fed_finish only"); if (rc) return rc; }
     if (!c->has_backing) { set_error("evs_cache_request: call evs_cache_set_backing first"); return EVS_ESTATE; }
     if (c->staged_mask) { set_error("evs_cache_request: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (B == 0) return EVS_OK;
@@ -4001,6 +4065,8 @@ static int serve_pause(evs_cache *c) {
 extern "C" int evs_cache_serve_start(evs_cache *c, int approx_thres, float *ring, int n_slots, int64_t idle_us) {
     using namespace evs;
     EVS_REQUIRE(c && ring && n_slots >= 1 && idle_us >= 1, "evs_cache_serve_start: bad argument");
+    { const int rc = fed_open_refuse(c, "evs_cache_serve_start"); if (rc) return rc; }
+    { const int rc = fed_refuse(c, "evs_cache_serve_start", EVS_ESTATE, "the resident server of the exact path reads a missing row from its table"); if (rc) return rc; }
     if (!c->has_backing) { set_error("evs_cache_serve_start: call evs_cache_set_backing first"); return EVS_ESTATE; }
     if (c->staged_mask) { set_error("evs_cache_serve_start: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (c->used == 2) { set_error("evs_cache_serve_start: this cache is used through the batched path"); return EVS_ESTATE; }
@@ -4247,6 +4313,8 @@ int exact_load_checked(evs_cache *c, int64_t n, const int64_t *entries, const in
     EVS_REQUIRE(c, "evs_cache_exact_load: NULL cache");
     const CacheState &cfg = c->host;
     if (!c->has_backing) { set_error("evs_cache_exact_load: call evs_cache_set_backing first"); return EVS_ESTATE; }
+    { const int rc = fed_open_refuse(c, "evs_cache_exact_load"); if (rc) return rc; }
+    { const int rc = fed_refuse(c, "evs_cache_exact_load", EVS_ESTATE, "the exact path reads its rows from their tables; a fed cache serves evs_cache_fed_begin / evs_cache_fed_finish only"); if (rc) return rc; }
     if (c->staged_mask) { set_error("evs_cache_exact_load: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (c->used == 2) { set_error("evs_cache_exact_load: this cache is used through the batched path"); return EVS_ESTATE; }
     if (c->serving) { set_error("evs_cache_exact_load: a resident server runs on this cache (evs_cache_serve_stop first)"); return EVS_ESTATE; }
@@ -4368,6 +4436,7 @@ static int resolved_batch_policy(evs_cache *c, bool single_tier = true);
 static int batch_check(evs_cache *c, const char *who) {
     using namespace evs;
     EVS_REQUIRE(c, "%s: NULL cache", who);
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
     EVS_REQUIRE(c->host.n_tables <= 32, "%s: at most 32 tables", who);
     if (!c->has_backing) { set_error("%s: call evs_cache_set_backing first", who); return EVS_ESTATE; }
     if (c->host.policy != kEvLFU) {   // LRU / LFU: the set-associative form or nothing (evs_cache_policy.hip), refused before anything is allocated
@@ -4878,11 +4947,49 @@ static int ensure_estamp(evs_cache *c, hipStream_t st) {
 // one more batch of B requests whose counters the close has not folded yet
 static void count_batch(evs_cache *c, int64_t B) { c->pending_batches++; c->pending_requests += B; }
 
+// the consumers of a (B, T) call over the pointer table (or, row_ids not NULL, the 4-byte row ids in its first half): the rows
+// themselves into out, the interaction into R -- shared by cache_batch_impl and the finish of a fed call
+static int batch_consumers(evs_cache *c, const int *row_ids, int64_t B, float *out, const float *x, int64_t x_stride, int itself, float *R, hipStream_t st) {
+    using namespace evs;
+    const int T = c->host.n_tables;
+    const int wide = kNumCu * 8;
+    if (out) {
+        long long nb = (B * T * (long long)c->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
+        if (c->host.codec == 32)
+            hipLaunchKernelGGL(cache_rows_from_ptrs_kernel, dim3((unsigned)nb), dim3(256), 0, st, c->row_ptrs, out,
+                               (long long)B, T, c->host.dim, c->host.codec);
+        else   // reduced precision: chunked decode through LDS tables
+            hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c->row_ptrs,
+                               (const unsigned char *)nullptr, out, (long long)B, T, c->host.dim, c->host.codec, c->host.codec);
+    }
+    if (R && c->host.codec != 32) {
+        // a reduced-precision tier: every row decoded inside the interaction kernel (evs_mixed.hip; all rows of one class --
+        // u8 / u4 rows take the (u8, u4) rows-in-registers kernel with every row in its first / second class)
+        const int rc = c->host.codec == 4
+            ? interact_from_mixed_rows(B, T, c->host.dim, x, x_stride, c->row_ptrs, nullptr, 8, 4, itself, R, st, 2)   // every row in the pair's second class
+            : interact_from_mixed_rows(B, T, c->host.dim, x, x_stride, c->row_ptrs, nullptr, c->host.codec,
+                                       c->host.codec == 8 ? 4 : c->host.codec, itself, R, st);
+        if (rc) return rc;
+    } else
+    if (R) {
+        const int rc = row_ids
+            ? fused_interact_from_row_ids(B, T, c->host.dim, x, x_stride, row_ids, c->a.arena,
+                                          reinterpret_cast<const void *const *>(c->backing), itself, R, st)
+            : fused_interact_from_row_ptrs(B, T, c->host.dim, x, x_stride, (const int64_t *)c->row_ptrs,
+                                           (const int64_t *)c->iota, itself, R, st);
+        if (rc) return rc;
+    }
+    return EVS_OK;
+}
+
 static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float *out, uint8_t *hit, const float *x,
                             int64_t x_stride, int itself, float *R, void *stream) {
     using namespace evs;
     if (B == 0) return EVS_OK;
     EVS_REQUIRE(hit, "evs_cache_lookup_batch: NULL hit");
+    { const int rc = fed_open_refuse(c, "evs_cache_lookup_batch"); if (rc) return rc; }
+    { const int rc = fed_refuse(c, "evs_cache_lookup_batch", EVS_ESTATE, "its missing rows come from the caller, between evs_cache_fed_begin and evs_cache_fed_finish / "
+                                "_fed_finish_interact -- the one-call lookups cannot ask for them"); if (rc) return rc; }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchArgs a;
     // fetch-first (evs_cache_set_miss_order): probe -> update -> sa_repoint -> consumers, the set-associative tier over tables in
@@ -4902,7 +5009,6 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
     if (prc) return prc;
     const int T = c->host.n_tables;
     const long long cap = c->host.cap;
-    const int wide = kNumCu * 8;
     a.out = out; a.hit = hit;
     // Host-memory miss tier: hits of this batch are pinned (stamp), the policy update runs FIRST, the missed keys
     // that got an entry are re-pointed at their arena rows and only then do the consumers read -- every missing
@@ -4913,35 +5019,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         a.estamp = c->estamp; a.stamp_hits = 1;
         a.stamp = next_batch_stamp(c);
     }
-    auto consumers = [&]() -> int {
-        if (out) {
-            long long nb = (B * T * (long long)c->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
-            if (c->host.codec == 32)
-                hipLaunchKernelGGL(cache_rows_from_ptrs_kernel, dim3((unsigned)nb), dim3(256), 0, st, c->row_ptrs, out,
-                                   (long long)B, T, c->host.dim, c->host.codec);
-            else   // reduced precision: chunked decode through LDS tables
-                hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c->row_ptrs,
-                                   (const unsigned char *)nullptr, out, (long long)B, T, c->host.dim, c->host.codec, c->host.codec);
-        }
-        if (R && c->host.codec != 32) {
-            // a reduced-precision tier: every row decoded inside the interaction kernel (evs_mixed.hip; all rows of one class --
-            // u8 / u4 rows take the (u8, u4) rows-in-registers kernel with every row in its first / second class)
-            const int rc = c->host.codec == 4
-                ? interact_from_mixed_rows(B, T, c->host.dim, x, x_stride, c->row_ptrs, nullptr, 8, 4, itself, R, st, 2)   // every row in the pair's second class
-                : interact_from_mixed_rows(B, T, c->host.dim, x, x_stride, c->row_ptrs, nullptr, c->host.codec,
-                                           c->host.codec == 8 ? 4 : c->host.codec, itself, R, st);
-            if (rc) return rc;
-        } else
-        if (R) {
-            const int rc = a.row_ids
-                ? fused_interact_from_row_ids(B, T, c->host.dim, x, x_stride, a.row_ids, c->a.arena,
-                                              reinterpret_cast<const void *const *>(c->backing), itself, R, st)
-                : fused_interact_from_row_ptrs(B, T, c->host.dim, x, x_stride, (const int64_t *)c->row_ptrs,
-                                               (const int64_t *)c->iota, itself, R, st);
-            if (rc) return rc;
-        }
-        return EVS_OK;
-    };
+    auto consumers = [&]() -> int { return batch_consumers(c, a.row_ids, B, out, x, x_stride, itself, R, st); };
     // The interaction alone as the consumer, tables in HBM, a shape the rows-in-registers kernel takes: K1 writes 4-byte
     // row ids (arena entry / table row) instead of 8-byte addresses and that kernel reads them (22.9 -> ~20 us at
     // B = 16 384).  The 8-byte address table is the (B,T) int64 buffer either way: the ids use its first half.
@@ -5302,6 +5380,10 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
                        "evs_cache_lookup_interact_c1c2: d must be 16, 32 or 36 and T <= 31");
     EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim,
                 "evs_cache_lookup_batch_c1c2: the tiers must agree on n_tables and dim");
+    for (evs_cache *c : {c1, c2}) {
+        { const int rc = fed_open_refuse(c, "evs_cache_lookup_batch_c1c2"); if (rc) return rc; }
+        { const int rc = fed_refuse(c, "evs_cache_lookup_batch_c1c2", EVS_EINVAL, "a fed cache is a tier alone (evs_cache_fed_begin / evs_cache_fed_finish), never a tier of a pair or a triple"); if (rc) return rc; }
+    }
     // Miss tiers outside HBM (BASELINE configs[4] composed: the reference's C1 / C2 read their misses from files inside the
     // request, evlfu_8.cpp:380-414 get_from_file + the reader pool :191-250, :603-625): pinned host tables
     // (evs_cache_set_backing) or file-backed ones (evs_cache_set_file_backing) under EITHER tier.  The pair then runs the
@@ -5589,6 +5671,214 @@ extern "C" int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t 
     return cache_batch_impl(c, B, rows, nullptr, hit, x, x_stride, itself, R, stream);
 }
 
+// ---- fed backing: the fetch-first chain cut in two (the contract: include/evstore_hip.h at evs_cache_fed_begin) ---------------
+//   begin    (EvLFU: flush ->) probe -> fed_list -> synchronise: the caller holds the distinct missing keys of the fed tables
+//   finish   update (fed form) -> sa_repoint (fed form) -> consumers -> close bookkeeping
+// Between the two the cache remembers the call (evs_cache::fedc) and refuses everything else (fed_open_refuse).
+static int fed_call_check(evs_cache *c, const char *who) {
+    using namespace evs;
+    const char *pn = policy_name(c->host.policy);
+    if (!c->fed_mask) { set_error("%s: this %s cache has no fed table (evs_cache_set_fed_backing)", who, pn); return EVS_ESTATE; }
+    EVS_REQUIRE(c->miss_order == 1, "%s: a fed %s cache runs fetch-first -- the update in front of the consumers is what gives a fed row a place to be read from: "
+                "tell evs_cache_set_miss_order(c, 1) before the first call", who, pn);
+    EVS_REQUIRE(c->batch_approx <= 0, "%s: this %s cache has an approximate threshold in force (evs_cache_set_batch_approx); the fed form has no approximating probe", who, pn);
+    { const int rc = batch_check(c, who); if (rc) return rc; }
+    return fetch_first_check(c, who, false);
+}
+// The probe of an open call adds its totals (hits, all-hit requests) into replica rows of the call's own instead of part1: every
+// begin clears them in front of its probe, the finish folds them into part1 in front of the close, and a call that is dropped
+// never gets them counted -- an abort launches nothing.  One block, plain adds: part1 is touched in stream order only.
+namespace evs {
+__global__ void __launch_bounds__(256) fed_part_fold_kernel(int *part1, const int *mine) {
+    for (int i = threadIdx.x; i < kReplicas * kPartCols; i += 256) {
+        const int v = mine[i];
+        if (v) part1[i] += v;
+    }
+}
+}  // namespace evs
+// the scratch of the list kernel for calls of up to n_pos positions (a slot per record, 2^k >= 2 n_pos keys and indices, the list length)
+static int fed_scratch(evs_cache *c, long long n_pos, long long n_rec, hipStream_t st, const char *who) {
+    using namespace evs;
+    { const int rc = ensure_counters(&c->fed_cnt, 2 * sizeof(unsigned long long) + (size_t)kReplicas * kPartCols * sizeof(int), st, who, "fed-backing"); if (rc) return rc; }
+    c->fed_part1 = reinterpret_cast<int *>(c->fed_cnt + 2);
+    if (n_pos <= c->fed_max_pos) return EVS_OK;
+    long long slots = 64;
+    while (slots < 2 * n_pos) slots <<= 1;
+    unsigned long long *slot_key = nullptr; int *slot_index = nullptr, *rec_slot = nullptr, *n = nullptr;
+    void *slab = nullptr;
+    SlabPlan sp;
+    sp.add(&slot_key, slots * 8); sp.add(&slot_index, slots * 4); sp.add(&rec_slot, n_rec * 4); sp.add(&n, 4);
+    if (!sp.carve(&slab)) { set_error("%s: allocating the fed-list scratch of a call of %lld positions failed", who, n_pos); return EVS_ENOMEM; }
+    if (c->slab_fed) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(c->slab_fed); }
+    c->slab_fed = slab; c->fed_slot_key = slot_key; c->fed_slot_index = slot_index; c->fed_rec_slot = rec_slot; c->fed_n = n;
+    c->fed_max_pos = n_pos;
+    return EVS_OK;
+}
+static evs::FedSrc fed_src(evs_cache *c, const void *fed, int64_t stride) {
+    evs::FedSrc f{};
+    f.fed = reinterpret_cast<const unsigned char *>(fed); f.stride = stride;
+    f.rec_slot = c->fed_rec_slot; f.slot_index = c->fed_slot_index; f.slot_key = c->fed_slot_key;
+    f.slot_mask = c->fedc.slot_mask; f.fed_mask = c->fed_mask; f.counters = c->fed_cnt; f.err = evs::index_error_flag();
+    // (the zero row of the cache's codec, where a row fits it: 4 KiB of fp32, 1 KiB of codes)
+    if (c->host.row_bytes <= (c->host.codec == 32 ? 4096 : 1024))
+        f.zero_row = reinterpret_cast<const unsigned char *>(c->host.codec == 32 ? evs::zero_page() : evs::zero_code_page(c->host.codec));
+    return f;
+}
+
+extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_fed_begin";
+    EVS_REQUIRE(c, "%s: NULL cache", who);
+    EVS_REQUIRE(rows && hit && keys && n_keys_host, "%s: NULL argument", who);
+    EVS_REQUIRE(B > 0, "%s: B = %lld", who, (long long)B);
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys) % 8 == 0, "%s: keys must be 8-byte aligned", who);
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    { const int rc = fed_call_check(c, who); if (rc) return rc; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    evs_cache::FedOpen &o = c->fedc;
+    o.stamp_counter0 = c->stamp_counter;
+    BatchArgs &a = o.a;
+    { const int rc = batch_prepare(c, B, rows, st, a, who); if (rc) return rc; }
+    // (from here on a refusal takes the call's ordinal back: batch_prepare has counted it)
+    auto fail = [&](int rc) {
+        c->batch_calls--; c->stamp_counter = o.stamp_counter0;
+        if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
+        return rc;
+    };
+    const int T = c->host.n_tables;
+    a.out = nullptr; a.hit = hit;
+    const int list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+    { const int rc = fetch_first_state(c, st, who); if (rc) return fail(rc); }
+    { const int rc = fed_scratch(c, B * T, (long long)a.g1 * list_cap, st, who); if (rc) return fail(rc); }
+    long long slots = 64;
+    while (slots < 2 * B * T) slots <<= 1;   // (this call's share of the scratch table: what is cleared and walked)
+    o.slot_mask = (unsigned)(slots - 1);
+    if (hipMemsetAsync(c->fed_slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(c->fed_n, 0, 4, st) != hipSuccess ||
+        hipMemsetAsync(c->fed_part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: clearing the fed-list scratch failed", who); return fail(EVS_EHIP);
+    }
+    a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt; a.list_cap = list_cap;
+    // The probe writes no way word (fed_probe_kernel): what a one-call lookup's probe does to the ways it hits -- the LRU / LFU touch,
+    // EvLFU's raise -- is the finish's first launch, so a call that is dropped leaves the tier as it found it.
+    const bool evlfu = c->host.policy == kEvLFU;
+    PolicyArgs &pa = o.pa;
+    pa = PolicyArgs{};
+    pa.sa = c->sa; pa.sau = c->sau;
+    if (evlfu) {
+        a.stamp = next_batch_stamp(c);
+        sampled_flush_if_wanted(c, st);   // (asked for by an earlier close: the tier's, not this call's -- it stands if the call is dropped)
+    } else {
+        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    }
+    pa.requests = rows; pa.hit = hit; pa.row_ptrs = c->row_ptrs; pa.row_ids = nullptr;
+    pa.miss_rec = c->miss_rec; pa.list_cnt = c->list_cnt; pa.list_cap = list_cap;
+    pa.part1 = c->fed_part1; pa.part2 = a.part2;   // (the probe's totals: folded by the finish, never counted for a dropped call)
+    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = c->backing_rows[k]; }
+    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
+    fed_probe_launch(pa, evlfu, a.g1, st);
+    FedListArgs la{};
+    la.miss_rec = c->miss_rec; la.list_cnt = c->list_cnt; la.list_cap = list_cap;
+    la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
+    la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
+    la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
+    fed_list_launch(la, a.g1, st);
+    int n = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return fail(EVS_EHIP);
+    }
+    o.open = true; o.B = B; o.rows = rows; o.hit = hit; o.n_keys = n;
+    *n_keys_host = n;
+    return EVS_OK;
+}
+
+static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
+                           const char *who) {
+    using namespace evs;
+    EVS_REQUIRE(c, "%s: NULL cache", who);
+    evs_cache::FedOpen &o = c->fedc;
+    if (!o.open) { set_error("%s: no fed call is open on this %s cache (evs_cache_fed_begin)", who, policy_name(c->host.policy)); return EVS_ESTATE; }
+    // argument errors leave the call open: finish again, or abort
+    const int rb = c->host.row_bytes;
+    const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
+    EVS_REQUIRE(fed || o.n_keys == 0, "%s: NULL fed with %lld keys listed", who, o.n_keys);
+    if (fed) {
+        EVS_REQUIRE(stride >= rb, "%s: fed_stride_bytes %lld is below the row size of %d bytes", who, (long long)stride, rb);
+        EVS_REQUIRE(reinterpret_cast<uintptr_t>(fed) % align == 0 && stride % align == 0, "%s: fed and fed_stride_bytes must be multiples of %lld bytes "
+                    "(what a table of %d-byte rows gives its rows)", who, (long long)align, rb);
+    }
+    if (R && c->host.codec == 32)
+        EVS_REQUIRE(evs_fused_dim_supported(c->host.dim) && c->host.n_tables + 1 <= EVS_MAX_FEATURES, "%s: needs a fused-kernel dimension and T <= 31", who);
+    if (R && c->host.codec != 32)
+        EVS_REQUIRE((c->host.dim == 16 || c->host.dim == 32 || c->host.dim == 36) && c->host.n_tables + 1 <= EVS_MAX_FEATURES && !c->host_backing,
+                    "%s: a reduced-precision cache needs d in {16, 32, 36}, T <= 31 and its addressed tables in HBM", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const BatchArgs &a = o.a;
+    const FedSrc fs = fed_src(c, fed, fed ? stride : 0);
+    o.open = false;   // (from here on the call is spent, whatever a consumer says)
+    c->fetch_calls++;
+    hipLaunchKernelGGL(fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    {   // the touch / the raise of the ways the begin hit, in front of the update (EvLFU: its histogram moves go into part1 itself)
+        PolicyArgs ha = o.pa;
+        ha.part1 = c->part1;
+        fed_hits_launch(ha, c->host.policy == kEvLFU, a.g1, st);
+    }
+    if (c->host.policy != kEvLFU) policy_insert_fed_launch(o.pa, fs, a.g1, sampled_list_threads(a), st);
+    else
+        with_row_shape(a.row_bytes, [&](auto s) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
+        });
+    RepointArgs ra = repoint_args(c, o.hit, c->row_ptrs, o.B);
+    ra.requests = o.rows; ra.n_pos = o.B * c->host.n_tables;
+    sa_repoint_fed_launch(ra, fs, a.g1, st);
+    { const int rc = batch_consumers(c, nullptr, o.B, out, x, x_stride, itself, R, st); if (rc) return rc; }   // (a consumer that refuses: the batch is not counted)
+    count_batch(c, o.B);
+    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+    c->fed_calls++; c->fed_keys += o.n_keys;
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+extern "C" int evs_cache_fed_finish(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *out, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c && out, "evs_cache_fed_finish: NULL %s", c ? "out" : "cache");
+    return fed_finish_impl(c, fed, fed_stride_bytes, out, nullptr, 0, 0, nullptr, stream, "evs_cache_fed_finish");
+}
+extern "C" int evs_cache_fed_finish_interact(evs_cache *c, const void *fed, int64_t fed_stride_bytes, const float *x, int64_t x_stride, int itself, float *R,
+                                             void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c && x && R, "evs_cache_fed_finish_interact: NULL %s", c ? "x / R" : "cache");
+    EVS_REQUIRE(x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "evs_cache_fed_finish_interact: x must be 16-byte aligned, stride % 4 == 0");
+    return fed_finish_impl(c, fed, fed_stride_bytes, nullptr, x, x_stride, itself, R, stream, "evs_cache_fed_finish_interact");
+}
+// Drops the open call.  The begin wrote no way word and counted its hits into rows of its own, so there is nothing to undo on the
+// device and nothing is launched: the call's ordinal and stamp are given back, and the tier and its counters are what they were.
+extern "C" int evs_cache_fed_abort(evs_cache *c) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_fed_abort: NULL cache");
+    if (!c->fedc.open) { set_error("evs_cache_fed_abort: no fed call is open on this %s cache (evs_cache_fed_begin)", policy_name(c->host.policy)); return EVS_ESTATE; }
+    c->fedc.open = false;
+    c->batch_calls--;
+    c->stamp_counter = c->fedc.stamp_counter0;
+    if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;   // (a flush the begin ran: before the next call, as ever)
+    return EVS_OK;
+}
+// out4 (host): [calls finished, keys listed, missed positions of fed tables, positions served straight from a fed block]
+extern "C" int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_fed_stats: NULL cache");
+    EVS_REQUIRE(out4, "evs_cache_fed_stats: NULL out4");
+    unsigned long long h[2] = {0ull, 0ull};
+    if (c->fed_cnt) {
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        EVS_HIP_CHECK(hipMemcpyAsync(h, c->fed_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    out4[0] = c->fed_calls; out4[1] = c->fed_keys; out4[2] = (int64_t)h[0]; out4[3] = (int64_t)h[1];
+    return EVS_OK;
+}
+
 // What the set-associative update (sa_list_block, sa_insert_one) reads of a tier when the bag chains hand it their miss lists: one
 // filler for the single-tier EvLFU bag chain and for both tiers of the pair's, so that a field the update starts reading is set in
 // one place.  No alt-key tier (c3_tags stays NULL: the bag forms refuse a pair that has one).
@@ -5701,6 +5991,8 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     const int T = bc.T, d = bc.d;
     const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
     const bool evlfu = c->host.policy == kEvLFU;
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    { const int rc = fed_refuse(c, who, EVS_ESTATE, "the fed form is the (B, T) lookup's (evs_cache_fed_begin / evs_cache_fed_finish); it has no bag form"); if (rc) return rc; }
     EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule says what a request's hit count is over bags "
                 "(its priority counts a request's hit keys); lru / lfu caches take ragged bags as they are", who, policy_name(c->host.policy));
     { const int rc = batch_check(c, who); if (rc) return rc; }
@@ -5882,6 +6174,8 @@ static int cache_bags_c1c2_impl(evs_cache *c1, evs_cache *c2, int64_t B, const i
     for (int k = 0; k < 2; k++) {
         evs_cache *c = cs[k];
         const char *cn = k ? "C2" : "C1";
+        { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+        { const int rc = fed_refuse(c, who, EVS_EINVAL, "a fed cache is a tier alone (evs_cache_fed_begin / evs_cache_fed_finish), never a tier of a pair"); if (rc) return rc; }
         EVS_REQUIRE(c->host.policy == kEvLFU, "%s: the tier pair is EvLFU's; %s is an %s cache", who, cn, policy_name(c->host.policy));
         EVS_REQUIRE(c->bag_rule == 1, "%s: %s has no bag rule: evs_cache_set_bag_rule(c, 1) says what a request's hit count is over bags, and the pair "
                     "needs it told to both tiers", who, cn);
@@ -6066,6 +6360,7 @@ extern "C" int evs_cache_lookup_bags_interact_c1c2(evs_cache *c1, evs_cache *c2,
 extern "C" int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist, void *stream) {
     using namespace evs;
     EVS_REQUIRE(c && out8 && c->bs, "evs_cache_batch_stats: the batched path has not been used");
+    { const int rc = fed_open_refuse(c, "evs_cache_batch_stats"); if (rc) return rc; }   // (the close would fold half a batch)
     BatchState h;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     sampled_close_pending(c, 0, st);
@@ -6083,6 +6378,7 @@ extern "C" int evs_cache_batch_stats(evs_cache *c, int64_t *out8, int64_t *hist,
 extern "C" int64_t evs_cache_batch_dump(evs_cache *c, int64_t *triples, int64_t max_triples, void *stream) {
     using namespace evs;
     if (!c || !c->bs) return EVS_EINVAL;
+    { const int rc = fed_open_refuse(c, "evs_cache_batch_dump"); if (rc) return rc; }
     sampled_close_pending(c, 0, reinterpret_cast<hipStream_t>(stream));
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) != hipSuccess) return EVS_EHIP;
     sampled_flush_if_wanted(c, reinterpret_cast<hipStream_t>(stream));
@@ -6136,6 +6432,7 @@ static const char *warm_geometry(int policy, long long cap, int T, const long lo
 static int warm_check(evs_cache *c, bool load, const char *who) {
     using namespace evs;
     { const int rc = batch_check(c, who); if (rc) return rc; }
+    { const int rc = fed_refuse(c, who, EVS_EINVAL, "the warm start reads the rows of the keys it places from their tables, and a fed table has no address"); if (rc) return rc; }
     EVS_REQUIRE(!c->tsrv && !(c->sa.tags && c->sa.line_words == 32u), "%s: this cache is a tier of a C1 + C2 (+ C3) lookup; the warm start is a tier alone's", who);
     EVS_REQUIRE(c->sa.tags ? c->sa.ways == kSaSingleWays : (c->host.policy != kEvLFU || sa_single_ways() == kSaSingleWays),
                 "%s: sets of 16 ways (EVS_SA_WAYS=16) have no warm start: the load places into 8-way sets", who);
@@ -6399,6 +6696,7 @@ static int pair_warm_check(evs_cache *c1, evs_cache *c2, const char *who) {
     EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
     for (evs_cache *c : {c1, c2}) {
         { const int rc = batch_check(c, who); if (rc) return rc; }
+        { const int rc = fed_refuse(c, who, EVS_EINVAL, "a fed cache is a tier alone, and the warm start reads the rows it places from their tables"); if (rc) return rc; }
         if (c->host_backing || c->ft) { set_error("%s: the warm start reads the tables in place from HBM (no host-memory / file-backed tables)", who); return EVS_ESTATE; }
         if (c->serving || c->tsrv) { set_error("%s: a resident server is running on a tier (or the tiers belong to a tier server)", who); return EVS_ESTATE; }
         // (both tiers fetch-first: the pair's own order, over HBM tables here -- the load launch does not depend on it)
@@ -6577,6 +6875,8 @@ static int cache_rows_impl(evs_cache *c, int64_t n, const int32_t *keys, const f
     EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys) % 8 == 0, "%s: keys must be 8-byte aligned", who);
     EVS_REQUIRE(refresh || values_stride >= c->host.dim, "%s: values_stride %lld is below dim = %d", who, (long long)values_stride, c->host.dim);
     if (!c->has_backing) { set_error("%s: call evs_cache_set_backing first", who); return EVS_ESTATE; }
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    { const int rc = fed_refuse(c, who, EVS_ESTATE, "there is no table to write or to read the rows again from (as for a file-backed tier with staged tables)"); if (rc) return rc; }
     if (!refresh && c->ft) { set_error("%s: the tables of a file-backed cache are read-only mappings (write the files, then evs_cache_refresh_rows)", who); return EVS_ESTATE; }
     if (refresh && c->staged_mask) { set_error("%s: a file-backed tier with staged tables has no device-visible rows to refresh from", who); return EVS_ESTATE; }
     // a resident server holds the policy state in its registers and reads rows inside a running launch, where another
@@ -6793,6 +7093,10 @@ extern "C" int evs_tiers_serve_start(evs_tier_server **out, evs_cache *c1, evs_c
     EVS_REQUIRE(c1->host.n_tables <= 28, "evs_tiers_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
     EVS_REQUIRE(!c3 || c3->n_tables == c1->host.n_tables, "evs_tiers_serve_start: alt-key tier has a different n_tables");
     if (!c1->has_backing || !c2->has_backing) { set_error("evs_tiers_serve_start: set the backing tables of both tiers first"); return EVS_ESTATE; }
+    for (evs_cache *c : {c1, c2}) {
+        { const int rc = fed_open_refuse(c, "evs_tiers_serve_start"); if (rc) return rc; }
+        { const int rc = fed_refuse(c, "evs_tiers_serve_start", EVS_EINVAL, "a fed cache is a tier alone, never a tier of a pair or a triple"); if (rc) return rc; }
+    }
     if (c1->staged_mask || c2->staged_mask) { set_error("evs_tiers_serve_start: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (c1->used == 2 || c2->used == 2) { set_error("evs_tiers_serve_start: a tier is used through the batched path"); return EVS_ESTATE; }
     if (c3 && !c3->has_alt) { set_error("evs_tiers_serve_start: call evs_aprx_set_altkeys first"); return EVS_ESTATE; }
@@ -6930,6 +7234,10 @@ extern "C" int evs_cache_request_c1c2c3(evs_cache *c1, evs_cache *c2, evs_aprx *
     EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim,
                 "evs_cache_request_c1c2c3: the tiers disagree on n_tables/dim");
     if (!c1->has_backing || !c2->has_backing) { set_error("evs_cache_request_c1c2c3: set the backing tables of both tiers first"); return EVS_ESTATE; }
+    for (evs_cache *c : {c1, c2}) {
+        { const int rc = fed_open_refuse(c, "evs_cache_request_c1c2c3"); if (rc) return rc; }
+        { const int rc = fed_refuse(c, "evs_cache_request_c1c2c3", EVS_EINVAL, "a fed cache is a tier alone, never a tier of a pair or a triple"); if (rc) return rc; }
+    }
     if (c3 && !c3->has_alt) { set_error("evs_cache_request_c1c2c3: call evs_aprx_set_altkeys first"); return EVS_ESTATE; }
     EVS_REQUIRE(!c3 || c3->n_tables == c1->host.n_tables, "evs_cache_request_c1c2c3: alt-key tier has a different n_tables");
     if (B == 0) return EVS_OK;

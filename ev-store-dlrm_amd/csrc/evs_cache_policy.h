@@ -180,6 +180,50 @@ void sa_repoint_launch(const RepointArgs &a, int grid, hipStream_t st);
 // flat form: the bag probe's grid and walk (block j: positions 256 (j + i grid) + thread, i < iters)
 void sa_repoint_flat_launch(const RepointArgs &a, int grid, hipStream_t st);
 
+// Fed backing (evs_cache_set_fed_backing; the contract: include/evstore_hip.h at evs_cache_fed_begin): a table in fed_mask has no
+// address the GPU reads -- the rows of its missing keys come from the caller, between the probe and the update.  The chain is the
+// fetch-first chain cut in two:  (flush ->) probe -> fed_list | the caller fetches | update (fed form) -> sa_repoint (fed form) ->
+// consumers -> close.  The begin writes no way word: a call that is dropped (evs_cache_fed_abort) leaves the tier as it found it.
+//   fed_probe  K1 of either producer (flags, addresses, miss lists, hit totals) without the LRU / LFU touch and without EvLFU's
+//              raise; fed_hits, first launch of the finish, touches / raises the ways of the positions the begin flagged 1.
+//   fed_list   walks the probe's per-block miss lists.  A record of a fed table is looked up in a scratch open-address table of
+//              64-bit keys (table_1based << 32 | row; a power of two >= 2 x positions, zero at the start of the launch): ONE
+//              compare-and-swap claims a slot, the claimant takes the next list index (the appends of a wave are one add of its
+//              claimant count), writes the key at keys[index] and stores the index at slot_index[slot]; every record -- claimant or
+//              not -- stores its slot at rec_slot[record].  A record of an addressed table gets -1.  Nobody READS slot_index in this
+//              launch: the update and the re-point run in later launches, so a key's index is visible to all its copies by then.
+//   update     a record with a slot copies its row from fed + slot_index[slot] * stride instead of from the table.
+//   re-point   a missed position of a fed table that found no way (its set took 8 new keys) finds its key's slot again and is
+//              pointed at its fed row; every missed position of a fed table is rewritten, so the NULL-based address the probe
+//              computed for it never reaches a consumer.
+struct FedSrc {
+    const unsigned char *fed; long long stride;   // row i of the fed block, in the cache's codec
+    const int *rec_slot;                          // per miss record (list j from j * list_cap): its slot, -1 = an addressed table
+    const int *slot_index;                        // per slot: the list index of the key that claimed it
+    const unsigned long long *slot_key;           // the scratch table
+    unsigned slot_mask, fed_mask;                 // slots - 1; bit t: table t is fed
+    unsigned long long *counters;                 // re-point: [0] missed positions of fed tables, [1] of those served from the fed block
+    int *err;                                     // re-point: the sticky index-error flag, raised for an index out of range
+    const unsigned char *zero_row;                // re-point: what a position is served whose key the scratch table does not hold (never: see there)
+};
+struct FedListArgs {
+    const uint4 *miss_rec; const int *list_cnt; int list_cap;   // the probe's lists (either producer: row, table | .. << 8, set, tag + 1)
+    unsigned long long *slot_key; int *slot_index; int *rec_slot;
+    unsigned slot_mask, fed_mask;
+    unsigned long long *keys;                     // out: the fed list
+    int *n_keys;                                  // its length (zero at the start of the launch)
+};
+// the begin's probe (policy_probe_launch's grid and walk) and the finish's touch / raise of the begin's hits; `a` as
+// policy_probe_launch takes it (EvLFU: lay and cur unused; fed_hits adds the histogram moves into a.part1)
+void fed_probe_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st);
+void fed_hits_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st);
+// block j (64 threads) takes miss list j
+void fed_list_launch(const FedListArgs &a, int grid, hipStream_t st);
+// the LRU / LFU insert over lists whose fed records read the fed block (policy_insert_launch's grid and threads)
+void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, unsigned threads, hipStream_t st);
+// sa_repoint_launch's (B, T) form for a cache with fed tables
+void sa_repoint_fed_launch(const RepointArgs &a, const FedSrc &f, int grid, hipStream_t st);
+
 // Fetch-first order of the C1 + C2 pair that shares its set records (both tiers at evs_cache_set_miss_order(c, 1); the chain:
 // evs_cache.hip, batch_c1c2_impl; the rule: include/evstore_hip.h at evs_cache_lookup_batch_c1c2).  The pair has no two-copy
 // arena, so behind the pair's update a way the batch HIT may hold another key.  Every position is searched again in the ways of

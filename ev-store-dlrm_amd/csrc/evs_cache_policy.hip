@@ -124,6 +124,114 @@ __global__ void __launch_bounds__(256) policy_probe_kernel(const PolicyArgs args
     if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
 }
 
+// The probe of a fed call's begin (evs_cache_fed_begin; evs_cache_policy.h at FedSrc), all three policies: K1's walk, flags,
+// addresses, miss lists and hit totals, and NO write to a way word -- the call may still be dropped (evs_cache_fed_abort), and a
+// dropped call must leave the tier as it found it.  What the probe of a one-call lookup does to the ways it hits (the LRU / LFU
+// touch, EvLFU's raise to the request's agg_hit) waits for the finish: fed_hits_kernel.  EVLFU: a miss record carries the request's
+// agg_hit (row, table | agg << 8, set, tag + 1), as cache_batch_probe_gather_kernel writes it.
+template <bool EVLFU>
+__global__ void __launch_bounds__(256) fed_probe_kernel(const PolicyArgs args) {
+    __shared__ int s_sum[2];   // hits / all-hit requests of this block
+    __shared__ int s_list_n;
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    __shared__ const unsigned char *s_table[32];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_list_n = 0;
+    const int T = args.T;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.backing_rows[threadIdx.x] : 0;
+        s_table[threadIdx.x] = args.backing[threadIdx.x];
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool req_on = req < args.B;
+        const bool key_on = req_on && hl < T;
+        const int row = key_on ? args.requests[req * T + hl] : -1;
+        const bool ok = key_on && row >= 0 && row < s_rows[hl];
+        PolKey key;
+        const bool is_hit = policy_probe_key<false>(g, args.sau, args.lay, args.cur, ok, s_base[hl] + (ok ? (unsigned)row : 0u), key);
+        const unsigned long long hm = __ballot(is_hit);
+        const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+        if (key_on) {
+            const long long at = req * T + hl;
+            args.hit[at] = is_hit ? 1 : 0;
+            const unsigned char *src = nullptr;
+            if (is_hit) src = args.arena + (long long)sa_entry(g, key.set, (unsigned)key.way, key.w) * args.row_bytes;
+            else if (ok) src = s_table[hl] + (long long)row * args.row_bytes;   // (a fed table: NULL-based, rewritten by sa_repoint_fed_kernel)
+            args.row_ptrs[at] = (long long)src;
+        }
+        {   // the half-wave's misses, packed, behind the block's earlier ones
+            const bool is_miss = ok && key.way < 0;
+            const unsigned long long mm = __ballot(is_miss);
+            const unsigned mh = (unsigned)(half ? (mm >> 32) : mm);
+            int base = 0;
+            if (hl == 0 && mh) base = atomicAdd(&s_list_n, __popc(mh));
+            base = __shfl(base, half * 32, 64);
+            if (is_miss) {
+                const int at = base + __popc(mh & ((1u << hl) - 1u));
+                if (at < args.list_cap)
+                    args.miss_rec[(long long)blockIdx.x * args.list_cap + at] =
+                        make_uint4((unsigned)row, (unsigned)hl | (EVLFU ? (unsigned)agg << 8 : 0u), key.set, key.tag1);
+            }
+        }
+        if (req_on && hl == 0) { atomicAdd(&s_sum[0], agg); if (agg == T) atomicAdd(&s_sum[1], 1); }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_sum[threadIdx.x])
+        atomicAdd(&args.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38 + threadIdx.x], s_sum[threadIdx.x]);
+    if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
+}
+
+// ... and, first launch of the finish, what that probe left undone: every position the begin flagged 1 finds its way again (the tier
+// has not moved: everything else is refused while the call is open) and is touched (LRU / LFU: policy_probe_key's plain store) or
+// raised to its request's agg_hit = the number of its flags that are 1 (EvLFU: sa_raise, the histogram moves into part1 columns
+// 0 .. T).  Nothing else writes a way word during this launch; the update runs behind it and reads what it would have read behind
+// a probe that touched and raised by itself.
+template <bool EVLFU>
+__global__ void __launch_bounds__(256) fed_hits_kernel(const PolicyArgs args) {
+    __shared__ int s_delta[64];   // priority histogram moves (0 .. T, T <= 32; sized by the word's 6-bit field)
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    const int T = args.T;
+    if (threadIdx.x < 64) s_delta[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.backing_rows[threadIdx.x] : 0;
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool key_on = req < args.B && hl < T;
+        const int row = key_on ? args.requests[req * T + hl] : -1;
+        const bool ok = key_on && row >= 0 && row < s_rows[hl] && args.hit[req * T + hl] == 1;   // the begin's hits alone
+        PolKey key;
+        const bool is_hit = policy_probe_key<!EVLFU>(g, args.sau, args.lay, args.cur, ok, s_base[hl] + (ok ? (unsigned)row : 0u), key);
+        (void)is_hit;
+        if constexpr (EVLFU) {
+            const unsigned long long hm = __ballot(ok);
+            const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+            if (is_hit && sa_prio(key.w) < agg) {
+                const int old = sa_raise(g, sa_ways_ptr(g, key.set) + key.way, key.w, agg);
+                if (old >= 0) { atomicSub(&s_delta[old], 1); atomicAdd(&s_delta[agg], 1); }
+            }
+        }
+    }
+    if constexpr (EVLFU) {
+        __syncthreads();
+        if ((int)threadIdx.x <= T && s_delta[threadIdx.x])
+            atomicAdd(&args.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], s_delta[threadIdx.x]);
+    }
+}
+
 // K1 over ragged bags: one lane per POSITION of the flat, table-major lookup list (evs_cache_lookup_bags).  The lane's table
 // comes from the prefix sums of nnz (five steps over an LDS table); per position the int64 index, its range check, the set
 // line, the touch (policy_probe_key), then the hit flag, the 8-byte row address for the pooling kernel and -- for a miss --
@@ -819,6 +927,112 @@ __global__ void __launch_bounds__(256) sa_repoint_kernel(const RepointArgs args)
     if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
+// ... of a cache with fed tables (evs_cache_policy.h at FedSrc), (B, T) form: the kernel above, and a missed position of a fed
+// table that found no way finds its key's slot of the scratch table again (the walk fed_list's compare-and-swap took, read-only
+// now) and is pointed at its fed row -- every missed position of a fed table leaves this launch with an address somebody owns.
+__global__ void __launch_bounds__(256) sa_repoint_fed_kernel(const RepointArgs args, const FedSrc fs) {
+    __shared__ int s_cnt[4];   // positions re-pointed / left in place / missed positions of fed tables / of those served from the fed block
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    const int T = args.T;
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.backing_rows[threadIdx.x] : 0;
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    int n_in = 0, n_out = 0, n_fed = 0, n_blk = 0;   // this wave's totals, kept on lane 0
+    bool bad = false;                                // an index out of range: no key, and the sticky flag says so
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool on = req < args.B && hl < T;
+        const long long p = req * T + hl;
+        const long long row = on ? (long long)args.requests[p] : -1;
+        const bool in_range = row >= 0 && row < s_rows[hl];
+        const bool want = on && args.hit[p] == 0 && in_range;
+        bad = bad || (on && !in_range);
+        unsigned set = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(args.sau, s_base[hl] + (want ? (unsigned)row : 0u)), set, tag1);
+        if (!want) set = 0u;
+        SaLine line;
+        sa_load<8>(g, set, line);
+        const int way = sa_find<8>(g, line, tag1, w);
+        const bool found = want && way >= 0;
+        const bool block = want && !found && ((fs.fed_mask >> hl) & 1u);
+        if (found) args.row_ptrs[p] = (long long)(args.arena + (long long)sa_entry(g, set, (unsigned)way, w) * args.row_bytes);
+        if (block) {
+            const unsigned long long key = ((unsigned long long)(hl + 1) << 32) | (unsigned)row;
+            // (fed_list has seen every record the probe wrote, so the key is there; were it not, the position is served the codec's
+            //  zero row and the sticky flag says so -- never an address nobody owns)
+            const unsigned char *src = fs.zero_row;
+            bool lost = true;
+            unsigned h = (unsigned)mix64(key) & fs.slot_mask;
+            for (unsigned n = 0; n <= fs.slot_mask; n++, h = (h + 1u) & fs.slot_mask) {
+                const unsigned long long kk = fs.slot_key[h];
+                if (kk == key) { src = fs.fed + (long long)fs.slot_index[h] * fs.stride; lost = false; break; }
+                if (kk == 0ull) break;
+            }
+            bad = bad || lost;
+            args.row_ptrs[p] = (long long)src;
+        }
+        const unsigned long long fm = __ballot(found), wm = __ballot(want);
+        n_in += __popcll(fm); n_out += __popcll(wm & ~fm);
+        n_fed += __popcll(__ballot(want && ((fs.fed_mask >> hl) & 1u))); n_blk += __popcll(__ballot(block));
+    }
+    if (bad) atomicOr(fs.err, 1);
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+        if (n_fed) atomicAdd(&s_cnt[2], n_fed);
+        if (n_blk) atomicAdd(&s_cnt[3], n_blk);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x >= 2 && threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&fs.counters[threadIdx.x - 2], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// The fed list (evs_cache_policy.h at FedSrc): block j walks miss list j, a record per lane.  The trip count is block-uniform (the
+// ballot); the claim is one compare-and-swap per slot visited -- 0 -> key wins the slot, the key itself means another copy (of this
+// or of another block) won it, anything else is another key's slot: next one.  The table has at least twice as many slots as the
+// call has positions, so the walk ends.  The wave's claimants take consecutive list indices from ONE add of their number.
+__global__ void __launch_bounds__(64) fed_list_kernel(const FedListArgs args) {
+    const uint4 *rec = args.miss_rec + (long long)blockIdx.x * args.list_cap;
+    int *rec_slot = args.rec_slot + (long long)blockIdx.x * args.list_cap;
+    const int n = args.list_cnt[blockIdx.x];
+    const int lane = threadIdx.x;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool on = i < n;
+        const uint4 r = rec[on ? i : 0];
+        const unsigned t = r.y & 0xffu;
+        const bool fed = on && ((args.fed_mask >> (t & 31u)) & 1u);
+        const unsigned long long key = ((unsigned long long)(t + 1u) << 32) | r.x;
+        unsigned h = (unsigned)mix64(key) & args.slot_mask;
+        bool claimed = false;
+        if (fed) {
+            for (;;) {
+                const unsigned long long prev = atomicCAS(&args.slot_key[h], 0ull, key);
+                if (prev == 0ull) { claimed = true; break; }
+                if (prev == key) break;
+                h = (h + 1u) & args.slot_mask;
+            }
+        }
+        const unsigned long long cm = __ballot(claimed);
+        int base = 0;
+        if (lane == 0 && cm) base = atomicAdd(args.n_keys, __popcll(cm));
+        base = __shfl(base, 0, 64);
+        if (claimed) {
+            const int at = base + __popcll(cm & ((1ull << lane) - 1ull));
+            args.keys[at] = key;
+            args.slot_index[h] = at;
+        }
+        if (on) rec_slot[i] = fed ? (int)h : -1;
+    }
+}
+
 // ... of the C1 + C2 pair that shares its set records (the rule: evs_cache_policy.h at Repoint2Args).  The pair keeps one arena
 // row per way, so a way this batch hit can have been this batch's victim: a hit position is searched again too, and one whose
 // key is gone is pointed at the table row of its tier -- the same bytes.  A position looks at the ways of the tier its serve byte
@@ -956,9 +1170,10 @@ template <> struct Native<NoTail> { using type = int; };
 // and the compare-and-swap go out when the line is there, the row -- a random line of a large table -- still on its way),
 // then the CAS, then the row stores nobody waits for.  PIECES x U (+ TAIL) = row_bytes; PIECES = 0: any row size, copied
 // after the claim.
-template <int PIECES, typename U, typename TAIL>
+// FED: fsrc, when not NULL, is the key's row in the caller's fed block and is read instead of the table row.
+template <int PIECES, typename U, typename TAIL, bool FED = false>
 __device__ __forceinline__ void policy_insert_one(const PolicyArgs &args, const unsigned char *table, unsigned row, unsigned set, unsigned tag1,
-                                                  int *s_stat) {
+                                                  int *s_stat, const unsigned char *fsrc = nullptr) {
     const SaGeom &g = args.sa;
     const PolLayout &L = args.lay;
     const unsigned cur = args.cur;
@@ -966,7 +1181,7 @@ __device__ __forceinline__ void policy_insert_one(const PolicyArgs &args, const 
     SaLine line;
     sa_load<8>(g, set, line);
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned char *srow = table + (long long)row * args.row_bytes;
+    const unsigned char *srow = (FED && fsrc) ? fsrc : table + (long long)row * args.row_bytes;
     using NU = typename Native<U>::type;
     using NT = typename Native<TAIL>::type;
     constexpr int NP = PIECES > 0 ? PIECES : 1;
@@ -1048,9 +1263,37 @@ __global__ void __launch_bounds__(256) policy_insert_kernel(const PolicyArgs arg
     }
 }
 
+// ... over lists whose records of fed tables carry a slot (evs_cache_policy.h at FedSrc): their row comes from the fed block
 template <int PIECES, typename U, typename TAIL = NoTail>
-void insert_launch_t(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) {
-    hipLaunchKernelGGL((policy_insert_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a);
+__global__ void __launch_bounds__(256) policy_insert_fed_kernel(const PolicyArgs args, const FedSrc fs) {
+    __shared__ int s_stat[2];
+    __shared__ const unsigned char *s_table[32];
+    if (threadIdx.x < 2) s_stat[threadIdx.x] = 0;
+    if (threadIdx.x < 32) s_table[threadIdx.x] = args.backing[threadIdx.x];
+    const uint4 *rec = args.miss_rec + (long long)blockIdx.x * args.list_cap;
+    const int *rec_slot = fs.rec_slot + (long long)blockIdx.x * args.list_cap;
+    const int nw = (int)blockDim.x >> 6;
+    const int i0 = ((int)threadIdx.x & 63) * nw + ((int)threadIdx.x >> 6);
+    const int n = args.list_cnt[blockIdx.x];
+    __syncthreads();
+    for (int i = i0; i < n; i += 64 * nw) {
+        const uint4 r = rec[i];
+        const int slot = rec_slot[i];
+        const unsigned char *fsrc = slot >= 0 ? fs.fed + (long long)fs.slot_index[slot] * fs.stride : nullptr;
+        policy_insert_one<PIECES, U, TAIL, true>(args, s_table[r.y & 31u], r.x, r.z, r.w, s_stat, fsrc);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int *p = args.part2 + (blockIdx.x % kPolReplicas) * kPolPartCols;
+        if (s_stat[0]) { atomicAdd(&p[0], s_stat[0]); atomicAdd(&p[33], s_stat[0]); }
+        if (s_stat[1]) atomicAdd(&p[34], s_stat[1]);
+    }
+}
+
+template <int PIECES, typename U, typename TAIL = NoTail>
+void insert_launch_t(const PolicyArgs &a, const FedSrc *f, int grid, unsigned threads, hipStream_t st) {
+    if (f) hipLaunchKernelGGL((policy_insert_fed_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a, *f);
+    else hipLaunchKernelGGL((policy_insert_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a);
 }
 
 }  // namespace
@@ -1164,21 +1407,41 @@ bool bags_pool2_launch(const BagPairArgs &a, int codec1, int codec2, hipStream_t
     return true;
 }
 
-// compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail)
-void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) {
+// compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail); f: the fed form
+static void policy_insert_dispatch(const PolicyArgs &a, const FedSrc *f, int grid, unsigned threads, hipStream_t st) {
     switch (a.row_bytes) {
-    case 144: insert_launch_t<9, float4>(a, grid, threads, st); break;     // d = 36 fp32
-    case 256: insert_launch_t<16, float4>(a, grid, threads, st); break;    // d = 64 fp32
-    case 128: insert_launch_t<8, float4>(a, grid, threads, st); break;     // d = 32 fp32, d = 64 u16
-    case 64: insert_launch_t<4, float4>(a, grid, threads, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
-    case 32: insert_launch_t<2, float4>(a, grid, threads, st); break;
-    case 16: insert_launch_t<1, float4>(a, grid, threads, st); break;
-    case 72: insert_launch_t<4, float4, uint2>(a, grid, threads, st); break;            // d = 36 u16: 4 x 16 + 8
-    case 36: insert_launch_t<2, float4, unsigned>(a, grid, threads, st); break;         // d = 36 u8: 2 x 16 + 4
-    case 18: insert_launch_t<1, float4, unsigned short>(a, grid, threads, st); break;   // d = 36 u4: 16 + 2
-    case 8: insert_launch_t<1, uint2>(a, grid, threads, st); break;
-    default: insert_launch_t<0, float4>(a, grid, threads, st); break;
+    case 144: insert_launch_t<9, float4>(a, f, grid, threads, st); break;     // d = 36 fp32
+    case 256: insert_launch_t<16, float4>(a, f, grid, threads, st); break;    // d = 64 fp32
+    case 128: insert_launch_t<8, float4>(a, f, grid, threads, st); break;     // d = 32 fp32, d = 64 u16
+    case 64: insert_launch_t<4, float4>(a, f, grid, threads, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
+    case 32: insert_launch_t<2, float4>(a, f, grid, threads, st); break;
+    case 16: insert_launch_t<1, float4>(a, f, grid, threads, st); break;
+    case 72: insert_launch_t<4, float4, uint2>(a, f, grid, threads, st); break;            // d = 36 u16: 4 x 16 + 8
+    case 36: insert_launch_t<2, float4, unsigned>(a, f, grid, threads, st); break;         // d = 36 u8: 2 x 16 + 4
+    case 18: insert_launch_t<1, float4, unsigned short>(a, f, grid, threads, st); break;   // d = 36 u4: 16 + 2
+    case 8: insert_launch_t<1, uint2>(a, f, grid, threads, st); break;
+    default: insert_launch_t<0, float4>(a, f, grid, threads, st); break;
     }
+}
+void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, nullptr, grid, threads, st); }
+void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, &f, grid, threads, st); }
+
+void fed_probe_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st) {
+    if (evlfu) hipLaunchKernelGGL(fed_probe_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(fed_probe_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void fed_hits_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st) {
+    if (evlfu) hipLaunchKernelGGL(fed_hits_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(fed_hits_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void fed_list_launch(const FedListArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(fed_list_kernel, dim3((unsigned)grid), dim3(64), 0, st, a);
+}
+
+void sa_repoint_fed_launch(const RepointArgs &a, const FedSrc &f, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(sa_repoint_fed_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, f);
 }
 
 }  // namespace evs

@@ -178,6 +178,7 @@ class GpuCache:
         ptrs = (C.c_void_p * self.n_tables)(*[_dev_ptr(t) for t in raws])   # pinned host tables: their device-side address
         rows = (C.c_int64 * self.n_tables)(*n_rows)
         _lib.check(_lib.lib().evs_cache_set_backing(self._h, ptrs, rows))
+        self._fed = False   # (an ordinary cache again: the one-call lookups go straight to the library)
 
     def set_file_backing(self, tier):
         """tier: FileTier -- the miss tier is a set of .bin files (registered tables zero-copy, the rest staged by the
@@ -186,6 +187,7 @@ class GpuCache:
         self._backing = tier  # keep alive
         self._backing_ev = None
         _lib.check(_lib.lib().evs_cache_set_file_backing(self._h, tier._h))
+        self._fed = False
 
     def staged_rows(self):
         return int(_lib.lib().evs_cache_staged_rows(self._h))
@@ -304,6 +306,139 @@ class GpuCache:
             d["victim_hits"] = int(s[3])
         return d
 
+    # ---- fed backing: the tier over rows the caller supplies (include/evstore_hip.h: evs_cache_fed_begin) ----
+    def set_fed_backing(self, tables, n_rows):
+        """set_backing where tables[k] may be None: table k is then FED -- the GPU never reads it, and the rows of its missing
+        keys come from the caller between lookup_begin and lookup_finish (or from set_row_source's function).  n_rows: the row
+        count of every table.  Tensors that are given are read in place (HBM or pinned host memory), as set_backing reads
+        them.  A fed cache runs 'fetch-first' (set_miss_order) and serves lookup_begin / lookup_finish[_interact] only."""
+        tables, n_rows = list(tables), [int(v) for v in n_rows]
+        assert len(tables) == self.n_tables and len(n_rows) == self.n_tables
+        rb = self.dim * self.codec // 8
+        for t, n in zip(tables, n_rows):
+            assert t is None or t.numel() * t.element_size() // rb >= n, "a table is shorter than its n_rows"
+        self._backing = tables   # keep alive
+        self._n_rows = n_rows
+        self._backing_ev = None
+        ptrs = (C.c_void_p * self.n_tables)(*[None if t is None else _dev_ptr(t) for t in tables])
+        rows = (C.c_int64 * self.n_tables)(*n_rows)
+        _lib.check(_lib.lib().evs_cache_set_fed_backing(self._h, ptrs, rows))
+        self._fed = any(t is None and n > 0 for t, n in zip(tables, n_rows))
+        return self
+
+    def set_row_source(self, fn):
+        """fn(keys) -> rows: keys a uint64 numpy array of table_1based << 32 | row, rows (n, row_bytes) uint8 in the cache's
+        codec -- numpy or tensor, host or device (FileTier.fetch is such a function).  With a source set, lookup_batch /
+        lookup_interact on a fed cache run lookup_begin -> fn -> a copy into a device block this object owns -> lookup_finish.
+        None takes the source away."""
+        self._row_source = fn
+        return self
+
+    def _fetch_fed(self, keys):
+        """the source's rows for `keys` in this object's device block (None for an empty list)"""
+        import numpy as np
+        n = int(keys.numel())
+        if n == 0:
+            return None
+        rb = self.dim * self.codec // 8
+        got = self._row_source(keys.cpu().numpy().view(np.uint64))
+        got = got if isinstance(got, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(got))
+        if got.dtype != torch.uint8:
+            got = got.contiguous().view(torch.uint8)
+        if got.numel() != n * rb:
+            raise _lib.EvsError(_lib.EVS_EINVAL, "the row source returned %d bytes for %d keys of %d-byte rows" % (got.numel(), n, rb))
+        blk = getattr(self, "_fed_block", None)
+        if blk is None or blk.shape[0] < n:
+            blk = self._fed_block = torch.empty((max(n, 256), rb), dtype=torch.uint8, device=self.device)
+        blk[:n].copy_(got.reshape(n, rb), non_blocking=False)
+        return blk[:n]
+
+    def _via_source(self, rows, hit, finish):
+        """begin -> the row source -> finish; whatever fails in between leaves no call open"""
+        hit, keys = self.lookup_begin(rows, hit)
+        try:
+            return hit, finish(self._fetch_fed(keys))
+        except BaseException:
+            if self._fed_call is not None:
+                try:
+                    self.lookup_abort()
+                except _lib.EvsError:   # (the library had already spent the call)
+                    self._fed_call = None
+            raise
+
+    def lookup_begin(self, rows, hit=None):
+        """First half of a lookup on a fed cache: the probe.  -> (hit, keys): hit the (B, n_tables) strict snapshot flags, keys
+        an int64 device tensor (a view of a buffer this object owns, valid until the next begin) with every distinct missing
+        key of a fed table once, as table_1based << 32 | row, in no particular order.  Synchronises.  `rows` and `hit` must
+        stay alive until the finish; everything else on this cache is refused until lookup_finish[_interact] or lookup_abort."""
+        B = _check_batch(self, rows, None, hit)
+        if hit is None:
+            hit = torch.empty((B, self.n_tables), dtype=torch.uint8, device=self.device)
+        kb = getattr(self, "_fed_keys", None)
+        if kb is None or kb.numel() < B * self.n_tables:
+            kb = self._fed_keys = torch.empty(B * self.n_tables, dtype=torch.int64, device=self.device)
+        n = C.c_int64()
+        _lib.check(_lib.lib().evs_cache_fed_begin(self._h, B, rows.data_ptr(), hit.data_ptr(), kb.data_ptr(), C.byref(n),
+                                                  torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = (rows, hit, B, int(n.value))   # keep alive
+        return hit, kb[:int(n.value)]
+
+    def _fed_args(self, fed):
+        if getattr(self, "_fed_call", None) is None:
+            raise _lib.EvsError(_lib.EVS_ESTATE, "lookup_finish: no call is open on this cache (lookup_begin)")
+        _, _, B, n = self._fed_call
+        rb = self.dim * self.codec // 8
+        if fed is None:
+            return B, 0, 0
+        if not (fed.is_cuda and fed.dim() == 2 and fed.shape[0] >= n and fed.shape[1] * fed.element_size() == rb and
+                fed.stride(1) == 1):
+            raise ValueError("fed must be a device tensor of at least %d rows of %d bytes with unit inner stride, got %s %s" %
+                             (n, rb, tuple(fed.shape), fed.dtype))
+        return B, fed.data_ptr(), int(fed.stride(0)) * fed.element_size() if fed.shape[0] > 1 else rb
+
+    def lookup_finish(self, fed, out=None):
+        """Second half: fed[i] is the row of keys[i] (device tensor, (n, row_bytes) uint8 or (n, dim) fp32 for codec 32; None
+        when the list was empty).  Runs the update, the re-point and the row consumer -> out (B, n_tables, dim) fp32.  `fed`
+        must stay unchanged until this call's kernels have run on the stream."""
+        B, ptr, stride = self._fed_args(fed)
+        if out is None:
+            out = torch.empty((B, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * self.n_tables * self.dim):
+            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * self.n_tables * self.dim))
+        _lib.check(_lib.lib().evs_cache_fed_finish(self._h, ptr, stride, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = None
+        return out
+
+    def lookup_finish_interact(self, fed, x, itself=False, out=None):
+        """lookup_finish with the fused interaction as the consumer -> out (B, dim + P), as lookup_interact returns it."""
+        B, ptr, stride = self._fed_args(fed)
+        F = self.n_tables + 1
+        P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
+        if out is None:
+            out = torch.empty((B, self.dim + P), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * (self.dim + P)):
+            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * (self.dim + P)))
+        if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (B, self.dim) and x.stride(1) == 1):
+            raise ValueError("x must be a (B, %d) fp32 device tensor with unit inner stride" % self.dim)
+        _lib.check(_lib.lib().evs_cache_fed_finish_interact(
+            self._h, ptr, stride, x.data_ptr(), int(x.stride(0)) if B > 1 else self.dim, int(bool(itself)), out.data_ptr(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = None
+        return out
+
+    def lookup_abort(self):
+        """Drops the open call: nothing was inserted, the batch is not counted, the same begin lists the same keys."""
+        _lib.check(_lib.lib().evs_cache_fed_abort(self._h))
+        self._fed_call = None
+
+    def fed_stats(self):
+        """Counters of the fed form, cumulative: 'calls' (finished), 'keys' (listed), 'missed' (missed positions of fed
+        tables) and 'from_block' (of those, served straight from the fed block: the key's set took 8 new keys in that call).
+        Synchronises."""
+        s = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().evs_cache_fed_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
+        return {"calls": int(s[0]), "keys": int(s[1]), "missed": int(s[2]), "from_block": int(s[3])}
+
     def set_batch_approx(self, thres):
         """The approximate-embedding mode of lookup_batch / lookup_interact on an 'evlfu' set-associative tier: a sample with at
         least `thres` of its T keys resident has every missed position served the row of its nearest earlier hit (a row of
@@ -331,6 +466,8 @@ class GpuCache:
         number (LFU: counter + 1 once per batch), every distinct missed key inserted into its own set over a free way, else
         the least recently touched / least frequently counted way the running batch has not touched."""
         B = _check_batch(self, rows, out, hit)
+        if getattr(self, "_row_source", None) is not None and getattr(self, "_fed", False):
+            return self._via_source(rows, hit, lambda fed: self.lookup_finish(fed, out))
         if out is None:
             out = torch.empty((B, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
         if hit is None:
@@ -347,6 +484,8 @@ class GpuCache:
         F = self.n_tables + 1
         P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
         B = _check_batch(self, rows, out, hit, out_cols=self.dim + P)
+        if getattr(self, "_row_source", None) is not None and getattr(self, "_fed", False):
+            return self._via_source(rows, hit, lambda fed: self.lookup_finish_interact(fed, x, itself, out))
         if out is None:
             out = torch.empty((B, self.dim + P), dtype=torch.float32, device=self.device)
         if hit is None:

@@ -828,6 +828,68 @@ EVS_API int evs_cache_set_miss_order(evs_cache *c, int order);
  * The fourth word stays 0 for a tier alone.
  * EVS_EINVAL for a NULL cache or a NULL out4, before the device is touched. */
 EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
+/* FED BACKING: the set-associative tier over rows the caller supplies -- the fetch-first chain cut in two where the bus fetch sits.
+ * evs_cache_set_fed_backing is evs_cache_set_backing, except that tables[k] may be NULL for a table with n_rows[k] > 0.  Such a
+ * table is a FED TABLE: the GPU never reads it, its missing rows come from the caller between evs_cache_fed_begin and
+ * evs_cache_fed_finish (a file larger than the pinned budget, a key-value store, a parameter server: whatever answers
+ * "rows for keys").  Non-NULL tables are read in place as today, from HBM or from pinned host memory.  A cache with at least one
+ * fed table is a FED CACHE; evs_cache_set_backing / evs_cache_set_file_backing make it an ordinary one again.
+ * EVS_EINVAL: a NULL argument, more than 32 tables, a negative row count.
+ *
+ * THE RULE.  A begin + finish pair is batch n of the cache under the fetch-first contract written at evs_cache_set_miss_order;
+ * nothing else changes.  Given rows equal to the table rows, flags, outputs, evs_cache_batch_dump, evs_cache_batch_stats (with
+ * hist) and evs_cache_fetch_stats are what the same calls leave on a fetch-first cache over the same tables in HBM, on every
+ * call whose outcome does not depend on timing.  Stronger than that: a served row of a fed table is always, byte for byte, a row
+ * the caller fed for that key -- from the arena once it is installed, from the fed block itself for a position whose set took 8
+ * new keys in the call (the chain's "left in place").
+ *
+ * evs_cache_fed_begin(c, B, rows, hit, keys, n_keys_host, stream) runs the pending EvLFU flush and the fetch-first probe (a form
+ *   that leaves the way words alone: see the abort): hit
+ *   (device, B * T) carries strict snapshot flags exactly as evs_cache_lookup_batch at order 1 writes them.  It then builds the
+ *   FED LIST: every distinct valid key of a fed table with flag 0, exactly once, as table_1based << 32 | row (the format
+ *   evs_filetier_fetch takes), in no particular order.  keys is device-addressable memory (device or pinned host, 8-byte
+ *   aligned) with room for B * T entries.  The call synchronises the stream and writes the count to *n_keys_host.  Not in the
+ *   list: an index out of range (no key: flag 0, a zero row; the finish raises the sticky flag of evs_check_index_errors for
+ *   it), a key of an addressed table, a hit.  rows and hit must stay valid until the finish.
+ * evs_cache_fed_finish(c, fed, fed_stride_bytes, out, stream) / evs_cache_fed_finish_interact(c, fed, fed_stride_bytes, x,
+ *   x_stride, itself, R, stream) run the update, the re-point, the consumers (evs_cache_lookup_batch's out / evs_cache_lookup_
+ *   interact's R) and the close bookkeeping.  fed is DEVICE memory: row i, in the cache's codec, is at fed + i * fed_stride_bytes
+ *   and is the row of keys[i].  fed and fed_stride_bytes are multiples of what a table gives its rows -- the largest of 16, 8,
+ *   4, 2, 1 that divides the row size -- and the stride is at least the row size.  fed == NULL is accepted when the list was
+ *   empty.  fed must stay valid until the consumers have run, in stream order; afterwards every installed key lives in the arena.
+ * evs_cache_fed_abort(c) drops the open call: nothing was inserted, the batch is not counted -- neither its requests nor the
+ *   hits its probe saw -- its ordinal and its stamp are given back, and the cache serves on.  The begin writes no way word (the
+ *   LRU / LFU touch and EvLFU's raise of the ways a call hits are the finish's first launch), so the tier, evs_cache_batch_stats
+ *   with hist, evs_cache_batch_dump with its scores and the other counters are what they were before the begin, whatever batch
+ *   follows; the same begin lists the same keys.  Nothing is launched and no stream is touched.  (An EvLFU flush that an
+ *   EARLIER close asked for and the begin ran is the tier's, not the call's: evs_cache_batch_stats runs it as well.)
+ * evs_cache_fed_stats(c, out4, stream): cumulative [calls finished, keys listed, missed positions of fed tables, positions served
+ *   straight from a fed block].  Synchronises the stream.
+ *
+ * THE ENVELOPE, checked at the begin before anything is allocated (the cache stays usable, the message names the policy): a tier
+ * alone; batch policy 2, given or resolved; 8-way sets; evs_cache_set_miss_order(c, 1); EvLFU over the two-copy arena, LRU or
+ * LFU; all four codecs (the interact form: evs_cache_lookup_interact's dimensions; a reduced-precision cache with its addressed
+ * tables in HBM).  Refused:
+ *   a fed cache at order 0                                         EVS_EINVAL, naming fetch-first
+ *   a threshold of evs_cache_set_batch_approx in force               EVS_EINVAL
+ *   evs_cache_lookup_batch / _lookup_interact on a fed cache         EVS_ESTATE, naming the begin / finish calls
+ *   evs_cache_lookup_bags / _lookup_bags_interact                    EVS_ESTATE
+ *   a fed cache as a tier of any pair / triple call (batched, bags, the exact request, the tier server)   EVS_EINVAL
+ *   evs_cache_batch_export / _batch_load / _pair_load                EVS_EINVAL
+ *   evs_cache_request, the resident server, evs_cache_exact_load     EVS_ESTATE
+ *   evs_cache_update_rows / _refresh_rows (no table to write or to read again: the file-backed case)   EVS_ESTATE
+ * Protocol errors are EVS_ESTATE: a begin on a cache without a fed table; finish or abort without an open call; a second begin;
+ * any other batched call, stats, dump, export, load, row update or change of backing while a call is open.  evs_cache_destroy
+ * with an open call is fine.  Argument errors are EVS_EINVAL and leave an open call open: NULL arguments, B < 1, fed == NULL with
+ * a non-empty list, a misaligned fed or stride, a stride below the row size.  A consumer that refuses behind the update ends the
+ * call as it ends evs_cache_lookup_batch: the batch is not counted. */
+EVS_API int evs_cache_set_fed_backing(evs_cache *c, const void *const *tables, const int64_t *n_rows);
+EVS_API int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream);
+EVS_API int evs_cache_fed_finish(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *out, void *stream);
+EVS_API int evs_cache_fed_finish_interact(evs_cache *c, const void *fed, int64_t fed_stride_bytes, const float *x, int64_t x_stride, int itself,
+                                          float *R, void *stream);
+EVS_API int evs_cache_fed_abort(evs_cache *c);
+EVS_API int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream);
 /* The approximate-embedding mode of the batched EvLFU rule (the reference: cache_algo/EvLFU_C1.py:122-125, :142-152 -- a request
  * whose agg_hit reaches approx_emb_thres does not fetch its missing rows; each reuses the vector of the hit before it and is
  * reported as a hit; nothing is inserted for it).  The exact batch-1 engines take it as evs_cache_request's approx_thres; this is

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""The set-associative cache tier over caller-fed rows (GpuCache.set_fed_backing; lookup_begin / lookup_finish_interact) beside the
+fetch-first chain it is cut from, as ONE JSON file.
+
+Shape (tools/policy_compare.py's): the Criteo-Kaggle cardinalities, fp32, d = 36, a 10 % EvLFU tier, B = 16 384, rows Zipf(0.75),
+the interaction as the consumer.  Every configuration is warmed until its size stops growing; then --steps batches are timed, the
+configurations alternating on the SAME batches in one process:
+    a  fetch-first over HBM tables                      -- the yardstick
+    b  fetch-first over pinned host tables
+    c  fed, a DEVICE source: one index_select from the HBM tables (what a GPU-side store would do)
+    d  fed, a HOST source: a numpy gather and one host-to-device copy (what a file, a key-value store or a remote server would do)
+A begin synchronises, so every call is timed by the host clock between two synchronises (a and b too: `wall_us`); a and b are
+also timed by a pair of device events as everywhere else (`median_us`).  c and d are split into begin (flush, probe, list launch,
+the synchronise and the 4-byte copy of the count), source and finish (update, re-point, consumer), and report the keys listed
+and the positions served straight from the fed block per batch.  `begin_over_a_us` is what the seam costs over the yardstick
+before a single row is fetched: c's begin + finish against a's call.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+import evstore_dlrm_amd as E  # noqa: E402
+from tools.host_setassoc_bench import pinned_tables  # noqa: E402
+
+NAMES = ("a_fetch_first_hbm", "b_fetch_first_pinned", "c_fed_device_source", "d_fed_host_source")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frac", type=float, default=0.10)
+    ap.add_argument("--batch", type=int, default=16384)
+    ap.add_argument("--alpha", type=float, default=0.75)
+    ap.add_argument("--steps", type=int, default=100, help="timed batches")
+    ap.add_argument("--max-warm", type=int, default=150, help="at most this many warm-up batches")
+    ap.add_argument("--scale", type=float, default=1.0, help="every table's rows times this")
+    ap.add_argument("--dim", type=int, default=36)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fed_backing.json"))
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    d, B = args.dim, args.batch
+    ln, ev, pinned, scale = pinned_tables(bench.KAGGLE_LN, d, args.scale, dev)
+    T = len(ln)
+    cap = int(args.frac * sum(ln))
+    rb = d * 4
+    # the sources: every table behind one base offset, on the device and on the host
+    base_np = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int64)
+    base_dev = torch.from_numpy(base_np).to(dev)
+    all_dev = torch.cat([ev.fp32_view(k) for k in range(T)])
+    all_host = np.concatenate([p.numpy() for p in pinned])
+
+    def device_source(keys):   # keys: int64 device tensor
+        return all_dev.index_select(0, base_dev[(keys >> 32) - 1] + (keys & 0xffffffff))
+
+    def host_source(keys):
+        k = keys.cpu().numpy()
+        return torch.from_numpy(all_host[base_np[(k >> 32) - 1] + (k & 0xffffffff)]).to(dev)
+
+    sources = {"c_fed_device_source": device_source, "d_fed_host_source": host_source}
+    n_b = args.max_warm + args.steps
+    rows = [b[1].t().contiguous().to(torch.int32) for b in bench.make_batches(ln, B, n_b, seed=3, device=dev, dist="zipf", alpha=args.alpha)]
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    out = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+    hit = torch.empty((B, T), dtype=torch.uint8, device=dev)
+
+    def call(name, c, r, split=None):
+        if name in sources:
+            t0 = time.perf_counter()
+            _, keys = c.lookup_begin(r, hit)                # (synchronises)
+            t1 = time.perf_counter()
+            fed = sources[name](keys) if keys.numel() else None
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            c.lookup_finish_interact(fed, x, out=out)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            if split is not None:
+                split.append((t1 - t0, t2 - t1, t3 - t2, int(keys.numel())))
+        else:
+            c.lookup_interact(r, x, out=out, hit=hit)
+
+    caches, warm = {}, {}
+    for name in NAMES:
+        c = E.GpuCache("evlfu", cap, T, d, 32, "python", dev).set_miss_order("fetch-first")
+        if name in sources:
+            c.set_fed_backing([None] * T, ln)
+        else:
+            c.set_backing(pinned if name.startswith("b_") else ev)
+        size = -1
+        for i in range(args.max_warm):
+            call(name, c, rows[i])
+            if i % 10 == 9:
+                s = c.batch_stats()["size"]
+                if s <= size:
+                    break
+                size = s
+        caches[name], warm[name] = c, i + 1
+        print("fed_backing_bench: %s warm after %d batches, size %d of %d" % (name, i + 1, c.batch_stats()["size"], cap), file=sys.stderr, flush=True)
+    timed = rows[args.max_warm:]
+    s0 = {n: (caches[n].batch_stats(), caches[n].fetch_stats(), caches[n].fed_stats()) for n in NAMES}
+    events, wall, split = {n: [] for n in NAMES}, {n: [] for n in NAMES}, {n: [] for n in sources}
+    for r in timed:
+        for n in NAMES:
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            call(n, caches[n], r, split.get(n))
+            e1.record()
+            torch.cuda.synchronize()
+            wall[n].append(time.perf_counter() - t0)
+            events[n].append((e0, e1))
+    res = {}
+    for n in NAMES:
+        s1, f1, fs1 = caches[n].batch_stats(), caches[n].fetch_stats(), caches[n].fed_stats()
+        w = np.array(wall[n]) * 1e6
+        res[n] = {"wall_us": round(float(np.median(w)), 2), "wall_p95_us": round(float(np.percentile(w, 95)), 2),
+                  "hit_rate": round((s1["n_hits"] - s0[n][0]["n_hits"]) / (T * B * len(timed)), 4), "size": s1["size"],
+                  "warm_batches": warm[n], "fetch_stats_delta": {k: f1[k] - s0[n][1][k] for k in f1}}
+        if n in sources:
+            sp = np.array(split[n], np.float64)
+            res[n].update({"begin_us": round(float(np.median(sp[:, 0])) * 1e6, 2), "source_us": round(float(np.median(sp[:, 1])) * 1e6, 2),
+                           "finish_us": round(float(np.median(sp[:, 2])) * 1e6, 2), "keys_per_batch": round(float(sp[:, 3].mean()), 1),
+                           "fed_bytes_per_batch": round(float(sp[:, 3].mean()) * rb),
+                           "fed_stats_delta": {k: fs1[k] - s0[n][2][k] for k in fs1}})
+        else:
+            us = np.array([a.elapsed_time(b) * 1e3 for a, b in events[n]])
+            res[n].update({"median_us": round(float(np.median(us)), 2), "p95_us": round(float(np.percentile(us, 95)), 2)})
+        print("fed_backing_bench: %s %s" % (n, res[n]), file=sys.stderr, flush=True)
+    a = res["a_fetch_first_hbm"]["wall_us"]
+    c_ = res["c_fed_device_source"]
+    doc = {"tool": "fed_backing_bench", "device": torch.cuda.get_device_name(0),
+           "shape": {"rows": sum(ln), "table_scale": scale, "capacity": cap, "frac": args.frac, "batch": B, "dim": d, "row_bytes": rb,
+                     "zipf_alpha": args.alpha, "timed_batches": len(timed), "policy": "evlfu",
+                     "consumer": "lookup_interact / lookup_finish_interact (the fused interaction through the address table)"},
+           "timing": "host clock between two synchronises around every call (wall_us; begin / source / finish each end on a synchronise); "
+                     "a and b also by a pair of device events (median_us); the configurations alternate on the same batches in one process",
+           "configs": res,
+           "begin_over_a_us": round(c_["begin_us"] + c_["finish_us"] - a, 2),
+           "c_over_a": round(c_["wall_us"] / a, 3), "d_over_a": round(res["d_fed_host_source"]["wall_us"] / a, 3),
+           "b_over_a": round(res["b_fetch_first_pinned"]["wall_us"] / a, 3)}
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"tool": "fed_backing_bench", "a_wall_us": a, "c_over_a": doc["c_over_a"], "d_over_a": doc["d_over_a"],
+                      "begin_over_a_us": doc["begin_over_a_us"], "out": args.out}))
+
+
+if __name__ == "__main__":
+    main()
