@@ -3540,7 +3540,12 @@ struct evs_cache {
         long long n_keys = 0;
         unsigned slot_mask = 0;
         long long stamp_counter0 = 0;   // what evs_cache_fed_abort puts back
+        // the bag form (evs_cache_fed_begin_bags): the chain's arguments over the bag slab, which the open call owns until it ends
+        bool bags = false;
+        evs::BagArgs ba;
+        int bag_grid = 0, bag_stamp = 0;
     } fedc;
+    long long fed_max_rec = 0;      // the records rec_slot has room for (the two forms round a call's lists differently)
 };
 // The tier pair / triple as a resident server (cache_c1c2_serve_kernel): the single-tier server's mailbox and ring rules, owned
 // by an object of its own because the state it mutates belongs to two or three handles.  Every entry point that reads or
@@ -5701,7 +5706,8 @@ static int fed_scratch(evs_cache *c, long long n_pos, long long n_rec, hipStream
     using namespace evs;
     { const int rc = ensure_counters(&c->fed_cnt, 2 * sizeof(unsigned long long) + (size_t)kReplicas * kPartCols * sizeof(int), st, who, "fed-backing"); if (rc) return rc; }
     c->fed_part1 = reinterpret_cast<int *>(c->fed_cnt + 2);
-    if (n_pos <= c->fed_max_pos) return EVS_OK;
+    if (n_pos <= c->fed_max_pos && n_rec <= c->fed_max_rec) return EVS_OK;
+    n_pos = std::max(n_pos, c->fed_max_pos); n_rec = std::max(n_rec, c->fed_max_rec);
     long long slots = 64;
     while (slots < 2 * n_pos) slots <<= 1;
     unsigned long long *slot_key = nullptr; int *slot_index = nullptr, *rec_slot = nullptr, *n = nullptr;
@@ -5711,7 +5717,7 @@ static int fed_scratch(evs_cache *c, long long n_pos, long long n_rec, hipStream
     if (!sp.carve(&slab)) { set_error("%s: allocating the fed-list scratch of a call of %lld positions failed", who, n_pos); return EVS_ENOMEM; }
     if (c->slab_fed) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(c->slab_fed); }
     c->slab_fed = slab; c->fed_slot_key = slot_key; c->fed_slot_index = slot_index; c->fed_rec_slot = rec_slot; c->fed_n = n;
-    c->fed_max_pos = n_pos;
+    c->fed_max_pos = n_pos; c->fed_max_rec = n_rec;
     return EVS_OK;
 }
 static evs::FedSrc fed_src(evs_cache *c, const void *fed, int64_t stride) {
@@ -5788,7 +5794,7 @@ extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows,
         hipStreamSynchronize(st) != hipSuccess) {
         (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return fail(EVS_EHIP);
     }
-    o.open = true; o.B = B; o.rows = rows; o.hit = hit; o.n_keys = n;
+    o.open = true; o.bags = false; o.B = B; o.rows = rows; o.hit = hit; o.n_keys = n;
     *n_keys_host = n;
     return EVS_OK;
 }
@@ -5799,6 +5805,11 @@ static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float 
     EVS_REQUIRE(c, "%s: NULL cache", who);
     evs_cache::FedOpen &o = c->fedc;
     if (!o.open) { set_error("%s: no fed call is open on this %s cache (evs_cache_fed_begin)", who, policy_name(c->host.policy)); return EVS_ESTATE; }
+    if (o.bags) {   // (the call stays open)
+        set_error("%s: the call open on this %s cache is a bag call (evs_cache_fed_begin_bags): finish it with evs_cache_fed_finish_bags / "
+                  "_fed_finish_bags_interact, or drop it with evs_cache_fed_abort", who, policy_name(c->host.policy));
+        return EVS_ESTATE;
+    }
     // argument errors leave the call open: finish again, or abort
     const int rb = c->host.row_bytes;
     const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
@@ -5958,6 +5969,36 @@ static int bag_pool_grow(evs_cache *c, int T, int64_t B, int d, hipStream_t st, 
     c->bag_pool = pool; c->bag_pool_floats = (long long)T * B * d;
     return EVS_OK;
 }
+// The bag slab of a tier alone, for calls of up to n_pos positions and B samples: pointer table, flag bytes, a miss list per block
+// of the probe's grid, the samples' words; EvLFU: the provisional records, the position -> sample map and the counts.  A cache
+// with fed tables keeps the provisional records whatever its policy (evs_cache_fed_begin_bags: the finish reads them).  Grown with
+// the largest call: the new slab first, the old one goes only when the new one exists.
+static int bag_slab_grow(evs_cache *c, long long n_pos, int64_t B, hipStream_t st, const char *who) {
+    using namespace evs;
+    const bool evlfu = c->host.policy == kEvLFU;
+    const bool want_prov = evlfu || c->fed_mask != 0;
+    if (n_pos <= c->bag_max_pos && B <= c->bag_max_b && (!want_prov || c->bag_prov)) return EVS_OK;
+    const long long np = std::max<long long>(n_pos, c->bag_max_pos), nb = std::max<long long>(B, c->bag_max_b);
+    long long *ptrs = nullptr; unsigned char *flags = nullptr; uint4 *rec = nullptr; int *cnt = nullptr, *sample = nullptr;
+    void *slab = nullptr;
+    SlabPlan sp;
+    sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, bag_list_records(np) * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
+    sp.add(&sample, nb * 4);
+    uint4 *prov = nullptr; int *pos_sample = nullptr, *agg = nullptr;
+    if (want_prov) sp.add(&prov, np * 16);
+    if (evlfu) { sp.add(&pos_sample, np * 4); sp.add(&agg, nb * 4); }
+    if (!sp.carve(&slab)) { set_error("%s: allocating the buffers of a call of %lld lookups failed", who, n_pos); return EVS_ENOMEM; }
+    if (c->slab_bags) {
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        (void)hipFree(c->slab_bags);
+    }
+    c->slab_bags = slab;
+    c->bag_ptrs = ptrs; c->bag_hit = flags; c->bag_rec = rec; c->bag_list_cnt = cnt; c->bag_sample = sample;
+    c->bag_prov = prov; c->bag_pos_sample = pos_sample; c->bag_agg = agg;
+    c->bag_max_pos = np; c->bag_max_b = nb;
+    EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
+    return EVS_OK;
+}
 // R = the dense interaction of x and the T pooled tables of that block
 static int bag_pool_interact(const float *pool, int T, int64_t B, int d, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
     const float *feats[EVS_MAX_FEATURES];
@@ -5992,7 +6033,8 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
     const bool evlfu = c->host.policy == kEvLFU;
     { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
-    { const int rc = fed_refuse(c, who, EVS_ESTATE, "the fed form is the (B, T) lookup's (evs_cache_fed_begin / evs_cache_fed_finish); it has no bag form"); if (rc) return rc; }
+    { const int rc = fed_refuse(c, who, EVS_ESTATE, "its missing rows come from the caller, between evs_cache_fed_begin_bags and evs_cache_fed_finish_bags / "
+                                "_fed_finish_bags_interact -- the one-call bag lookups cannot ask for them"); if (rc) return rc; }
     EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule says what a request's hit count is over bags "
                 "(its priority counts a request's hit keys); lru / lfu caches take ragged bags as they are", who, policy_name(c->host.policy));
     { const int rc = batch_check(c, who); if (rc) return rc; }
@@ -6023,27 +6065,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
 
-    // (a miss list per block of the probe's grid)
-    if (n_pos > c->bag_max_pos || B > c->bag_max_b) {   // grow: the new slab first, the old one goes only when the new one exists
-        const long long np = std::max<long long>(n_pos, c->bag_max_pos), nb = std::max<long long>(B, c->bag_max_b);
-        long long *ptrs = nullptr; unsigned char *flags = nullptr; uint4 *rec = nullptr; int *cnt = nullptr, *sample = nullptr;
-        void *slab = nullptr;
-        SlabPlan sp;
-        sp.add(&ptrs, np * 8); sp.add(&flags, np); sp.add(&rec, bag_list_records(np) * 16); sp.add(&cnt, (long long)kProbeGridMax * 4);
-        sp.add(&sample, nb * 4);
-        uint4 *prov = nullptr; int *pos_sample = nullptr, *agg = nullptr;
-        if (evlfu) { sp.add(&prov, np * 16); sp.add(&pos_sample, np * 4); sp.add(&agg, nb * 4); }
-        if (!sp.carve(&slab)) { set_error("%s: allocating the buffers of a call of %lld lookups failed", who, n_pos); return EVS_ENOMEM; }
-        if (c->slab_bags) {
-            EVS_HIP_CHECK(hipStreamSynchronize(st));
-            (void)hipFree(c->slab_bags);
-        }
-        c->slab_bags = slab;
-        c->bag_ptrs = ptrs; c->bag_hit = flags; c->bag_rec = rec; c->bag_list_cnt = cnt; c->bag_sample = sample;
-        c->bag_prov = prov; c->bag_pos_sample = pos_sample; c->bag_agg = agg;
-        c->bag_max_pos = np; c->bag_max_b = nb;
-        EVS_HIP_CHECK(hipMemsetAsync(sample, 0, nb * 4, st));
-    }
+    { const int rc = bag_slab_grow(c, n_pos, B, st, who); if (rc) return rc; }
     if (interact) { const int rc = bag_pool_grow(c, T, B, d, st, who); if (rc) return rc; }
     c->used = 2;
     c->batch_calls++;
@@ -6132,6 +6154,195 @@ extern "C" int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int
     using namespace evs;
     EVS_REQUIRE(B <= 0 || (x && R), "evs_cache_lookup_bags_interact: NULL x / R");
     return cache_bags_impl(c, B, indices, offsets, nnz, nullptr, 0, 0, x, x_stride, itself, R, hit, stream, "evs_cache_lookup_bags_interact");
+}
+
+// ---- ragged bags over fed backing: the count-first fetch-first bag chain cut in two (the contract: include/evstore_hip.h at
+// evs_cache_fed_begin_bags; the kernels: evs_cache_policy.h at bags_fed_probe_launch) -------------------------------------------
+//   begin    (EvLFU: flush ->) bags_fed_probe -> (EvLFU: bags_count -> bags_fed_list) -> fed_list -> synchronise
+//   finish   fold -> bags_fed_hits -> the fed insert of the policy -> bags_repoint_fed -> bags_pool (-> dense interaction) -> close
+// The begin writes no way word and counts into the call's own replica rows (fed_part1), so evs_cache_fed_abort serves both forms.
+// The open call owns the bag slab until it ends: every other batched call is refused meanwhile (fed_open_refuse).
+extern "C" int evs_cache_fed_begin_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
+                                        uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_fed_begin_bags";
+    EVS_REQUIRE(c, "%s: NULL cache", who);
+    EVS_REQUIRE(indices && offsets && nnz && keys && n_keys_host, "%s: NULL argument", who);
+    EVS_REQUIRE(B >= 1, "%s: B = %lld", who, (long long)B);
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys) % 8 == 0, "%s: keys must be 8-byte aligned", who);
+    { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    { const int rc = fed_call_check(c, who); if (rc) return rc; }
+    const bool evlfu = c->host.policy == kEvLFU;
+    EVS_REQUIRE(!evlfu || c->bag_rule == 1, "%s: an %s cache has no bag form until evs_cache_set_bag_rule(c, 1) says what a request's hit count is over bags", who,
+                policy_name(c->host.policy));
+    EVS_REQUIRE(!evlfu || c->bag_count == 1, "%s: the bag form of a fed %s cache runs fetch-first, so it needs the samples' counts in front of the update: "
+                "tell evs_cache_set_bag_count(c, 1) before the first call", who, policy_name(c->host.policy));
+    BagCall bc;
+    {   // (the outputs are the finish's: the checks of the bag form run here with a stand-in for them)
+        alignas(16) static const float stand_in[4] = {0.f, 0.f, 0.f, 0.f};
+        const int rc = bag_call_check(who, B, indices, offsets, nnz, stand_in, 0, 0, nullptr, 0, nullptr, [&](int &T, int &d) -> int {
+            T = c->host.n_tables; d = c->host.dim;
+            return EVS_OK;
+        }, bc);
+        if (rc) return rc;
+    }
+    const int T = bc.T, d = bc.d;
+    const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
+    const int piece_bytes = c->host.codec / 2;
+    for (int k = 0; k < T; k++)
+        EVS_REQUIRE(reinterpret_cast<uintptr_t>(c->backing[k]) % piece_bytes == 0, "%s: table %d is not %d-byte aligned", who, k, piece_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = batch_state(c, st, who); if (rc) return rc; }
+    { const int rc = fetch_first_state(c, st, who); if (rc) return rc; }
+    int *err = index_error_flag();
+    if (!err) return EVS_EHIP;
+    { const int rc = bag_slab_grow(c, n_pos, B, st, who); if (rc) return rc; }
+    { const int rc = fed_scratch(c, n_pos, bag_list_records(n_pos), st, who); if (rc) return rc; }
+    evs_cache::FedOpen &o = c->fedc;
+    o.stamp_counter0 = c->stamp_counter;
+    c->used = 2;
+    c->batch_calls++;
+    // (from here on a refusal takes the call's ordinal back)
+    auto fail = [&](int rc) {
+        c->batch_calls--; c->stamp_counter = o.stamp_counter0;
+        if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
+        return rc;
+    };
+    long long slots = 64;
+    while (slots < 2 * n_pos) slots <<= 1;   // (this call's share of the scratch table: what is cleared and walked)
+    o.slot_mask = (unsigned)(slots - 1);
+    if (hipMemsetAsync(c->fed_slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(c->fed_n, 0, 4, st) != hipSuccess ||
+        hipMemsetAsync(c->fed_part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: clearing the fed-list scratch failed", who); return fail(EVS_EHIP);
+    }
+    BagArgs &a = o.ba;
+    a = BagArgs{};
+    PolicyArgs &pa = a.p;
+    pa.sa = c->sa; pa.sau = c->sau;
+    o.bag_stamp = 0;
+    if (evlfu) {
+        o.bag_stamp = next_batch_stamp(c);
+        sampled_flush_if_wanted(c, st);   // (asked for by an earlier close: the tier's, not this call's -- it stands if the call is dropped)
+    } else {
+        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    }
+    pa.requests = nullptr; pa.hit = hit ? hit : c->bag_hit; pa.row_ptrs = c->bag_ptrs; pa.row_ids = nullptr;
+    pa.miss_rec = c->bag_rec; pa.list_cnt = c->bag_list_cnt; pa.list_cap = (int)(iters * 256);
+    pa.part1 = c->fed_part1; pa.part2 = c->part2;   // (the begin's totals: folded by the finish, never counted for a dropped call)
+    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = k < T ? c->backing_rows[k] : 0; }
+    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
+    a.pos0[0] = 0;
+    for (int k = 0; k < 32; k++) {
+        a.indices[k] = k < T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
+        a.offsets[k] = k < T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
+        a.pos0[k + 1] = a.pos0[k] + (k < T ? nnz[k] : 0);
+    }
+    a.n_pos = n_pos; a.iters = (int)iters; a.err = err;
+    a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
+    a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
+    a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
+    a.pool_flags = pa.hit;
+    a.pool_only = evlfu ? 1 : 0;
+    if (grid) bags_fed_probe_launch(a, (int)grid, st);
+    if (evlfu) {
+        bags_count_launch(a, st);   // (column 39 into the call's rows; sample_cnt is zero again behind it)
+        if (grid) bags_fed_list_launch(a, (int)grid, st);
+    }
+    if (grid) {
+        FedListArgs la{};
+        la.miss_rec = c->bag_rec; la.list_cnt = c->bag_list_cnt; la.list_cap = pa.list_cap;
+        la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
+        la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
+        la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
+        fed_list_launch(la, (int)grid, st);
+    }
+    int n = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return fail(EVS_EHIP);
+    }
+    o.open = true; o.bags = true; o.B = B; o.rows = nullptr; o.hit = pa.hit; o.n_keys = n; o.bag_grid = (int)grid;
+    *n_keys_host = n;
+    return EVS_OK;
+}
+
+static int fed_finish_bags_impl(evs_cache *c, const void *fed, int64_t stride, float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x,
+                                int64_t x_stride, int itself, float *R, void *stream, const char *who) {
+    using namespace evs;
+    evs_cache::FedOpen &o = c->fedc;
+    const char *pn = policy_name(c->host.policy);
+    if (!o.open) { set_error("%s: no fed call is open on this %s cache (evs_cache_fed_begin_bags)", who, pn); return EVS_ESTATE; }
+    if (!o.bags) {   // (the call stays open)
+        set_error("%s: the call open on this %s cache is a (B, T) call (evs_cache_fed_begin): finish it with evs_cache_fed_finish / _fed_finish_interact, "
+                  "or drop it with evs_cache_fed_abort", who, pn);
+        return EVS_ESTATE;
+    }
+    // argument errors leave the call open: finish again, or abort
+    const bool interact = R != nullptr;
+    const int rb = c->host.row_bytes, T = c->host.n_tables, d = c->host.dim;
+    const int64_t B = o.B;
+    const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
+    EVS_REQUIRE(fed || o.n_keys == 0, "%s: NULL fed with %lld keys listed", who, o.n_keys);
+    if (fed) {
+        EVS_REQUIRE(stride >= rb, "%s: fed_stride_bytes %lld is below the row size of %d bytes", who, (long long)stride, rb);
+        EVS_REQUIRE(reinterpret_cast<uintptr_t>(fed) % align == 0 && stride % align == 0, "%s: fed and fed_stride_bytes must be multiples of %lld bytes "
+                    "(what a table of %d-byte rows gives its rows)", who, (long long)align, rb);
+    }
+    EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
+    if (interact)
+        EVS_REQUIRE(T + 1 <= EVS_MAX_FEATURES && evs_fused_dim_supported(d), "%s: the interaction takes at most %d features and a fused-kernel dim, not T = %d, d = %d",
+                    who, EVS_MAX_FEATURES, T, d);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (interact) { const int rc = bag_pool_grow(c, T, B, d, st, who); if (rc) return rc; }
+    const FedSrc fs = fed_src(c, fed, fed ? stride : 0);
+    const bool evlfu = c->host.policy == kEvLFU;
+    const int grid = o.bag_grid;
+    o.open = false;   // (from here on the call is spent, whatever a consumer says)
+    c->fetch_calls++;
+    BagArgs a = o.ba;
+    a.p.part1 = c->part1;   // (from here on the tier's own rows: the raises' histogram moves, LRU / LFU: the pooling's column 39)
+    a.out = interact ? c->bag_pool : pooled;
+    a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
+    hipLaunchKernelGGL(fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    if (grid) {
+        bags_fed_hits_launch(a, grid, st);   // the touch / the raise of the ways the begin hit, in front of the update
+        if (!evlfu) policy_insert_fed_launch(a.p, fs, grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
+        else {
+            const BatchArgs u = bag_update_args(c, B, o.bag_stamp, c->bag_rec, c->bag_list_cnt, a.p.list_cap, grid);
+            with_row_shape(u.row_bytes, [&](auto s) {
+                using S = decltype(s);
+                hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)grid), dim3(sampled_list_threads(u)), 0, st, u, fs);
+            });
+        }
+        BagRepointFedArgs ra{};
+        ra.sa = c->sa; ra.prov = c->bag_prov; ra.row_ptrs = c->bag_ptrs; ra.arena = c->a.arena; ra.counters = c->fetch_cnt;
+        ra.n_pos = a.n_pos; ra.iters = a.iters; ra.row_bytes = rb;
+        bags_repoint_fed_launch(ra, fs, grid, st);
+    }
+    bags_pool_launch(a, c->host.codec, st);
+    if (interact) {
+        const int rc = bag_pool_interact(c->bag_pool, T, B, d, x, x_stride, itself, R, stream);
+        if (rc) return rc;   // (a consumer that refuses: the batch is not counted)
+    }
+    count_batch(c, B);
+    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
+    c->fed_calls++; c->fed_keys += o.n_keys;
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+extern "C" int evs_cache_fed_finish_bags(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *pooled, int64_t out_table_stride,
+                                         int64_t out_bag_stride, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c && pooled, "evs_cache_fed_finish_bags: NULL %s", c ? "pooled" : "cache");
+    return fed_finish_bags_impl(c, fed, fed_stride_bytes, pooled, out_table_stride, out_bag_stride, nullptr, 0, 0, nullptr, stream, "evs_cache_fed_finish_bags");
+}
+extern "C" int evs_cache_fed_finish_bags_interact(evs_cache *c, const void *fed, int64_t fed_stride_bytes, const float *x, int64_t x_stride, int itself,
+                                                  float *R, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c && x && R, "evs_cache_fed_finish_bags_interact: NULL %s", c ? "x / R" : "cache");
+    return fed_finish_bags_impl(c, fed, fed_stride_bytes, nullptr, 0, 0, x, x_stride, itself, R, stream, "evs_cache_fed_finish_bags_interact");
 }
 
 // ---- ragged bags through the batched C1 + C2 pair (the rule: include/evstore_hip.h at evs_cache_lookup_bags_c1c2) -------------

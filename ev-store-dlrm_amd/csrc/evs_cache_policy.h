@@ -224,6 +224,38 @@ void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, un
 // sa_repoint_launch's (B, T) form for a cache with fed tables
 void sa_repoint_fed_launch(const RepointArgs &a, const FedSrc &f, int grid, hipStream_t st);
 
+// Ragged bags over fed backing (evs_cache_fed_begin_bags; the contract: include/evstore_hip.h there): the count-first fetch-first
+// bag chain cut in two where the fed chain above is cut:
+//   begin    (flush ->) bags_fed_probe -> (EvLFU: bags_count, its column 39 into the call's own replica rows -> bags_fed_list) ->
+//            fed_list, as it is, over the bag slab's lists
+//   finish   fold -> bags_fed_hits -> the fed insert of the policy, as it is -> bags_repoint_fed -> bags_pool (-> dense interaction)
+// All four new kernels walk the flat position list as bags_probe_launch does (block j: positions 256 (j + i grid) + thread,
+// i < iters), so list j and rec_slot line up with what the update walks.  `a` is the BagArgs of bags_probe_launch; prov is written
+// for all three policies (row, table, set, bit 31 | hit way -- or tag + 1 of a miss -- or 0: no key).
+//   bags_fed_probe  flags, addresses (NULL-based for a miss of a fed table), hit totals into a.p.part1, prov; LRU / LFU: the miss
+//                   lists too (their records need no count); EvLFU: pos_sample preset to -1.  Writes NO way word.
+//   bags_fed_list   EvLFU, behind bags_count: bags_raise_list's listing (row, table | agg << 8, set, tag + 1) without its raise.
+//   bags_fed_hits   first launch of the finish: every position prov calls a hit -- LRU / LFU the plain-store touch of the probe,
+//                   once per way and batch; EvLFU the raise to agg[pos_sample[p]] with the histogram moves into a.p.part1 (read
+//                   first, compare-and-swap only while the priority is below).  Nothing else writes a way word in that launch.
+void bags_fed_probe_launch(const BagArgs &a, int grid, hipStream_t st);
+void bags_fed_list_launch(const BagArgs &a, int grid, hipStream_t st);
+void bags_fed_hits_launch(const BagArgs &a, int grid, hipStream_t st);
+// The flat form of sa_repoint_fed_launch, read from prov (no index is loaded, nothing is permuted again): a miss that got a way is
+// pointed at its arena row; a miss of a fed table that got none at its fed row through the scratch table (read-only; a key not found
+// there: the zero row and the sticky flag); a miss of an addressed table that got none keeps its table address.  A position that
+// is no key raises the sticky flag.  counters: the (B, T) form's four ([0] / [1] of `counters`, [0] / [1] of f.counters).
+struct BagRepointFedArgs {
+    SaGeom sa;
+    const uint4 *prov;                     // n_pos records as bags_fed_probe wrote them
+    long long *row_ptrs;                   // n_pos slots of the pointer table
+    unsigned char *arena;
+    unsigned long long *counters;
+    long long n_pos;
+    int iters, row_bytes;
+};
+void bags_repoint_fed_launch(const BagRepointFedArgs &a, const FedSrc &f, int grid, hipStream_t st);
+
 // Fetch-first order of the C1 + C2 pair that shares its set records (both tiers at evs_cache_set_miss_order(c, 1); the chain:
 // evs_cache.hip, batch_c1c2_impl; the rule: include/evstore_hip.h at evs_cache_lookup_batch_c1c2).  The pair has no two-copy
 // arena, so behind the pair's update a way the batch HIT may hold another key.  Every position is searched again in the ways of

@@ -21,6 +21,8 @@
 // count, so the counts come from a pass over the code bytes IN FRONT of the pooling, and the pooling decodes per position.
 // Both tiers at order 1 and "count first":  bags_probe2 -> bags_count2 -> bags_route2 -> cache_batch_sa_list2_kernel ->
 // bags_repoint2 -> bags_pool2 (-> dense interaction), every missing row read once, by the update.
+// Fed backing (evs_cache_fed_begin[_bags]) cuts the fetch-first chains in two where the rows are fetched; its kernels, (B, T) and
+// flat, are described in evs_cache_policy.h at FedSrc and at bags_fed_probe_launch.
 #include <type_traits>
 
 #include "evs_cache_policy.h"
@@ -1033,6 +1035,212 @@ __global__ void __launch_bounds__(64) fed_list_kernel(const FedListArgs args) {
     }
 }
 
+// ---- ragged bags over fed backing (evs_cache_fed_begin_bags; evs_cache_policy.h at bags_fed_probe_launch) --------------------
+// The probe of a bag begin, all three policies: bags_probe_kernel's walk, flags, addresses and hit totals, a provisional record per
+// position whatever the policy (the finish touches / raises and re-points from it: nothing is searched twice, no index is loaded
+// again), and NO write to a way word.  LRU / LFU: the per-block miss lists as bags_probe_kernel writes them.  EVLFU: the lists
+// wait for the counts (bags_fed_list_kernel); pos_sample is preset to "no bag covers it".
+template <bool EVLFU>
+__global__ void __launch_bounds__(256) bags_fed_probe_kernel(const BagArgs args) {
+    __shared__ int s_hits, s_list_n;
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32], s_pos0[32];
+    __shared__ const long long *s_idx[32];
+    __shared__ const unsigned char *s_table[32];
+    const PolicyArgs &pa = args.p;
+    const int T = pa.T;
+    if (threadIdx.x == 0) { s_hits = 0; s_list_n = 0; }
+    if (threadIdx.x < 32) {
+        const bool tab = (int)threadIdx.x < T;
+        s_base[threadIdx.x] = pa.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = tab ? pa.backing_rows[threadIdx.x] : 0;
+        s_table[threadIdx.x] = pa.backing[threadIdx.x];
+        s_idx[threadIdx.x] = args.indices[threadIdx.x];
+        s_pos0[threadIdx.x] = tab ? args.pos0[threadIdx.x] : args.n_pos;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = p < args.n_pos;
+        int k = 0;
+#pragma unroll
+        for (int step = 16; step >= 1; step >>= 1) k += (on && s_pos0[k + step] <= p) ? step : 0;
+        const long long row = on ? s_idx[k][p - s_pos0[k]] : -1;
+        const bool ok = on && row >= 0 && row < s_rows[k];
+        bad = bad || (on && !ok);
+        PolKey key;
+        const bool is_hit = policy_probe_key<false>(pa.sa, pa.sau, pa.lay, pa.cur, ok, s_base[k] + (ok ? (unsigned)row : 0u), key);
+        if (on) {
+            pa.hit[p] = is_hit ? 1 : 0;
+            const unsigned char *src = nullptr;
+            if (is_hit) src = pa.arena + (long long)sa_entry(pa.sa, key.set, (unsigned)key.way, key.w) * pa.row_bytes;
+            else if (ok) src = s_table[k] + row * pa.row_bytes;   // (a fed table: NULL-based, rewritten by bags_repoint_fed_kernel)
+            pa.row_ptrs[p] = (long long)src;
+            args.prov[p] = make_uint4((unsigned)row, (unsigned)k, key.set, is_hit ? (0x80000000u | (unsigned)key.way) : (ok ? key.tag1 : 0u));
+            if constexpr (EVLFU) args.pos_sample[p] = -1;
+        }
+        const unsigned long long hm = __ballot(is_hit);
+        if (lane == 0 && hm) atomicAdd(&s_hits, __popcll(hm));
+        if constexpr (!EVLFU) {   // the wave's misses, packed, behind the block's earlier ones
+            const bool is_miss = ok && key.way < 0;
+            const unsigned long long mm = __ballot(is_miss);
+            int base = 0;
+            if (lane == 0 && mm) base = atomicAdd(&s_list_n, __popcll(mm));
+            base = __shfl(base, 0, 64);
+            if (is_miss) {
+                const int at = base + __popcll(mm & ((1ull << lane) - 1ull));
+                if (at < pa.list_cap)
+                    pa.miss_rec[(long long)blockIdx.x * pa.list_cap + at] = make_uint4((unsigned)row, (unsigned)k, key.set, key.tag1);
+            }
+        }
+    }
+    if (bad) atomicOr(args.err, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_hits) atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38], s_hits);
+        if constexpr (!EVLFU) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
+    }
+}
+
+// EvLFU, behind bags_count_kernel: bags_raise_list_kernel's listing without its raise -- every missed position into the block's
+// list with its sample's count (0 when no valid bag covers it), the record cache_batch_sa_list_fed_kernel reads.  The probe's
+// grid and walk, so record i of list j is the one fed_list_kernel gives rec_slot[j * list_cap + i].  Writes no way word.
+__global__ void __launch_bounds__(256) bags_fed_list_kernel(const BagArgs args) {
+    __shared__ int s_list_n;
+    const PolicyArgs &pa = args.p;
+    if (threadIdx.x == 0) s_list_n = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballot below)
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+        int a = 0;
+        if (p < args.n_pos) {
+            r = args.prov[p];
+            const int b = args.pos_sample[p];
+            if (b >= 0) a = args.agg[b];
+        }
+        const bool is_miss = (r.w & 0x80000000u) == 0u && r.w != 0u;
+        const unsigned long long mm = __ballot(is_miss);
+        int base = 0;
+        if (lane == 0 && mm) base = atomicAdd(&s_list_n, __popcll(mm));
+        base = __shfl(base, 0, 64);
+        if (is_miss) {
+            const int at = base + __popcll(mm & ((1ull << lane) - 1ull));
+            if (at < pa.list_cap)
+                pa.miss_rec[(long long)blockIdx.x * pa.list_cap + at] = make_uint4(r.x, r.y | ((unsigned)a << 8), r.z, r.w);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) pa.list_cnt[blockIdx.x] = s_list_n < pa.list_cap ? s_list_n : pa.list_cap;
+}
+
+// First launch of a bag finish: what bags_fed_probe_kernel left undone to the ways it hit.  The tier has not moved since the begin
+// (everything else is refused while the call is open), so the way a record names still holds its key.  LRU / LFU: policy_probe_key's
+// touch -- a pure function of the word of before the batch, a plain store, once per way and batch.  EVLFU: bags_raise_list_kernel's
+// raise to the count of the position's sample, the histogram moves into part1 columns 0 .. T.
+template <bool EVLFU>
+__global__ void __launch_bounds__(256) bags_fed_hits_kernel(const BagArgs args) {
+    __shared__ int s_delta[64];   // priority histogram moves (0 .. T, T <= 32; sized by the word's 6-bit field)
+    const PolicyArgs &pa = args.p;
+    const SaGeom &g = pa.sa;
+    const int T = pa.T;
+    if (threadIdx.x < 64) s_delta[threadIdx.x] = 0;
+    __syncthreads();
+    for (int i = 0; i < args.iters; i++) {
+        const long long p = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        if (p >= args.n_pos) continue;
+        const uint4 r = args.prov[p];
+        if ((r.w & 0x80000000u) == 0u) continue;
+        unsigned *wp = sa_ways_ptr(g, r.z) + (r.w & 7u);
+        const unsigned w = *wp;
+        if constexpr (EVLFU) {
+            const int b = args.pos_sample[p];
+            const int a = b >= 0 ? args.agg[b] : 0;
+            if (a > 0 && sa_prio(w) < a) {
+                const int old = sa_raise(g, wp, w, a);
+                if (old >= 0) { atomicSub(&s_delta[old], 1); atomicAdd(&s_delta[a], 1); }
+            }
+        } else {
+            const PolLayout &L = pa.lay;
+            if (pol_last(L, w) != pa.cur) {
+                const unsigned c = pol_cnt(w);
+                *wp = pol_word(L, w & L.tag_mask, pa.cur, c < kPolCntMax ? c + 1u : kPolCntMax, pol_sel(L, w));
+            }
+        }
+    }
+    if constexpr (EVLFU) {
+        __syncthreads();
+        if ((int)threadIdx.x <= T && s_delta[threadIdx.x])
+            atomicAdd(&pa.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + threadIdx.x], s_delta[threadIdx.x]);
+    }
+}
+
+// The flat form of sa_repoint_fed_kernel, behind the fed insert: one lane per position, read from the begin's records as
+// bags_repoint2_kernel reads the pair's.  A miss is searched in its set (the (set, tag + 1) the probe computed): found, it is
+// pointed at its arena row; a miss of a fed table that found no way finds its key's slot of the scratch table (read-only) and is
+// pointed at its fed row, so the NULL-based address the probe computed for it never reaches the pooling; a miss of an addressed
+// table that found no way keeps its table address.  Writes no way word, reads no table and no index.
+__global__ void __launch_bounds__(256) bags_repoint_fed_kernel(const BagRepointFedArgs args, const FedSrc fs) {
+    __shared__ int s_cnt[4];   // positions re-pointed / left in place / missed positions of fed tables / of those served from the fed block
+    if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63;
+    int n_in = 0, n_out = 0, n_fed = 0, n_blk = 0;   // this wave's totals, kept on lane 0
+    bool bad = false;
+    for (int i = 0; i < args.iters; i++) {   // block-uniform trip count (the ballots)
+        const long long at = ((long long)blockIdx.x + (long long)i * gridDim.x) * 256 + threadIdx.x;
+        const bool on = at < args.n_pos;
+        const long long p = on ? at : 0;
+        const uint4 r = args.prov[p];
+        const bool hit = (r.w & 0x80000000u) != 0u;
+        const bool want = on && !hit && r.w != 0u;
+        bad = bad || (on && r.w == 0u);   // an index out of range: no key, and the sticky flag says so
+        const int k = (int)(r.y & 31u);
+        // (a hit, a bad index and a lane without a position all read set 0 and store nothing)
+        const unsigned set = want ? r.z : 0u, tag1 = want ? r.w : 0u;
+        unsigned w = 0u;
+        SaLine line;
+        sa_load<8>(g, set, line);
+        const int way = sa_find<8>(g, line, tag1, w);
+        const bool found = want && way >= 0;
+        const bool of_fed = want && ((fs.fed_mask >> k) & 1u);
+        const bool block = of_fed && !found;
+        if (found) args.row_ptrs[p] = (long long)(args.arena + (long long)sa_entry(g, set, (unsigned)way, w) * args.row_bytes);
+        if (block) {
+            const unsigned long long key = ((unsigned long long)(k + 1) << 32) | r.x;
+            // (fed_list has seen every record of the lists, so the key is there; were it not, the position is served the codec's zero
+            //  row and the sticky flag says so -- never an address nobody owns)
+            const unsigned char *src = fs.zero_row;
+            bool lost = true;
+            unsigned h = (unsigned)mix64(key) & fs.slot_mask;
+            for (unsigned n = 0; n <= fs.slot_mask; n++, h = (h + 1u) & fs.slot_mask) {
+                const unsigned long long kk = fs.slot_key[h];
+                if (kk == key) { src = fs.fed + (long long)fs.slot_index[h] * fs.stride; lost = false; break; }
+                if (kk == 0ull) break;
+            }
+            bad = bad || lost;
+            args.row_ptrs[p] = (long long)src;
+        }
+        const unsigned long long fm = __ballot(found), wm = __ballot(want);
+        n_in += __popcll(fm); n_out += __popcll(wm & ~fm);
+        n_fed += __popcll(__ballot(of_fed)); n_blk += __popcll(__ballot(block));
+    }
+    if (bad) atomicOr(fs.err, 1);
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+        if (n_fed) atomicAdd(&s_cnt[2], n_fed);
+        if (n_blk) atomicAdd(&s_cnt[3], n_blk);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x >= 2 && threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&fs.counters[threadIdx.x - 2], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
 // ... of the C1 + C2 pair that shares its set records (the rule: evs_cache_policy.h at Repoint2Args).  The pair keeps one arena
 // row per way, so a way this batch hit can have been this batch's victim: a hit position is searched again too, and one whose
 // key is gone is pointed at the table row of its tier -- the same bytes.  A position looks at the ways of the tier its serve byte
@@ -1442,6 +1650,24 @@ void fed_list_launch(const FedListArgs &a, int grid, hipStream_t st) {
 
 void sa_repoint_fed_launch(const RepointArgs &a, const FedSrc &f, int grid, hipStream_t st) {
     hipLaunchKernelGGL(sa_repoint_fed_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, f);
+}
+
+void bags_fed_probe_launch(const BagArgs &a, int grid, hipStream_t st) {
+    if (a.evlfu) hipLaunchKernelGGL(bags_fed_probe_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bags_fed_probe_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_fed_list_launch(const BagArgs &a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_fed_list_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_fed_hits_launch(const BagArgs &a, int grid, hipStream_t st) {
+    if (a.evlfu) hipLaunchKernelGGL(bags_fed_hits_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bags_fed_hits_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void bags_repoint_fed_launch(const BagRepointFedArgs &a, const FedSrc &f, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(bags_repoint_fed_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, f);
 }
 
 }  // namespace evs

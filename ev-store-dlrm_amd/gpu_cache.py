@@ -311,7 +311,8 @@ class GpuCache:
         """set_backing where tables[k] may be None: table k is then FED -- the GPU never reads it, and the rows of its missing
         keys come from the caller between lookup_begin and lookup_finish (or from set_row_source's function).  n_rows: the row
         count of every table.  Tensors that are given are read in place (HBM or pinned host memory), as set_backing reads
-        them.  A fed cache runs 'fetch-first' (set_miss_order) and serves lookup_begin / lookup_finish[_interact] only."""
+        them.  A fed cache runs 'fetch-first' (set_miss_order) and serves lookup_begin / lookup_finish[_interact] and their bag
+        form, lookup_bags_begin / lookup_bags_finish[_interact], only."""
         tables, n_rows = list(tables), [int(v) for v in n_rows]
         assert len(tables) == self.n_tables and len(n_rows) == self.n_tables
         rb = self.dim * self.codec // 8
@@ -326,12 +327,14 @@ class GpuCache:
         self._fed = any(t is None and n > 0 for t, n in zip(tables, n_rows))
         return self
 
-    def set_row_source(self, fn):
+    def set_row_source(self, fn, bags=False):
         """fn(keys) -> rows: keys a uint64 numpy array of table_1based << 32 | row, rows (n, row_bytes) uint8 in the cache's
         codec -- numpy or tensor, host or device (FileTier.fetch is such a function).  With a source set, lookup_batch /
         lookup_interact on a fed cache run lookup_begin -> fn -> a copy into a device block this object owns -> lookup_finish.
-        None takes the source away."""
+        bags=True: lookup_bags / lookup_bags_interact run lookup_bags_begin -> fn -> lookup_bags_finish[_interact] as well
+        (the default leaves them the library's refusal, as before the bag form existed).  None takes the source away."""
         self._row_source = fn
+        self._row_source_bags = bool(bags) and fn is not None
         return self
 
     def _fetch_fed(self, keys):
@@ -353,9 +356,10 @@ class GpuCache:
         blk[:n].copy_(got.reshape(n, rb), non_blocking=False)
         return blk[:n]
 
-    def _via_source(self, rows, hit, finish):
-        """begin -> the row source -> finish; whatever fails in between leaves no call open"""
-        hit, keys = self.lookup_begin(rows, hit)
+    def _via_source(self, rows, hit, finish, begin=None):
+        """begin -> the row source -> finish; whatever fails in between leaves no call open.  begin: the bag form's (rows and
+        hit are then unused)"""
+        hit, keys = begin() if begin is not None else self.lookup_begin(rows, hit)
         try:
             return hit, finish(self._fetch_fed(keys))
         except BaseException:
@@ -555,6 +559,55 @@ class GpuCache:
         nnz_c = (C.c_int64 * T)(*nnz)
         return B, idx_c, off_c, nnz_c, flat, hits, (lo, li)
 
+    # ---- ragged bags over fed backing (include/evstore_hip.h: evs_cache_fed_begin_bags) ----
+    def lookup_bags_begin(self, lS_o, lS_i):
+        """First half of lookup_bags on a fed cache: the probe (an 'evlfu' cache: and the count pass; it needs
+        set_bag_rule('served-bags') and set_bag_count('count-first')).  -> (hits, keys): hits as lookup_bags gives them, keys an
+        int64 device tensor (a view of a buffer this object owns, valid until the next begin) with every distinct missing key of
+        a fed table once, as table_1based << 32 | row, in no particular order.  Synchronises.  Everything else on this cache is
+        refused until lookup_bags_finish[_interact] or lookup_abort."""
+        B, idx_c, off_c, nnz_c, flat, hits, keep = self._bags_call(lS_o, lS_i)
+        n_pos = int(flat.numel())
+        kb = getattr(self, "_fed_keys", None)
+        if kb is None or kb.numel() < max(n_pos, 1):
+            kb = self._fed_keys = torch.empty(max(n_pos, 1), dtype=torch.int64, device=self.device)
+        n = C.c_int64()
+        _lib.check(_lib.lib().evs_cache_fed_begin_bags(self._h, B, idx_c, off_c, nnz_c, flat.data_ptr(), kb.data_ptr(), C.byref(n),
+                                                       torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = ((keep, hits, "bags"), flat, B, int(n.value))   # keep alive
+        return hits, kb[:int(n.value)]
+
+    def lookup_bags_finish(self, fed, out=None):
+        """Second half: fed[i] is the row of keys[i], as lookup_finish takes it.  Touches / raises the ways the begin hit, runs the
+        update, the re-point and the pooling -> ly: T (B, dim) fp32 tensors, views of one (T, B, dim) block -- `out`, when given."""
+        B, ptr, stride = self._fed_args(fed)
+        T, d = self.n_tables, self.dim
+        if out is None:
+            out = torch.empty((T, B, d), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, B, d)):
+            raise ValueError("out must be a contiguous (%d, %d, %d) fp32 device tensor" % (T, B, d))
+        _lib.check(_lib.lib().evs_cache_fed_finish_bags(self._h, ptr, stride, out.data_ptr(), B * d, d,
+                                                        torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = None
+        return list(out.unbind(0))
+
+    def lookup_bags_finish_interact(self, fed, x, itself=False, out=None):
+        """lookup_bags_finish with the dense interaction behind the pooling -> R (B, dim + P), as lookup_bags_interact returns it."""
+        B, ptr, stride = self._fed_args(fed)
+        F = self.n_tables + 1
+        P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
+        if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (B, self.dim) and x.stride(1) == 1):
+            raise ValueError("x must be a (B, %d) fp32 device tensor with unit inner stride" % self.dim)
+        if out is None:
+            out = torch.empty((B, self.dim + P), dtype=torch.float32, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * (self.dim + P)):
+            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * (self.dim + P)))
+        _lib.check(_lib.lib().evs_cache_fed_finish_bags_interact(
+            self._h, ptr, stride, x.data_ptr(), int(x.stride(0)) if B > 1 else self.dim, int(bool(itself)), out.data_ptr(),
+            torch.cuda.current_stream(self.device).cuda_stream))
+        self._fed_call = None
+        return out
+
     def lookup_bags(self, lS_o, lS_i, out=None):
         """Multi-hot lookup on an 'lru' / 'lfu' tier: every position of every index array is one lookup of "the batched rule"
         (flags = residency at arrival, one touch per way and batch, every distinct missed key inserted once), the bags pool the
@@ -562,7 +615,10 @@ class GpuCache:
         An 'evlfu' tier (set-associative, after set_bag_rule('served-bags')): strict snapshot flags, every hit way raised to
         the served-bag count of the samples that name it, every distinct missed key inserted once at the largest such count.
         -> (hits: T uint8 tensors, one flag per index, views of one flat array; ly: T (B, dim) fp32 tensors, views of one
-        (T, B, dim) block -- `out`, when given)."""
+        (T, B, dim) block -- `out`, when given).  A fed cache with a row source for bags (set_row_source(fn, bags=True)) runs
+        lookup_bags_begin -> the source -> lookup_bags_finish."""
+        if getattr(self, "_row_source_bags", False) and getattr(self, "_fed", False):
+            return self._via_source(None, None, lambda fed: self.lookup_bags_finish(fed, out), begin=lambda: self.lookup_bags_begin(lS_o, lS_i))
         B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
         T, d = self.n_tables, self.dim
         if out is None:
@@ -577,6 +633,9 @@ class GpuCache:
         """R = interact_features(x, the T pooled bags of lookup_bags): probe, pooling into a (T, B, dim) block the cache owns,
         the dense interaction, insert ('evlfu': raise + list, then the insert) -- the rule and the flags of lookup_bags
         (include/evstore_hip.h: evs_cache_lookup_bags_interact).  -> (hits as lookup_bags gives them, R (B, dim + F (F - 1) / 2) with F = T + 1)."""
+        if getattr(self, "_row_source_bags", False) and getattr(self, "_fed", False):
+            return self._via_source(None, None, lambda fed: self.lookup_bags_finish_interact(fed, x, itself, out),
+                                    begin=lambda: self.lookup_bags_begin(lS_o, lS_i))
         B, idx_c, off_c, nnz_c, flat, hits, _keep = self._bags_call(lS_o, lS_i)
         F = self.n_tables + 1
         P = F * (F + 1) // 2 if itself else F * (F - 1) // 2

@@ -873,7 +873,7 @@ EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
  *   a fed cache at order 0                                         EVS_EINVAL, naming fetch-first
  *   a threshold of evs_cache_set_batch_approx in force               EVS_EINVAL
  *   evs_cache_lookup_batch / _lookup_interact on a fed cache         EVS_ESTATE, naming the begin / finish calls
- *   evs_cache_lookup_bags / _lookup_bags_interact                    EVS_ESTATE
+ *   evs_cache_lookup_bags / _lookup_bags_interact                    EVS_ESTATE, naming evs_cache_fed_begin_bags / _fed_finish_bags
  *   a fed cache as a tier of any pair / triple call (batched, bags, the exact request, the tier server)   EVS_EINVAL
  *   evs_cache_batch_export / _batch_load / _pair_load                EVS_EINVAL
  *   evs_cache_request, the resident server, evs_cache_exact_load     EVS_ESTATE
@@ -890,6 +890,50 @@ EVS_API int evs_cache_fed_finish_interact(evs_cache *c, const void *fed, int64_t
                                           float *R, void *stream);
 EVS_API int evs_cache_fed_abort(evs_cache *c);
 EVS_API int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream);
+/* RAGGED BAGS OVER FED BACKING: the begin / finish form of evs_cache_lookup_bags / _lookup_bags_interact on a fed cache -- the
+ * count-first fetch-first bag chain cut in two where the bus fetch sits.  evs_cache_fed_abort and evs_cache_fed_stats serve
+ * both forms.
+ *
+ * THE RULE.  A bag begin + finish pair is batch n of the cache and runs exactly as evs_cache_lookup_bags runs it on an order-1
+ * cache (EvLFU: with evs_cache_set_bag_rule(c, 1) and evs_cache_set_bag_count(c, 1)); nothing else changes.  Given rows equal to
+ * the table rows, the flags, the pooled bits, R, evs_cache_batch_dump, evs_cache_batch_stats (with hist and n_perfect_hits) and
+ * evs_cache_fetch_stats are what the same calls leave on a fetch-first cache over the same tables in HBM, on every call whose
+ * outcome does not depend on timing.  A served row of a fed table is, byte for byte, a row the caller fed for that key: from the
+ * arena once installed, from the fed block for a position whose set took 8 new keys in the call.
+ *
+ * evs_cache_fed_begin_bags(c, B, indices, offsets, nnz, hit, keys, n_keys_host, stream): the bag inputs are evs_cache_lookup_bags'
+ *   (host arrays of device pointers, B bag starts per table, the last bag runs to nnz[k]); B >= 1.  hit is a flat device array of
+ *   sum(nnz) bytes, table-major, or NULL (the cache's own flag bytes are used).  Runs the pending EvLFU flush, a probe that leaves
+ *   the way words alone and, EvLFU, the count pass; then builds the FED LIST into keys (device-addressable, 8-byte aligned, room
+ *   for sum(nnz) entries): every distinct valid key of a fed table that at least one position missed, exactly once, as
+ *   table_1based << 32 | row, in no particular order -- however many positions, bags and samples name it, and whether or not a
+ *   valid bag covers those positions (an uncovered key is inserted at priority 0, as the bag rule has it).  Not in the list: an
+ *   index out of range, a key of an addressed table, a hit.  Synchronises the stream and writes the count to *n_keys_host.
+ *   indices, offsets and hit must stay valid until the finish.
+ * evs_cache_fed_finish_bags(c, fed, fed_stride_bytes, pooled, out_table_stride, out_bag_stride, stream) /
+ * evs_cache_fed_finish_bags_interact(c, fed, fed_stride_bytes, x, x_stride, itself, R, stream) touch / raise the ways the begin
+ *   hit, run the update, the re-point, the pooling (evs_cache_lookup_bags' pooled / _lookup_bags_interact's R) and the close
+ *   bookkeeping.  fed is as evs_cache_fed_finish takes it.
+ * The sticky flag of evs_check_index_errors is raised, at the latest when the finish returns, for every index out of range and
+ *   every bad bag; a begin may already have raised it, and evs_cache_fed_abort does not clear it.
+ * evs_cache_fed_abort after a bag begin: as after evs_cache_fed_begin.  The begin writes no way word (for LRU / LFU too: the touch
+ *   is the finish's first launch), its totals go into rows of the call's own and the samples' words are zero again when it returns.
+ *
+ * THE ENVELOPE, checked at the begin before anything is allocated: a fed cache's, as above, and the order-1 bag form's -- an
+ * EvLFU cache without evs_cache_set_bag_rule(c, 1) or without evs_cache_set_bag_count(c, 1) is EVS_EINVAL naming the setter; the
+ * argument checks of evs_cache_lookup_bags (dim % 4 == 0 and <= 256, fewer than 2^31 lookups, no NULL indices[k] with nnz[k] > 0;
+ * the interact finish: a fused-kernel dim and T <= 31).  evs_cache_lookup_bags / _lookup_bags_interact themselves stay EVS_ESTATE
+ * on a fed cache.
+ * PROTOCOL.  A finish of the other form than the open begin's is EVS_ESTATE, names the right call and leaves the call open
+ * (evs_cache_fed_finish after a bag begin, evs_cache_fed_finish_bags after evs_cache_fed_begin).  Everything an open (B, T) call
+ * refuses, an open bag call refuses.  Argument errors of the finish are EVS_EINVAL and leave the call open.  Bag calls and (B, T)
+ * calls may alternate on one fed cache: they share stamp, ordinal, counters and the pending flush. */
+EVS_API int evs_cache_fed_begin_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
+                                     const int64_t *nnz, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream);
+EVS_API int evs_cache_fed_finish_bags(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *pooled,
+                                      int64_t out_table_stride, int64_t out_bag_stride, void *stream);
+EVS_API int evs_cache_fed_finish_bags_interact(evs_cache *c, const void *fed, int64_t fed_stride_bytes, const float *x, int64_t x_stride,
+                                               int itself, float *R, void *stream);
 /* The approximate-embedding mode of the batched EvLFU rule (the reference: cache_algo/EvLFU_C1.py:122-125, :142-152 -- a request
  * whose agg_hit reaches approx_emb_thres does not fetch its missing rows; each reuses the vector of the hit before it and is
  * reported as a hit; nothing is inserted for it).  The exact batch-1 engines take it as evs_cache_request's approx_thres; this is

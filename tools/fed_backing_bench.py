@@ -30,6 +30,128 @@ import evstore_dlrm_amd as E  # noqa: E402
 from tools.host_setassoc_bench import pinned_tables  # noqa: E402
 
 NAMES = ("a_fetch_first_hbm", "b_fetch_first_pinned", "c_fed_device_source", "d_fed_host_source")
+BAG_NAMES = ("a_bags_count_first_fetch_first_hbm", "b_fed_bags_device_source", "c_fed_bags_host_source")
+
+
+def main_bags(args):
+    """--bags: the bag form (lookup_bags_begin / lookup_bags_finish_interact) beside the order-1 count-first bag chain it is cut from
+    -> profiles/fed_bags.json.  tools/bags_cache_bench.py's ragged stream (bags of 1 .. --max-bag indices, rows Zipf) at this tool's
+    shape; a: lookup_bags_interact over HBM tables, the yardstick; b: fed, a device index_select source; c: fed, a host source.
+    Timed as above: the host clock between two synchronises, b and c split into begin / source / finish."""
+    from tools.bags_cache_bench import make_batch
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    d, B = args.dim, args.batch
+    ln, ev, pinned, scale = pinned_tables(bench.KAGGLE_LN, d, args.scale, dev)
+    T = len(ln)
+    cap = int(args.frac * sum(ln))
+    rb = d * 4
+    base_np = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int64)
+    base_dev = torch.from_numpy(base_np).to(dev)
+    all_dev = torch.cat([ev.fp32_view(k) for k in range(T)])
+    all_host = np.concatenate([p.numpy() for p in pinned])
+
+    def device_source(keys):
+        return all_dev.index_select(0, base_dev[(keys >> 32) - 1] + (keys & 0xffffffff))
+
+    def host_source(keys):
+        k = keys.cpu().numpy()
+        return torch.from_numpy(all_host[base_np[(k >> 32) - 1] + (k & 0xffffffff)]).to(dev)
+
+    sources = {"b_fed_bags_device_source": device_source, "c_fed_bags_host_source": host_source}
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    out = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+
+    def call(name, c, lo, li, split=None):
+        if name in sources:
+            t0 = time.perf_counter()
+            _, keys = c.lookup_bags_begin(lo, li)           # (synchronises)
+            t1 = time.perf_counter()
+            fed = sources[name](keys) if keys.numel() else None
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            c.lookup_bags_finish_interact(fed, x, out=out)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            if split is not None:
+                split.append((t1 - t0, t2 - t1, t3 - t2, int(keys.numel())))
+        else:
+            c.lookup_bags_interact(lo, li, x, out=out)
+
+    caches, warm = {}, {}
+    for name in BAG_NAMES:
+        c = E.GpuCache("evlfu", cap, T, d, 32, "python", dev).set_miss_order("fetch-first")
+        c.set_bag_rule("served-bags").set_bag_count("count-first")
+        if name in sources:
+            c.set_fed_backing([None] * T, ln)
+        else:
+            c.set_backing(ev)
+        g = torch.Generator(device=dev).manual_seed(7)       # (every configuration warms on the same batches)
+        size = -1
+        for i in range(args.max_warm):
+            call(name, c, *make_batch(ln, B, g, dev, args.max_bag, args.alpha))
+            if i % 10 == 9:
+                s = c.batch_stats()["size"]
+                if s - size < 0.002 * cap:
+                    break
+                size = s
+        caches[name], warm[name] = c, i + 1
+        print("fed_backing_bench: %s warm after %d batches, size %d of %d" % (name, i + 1, c.batch_stats()["size"], cap), file=sys.stderr, flush=True)
+    g = torch.Generator(device=dev).manual_seed(11)
+    timed = [make_batch(ln, B, g, dev, args.max_bag, args.alpha) for _ in range(args.steps)]
+    n_pos = sum(int(t.numel()) for _, li in timed for t in li)
+    s0 = {n: (caches[n].batch_stats(), caches[n].fetch_stats(), caches[n].fed_stats()) for n in BAG_NAMES}
+    events, wall, split = {n: [] for n in BAG_NAMES}, {n: [] for n in BAG_NAMES}, {n: [] for n in sources}
+    for lo, li in timed:
+        for n in BAG_NAMES:
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            call(n, caches[n], lo, li, split.get(n))
+            e1.record()
+            torch.cuda.synchronize()
+            wall[n].append(time.perf_counter() - t0)
+            events[n].append((e0, e1))
+    res = {}
+    for n in BAG_NAMES:
+        s1, f1, fs1 = caches[n].batch_stats(), caches[n].fetch_stats(), caches[n].fed_stats()
+        w = np.array(wall[n]) * 1e6
+        res[n] = {"wall_us": round(float(np.median(w)), 2), "wall_p95_us": round(float(np.percentile(w, 95)), 2),
+                  "hit_rate": round((s1["n_hits"] - s0[n][0]["n_hits"]) / n_pos, 4), "size": s1["size"], "warm_batches": warm[n],
+                  "flushes": s1["n_flush"] - s0[n][0]["n_flush"], "fetch_stats_delta": {k: f1[k] - s0[n][1][k] for k in f1}}
+        if n in sources:
+            sp = np.array(split[n], np.float64)
+            res[n].update({"begin_us": round(float(np.median(sp[:, 0])) * 1e6, 2), "source_us": round(float(np.median(sp[:, 1])) * 1e6, 2),
+                           "finish_us": round(float(np.median(sp[:, 2])) * 1e6, 2), "keys_per_batch": round(float(sp[:, 3].mean()), 1),
+                           "fed_bytes_per_batch": round(float(sp[:, 3].mean()) * rb),
+                           "fed_stats_delta": {k: fs1[k] - s0[n][2][k] for k in fs1}})
+        else:
+            us = np.array([a.elapsed_time(b) * 1e3 for a, b in events[n]])
+            res[n].update({"median_us": round(float(np.median(us)), 2), "p95_us": round(float(np.percentile(us, 95)), 2)})
+        print("fed_backing_bench: %s %s" % (n, res[n]), file=sys.stderr, flush=True)
+    a = res[BAG_NAMES[0]]["wall_us"]
+    b_ = res[BAG_NAMES[1]]
+    doc = {"tool": "fed_backing_bench --bags", "device": torch.cuda.get_device_name(0),
+           "shape": {"rows": sum(ln), "table_scale": scale, "capacity": cap, "frac": args.frac, "batch": B, "dim": d, "row_bytes": rb,
+                     "zipf_alpha": args.alpha, "bags": "1 .. %d" % args.max_bag, "lookups_per_call": round(n_pos / len(timed), 1),
+                     "timed_batches": len(timed), "policy": "evlfu (served bags, count first)",
+                     "consumer": "lookup_bags_interact / lookup_bags_finish_interact (pooling, then the dense interaction)"},
+           "chains": {"a": "bags_probe -> bags_count -> bags_raise_list -> cache_batch_sa_list -> sa_repoint (flat) -> bags_pool -> dense interaction",
+                      "b, c": "begin: bags_fed_probe -> bags_count -> bags_fed_list -> fed_list -> synchronise | source | finish: fold -> bags_fed_hits -> "
+                              "cache_batch_sa_list_fed -> bags_repoint_fed -> bags_pool -> dense interaction"},
+           "timing": "host clock between two synchronises around every call (wall_us; begin / source / finish each end on a synchronise); a also by a "
+                     "pair of device events (median_us); the configurations alternate on the same batches in one process; one run on one box",
+           "configs": res,
+           "begin_plus_finish_over_a_us": round(b_["begin_us"] + b_["finish_us"] - a, 2),
+           "b_over_a": round(b_["wall_us"] / a, 3), "c_over_a": round(res[BAG_NAMES[2]]["wall_us"] / a, 3)}
+    path = args.out or os.path.join(ROOT, "profiles", "fed_bags.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"tool": doc["tool"], "a_wall_us": a, "b_over_a": doc["b_over_a"], "c_over_a": doc["c_over_a"],
+                      "begin_plus_finish_over_a_us": doc["begin_plus_finish_over_a_us"], "out": path}))
 
 
 def main():
@@ -41,8 +163,13 @@ def main():
     ap.add_argument("--max-warm", type=int, default=150, help="at most this many warm-up batches")
     ap.add_argument("--scale", type=float, default=1.0, help="every table's rows times this")
     ap.add_argument("--dim", type=int, default=36)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fed_backing.json"))
+    ap.add_argument("--bags", action="store_true", help="the bag form beside the count-first fetch-first bag chain -> profiles/fed_bags.json")
+    ap.add_argument("--max-bag", type=int, default=10, help="--bags: bags of 1 .. this many indices")
+    ap.add_argument("--out", default="", help="default: profiles/fed_backing.json (--bags: profiles/fed_bags.json)")
     args = ap.parse_args()
+    if args.bags:
+        return main_bags(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "fed_backing.json")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     d, B = args.dim, args.batch
