@@ -4512,6 +4512,8 @@ static int batch_state(evs_cache *c, hipStream_t st, const char *who) {
     }
     return EVS_OK;
 }
+// the records each of the g1 miss lists of a (B, T) call has room for: the T keys of the samples its block walks, 8 at a time
+static long long list_cap(int64_t B, long long g1, int T) { return (B + 8 * g1 - 1) / (8 * g1) * 8 * T; }
 static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream_t st, evs::BatchArgs &a, const char *who) {
     using namespace evs;
     { const int rc = batch_check(c, who); if (rc) return rc; }
@@ -4530,10 +4532,9 @@ static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream
         void *slab = nullptr;
         SlabPlan sp;
         long long g1n = (B + 7) / 8; if (g1n > kProbeGridMax) g1n = kProbeGridMax;
-        const long long iters = (B + 8 * g1n - 1) / (8 * g1n);
         sp.add(&miss_info, B * T * 4); sp.add(&new_slot, g2 * 256 * 4); sp.add(&block_cnt, g2 * 4); sp.add(&block_base, g2 * 4);
         sp.add(&row_ptrs, B * T * 8); sp.add(&row_tier, B * T); sp.add(&iota, B * 8);
-        sp.add(&miss_rec, g1n * iters * 8 * T * 16);   // K1's per-block miss lists (sampled update)
+        sp.add(&miss_rec, g1n * list_cap(B, g1n, T) * 16);   // K1's per-block miss lists (sampled update)
         // one counter per list: K1 has g1n lists, the probe folded into the consumer one per 16-sample block -- more than
         // g1n once B > 16 * kProbeGridMax (the fold is bounded by rf_max_batch(), which EVS_FUSED_RF_MAX_B can raise)
         sp.add(&list_cnt, std::max<long long>(g1n, (B + 15) / 16) * 4);
@@ -4721,6 +4722,13 @@ static void launch_sa_update(const evs::BatchArgs &a, hipStream_t st) {
     with_row_shape(a.row_bytes, [&](auto s) {
         using S = decltype(s);
         hipLaunchKernelGGL((evs::cache_batch_sa_list_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a);
+    });
+}
+// ... over lists whose fed records read the caller's block (the finish of a fed call, either form)
+static void launch_sa_update_fed(const evs::BatchArgs &a, const evs::FedSrc &fs, hipStream_t st) {
+    with_row_shape(a.row_bytes, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
     });
 }
 
@@ -4951,6 +4959,43 @@ static int ensure_estamp(evs_cache *c, hipStream_t st) {
 }
 // one more batch of B requests whose counters the close has not folded yet
 static void count_batch(evs_cache *c, int64_t B) { c->pending_batches++; c->pending_requests += B; }
+// the tail of every call on a set-associative tier alone: the batch is counted, its counters folded every kCloseEvery-th batch
+static int tier_alone_done(evs_cache *c, int64_t B, hipStream_t st) {
+    count_batch(c, B);
+    if (c->pending_batches >= evs::kCloseEvery) sampled_close_pending(c, 0, st);
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+// What the LRU / LFU kernels and the fed probes read of a tier alone (evs_cache_policy.h: PolicyArgs), for the (B, T) chains
+// (requests, the per-batch slab) and the bag chains (no requests, the bag slab) alike.  Everything that comes from the cache is set
+// here, so that a field the probe or the insert starts reading is set in one place; lay / cur: tier_next_batch.  backing_rows
+// takes no k < T guard: evs_cache::backing_rows starts out all zero, and set_backing_impl / evs_cache_set_file_backing write its
+// first n_tables entries only -- beyond them it is always 0.
+static evs::PolicyArgs policy_args(evs_cache *c, int64_t B, const int32_t *requests, unsigned char *hit, long long *row_ptrs, uint4 *rec, int *cnt,
+                                   int rec_cap, int *part1) {
+    evs::PolicyArgs pa{};
+    pa.sa = c->sa; pa.sau = c->sau;
+    pa.requests = requests; pa.hit = hit; pa.row_ptrs = row_ptrs;
+    pa.miss_rec = rec; pa.list_cnt = cnt; pa.list_cap = rec_cap;
+    pa.part1 = part1; pa.part2 = c->part2;
+    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = c->backing_rows[k]; }
+    pa.arena = c->a.arena; pa.B = B; pa.T = c->host.n_tables; pa.row_bytes = c->host.row_bytes;
+    return pa;
+}
+// A tier's step into a new batch, in front of the batch's probe.  EvLFU: the next batch stamp, handed back, and the flush the close
+// of an earlier batch asked for (the tier's, not the call's: it stands if a fed call is dropped).  LRU / LFU: the layout of the way
+// words and the batch number n = 1, 2, ... modulo 2^S into pa; 0 is handed back.
+static int tier_next_batch(evs_cache *c, evs::PolicyArgs &pa, hipStream_t st) {
+    using namespace evs;
+    if (c->host.policy == kEvLFU) {
+        const int stamp = next_batch_stamp(c);
+        sampled_flush_if_wanted(c, st);
+        return stamp;
+    }
+    pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
+    pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+    return 0;
+}
 
 // the consumers of a (B, T) call over the pointer table (or, row_ids not NULL, the 4-byte row ids in its first half): the rows
 // themselves into out, the interaction into R -- shared by cache_batch_impl and the finish of a fed call
@@ -5066,28 +5111,16 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
             if (!ff) update();
             return EVS_OK;
         };
-        auto done = [&]() -> int {
-            count_batch(c, B);
-            if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-            EVS_HIP_CHECK(hipGetLastError());
-            return EVS_OK;
-        };
+        auto done = [&]() -> int { return tier_alone_done(c, B, st); };
         const auto sa_update = [&] { launch_sa_update(a, st); };
         if (c->host.policy != kEvLFU) {
             // LRU / LFU (evs_cache_policy.hip): probe + touch -> consumers -> insert, always as launches of their own; batch
             // number n = 1, 2, ... rides in the way words modulo 2^S
-            PolicyArgs pa;
-            pa.sa = c->sa; pa.sau = c->sau;
-            pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
-            pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
+            a.list_cap = (int)list_cap(B, a.g1, T);
+            PolicyArgs pa = policy_args(c, B, rows, hit, c->row_ptrs, c->miss_rec, c->list_cnt, a.list_cap, c->part1);
+            tier_next_batch(c, pa, st);
             if ((cap << c->sa.dual) >= (1ll << 30)) a.row_ids = nullptr;   // (a row id carries the arena entry in 30 bits)
-            pa.requests = rows; pa.hit = hit; pa.row_ptrs = c->row_ptrs; pa.row_ids = a.row_ids;
-            pa.miss_rec = c->miss_rec; pa.list_cnt = c->list_cnt;
-            pa.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
-            pa.part1 = a.part1; pa.part2 = a.part2;
-            for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = c->backing_rows[k]; }
-            pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
-            a.list_cap = pa.list_cap;
+            pa.row_ids = a.row_ids;
             policy_probe_launch(pa, a.g1, st);
             // (fetch first: a way hit in this batch is touched, so never this batch's victim: its arena row is intact behind the insert)
             { const int rc = chain([&] { policy_insert_launch(pa, a.g1, sampled_list_threads(a), st); }); if (rc) return rc; }
@@ -5096,7 +5129,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         a.stamp = next_batch_stamp(c);
         sampled_flush_if_wanted(c, st);
         a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
-        a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+        a.list_cap = (int)list_cap(B, a.g1, T);
         if (apx) {
             // A threshold in force: always the unfolded chain in pointer mode.  An approximated position holds the address its
             // nearest earlier HIT is served, and that address stays valid until the consumers have read it for the reason a
@@ -5164,7 +5197,7 @@ static int cache_batch_impl(evs_cache *c, int64_t B, const int32_t *rows, float 
         sampled_flush_if_wanted(c, st);   // EvLFU flush the close of an earlier batch asked for: before this batch's probe
         if (!host_tier) {   // K1 lists the misses itself (the patch kernel of the host tier reads the per-position records)
             a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt;
-            a.list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+            a.list_cap = (int)list_cap(B, a.g1, T);
         }
         // the probe inside the consumer: one launch instead of two when the consumer is the rows-in-registers kernel
         // (EVS_CACHE_FOLD=0: the two-launch form)
@@ -5518,7 +5551,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
     if (sampled2) {
         // the probe lists each tier's misses per block (as K1 does for one tier); with the alt-key tier attached a list
         // kernel block stages its victims in LDS: lists of at most kListVictMax records
-        const long long lc = (B + 8 * (long long)a1.g1 - 1) / (8 * (long long)a1.g1) * 8 * T;
+        const long long lc = list_cap(B, a1.g1, T);
         static const bool list_on = evs::env_switch_on("EVS_CACHE_LIST2");
         if (sa2 || (list_on && !host2 && a1.g1 == a2.g1 && (!c3 || lc <= kListVictMax))) {   // (host tiers: the patch kernel reads the per-position records)
             a1.miss_rec = c1->miss_rec; a1.list_cnt = c1->list_cnt; a1.list_cap = (int)lc;
@@ -5677,9 +5710,12 @@ extern "C" int evs_cache_lookup_interact(evs_cache *c, int64_t B, const int32_t 
 }
 
 // ---- fed backing: the fetch-first chain cut in two (the contract: include/evstore_hip.h at evs_cache_fed_begin) ---------------
-//   begin    (EvLFU: flush ->) probe -> fed_list -> synchronise: the caller holds the distinct missing keys of the fed tables
-//   finish   update (fed form) -> sa_repoint (fed form) -> consumers -> close bookkeeping
-// Between the two the cache remembers the call (evs_cache::fedc) and refuses everything else (fed_open_refuse).
+//   begin    three clears (fed_open_scratch) -> (EvLFU: flush ->) fed_probe -> fed_list -> synchronise (fed_list_keys): the caller
+//            holds the distinct missing keys of the fed tables
+//   finish   fold (fed_finish_enter) -> fed_hits -> update (fed form) -> sa_repoint (fed form) -> consumers -> close bookkeeping
+// Between the two the cache remembers the call (evs_cache::fedc) and refuses everything else (fed_open_refuse).  The bag form
+// (evs_cache_fed_begin_bags) stands on the same frame: fed_open_scratch / fed_take_back / fed_list_keys under both begins,
+// fed_finish_check / fed_finish_enter / fed_finish_done under both finishes.
 static int fed_call_check(evs_cache *c, const char *who) {
     using namespace evs;
     const char *pn = policy_name(c->host.policy);
@@ -5701,23 +5737,61 @@ __global__ void __launch_bounds__(256) fed_part_fold_kernel(int *part1, const in
     }
 }
 }  // namespace evs
-// the scratch of the list kernel for calls of up to n_pos positions (a slot per record, 2^k >= 2 n_pos keys and indices, the list length)
-static int fed_scratch(evs_cache *c, long long n_pos, long long n_rec, hipStream_t st, const char *who) {
+// The scratch of the list kernel for a begin of n_pos positions whose lists hold n_rec records (a slot per record, 2^k >= 2 n_pos
+// keys and indices, the list length), grown with the largest call; then this call's share of the slot table -- what is cleared
+// and walked (FedOpen::slot_mask) --, the list length and the call's replica rows cleared on st.
+static int fed_open_scratch(evs_cache *c, long long n_pos, long long n_rec, hipStream_t st, const char *who) {
     using namespace evs;
     { const int rc = ensure_counters(&c->fed_cnt, 2 * sizeof(unsigned long long) + (size_t)kReplicas * kPartCols * sizeof(int), st, who, "fed-backing"); if (rc) return rc; }
     c->fed_part1 = reinterpret_cast<int *>(c->fed_cnt + 2);
-    if (n_pos <= c->fed_max_pos && n_rec <= c->fed_max_rec) return EVS_OK;
-    n_pos = std::max(n_pos, c->fed_max_pos); n_rec = std::max(n_rec, c->fed_max_rec);
-    long long slots = 64;
-    while (slots < 2 * n_pos) slots <<= 1;
-    unsigned long long *slot_key = nullptr; int *slot_index = nullptr, *rec_slot = nullptr, *n = nullptr;
-    void *slab = nullptr;
-    SlabPlan sp;
-    sp.add(&slot_key, slots * 8); sp.add(&slot_index, slots * 4); sp.add(&rec_slot, n_rec * 4); sp.add(&n, 4);
-    if (!sp.carve(&slab)) { set_error("%s: allocating the fed-list scratch of a call of %lld positions failed", who, n_pos); return EVS_ENOMEM; }
-    if (c->slab_fed) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(c->slab_fed); }
-    c->slab_fed = slab; c->fed_slot_key = slot_key; c->fed_slot_index = slot_index; c->fed_rec_slot = rec_slot; c->fed_n = n;
-    c->fed_max_pos = n_pos; c->fed_max_rec = n_rec;
+    auto slots_of = [](long long np) { long long s = 64; while (s < 2 * np) s <<= 1; return s; };
+    if (n_pos > c->fed_max_pos || n_rec > c->fed_max_rec) {
+        const long long np = std::max(n_pos, c->fed_max_pos), nr = std::max(n_rec, c->fed_max_rec), slots = slots_of(np);
+        unsigned long long *slot_key = nullptr; int *slot_index = nullptr, *rec_slot = nullptr, *n = nullptr;
+        void *slab = nullptr;
+        SlabPlan sp;
+        sp.add(&slot_key, slots * 8); sp.add(&slot_index, slots * 4); sp.add(&rec_slot, nr * 4); sp.add(&n, 4);
+        if (!sp.carve(&slab)) { set_error("%s: allocating the fed-list scratch of a call of %lld positions failed", who, np); return EVS_ENOMEM; }
+        if (c->slab_fed) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(c->slab_fed); }
+        c->slab_fed = slab; c->fed_slot_key = slot_key; c->fed_slot_index = slot_index; c->fed_rec_slot = rec_slot; c->fed_n = n;
+        c->fed_max_pos = np; c->fed_max_rec = nr;
+    }
+    const long long slots = slots_of(n_pos);
+    c->fedc.slot_mask = (unsigned)(slots - 1);
+    if (hipMemsetAsync(c->fed_slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(c->fed_n, 0, 4, st) != hipSuccess ||
+        hipMemsetAsync(c->fed_part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: clearing the fed-list scratch failed", who); return EVS_EHIP;
+    }
+    return EVS_OK;
+}
+// a begin that refuses behind the point where the call was counted, and evs_cache_fed_abort: the call's ordinal and stamp go back
+// (a flush the begin ran stands: it is due before the next call, as ever)
+static void fed_take_back(evs_cache *c) {
+    c->batch_calls--; c->stamp_counter = c->fedc.stamp_counter0;
+    if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
+}
+// The end of both begins: the distinct missing keys of the fed tables out of the probe's `grid` miss lists into keys (grid 0: a call
+// without a position lists nothing), their number to the host, and -- the stream synchronised -- the call written down as open.
+// bag_grid: the bag form's grid, which its finish launches over again.
+static int fed_list_keys(evs_cache *c, const uint4 *rec, const int *cnt, int rec_cap, uint64_t *keys, int grid, hipStream_t st, const char *who,
+                         bool bags, int64_t B, const int32_t *rows, uint8_t *hit, int64_t *n_keys_host) {
+    using namespace evs;
+    evs_cache::FedOpen &o = c->fedc;
+    if (grid) {
+        FedListArgs la{};
+        la.miss_rec = rec; la.list_cnt = cnt; la.list_cap = rec_cap;
+        la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
+        la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
+        la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
+        fed_list_launch(la, grid, st);
+    }
+    int n = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return EVS_EHIP;
+    }
+    o.open = true; o.bags = bags; o.B = B; o.rows = rows; o.hit = hit; o.n_keys = n; o.bag_grid = bags ? grid : 0;
+    *n_keys_host = n;
     return EVS_OK;
 }
 static evs::FedSrc fed_src(evs_cache *c, const void *fed, int64_t stride) {
@@ -5746,71 +5820,36 @@ extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows,
     BatchArgs &a = o.a;
     { const int rc = batch_prepare(c, B, rows, st, a, who); if (rc) return rc; }
     // (from here on a refusal takes the call's ordinal back: batch_prepare has counted it)
-    auto fail = [&](int rc) {
-        c->batch_calls--; c->stamp_counter = o.stamp_counter0;
-        if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
-        return rc;
-    };
+    auto fail = [&](int rc) { fed_take_back(c); return rc; };
     const int T = c->host.n_tables;
     a.out = nullptr; a.hit = hit;
-    const int list_cap = (int)((B + 8 * (long long)a.g1 - 1) / (8 * (long long)a.g1)) * 8 * T;
+    a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt; a.list_cap = (int)list_cap(B, a.g1, T);
     { const int rc = fetch_first_state(c, st, who); if (rc) return fail(rc); }
-    { const int rc = fed_scratch(c, B * T, (long long)a.g1 * list_cap, st, who); if (rc) return fail(rc); }
-    long long slots = 64;
-    while (slots < 2 * B * T) slots <<= 1;   // (this call's share of the scratch table: what is cleared and walked)
-    o.slot_mask = (unsigned)(slots - 1);
-    if (hipMemsetAsync(c->fed_slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(c->fed_n, 0, 4, st) != hipSuccess ||
-        hipMemsetAsync(c->fed_part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
-        (void)hipGetLastError(); set_error("%s: clearing the fed-list scratch failed", who); return fail(EVS_EHIP);
-    }
-    a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt; a.list_cap = list_cap;
+    { const int rc = fed_open_scratch(c, B * T, (long long)a.g1 * a.list_cap, st, who); if (rc) return fail(rc); }
     // The probe writes no way word (fed_probe_kernel): what a one-call lookup's probe does to the ways it hits -- the LRU / LFU touch,
-    // EvLFU's raise -- is the finish's first launch, so a call that is dropped leaves the tier as it found it.
-    const bool evlfu = c->host.policy == kEvLFU;
+    // EvLFU's raise -- is the finish's first launch, so a call that is dropped leaves the tier as it found it.  Its totals go into
+    // fed_part1: folded by the finish, never counted for a dropped call.
     PolicyArgs &pa = o.pa;
-    pa = PolicyArgs{};
-    pa.sa = c->sa; pa.sau = c->sau;
-    if (evlfu) {
-        a.stamp = next_batch_stamp(c);
-        sampled_flush_if_wanted(c, st);   // (asked for by an earlier close: the tier's, not this call's -- it stands if the call is dropped)
-    } else {
-        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
-        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
-    }
-    pa.requests = rows; pa.hit = hit; pa.row_ptrs = c->row_ptrs; pa.row_ids = nullptr;
-    pa.miss_rec = c->miss_rec; pa.list_cnt = c->list_cnt; pa.list_cap = list_cap;
-    pa.part1 = c->fed_part1; pa.part2 = a.part2;   // (the probe's totals: folded by the finish, never counted for a dropped call)
-    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = c->backing_rows[k]; }
-    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
-    fed_probe_launch(pa, evlfu, a.g1, st);
-    FedListArgs la{};
-    la.miss_rec = c->miss_rec; la.list_cnt = c->list_cnt; la.list_cap = list_cap;
-    la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
-    la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
-    la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
-    fed_list_launch(la, a.g1, st);
-    int n = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return fail(EVS_EHIP);
-    }
-    o.open = true; o.bags = false; o.B = B; o.rows = rows; o.hit = hit; o.n_keys = n;
-    *n_keys_host = n;
+    pa = policy_args(c, B, rows, hit, c->row_ptrs, c->miss_rec, c->list_cnt, a.list_cap, c->fed_part1);
+    a.stamp = tier_next_batch(c, pa, st);
+    fed_probe_launch(pa, c->host.policy == kEvLFU, a.g1, st);
+    { const int rc = fed_list_keys(c, c->miss_rec, c->list_cnt, a.list_cap, keys, a.g1, st, who, false, B, rows, hit, n_keys_host); if (rc) return fail(rc); }
     return EVS_OK;
 }
 
-static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
-                           const char *who) {
+// ---- what the finishes of both forms share: the head (checks, then the call is spent and the fold is launched) and the tail ----
+// No call open, the other form's call open (it stays open), the fed block: argument errors leave the call open -- finish again, or abort.
+static int fed_finish_check(evs_cache *c, bool want_bags, const void *fed, int64_t stride, const char *who) {
     using namespace evs;
-    EVS_REQUIRE(c, "%s: NULL cache", who);
-    evs_cache::FedOpen &o = c->fedc;
-    if (!o.open) { set_error("%s: no fed call is open on this %s cache (evs_cache_fed_begin)", who, policy_name(c->host.policy)); return EVS_ESTATE; }
-    if (o.bags) {   // (the call stays open)
-        set_error("%s: the call open on this %s cache is a bag call (evs_cache_fed_begin_bags): finish it with evs_cache_fed_finish_bags / "
-                  "_fed_finish_bags_interact, or drop it with evs_cache_fed_abort", who, policy_name(c->host.policy));
+    const evs_cache::FedOpen &o = c->fedc;
+    const char *pn = policy_name(c->host.policy);
+    if (!o.open) { set_error("%s: no fed call is open on this %s cache (%s)", who, pn, want_bags ? "evs_cache_fed_begin_bags" : "evs_cache_fed_begin"); return EVS_ESTATE; }
+    if (o.bags != want_bags) {
+        set_error("%s: the call open on this %s cache is a %s: finish it with %s, or drop it with evs_cache_fed_abort", who, pn,
+                  o.bags ? "bag call (evs_cache_fed_begin_bags)" : "(B, T) call (evs_cache_fed_begin)",
+                  o.bags ? "evs_cache_fed_finish_bags / _fed_finish_bags_interact" : "evs_cache_fed_finish / _fed_finish_interact");
         return EVS_ESTATE;
     }
-    // argument errors leave the call open: finish again, or abort
     const int rb = c->host.row_bytes;
     const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
     EVS_REQUIRE(fed || o.n_keys == 0, "%s: NULL fed with %lld keys listed", who, o.n_keys);
@@ -5819,6 +5858,27 @@ static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float 
         EVS_REQUIRE(reinterpret_cast<uintptr_t>(fed) % align == 0 && stride % align == 0, "%s: fed and fed_stride_bytes must be multiples of %lld bytes "
                     "(what a table of %d-byte rows gives its rows)", who, (long long)align, rb);
     }
+    return EVS_OK;
+}
+// from here on the call is spent, whatever a consumer says; the begin's totals are folded into the tier's rows
+static evs::FedSrc fed_finish_enter(evs_cache *c, const void *fed, int64_t stride, hipStream_t st) {
+    const evs::FedSrc fs = fed_src(c, fed, fed ? stride : 0);
+    c->fedc.open = false;
+    c->fetch_calls++;
+    hipLaunchKernelGGL(evs::fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    return fs;
+}
+static int fed_finish_done(evs_cache *c, int64_t B, hipStream_t st) {
+    const int rc = tier_alone_done(c, B, st);
+    c->fed_calls++; c->fed_keys += c->fedc.n_keys;   // (behind the close, whatever the last launch said)
+    return rc;
+}
+
+static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
+                           const char *who) {
+    using namespace evs;
+    evs_cache::FedOpen &o = c->fedc;
+    { const int rc = fed_finish_check(c, false, fed, stride, who); if (rc) return rc; }
     if (R && c->host.codec == 32)
         EVS_REQUIRE(evs_fused_dim_supported(c->host.dim) && c->host.n_tables + 1 <= EVS_MAX_FEATURES, "%s: needs a fused-kernel dimension and T <= 31", who);
     if (R && c->host.codec != 32)
@@ -5826,30 +5886,19 @@ static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float 
                     "%s: a reduced-precision cache needs d in {16, 32, 36}, T <= 31 and its addressed tables in HBM", who);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const BatchArgs &a = o.a;
-    const FedSrc fs = fed_src(c, fed, fed ? stride : 0);
-    o.open = false;   // (from here on the call is spent, whatever a consumer says)
-    c->fetch_calls++;
-    hipLaunchKernelGGL(fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    const FedSrc fs = fed_finish_enter(c, fed, stride, st);
     {   // the touch / the raise of the ways the begin hit, in front of the update (EvLFU: its histogram moves go into part1 itself)
         PolicyArgs ha = o.pa;
         ha.part1 = c->part1;
         fed_hits_launch(ha, c->host.policy == kEvLFU, a.g1, st);
     }
     if (c->host.policy != kEvLFU) policy_insert_fed_launch(o.pa, fs, a.g1, sampled_list_threads(a), st);
-    else
-        with_row_shape(a.row_bytes, [&](auto s) {
-            using S = decltype(s);
-            hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
-        });
+    else launch_sa_update_fed(a, fs, st);
     RepointArgs ra = repoint_args(c, o.hit, c->row_ptrs, o.B);
     ra.requests = o.rows; ra.n_pos = o.B * c->host.n_tables;
     sa_repoint_fed_launch(ra, fs, a.g1, st);
     { const int rc = batch_consumers(c, nullptr, o.B, out, x, x_stride, itself, R, st); if (rc) return rc; }   // (a consumer that refuses: the batch is not counted)
-    count_batch(c, o.B);
-    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-    c->fed_calls++; c->fed_keys += o.n_keys;
-    EVS_HIP_CHECK(hipGetLastError());
-    return EVS_OK;
+    return fed_finish_done(c, o.B, st);
 }
 extern "C" int evs_cache_fed_finish(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *out, void *stream) {
     using namespace evs;
@@ -5870,9 +5919,7 @@ extern "C" int evs_cache_fed_abort(evs_cache *c) {
     EVS_REQUIRE(c, "evs_cache_fed_abort: NULL cache");
     if (!c->fedc.open) { set_error("evs_cache_fed_abort: no fed call is open on this %s cache (evs_cache_fed_begin)", policy_name(c->host.policy)); return EVS_ESTATE; }
     c->fedc.open = false;
-    c->batch_calls--;
-    c->stamp_counter = c->fedc.stamp_counter0;
-    if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;   // (a flush the begin ran: before the next call, as ever)
+    fed_take_back(c);
     return EVS_OK;
 }
 // out4 (host): [calls finished, keys listed, missed positions of fed tables, positions served straight from a fed block]
@@ -6007,6 +6054,25 @@ static int bag_pool_interact(const float *pool, int T, int64_t B, int d, const f
     for (int k = 0; k < T; k++) { feats[k + 1] = pool + (long long)k * B * d; strides[k + 1] = d; }
     return evs_interact_dot(B, T + 1, d, feats, strides, itself, R, stream);
 }
+// What the bag kernels of a tier alone read (evs_cache_policy.h: BagArgs), for the one-call form and the fed begin: the tier
+// (policy_args over the bag slab, the totals into part1), the call's index arrays and everything else that comes from the cache.
+// The caller sets what differs: out and its strides, pool_flags, pool_only -- and p.part1, where the totals are not the tier's yet.
+static evs::BagArgs bag_args(evs_cache *c, const BagCall &bc, int64_t B, const int64_t *const *indices, const int64_t *const *offsets, const int64_t *nnz,
+                             uint8_t *hit, int *err) {
+    using namespace evs;
+    BagArgs a{};
+    a.p = policy_args(c, B, nullptr, hit ? hit : c->bag_hit, c->bag_ptrs, c->bag_rec, c->bag_list_cnt, (int)(bc.iters * 256), c->part1);
+    for (int k = 0; k < 32; k++) {
+        a.indices[k] = k < bc.T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
+        a.offsets[k] = k < bc.T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
+        a.pos0[k + 1] = a.pos0[k] + (k < bc.T ? nnz[k] : 0);
+    }
+    a.n_pos = bc.n_pos; a.iters = (int)bc.iters; a.err = err;
+    a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
+    a.sample_cnt = c->bag_sample; a.d = bc.d;
+    a.evlfu = c->host.policy == kEvLFU ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
+    return a;
+}
 
 // ---- ragged bags through an LRU / LFU / EvLFU tier (the rule: include/evstore_hip.h at evs_cache_lookup_bags) ---------------
 // probe + touch over the flat position list -> pooling through the pointer table (-> the dense interaction) -> the insert
@@ -6070,35 +6136,11 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
     c->used = 2;
     c->batch_calls++;
 
-    BagArgs a;
+    BagArgs a = bag_args(c, bc, B, indices, offsets, nnz, hit, err);
     PolicyArgs &pa = a.p;
-    pa.sa = c->sa; pa.sau = c->sau;
-    pa.lay = PolLayout{}; pa.cur = 0u;
-    int stamp = 0;
-    if (evlfu) {   // the (B, T) chain's batch stamp, and the flush the close of an earlier batch asked for: before this batch's probe
-        stamp = next_batch_stamp(c);
-        sampled_flush_if_wanted(c, st);
-    } else {
-        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
-        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
-    }
-    pa.requests = nullptr; pa.hit = hit ? hit : c->bag_hit; pa.row_ptrs = c->bag_ptrs; pa.row_ids = nullptr;
-    pa.miss_rec = c->bag_rec; pa.list_cnt = c->bag_list_cnt; pa.list_cap = (int)(iters * 256);
-    pa.part1 = c->part1; pa.part2 = c->part2;
-    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = k < T ? c->backing_rows[k] : 0; }
-    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
-    a.pos0[0] = 0;
-    for (int k = 0; k < 32; k++) {
-        a.indices[k] = k < T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
-        a.offsets[k] = k < T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
-        a.pos0[k + 1] = a.pos0[k] + (k < T ? nnz[k] : 0);
-    }
-    a.n_pos = n_pos; a.iters = (int)iters; a.err = err;
+    const int stamp = tier_next_batch(c, pa, st);   // (EvLFU: the (B, T) chain's batch stamp, and a flush that is due: before this batch's probe)
     a.out = interact ? c->bag_pool : pooled;
     a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
-    a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
-    a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
-    a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
     a.pool_flags = ff ? pa.hit : nullptr;
     a.pool_only = cf ? 1 : 0;
 
@@ -6135,10 +6177,7 @@ static int cache_bags_impl(evs_cache *c, int64_t B, const int64_t *const *indice
         if (rc) return rc;   // (nothing is inserted: the touches stand, as after any launch failure behind the probe)
     }
     if (grid && !ff) update();
-    count_batch(c, B);
-    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-    EVS_HIP_CHECK(hipGetLastError());
-    return EVS_OK;
+    return tier_alone_done(c, B, st);
 }
 
 extern "C" int evs_cache_lookup_bags(evs_cache *c, int64_t B, const int64_t *const *indices, const int64_t *const *offsets,
@@ -6158,7 +6197,7 @@ extern "C" int evs_cache_lookup_bags_interact(evs_cache *c, int64_t B, const int
 
 // ---- ragged bags over fed backing: the count-first fetch-first bag chain cut in two (the contract: include/evstore_hip.h at
 // evs_cache_fed_begin_bags; the kernels: evs_cache_policy.h at bags_fed_probe_launch) -------------------------------------------
-//   begin    (EvLFU: flush ->) bags_fed_probe -> (EvLFU: bags_count -> bags_fed_list) -> fed_list -> synchronise
+//   begin    three clears -> (EvLFU: flush ->) bags_fed_probe -> (EvLFU: bags_count -> bags_fed_list) -> fed_list -> synchronise
 //   finish   fold -> bags_fed_hits -> the fed insert of the policy -> bags_repoint_fed -> bags_pool (-> dense interaction) -> close
 // The begin writes no way word and counts into the call's own replica rows (fed_part1), so evs_cache_fed_abort serves both forms.
 // The open call owns the bag slab until it ends: every other batched call is refused meanwhile (fed_open_refuse).
@@ -6186,10 +6225,9 @@ extern "C" int evs_cache_fed_begin_bags(evs_cache *c, int64_t B, const int64_t *
         }, bc);
         if (rc) return rc;
     }
-    const int T = bc.T, d = bc.d;
-    const long long n_pos = bc.n_pos, grid = bc.grid, iters = bc.iters;
+    const long long n_pos = bc.n_pos, grid = bc.grid;
     const int piece_bytes = c->host.codec / 2;
-    for (int k = 0; k < T; k++)
+    for (int k = 0; k < bc.T; k++)
         EVS_REQUIRE(reinterpret_cast<uintptr_t>(c->backing[k]) % piece_bytes == 0, "%s: table %d is not %d-byte aligned", who, k, piece_bytes);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     { const int rc = batch_state(c, st, who); if (rc) return rc; }
@@ -6197,98 +6235,36 @@ extern "C" int evs_cache_fed_begin_bags(evs_cache *c, int64_t B, const int64_t *
     int *err = index_error_flag();
     if (!err) return EVS_EHIP;
     { const int rc = bag_slab_grow(c, n_pos, B, st, who); if (rc) return rc; }
-    { const int rc = fed_scratch(c, n_pos, bag_list_records(n_pos), st, who); if (rc) return rc; }
+    { const int rc = fed_open_scratch(c, n_pos, bag_list_records(n_pos), st, who); if (rc) return rc; }
     evs_cache::FedOpen &o = c->fedc;
     o.stamp_counter0 = c->stamp_counter;
     c->used = 2;
     c->batch_calls++;
     // (from here on a refusal takes the call's ordinal back)
-    auto fail = [&](int rc) {
-        c->batch_calls--; c->stamp_counter = o.stamp_counter0;
-        if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
-        return rc;
-    };
-    long long slots = 64;
-    while (slots < 2 * n_pos) slots <<= 1;   // (this call's share of the scratch table: what is cleared and walked)
-    o.slot_mask = (unsigned)(slots - 1);
-    if (hipMemsetAsync(c->fed_slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(c->fed_n, 0, 4, st) != hipSuccess ||
-        hipMemsetAsync(c->fed_part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
-        (void)hipGetLastError(); set_error("%s: clearing the fed-list scratch failed", who); return fail(EVS_EHIP);
-    }
     BagArgs &a = o.ba;
-    a = BagArgs{};
-    PolicyArgs &pa = a.p;
-    pa.sa = c->sa; pa.sau = c->sau;
-    o.bag_stamp = 0;
-    if (evlfu) {
-        o.bag_stamp = next_batch_stamp(c);
-        sampled_flush_if_wanted(c, st);   // (asked for by an earlier close: the tier's, not this call's -- it stands if the call is dropped)
-    } else {
-        pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
-        pa.cur = (unsigned)((unsigned long long)(++c->stamp_counter) & pol_stamp_mask(pa.lay));
-    }
-    pa.requests = nullptr; pa.hit = hit ? hit : c->bag_hit; pa.row_ptrs = c->bag_ptrs; pa.row_ids = nullptr;
-    pa.miss_rec = c->bag_rec; pa.list_cnt = c->bag_list_cnt; pa.list_cap = (int)(iters * 256);
-    pa.part1 = c->fed_part1; pa.part2 = c->part2;   // (the begin's totals: folded by the finish, never counted for a dropped call)
-    for (int k = 0; k < 32; k++) { pa.backing[k] = c->backing[k]; pa.backing_rows[k] = k < T ? c->backing_rows[k] : 0; }
-    pa.arena = c->a.arena; pa.B = B; pa.T = T; pa.row_bytes = c->host.row_bytes;
-    a.pos0[0] = 0;
-    for (int k = 0; k < 32; k++) {
-        a.indices[k] = k < T ? reinterpret_cast<const long long *>(indices[k]) : nullptr;
-        a.offsets[k] = k < T ? reinterpret_cast<const long long *>(offsets[k]) : nullptr;
-        a.pos0[k + 1] = a.pos0[k] + (k < T ? nnz[k] : 0);
-    }
-    a.n_pos = n_pos; a.iters = (int)iters; a.err = err;
-    a.arena_end = c->a.arena + ((((size_t)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual) * (size_t)c->host.row_bytes;
-    a.sample_cnt = c->bag_sample; a.chunks_per_table = 0; a.d = d;
-    a.evlfu = evlfu ? 1 : 0; a.prov = c->bag_prov; a.pos_sample = c->bag_pos_sample; a.agg = c->bag_agg;
-    a.pool_flags = pa.hit;
+    a = bag_args(c, bc, B, indices, offsets, nnz, hit, err);
+    a.p.part1 = c->fed_part1;   // (the begin's totals: folded by the finish, never counted for a dropped call)
+    o.bag_stamp = tier_next_batch(c, a.p, st);
+    a.pool_flags = a.p.hit;
     a.pool_only = evlfu ? 1 : 0;
     if (grid) bags_fed_probe_launch(a, (int)grid, st);
     if (evlfu) {
         bags_count_launch(a, st);   // (column 39 into the call's rows; sample_cnt is zero again behind it)
         if (grid) bags_fed_list_launch(a, (int)grid, st);
     }
-    if (grid) {
-        FedListArgs la{};
-        la.miss_rec = c->bag_rec; la.list_cnt = c->bag_list_cnt; la.list_cap = pa.list_cap;
-        la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
-        la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
-        la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
-        fed_list_launch(la, (int)grid, st);
-    }
-    int n = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return fail(EVS_EHIP);
-    }
-    o.open = true; o.bags = true; o.B = B; o.rows = nullptr; o.hit = pa.hit; o.n_keys = n; o.bag_grid = (int)grid;
-    *n_keys_host = n;
-    return EVS_OK;
+    const int rc = fed_list_keys(c, c->bag_rec, c->bag_list_cnt, a.p.list_cap, keys, (int)grid, st, who, true, B, nullptr, a.p.hit, n_keys_host);
+    if (rc) fed_take_back(c);
+    return rc;
 }
 
 static int fed_finish_bags_impl(evs_cache *c, const void *fed, int64_t stride, float *pooled, int64_t out_tstride, int64_t out_bstride, const float *x,
                                 int64_t x_stride, int itself, float *R, void *stream, const char *who) {
     using namespace evs;
     evs_cache::FedOpen &o = c->fedc;
-    const char *pn = policy_name(c->host.policy);
-    if (!o.open) { set_error("%s: no fed call is open on this %s cache (evs_cache_fed_begin_bags)", who, pn); return EVS_ESTATE; }
-    if (!o.bags) {   // (the call stays open)
-        set_error("%s: the call open on this %s cache is a (B, T) call (evs_cache_fed_begin): finish it with evs_cache_fed_finish / _fed_finish_interact, "
-                  "or drop it with evs_cache_fed_abort", who, pn);
-        return EVS_ESTATE;
-    }
-    // argument errors leave the call open: finish again, or abort
+    { const int rc = fed_finish_check(c, true, fed, stride, who); if (rc) return rc; }
     const bool interact = R != nullptr;
-    const int rb = c->host.row_bytes, T = c->host.n_tables, d = c->host.dim;
+    const int T = c->host.n_tables, d = c->host.dim;
     const int64_t B = o.B;
-    const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
-    EVS_REQUIRE(fed || o.n_keys == 0, "%s: NULL fed with %lld keys listed", who, o.n_keys);
-    if (fed) {
-        EVS_REQUIRE(stride >= rb, "%s: fed_stride_bytes %lld is below the row size of %d bytes", who, (long long)stride, rb);
-        EVS_REQUIRE(reinterpret_cast<uintptr_t>(fed) % align == 0 && stride % align == 0, "%s: fed and fed_stride_bytes must be multiples of %lld bytes "
-                    "(what a table of %d-byte rows gives its rows)", who, (long long)align, rb);
-    }
     EVS_REQUIRE(out_tstride % 4 == 0 && out_bstride % 4 == 0 && x_stride % 4 == 0, "%s: strides must be multiples of 4 floats", who);
     EVS_REQUIRE(reinterpret_cast<uintptr_t>(interact ? (const void *)x : (const void *)pooled) % 16 == 0, "%s: %s must be 16-byte aligned", who, interact ? "x" : "pooled");
     if (interact)
@@ -6296,29 +6272,20 @@ static int fed_finish_bags_impl(evs_cache *c, const void *fed, int64_t stride, f
                     who, EVS_MAX_FEATURES, T, d);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (interact) { const int rc = bag_pool_grow(c, T, B, d, st, who); if (rc) return rc; }
-    const FedSrc fs = fed_src(c, fed, fed ? stride : 0);
+    const FedSrc fs = fed_finish_enter(c, fed, stride, st);
     const bool evlfu = c->host.policy == kEvLFU;
     const int grid = o.bag_grid;
-    o.open = false;   // (from here on the call is spent, whatever a consumer says)
-    c->fetch_calls++;
     BagArgs a = o.ba;
     a.p.part1 = c->part1;   // (from here on the tier's own rows: the raises' histogram moves, LRU / LFU: the pooling's column 39)
     a.out = interact ? c->bag_pool : pooled;
     a.out_tstride = interact ? B * d : out_tstride; a.out_bstride = interact ? d : out_bstride;
-    hipLaunchKernelGGL(fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
     if (grid) {
         bags_fed_hits_launch(a, grid, st);   // the touch / the raise of the ways the begin hit, in front of the update
         if (!evlfu) policy_insert_fed_launch(a.p, fs, grid, 128u, st);   // (lists of up to 256 records and more: two waves each)
-        else {
-            const BatchArgs u = bag_update_args(c, B, o.bag_stamp, c->bag_rec, c->bag_list_cnt, a.p.list_cap, grid);
-            with_row_shape(u.row_bytes, [&](auto s) {
-                using S = decltype(s);
-                hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)grid), dim3(sampled_list_threads(u)), 0, st, u, fs);
-            });
-        }
+        else launch_sa_update_fed(bag_update_args(c, B, o.bag_stamp, c->bag_rec, c->bag_list_cnt, a.p.list_cap, grid), fs, st);
         BagRepointFedArgs ra{};
         ra.sa = c->sa; ra.prov = c->bag_prov; ra.row_ptrs = c->bag_ptrs; ra.arena = c->a.arena; ra.counters = c->fetch_cnt;
-        ra.n_pos = a.n_pos; ra.iters = a.iters; ra.row_bytes = rb;
+        ra.n_pos = a.n_pos; ra.iters = a.iters; ra.row_bytes = c->host.row_bytes;
         bags_repoint_fed_launch(ra, fs, grid, st);
     }
     bags_pool_launch(a, c->host.codec, st);
@@ -6326,11 +6293,7 @@ static int fed_finish_bags_impl(evs_cache *c, const void *fed, int64_t stride, f
         const int rc = bag_pool_interact(c->bag_pool, T, B, d, x, x_stride, itself, R, stream);
         if (rc) return rc;   // (a consumer that refuses: the batch is not counted)
     }
-    count_batch(c, B);
-    if (c->pending_batches >= kCloseEvery) sampled_close_pending(c, 0, st);
-    c->fed_calls++; c->fed_keys += o.n_keys;
-    EVS_HIP_CHECK(hipGetLastError());
-    return EVS_OK;
+    return fed_finish_done(c, B, st);
 }
 extern "C" int evs_cache_fed_finish_bags(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *pooled, int64_t out_table_stride,
                                          int64_t out_bag_stride, void *stream) {
