@@ -13,7 +13,7 @@ from .dlrm_ops import (EVTables, InteractServer, LazyPooled, apply_emb, apply_em
                        interact_features, materialize)
 from .gpu_cache import (FileTier, GpuAltKeyTier, GpuCache, TierServer, export_state_c1c2, load_state_c1c2, lookup_batch_c1c2, lookup_batch_c1c2c3,
                         lookup_bags_c1c2, lookup_bags_interact_c1c2, lookup_interact_c1c2, lookup_interact_c1c2c3, request_c1c2, request_c1c2c3,
-                        save_state_c1c2)
+                        save_state_c1c2, fed_stats_c1c2, lookup_abort_c1c2, lookup_begin_c1c2, lookup_finish_c1c2, lookup_finish_interact_c1c2)
 
 
 
@@ -49,4 +49,5 @@ def configure_runtime(hw_queues=8):
 __all__ = ["EvsError", "build", "configure_runtime", "runtime_started", "EVTables", "InteractServer", "LazyPooled", "apply_emb", "apply_emb_interact", "apply_emb_interact_multi", "apply_emb_interact_mlp1", "interact_features", "materialize", "fused_supported",
            "GpuCache", "FileTier", "GpuAltKeyTier", "TierServer", "request_c1c2", "request_c1c2c3", "lookup_batch_c1c2", "lookup_interact_c1c2",
            "lookup_batch_c1c2c3", "lookup_interact_c1c2c3", "export_state_c1c2", "save_state_c1c2", "load_state_c1c2",
-           "lookup_bags_c1c2", "lookup_bags_interact_c1c2"]
+           "lookup_bags_c1c2", "lookup_bags_interact_c1c2", "lookup_begin_c1c2", "lookup_finish_c1c2", "lookup_finish_interact_c1c2", "lookup_abort_c1c2",
+           "fed_stats_c1c2"]

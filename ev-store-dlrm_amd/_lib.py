@@ -128,6 +128,11 @@ _PROTOS = {
     "evs_cache_fed_begin_bags": (_int, [_vp, _i64, _pp, _pp, _i64p, _vp, _vp, _i64p, _vp]),
     "evs_cache_fed_finish_bags": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "evs_cache_fed_finish_bags_interact": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "evs_cache_pair_fed_begin": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _i64p, _vp, _i64p, _vp]),
+    "evs_cache_pair_fed_finish": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "evs_cache_pair_fed_finish_interact": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "evs_cache_pair_fed_abort": (_int, [_vp, _vp]),
+    "evs_cache_pair_fed_stats": (_int, [_vp, _vp, _i64p, _vp]),
     "evs_cache_set_batch_approx": (_int, [_vp, _int]),
     "evs_cache_approx_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_serve_stop": (_int, [_vp]),

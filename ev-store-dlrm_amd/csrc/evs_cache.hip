@@ -1976,9 +1976,21 @@ struct TwoTierArgs {
     C3Batch c3;
 };
 
-__global__ void __launch_bounds__(256) cache_batch_probe2_kernel(const BatchArgs a1, const BatchArgs a2, const TwoTierArgs tt) {
+// FEDP: the begin of a fed pair call (evs_cache_pair_fed_begin; evs_cache_policy.h at PairFedArgs) -- the same walk, codes, serve
+// bytes, addresses, miss lists and totals, and NO write to a way word (the raise waits for pair_fed_hits_kernel; the caller hands in
+// no route filter and replica rows of the call's own); a missed position of a fed table gets the zero row of its destination tier's
+// codec instead of an address computed from a NULL table base.  The flag is the KERNEL's, and <false> takes an empty struct where
+// <true> takes PairFedProbe: with the body in a function of its own the non-fed kernel came out 700 bytes shorter -- other code --,
+// this way it compiles to the size it had before the flag existed.
+struct PairFedProbe { unsigned fed_mask; const unsigned char *zero1, *zero2; };
+struct NoFedProbe {};
+template <bool FEDP>
+__global__ void __launch_bounds__(256) cache_batch_probe2_kernel(const BatchArgs a1, const BatchArgs a2, const TwoTierArgs tt,
+                                                                   const std::conditional_t<FEDP, PairFedProbe, NoFedProbe> fp) {
     __shared__ int s_d1[kMaxBuckets], s_d2[kMaxBuckets];
     __shared__ int s_sum[4];   // C1 hits, C2 hits, perfect requests, alt-key hits
+    auto fed_miss = [&](int t) { if constexpr (FEDP) return ((fp.fed_mask >> t) & 1u) != 0u; else return false; };
+    auto fed_zero = [&](int dest_tier) -> const unsigned char * { if constexpr (FEDP) return dest_tier == 1 ? fp.zero1 : fp.zero2; else return nullptr; };
     __shared__ int s_list_n[2];   // list mode (as K1): the misses this block has listed for C1 / for C2
     for (int i = threadIdx.x; i < kMaxBuckets; i += blockDim.x) { s_d1[i] = 0; s_d2[i] = 0; }
     if (threadIdx.x < 4) s_sum[threadIdx.x] = 0;
@@ -2051,6 +2063,8 @@ __global__ void __launch_bounds__(256) cache_batch_probe2_kernel(const BatchArgs
         }
         const unsigned long long hm = __ballot(e1 >= 0 || e2 >= 0 || alt_tier != 0);
         const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+        if constexpr (FEDP) {
+        } else
         if (sa) {   // the priority rides in the key word: one atomicMax on it
             if (e1 >= 0 && sa_prio(w1) < agg) {
                 const int old = sa_raise(a1.sa, sa_ways_ptr(a1.sa, (unsigned)end1) + y1, w1, agg);
@@ -2087,9 +2101,10 @@ __global__ void __launch_bounds__(256) cache_batch_probe2_kernel(const BatchArgs
         else if (e2 >= 0) { src = a2.a.arena + (long long)e2 * a2.row_bytes; codec_of = 2; }
         else if (alt_tier == 1) { src = a1.a.arena + (long long)ea * a1.row_bytes; codec_of = 1; }   // the ALT row, at the precision of the tier holding it
         else if (alt_tier == 2) { src = a2.a.arena + (long long)ea * a2.row_bytes; codec_of = 2; }
+        else if (miss && fed_miss(hl)) { src = fed_zero(dest); codec_of = dest; }
         else if (miss && dest == 1) { src = a1.backing[hl] + (long long)row * a1.row_bytes; codec_of = 1; }
         else if (miss) { src = a2.backing[hl] + (long long)row * a2.row_bytes; codec_of = 2; }
-        if (tt.route_filter && miss && dest == 1 && (hl & 1)) tt.route_filter[mix64(key) & tt.route_mask] = tt.route_stamp;
+        if (!FEDP && tt.route_filter && miss && dest == 1 && (hl & 1)) tt.route_filter[mix64(key) & tt.route_mask] = tt.route_stamp;
         if (key_on) {
             const long long m = req * T + hl;
             // (bit 30: hit -- or, of a miss, "the hinted slot is a tombstone", as in K1)
@@ -2855,9 +2870,14 @@ template <> struct SaNative<NoTail> { using type = int; };
 // and a way changes at most once per launch (old -> stamped), which is all the argument needs (docs/HISTORY.md 3.4).
 // FED (a cache with fed tables, evs_cache_policy.h at FedSrc): fsrc, when not NULL, is the key's row in the caller's fed block and
 // is read instead of the table row.
-template <int PIECES, typename U, typename TAIL = NoTail, int W = 0, bool FED = false>
+// SPILL (a tier of the fed pair; evs_cache_policy.h at PairFedArgs, "the spill"): the pair keeps one arena row per way, so the row
+// this thread is about to overwrite may be one the call HIT.  Where the way was occupied by a key of a fed table, the thread copies
+// the way's arena row into slot `rec` (the record's own index) of fs->spill and writes rec at fs->spill_of[entry] -- behind its
+// compare-and-swap (the way is this thread's alone: a way changes at most once per launch, so nobody else writes that arena row or
+// that spill_of word in this launch) and in front of the new row's stores.  One more dependent load, paid by this form alone.
+template <int PIECES, typename U, typename TAIL = NoTail, int W = 0, bool FED = false, bool SPILL = false>
 __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsigned char *table, int t, unsigned row, int agg, unsigned set, unsigned tag1, int *s_delta, int *s_stat,
-                                              const unsigned char *fsrc = nullptr) {
+                                              const unsigned char *fsrc = nullptr, const FedSrc *fs = nullptr, long long rec = 0, int *s_spilled = nullptr) {
     constexpr int NW = W > 0 ? W : kSaMaxWays;   // ways the scans below walk (W = 0: any geometry, masked by args.sa.ways)
     const unsigned long long key = ((unsigned long long)(t + 1) << 32) | row;
     // two tiers: the other tier took this key in this very batch (only an odd table index can be routed both ways by two
@@ -2944,6 +2964,23 @@ __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsig
     else atomicAdd(&s_stat[0], 1);
     atomicAdd(&s_delta[agg], 1);
     unsigned char *drow = args.a.arena + (long long)sa_entry(g, set, (unsigned)way, (sa_sel(g, old_word) ^ 1u) << kSaSelShift) * args.row_bytes;
+    if constexpr (SPILL) {
+        if (old_prio >= 0 && rec < fs->spill_rows) {
+            const int vt = (int)(sa_key_of(args.sau, g, set, old_word) >> 32) - 1;   // the victim's table
+            if ((fs->fed_mask >> (vt & 31)) & 1u) {
+                const long long entry = (long long)sa_entry(g, set, (unsigned)way, old_word);
+                const unsigned char *orow = args.a.arena + entry * args.row_bytes;
+                unsigned char *sp = fs->spill + rec * args.row_bytes;
+                if constexpr (PIECES > 0) {
+#pragma unroll
+                    for (int k = 0; k < PIECES; k++) reinterpret_cast<NU *>(sp)[k] = reinterpret_cast<const NU *>(orow)[k];
+                    if constexpr (!std::is_same<TAIL, NoTail>::value) *reinterpret_cast<NT *>(sp + PIECES * sizeof(U)) = *reinterpret_cast<const NT *>(orow + PIECES * sizeof(U));
+                } else { for (int c = 0; c < args.row_bytes; c++) sp[c] = orow[c]; }
+                fs->spill_of[entry] = (int)rec;
+                atomicAdd(s_spilled, 1);
+            }
+        }
+    }
     if constexpr (PIECES > 0) {
         if constexpr (PIECES > 0) reinterpret_cast<NU *>(drow)[0] = r0;
         if constexpr (PIECES > 1) reinterpret_cast<NU *>(drow)[1] = r1;
@@ -3011,7 +3048,7 @@ __global__ void __launch_bounds__(256) cache_batch_sampled_list_kernel(const Bat
 // the set-associative policy's update: the same lists, sa_insert_one per record.  The list's length, the lane's first
 // record and the table base addresses (into LDS: a per-lane index into the kernel arguments is a memory access) are
 // asked for together -- three dependent round trips per record: those, {set line, source row}, the CAS.
-template <int PIECES, typename U, typename TAIL, bool FED = false>
+template <int PIECES, typename U, typename TAIL, bool FED = false, bool SPILL = false>
 __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs = nullptr);
 template <int PIECES, typename U, typename TAIL = NoTail>
 __global__ void __launch_bounds__(256) cache_batch_sa_list_kernel(const BatchArgs args) { sa_list_block<PIECES, U, TAIL>(args, (int)blockIdx.x); }
@@ -3026,10 +3063,15 @@ __global__ void __launch_bounds__(256) cache_batch_sa_list2_kernel(const BatchAr
 // slot of the scratch table beside it, and its row is read from the caller's fed block at the index that slot names
 template <int PIECES, typename U, typename TAIL = NoTail>
 __global__ void __launch_bounds__(256) cache_batch_sa_list_fed_kernel(const BatchArgs args, const FedSrc fs) { sa_list_block<PIECES, U, TAIL, true>(args, (int)blockIdx.x, &fs); }
-template <int PIECES, typename U, typename TAIL, bool FED>
+// ... and of a tier of the fed pair: the same, and an occupied way's old row is spilled first (sa_insert_one, SPILL)
+template <int PIECES, typename U, typename TAIL = NoTail>
+__global__ void __launch_bounds__(256) cache_batch_sa_list_fed_spill_kernel(const BatchArgs args, const FedSrc fs) { sa_list_block<PIECES, U, TAIL, true, true>(args, (int)blockIdx.x, &fs); }
+template <int PIECES, typename U, typename TAIL, bool FED, bool SPILL>
 __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs) {
     __shared__ int s_delta[kMaxBuckets];
     __shared__ int s_stat[3];
+    __shared__ int s_spilled;
+    if constexpr (SPILL) { if (threadIdx.x == 0) s_spilled = 0; }
     __shared__ const unsigned char *s_table[32];
     for (int i = threadIdx.x; i < kMaxBuckets; i += blockDim.x) s_delta[i] = 0;
     if (threadIdx.x < 3) s_stat[threadIdx.x] = 0;
@@ -3049,7 +3091,8 @@ __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, co
             if constexpr (FED) {
                 const int slot = fs->rec_slot[(long long)bid * args.list_cap + i];
                 const unsigned char *fsrc = slot >= 0 ? fs->fed + (long long)fs->slot_index[slot] * fs->stride : nullptr;
-                sa_insert_one<PIECES, U, TAIL, W, true>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat, fsrc);
+                sa_insert_one<PIECES, U, TAIL, W, true, SPILL>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat, fsrc, fs,
+                                                               (long long)bid * args.list_cap + i, &s_spilled);
             } else
             sa_insert_one<PIECES, U, TAIL, W>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat);
         }
@@ -3061,6 +3104,9 @@ __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, co
         const int i = threadIdx.x;
         const int v = i <= args.T ? s_delta[i] : (i >= 33 && i <= 35) ? s_stat[i - 33] : 0;
         if (v) atomicAdd(&args.part2[(bid % kReplicas) * kPartCols + i], v);
+    }
+    if constexpr (SPILL) {   // (rows spilled: word 2 of the pair's replica rows)
+        if (threadIdx.x == 0 && s_spilled) atomicAdd(&fs->pair_cnt[(bid % kFetchReplicas) * kFetchRowWords + 2], (unsigned long long)s_spilled);
     }
 }
 // both tiers of a two-tier lookup in one launch (their updates are independent once the probe has stamped the route
@@ -3544,8 +3590,19 @@ struct evs_cache {
         bool bags = false;
         evs::BagArgs ba;
         int bag_grid = 0, bag_stamp = 0;
+        // a call of the fed C1 + C2 pair (evs_cache_pair_fed_begin) is written down as open on BOTH tiers, each naming the other;
+        // what the finish needs beyond `a` is kept on C1's copy
+        bool pair = false;
+        evs_cache *partner = nullptr;
+        uint8_t *tier = nullptr; int threshold = 0;
     } fedc;
     long long fed_max_rec = 0;      // the records rec_slot has room for (the two forms round a call's lists differently)
+    // a tier of the fed pair: the spill block (a row slot per miss record of the largest call) and spill_of (an int32 per arena
+    // entry), evs_cache_policy.h at PairFedArgs; C1 keeps the pair's totals: replica rows on the device, calls and keys here
+    unsigned char *fed_spill = nullptr; long long fed_spill_rows = 0;
+    int *fed_spill_of = nullptr;
+    unsigned long long *pair_fed_cnt = nullptr;
+    long long pair_fed_calls = 0, pair_fed_keys1 = 0, pair_fed_keys2 = 0;
 };
 // The tier pair / triple as a resident server (cache_c1c2_serve_kernel): the single-tier server's mailbox and ring rules, owned
 // by an object of its own because the state it mutates belongs to two or three handles.  Every entry point that reads or
@@ -3690,7 +3747,7 @@ unsigned long long sa_key_of_host(const evs::SaUniverse &u, const evs::SaGeom &g
 extern "C" int evs_cache_destroy(evs_cache *c) {
     if (!c) return EVS_OK;
     if (c->tsrv) tiers_member_gone(c->tsrv);   // (the server goes home before the memory it works on is freed)
-    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt, c->slab_fed, c->fed_cnt};
+    void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt, c->slab_fed, c->fed_cnt, c->fed_spill, c->fed_spill_of, c->pair_fed_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
@@ -3832,12 +3889,14 @@ extern "C" int evs_cache_set_miss_order(evs_cache *c, int order) {
     return EVS_OK;
 }
 
+static int fed_open_refuse(evs_cache *c, const char *who);
 // out4 (host): [batched calls run fetch-first, positions re-pointed at the arena, positions served in place from their table, 0];
 // C1 of a fetch-first pair: the pair's calls and re-point totals, [3] = hit positions whose way the call's own update took
 extern "C" int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream) {
     using namespace evs;
     EVS_REQUIRE(c, "evs_cache_fetch_stats: NULL cache");
     EVS_REQUIRE(out4, "evs_cache_fetch_stats: NULL out4");
+    if (c->fedc.open && c->fedc.pair) return fed_open_refuse(c, "evs_cache_fetch_stats");   // (an open pair call: everything else on either tier waits)
     unsigned long long h[3] = {0ull, 0ull, 0ull};
     if (c->fetch_cnt) {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -3921,6 +3980,11 @@ static int exact_launched(evs_cache *c, hipStream_t st);
 // a begin without its finish (evs_cache_fed_begin): everything that would read or move the state the open call stands on is refused
 static int fed_open_refuse(evs_cache *c, const char *who) {
     if (!c || !c->fedc.open) return EVS_OK;
+    if (c->fedc.pair) {
+        evs::set_error("%s: a fed pair call is open on this %s cache (evs_cache_pair_fed_begin without evs_cache_pair_fed_finish / evs_cache_pair_fed_abort)", who,
+                       policy_name(c->host.policy));
+        return EVS_ESTATE;
+    }
     evs::set_error("%s: a fed call is open on this %s cache (evs_cache_fed_begin without evs_cache_fed_finish / evs_cache_fed_abort)", who, policy_name(c->host.policy));
     return EVS_ESTATE;
 }
@@ -4729,6 +4793,14 @@ static void launch_sa_update_fed(const evs::BatchArgs &a, const evs::FedSrc &fs,
     with_row_shape(a.row_bytes, [&](auto s) {
         using S = decltype(s);
         hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
+    });
+}
+
+// ... of a tier of the fed pair (the spill form)
+static void launch_sa_update_fed_spill(const evs::BatchArgs &a, const evs::FedSrc &fs, hipStream_t st) {
+    with_row_shape(a.row_bytes, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_spill_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
     });
 }
 
@@ -5591,7 +5663,7 @@ static int batch_c1c2_impl(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int64_t B
         rc = probe2_interact_mixed84(B, T, c1->host.dim, x, x_stride, pa, itself, R, st);
         if (rc) return rc;
     } else
-    hipLaunchKernelGGL(cache_batch_probe2_kernel, dim3((unsigned)a1.g1), dim3(256), 0, st, a1, a2, tt);
+    hipLaunchKernelGGL(cache_batch_probe2_kernel<false>, dim3((unsigned)a1.g1), dim3(256), 0, st, a1, a2, tt, NoFedProbe{});
     if (host2) {
         // host-memory / file-backed miss tiers: updates first, then the re-pointed consumers
         a2.row_ptrs = c1->row_ptrs;   // both tiers' positions live in C1's pointer table
@@ -5844,6 +5916,7 @@ static int fed_finish_check(evs_cache *c, bool want_bags, const void *fed, int64
     const evs_cache::FedOpen &o = c->fedc;
     const char *pn = policy_name(c->host.policy);
     if (!o.open) { set_error("%s: no fed call is open on this %s cache (%s)", who, pn, want_bags ? "evs_cache_fed_begin_bags" : "evs_cache_fed_begin"); return EVS_ESTATE; }
+    { const int rc = o.pair ? fed_open_refuse(c, who) : EVS_OK; if (rc) return rc; }   // (a pair call: evs_cache_pair_fed_finish / _abort end it)
     if (o.bags != want_bags) {
         set_error("%s: the call open on this %s cache is a %s: finish it with %s, or drop it with evs_cache_fed_abort", who, pn,
                   o.bags ? "bag call (evs_cache_fed_begin_bags)" : "(B, T) call (evs_cache_fed_begin)",
@@ -5918,6 +5991,7 @@ extern "C" int evs_cache_fed_abort(evs_cache *c) {
     using namespace evs;
     EVS_REQUIRE(c, "evs_cache_fed_abort: NULL cache");
     if (!c->fedc.open) { set_error("evs_cache_fed_abort: no fed call is open on this %s cache (evs_cache_fed_begin)", policy_name(c->host.policy)); return EVS_ESTATE; }
+    { const int rc = c->fedc.pair ? fed_open_refuse(c, "evs_cache_fed_abort") : EVS_OK; if (rc) return rc; }
     c->fedc.open = false;
     fed_take_back(c);
     return EVS_OK;
@@ -5927,6 +6001,7 @@ extern "C" int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream) {
     using namespace evs;
     EVS_REQUIRE(c, "evs_cache_fed_stats: NULL cache");
     EVS_REQUIRE(out4, "evs_cache_fed_stats: NULL out4");
+    if (c->fedc.open && c->fedc.pair) return fed_open_refuse(c, "evs_cache_fed_stats");
     unsigned long long h[2] = {0ull, 0ull};
     if (c->fed_cnt) {
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -5934,6 +6009,266 @@ extern "C" int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream) {
         EVS_HIP_CHECK(hipStreamSynchronize(st));
     }
     out4[0] = c->fed_calls; out4[1] = c->fed_keys; out4[2] = (int64_t)h[0]; out4[3] = (int64_t)h[1];
+    return EVS_OK;
+}
+
+// ---- fed backing of the fetch-first C1 + C2 pair (the contract: include/evstore_hip.h at evs_cache_pair_fed_begin; the chain and
+// the spill: evs_cache_policy.h at PairFedArgs) --------------------------------------------------------------------------------
+//   begin    the envelope -> pair_start -> clears (fed_open_scratch, once per tier) -> (flush of either tier ->) the pair's probe in
+//            fed form -> fed_list once per tier -> synchronise: the caller holds each tier's distinct missing keys of the fed tables
+//   finish   fold x 2 -> pair_fed_hits -> the update in fed + spill form, a launch per tier -> sa_repoint2_fed -> consumers -> close
+// The call is written down as open on BOTH tiers (FedOpen::pair, ::partner), so fed_open_refuse turns everything else away on either.
+// A begin + finish is batch n of the pair exactly as a call of batch_c1c2_impl on a fetch-first pair is: the same ordinals, stamps,
+// flush at entry, route stamp and close rhythm.
+static int pair_fed_check(evs_cache *c1, evs_cache *c2, const char *who) {
+    using namespace evs;
+    EVS_REQUIRE(c1 != c2, "%s: C1 and C2 are the same cache", who);
+    EVS_REQUIRE(c1->host.policy == kEvLFU && c2->host.policy == kEvLFU,
+                "%s: the tier pair is evlfu's (C1 %s, C2 %s); an lru / lfu cache takes fed rows as a single tier (evs_cache_fed_begin / evs_cache_fed_finish)", who,
+                policy_name(c1->host.policy), policy_name(c2->host.policy));
+    const char *pn = policy_name(c1->host.policy);
+    EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "%s: the tiers must agree on n_tables and dim", who);
+    for (evs_cache *c : {c1, c2}) { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
+    EVS_REQUIRE(c1->fed_mask && c1->fed_mask == c2->fed_mask, "%s: both tiers of a fed %s pair are fed caches over the SAME fed tables (evs_cache_set_fed_backing on "
+                "each, in its own codec; C1's fed mask is 0x%x, C2's 0x%x); a pair without fed tables runs evs_cache_lookup_batch_c1c2", who, pn, c1->fed_mask, c2->fed_mask);
+    EVS_REQUIRE(c1->miss_order == 1 && c2->miss_order == 1, "%s: a fed %s pair runs fetch-first -- the update in front of the consumers is what gives a fed row a place to be "
+                "read from: tell evs_cache_set_miss_order(c, 1) to both tiers before the first call", who, pn);
+    EVS_REQUIRE(c1->batch_approx <= 0 && c2->batch_approx <= 0, "%s: %s is an %s cache with an approximate threshold on (evs_cache_set_batch_approx): "
+                "that mode is a tier alone's; the fed pair has no approximating probe", who, c1->batch_approx > 0 ? "C1" : "C2", pn);
+    { const int rc = pair_fetch_first_check(c1, c2, nullptr, who); if (rc) return rc; }
+    for (evs_cache *c : {c1, c2})
+        EVS_REQUIRE(c->host.row_bytes <= (c->host.codec == 32 ? 4096 : 1024), "%s: a row of this %s tier has %d bytes; the zero row a missed position of a fed table holds "
+                    "between begin and finish has %d", who, pn, c->host.row_bytes, c->host.codec == 32 ? 4096 : 1024);
+    return EVS_OK;
+}
+// a tier's spill block for a call whose lists hold n_rec records, and spill_of at its first call (never cleared: PairFedArgs)
+static int pair_fed_spill(evs_cache *c, long long n_rec, hipStream_t st, const char *who) {
+    using namespace evs;
+    if (n_rec > c->fed_spill_rows) {
+        unsigned char *p = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&p), (size_t)n_rec * c->host.row_bytes + 16) != hipSuccess) {
+            (void)hipGetLastError(); set_error("%s: allocating the spill block of a call of %lld miss records failed", who, n_rec); return EVS_ENOMEM;
+        }
+        if (c->fed_spill) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(c->fed_spill); }
+        c->fed_spill = p; c->fed_spill_rows = n_rec;
+    }
+    if (!c->fed_spill_of) {
+        const long long entries = (((long long)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual;
+        if (hipMalloc(reinterpret_cast<void **>(&c->fed_spill_of), (size_t)entries * 4) != hipSuccess || hipMemsetAsync(c->fed_spill_of, 0xff, (size_t)entries * 4, st) != hipSuccess) {
+            (void)hipGetLastError();
+            if (c->fed_spill_of) { (void)hipFree(c->fed_spill_of); c->fed_spill_of = nullptr; }
+            set_error("%s: allocating the spill index of %lld arena entries failed", who, entries); return EVS_ENOMEM;
+        }
+    }
+    return EVS_OK;
+}
+static evs::FedSrc pair_fed_src(evs_cache *c, evs_cache *c1, const void *fed, int64_t stride) {
+    evs::FedSrc f = fed_src(c, fed, fed ? stride : 0);
+    f.spill = c->fed_spill; f.spill_of = c->fed_spill_of; f.pair_cnt = c1->pair_fed_cnt;
+    f.spill_rows = c->fed_spill_rows;
+    f.entries = (((long long)c->sa.nset << c->sa.sub_shift) * c->sa.ways) << c->sa.dual;
+    return f;
+}
+
+extern "C" int evs_cache_pair_fed_begin(evs_cache *c1, evs_cache *c2, int64_t B, const int32_t *rows, uint8_t *tier, int high_agghit_threshold, uint64_t *keys1,
+                                        int64_t *n_keys1_host, uint64_t *keys2, int64_t *n_keys2_host, void *stream) {
+    using namespace evs;
+    const char *who = "evs_cache_pair_fed_begin";
+    EVS_REQUIRE(c1 && c2, "%s: NULL cache", who);
+    EVS_REQUIRE(rows && tier && keys1 && n_keys1_host && keys2 && n_keys2_host, "%s: NULL argument", who);
+    EVS_REQUIRE(B > 0, "%s: B = %lld", who, (long long)B);
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys1) % 8 == 0 && reinterpret_cast<uintptr_t>(keys2) % 8 == 0, "%s: keys1 / keys2 must be 8-byte aligned", who);
+    { const int rc = pair_fed_check(c1, c2, who); if (rc) return rc; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = pair_start(c1, c2, st, who); if (rc) return rc; }
+    if (memcmp(&c1->sau, &c2->sau, sizeof(SaUniverse)) != 0) {
+        set_error("%s: the tiers were built over different key universes (table row counts differ); make both over the same tables", who);
+        return EVS_ESTATE;
+    }
+    c1->fedc.stamp_counter0 = c1->stamp_counter; c2->fedc.stamp_counter0 = c2->stamp_counter;
+    BatchArgs &a1 = c1->fedc.a, &a2 = c2->fedc.a;
+    { const int rc = batch_prepare(c1, B, rows, st, a1, who); if (rc) return rc; }
+    { const int rc = batch_prepare(c2, B, rows, st, a2, who); if (rc) { fed_take_back(c1); return rc; } }
+    // (from here on a refusal takes both tiers' ordinals back: batch_prepare has counted the call)
+    auto fail = [&](int rc) { fed_take_back(c1); fed_take_back(c2); return rc; };
+    const int T = c1->host.n_tables;
+    { const int rc = fetch_first_state(c1, st, who); if (rc) return fail(rc); }   // (the pair's counters are C1's)
+    if (!index_error_flag()) return fail(EVS_EHIP);
+    { const int rc = pair_route_filter(c1, st); if (rc) return fail(rc); }
+    { const int rc = ensure_counters(&c1->pair_fed_cnt, (size_t)kFetchReplicas * kFetchRowWords * sizeof(unsigned long long), st, who, "fed-pair"); if (rc) return fail(rc); }
+    const long long lc = list_cap(B, a1.g1, T), n_rec = (long long)a1.g1 * lc;
+    const unsigned char *zero[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = k ? c2 : c1;
+        BatchArgs &a = k ? a2 : a1;
+        a.miss_rec = c->miss_rec; a.list_cnt = c->list_cnt; a.list_cap = (int)lc;
+        { const int rc = fed_open_scratch(c, B * T, n_rec, st, who); if (rc) return fail(rc); }
+        { const int rc = pair_fed_spill(c, n_rec, st, who); if (rc) return fail(rc); }
+        zero[k] = reinterpret_cast<const unsigned char *>(c->host.codec == 32 ? zero_page() : zero_code_page(c->host.codec));
+        if (!zero[k]) return fail(EVS_ENOMEM);
+    }
+    for (int k = 0; k < 2; k++) {   // each tier's step into batch n, as batch_c1c2_impl takes it
+        evs_cache *c = k ? c2 : c1;
+        BatchArgs &a = k ? a2 : a1;
+        a.stamp = next_batch_stamp(c);
+        a.tomb_parity = -1;
+        sampled_flush_if_wanted(c, st);
+        a.part1 = c->fed_part1;   // the probe's totals: rows of the call's own, folded by the finish, never counted for a dropped call
+    }
+    // what C2's update reads of the route filter (the finish stamps it: pair_fed_hits)
+    a2.route_filter = c1->route_filter; a2.route_mask = kRouteWords - 1; a2.route_stamp = (unsigned)a1.stamp;
+    TwoTierArgs tt;
+    tt.row_tier = c1->row_tier; tt.tier_out = tier; tt.threshold = high_agghit_threshold;
+    tt.route_filter = nullptr; tt.route_mask = 0; tt.route_stamp = 0;   // (the begin writes no route-filter word)
+    tt.c3.tags = nullptr; tt.c3.nset = 0; tt.c3.stat = nullptr;
+    for (int k = 0; k < kMaxTables; k++) { tt.c3.alt_tables[k] = nullptr; tt.c3.alt_rows[k] = 0; }
+    PairFedProbe fp;
+    fp.fed_mask = c1->fed_mask; fp.zero1 = zero[0]; fp.zero2 = zero[1];
+    hipLaunchKernelGGL(cache_batch_probe2_kernel<true>, dim3((unsigned)a1.g1), dim3(256), 0, st, a1, a2, tt, fp);
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = k ? c2 : c1;
+        FedListArgs la{};
+        la.miss_rec = c->miss_rec; la.list_cnt = c->list_cnt; la.list_cap = (int)lc;
+        la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
+        la.slot_mask = c->fedc.slot_mask; la.fed_mask = c->fed_mask;
+        la.keys = reinterpret_cast<unsigned long long *>(k ? keys2 : keys1); la.n_keys = c->fed_n;
+        fed_list_launch(la, a1.g1, st);
+    }
+    int n[2] = {0, 0};
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n[0], c1->fed_n, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&n[1], c2->fed_n, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: the probe or a list launch failed", who); return fail(EVS_EHIP);
+    }
+    for (int k = 0; k < 2; k++) {
+        evs_cache *c = k ? c2 : c1;
+        evs_cache::FedOpen &o = c->fedc;
+        o.open = true; o.bags = false; o.pair = true; o.partner = k ? c1 : c2;
+        o.B = B; o.rows = rows; o.hit = nullptr; o.n_keys = n[k]; o.bag_grid = 0;
+        o.tier = k ? nullptr : tier; o.threshold = high_agghit_threshold;   // (tier: C1's copy alone -- it tells the finish which tier is C1)
+    }
+    *n_keys1_host = n[0]; *n_keys2_host = n[1];
+    return EVS_OK;
+}
+
+// no pair call open on (c1, c2) in this order: EVS_ESTATE -- a call of a tier alone, or the call of another pair, stays open
+static int pair_fed_open_check(evs_cache *c1, evs_cache *c2, const char *who) {
+    using namespace evs;
+    EVS_REQUIRE(c1 && c2, "%s: NULL cache", who);
+    const char *pn = policy_name(c1->host.policy);
+    if (!c1->fedc.open || !c1->fedc.pair || !c2->fedc.open || !c2->fedc.pair) {
+        set_error("%s: no fed pair call is open on these %s tiers (evs_cache_pair_fed_begin)", who, pn);
+        return EVS_ESTATE;
+    }
+    if (c1->fedc.partner != c2 || c2->fedc.partner != c1 || !c1->fedc.tier) {
+        set_error("%s: the fed pair call open on this %s cache was begun with a different partner (or with the tiers the other way round): end it with the "
+                  "(C1, C2) evs_cache_pair_fed_begin took", who, pn);
+        return EVS_ESTATE;
+    }
+    return EVS_OK;
+}
+static int pair_fed_block_check(evs_cache *c, const char *name, const void *fed, int64_t stride, const char *who) {
+    using namespace evs;
+    const int rb = c->host.row_bytes;
+    const int64_t align = (rb % 16 == 0) ? 16 : (rb % 8 == 0) ? 8 : (rb % 4 == 0) ? 4 : (rb % 2 == 0) ? 2 : 1;
+    EVS_REQUIRE(fed || c->fedc.n_keys == 0, "%s: NULL %s with %lld keys listed", who, name, c->fedc.n_keys);
+    if (fed) {
+        EVS_REQUIRE(stride >= rb, "%s: %s_stride_bytes %lld is below the tier's row size of %d bytes", who, name, (long long)stride, rb);
+        EVS_REQUIRE(reinterpret_cast<uintptr_t>(fed) % align == 0 && stride % align == 0, "%s: %s and %s_stride_bytes must be multiples of %lld bytes "
+                    "(what a table of %d-byte rows gives its rows)", who, name, name, (long long)align, rb);
+    }
+    return EVS_OK;
+}
+static int pair_fed_finish_impl(evs_cache *c1, evs_cache *c2, const void *fed1, int64_t stride1, const void *fed2, int64_t stride2, float *out, const float *x,
+                                int64_t x_stride, int itself, float *R, void *stream, const char *who) {
+    using namespace evs;
+    { const int rc = pair_fed_open_check(c1, c2, who); if (rc) return rc; }
+    { const int rc = pair_fed_block_check(c1, "fed1", fed1, stride1, who); if (rc) return rc; }
+    { const int rc = pair_fed_block_check(c2, "fed2", fed2, stride2, who); if (rc) return rc; }
+    if (R) EVS_REQUIRE((c1->host.dim == 16 || c1->host.dim == 32 || c1->host.dim == 36) && c1->host.n_tables + 1 <= EVS_MAX_FEATURES,
+                       "%s: d must be 16, 32 or 36 and T <= 31", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    evs_cache::FedOpen &o = c1->fedc;
+    const BatchArgs &a1 = c1->fedc.a, &a2 = c2->fedc.a;
+    const int64_t B = o.B;
+    const int T = c1->host.n_tables;
+    // from here on the call is spent, whatever a consumer says
+    PairFedArgs pa{};
+    pa.f1 = pair_fed_src(c1, c1, fed1, stride1); pa.f2 = pair_fed_src(c2, c1, fed2, stride2);
+    c1->fedc.open = c2->fedc.open = false; c1->fedc.pair = c2->fedc.pair = false;
+    c1->fetch_calls++;
+    for (evs_cache *c : {c1, c2}) hipLaunchKernelGGL(evs::fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    Repoint2Args &ra = pa.r;
+    ra.sa1 = c1->sa; ra.sa2 = c2->sa; ra.sau = c1->sau;
+    ra.requests = o.rows; ra.code = o.tier; ra.serve = c1->row_tier; ra.row_ptrs = c1->row_ptrs;
+    for (int k = 0; k < 32; k++) {
+        ra.rows[k] = k < T ? std::min(c1->backing_rows[k], c2->backing_rows[k]) : 0;
+        ra.backing1[k] = k < T ? c1->backing[k] : nullptr; ra.backing2[k] = k < T ? c2->backing[k] : nullptr;
+    }
+    ra.arena1 = c1->a.arena; ra.arena2 = c2->a.arena; ra.counters = c1->fetch_cnt; ra.err = index_error_flag();
+    ra.B = B; ra.T = T; ra.row_bytes1 = c1->host.row_bytes; ra.row_bytes2 = c2->host.row_bytes;
+    pa.fed_mask = c1->fed_mask; pa.pair_cnt = c1->pair_fed_cnt;
+    pa.part1_1 = c1->part1; pa.part1_2 = c2->part1;
+    pa.route_filter = c1->route_filter; pa.route_mask = kRouteWords - 1; pa.route_stamp = (unsigned)a1.stamp;
+    pair_fed_hits_launch(pa, a1.g1, st);
+    launch_sa_update_fed_spill(a1, pa.f1, st);
+    launch_sa_update_fed_spill(a2, pa.f2, st);
+    sa_repoint2_fed_launch(pa, a1.g1, st);
+    if (out) {
+        const int wide = kNumCu * 8;
+        long long nb = (B * T * (long long)c1->host.dim / 4 + 255) / 256; if (nb > wide) nb = wide; if (nb < 1) nb = 1;
+        hipLaunchKernelGGL(cache_rows_from_ptrs2_kernel, dim3((unsigned)nb), dim3(256), 0, st, c1->row_ptrs, c1->row_tier, out,
+                           (long long)B, T, c1->host.dim, c1->host.codec, c2->host.codec);
+    }
+    if (R) {
+        const int rc = interact_from_mixed_rows(B, T, c1->host.dim, x, x_stride, c1->row_ptrs, c1->row_tier, c1->host.codec, c2->host.codec, itself, R, st);
+        if (rc) return rc;   // (a consumer that refuses: the batch is not counted)
+    }
+    pair_count_batch(c1, c2, B);
+    if (c1->pending_batches >= kCloseEvery || c2->pending_batches >= kCloseEvery || a1.rebuild || a2.rebuild)
+        sampled_close_pending2(c1, a1.rebuild, c2, a2.rebuild, st);
+    c1->pair_fed_calls++; c1->pair_fed_keys1 += c1->fedc.n_keys; c1->pair_fed_keys2 += c2->fedc.n_keys;
+    EVS_HIP_CHECK(hipGetLastError());
+    return EVS_OK;
+}
+extern "C" int evs_cache_pair_fed_finish(evs_cache *c1, evs_cache *c2, const void *fed1, int64_t fed1_stride_bytes, const void *fed2, int64_t fed2_stride_bytes,
+                                         float *out, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c1 && c2 && out, "evs_cache_pair_fed_finish: NULL %s", (c1 && c2) ? "out" : "cache");
+    return pair_fed_finish_impl(c1, c2, fed1, fed1_stride_bytes, fed2, fed2_stride_bytes, out, nullptr, 0, 0, nullptr, stream, "evs_cache_pair_fed_finish");
+}
+extern "C" int evs_cache_pair_fed_finish_interact(evs_cache *c1, evs_cache *c2, const void *fed1, int64_t fed1_stride_bytes, const void *fed2,
+                                                  int64_t fed2_stride_bytes, const float *x, int64_t x_stride, int itself, float *R, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c1 && c2 && x && R, "evs_cache_pair_fed_finish_interact: NULL %s", (c1 && c2) ? "x / R" : "cache");
+    EVS_REQUIRE(x_stride % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0, "evs_cache_pair_fed_finish_interact: x must be 16-byte aligned, stride % 4 == 0");
+    return pair_fed_finish_impl(c1, c2, fed1, fed1_stride_bytes, fed2, fed2_stride_bytes, nullptr, x, x_stride, itself, R, stream, "evs_cache_pair_fed_finish_interact");
+}
+// Drops the open pair call.  The begin wrote no way word and no route-filter word and counted its hits into rows of its own, so
+// nothing is launched and no stream is touched: both tiers' ordinals and stamps go back, and the pair is what it was.
+extern "C" int evs_cache_pair_fed_abort(evs_cache *c1, evs_cache *c2) {
+    using namespace evs;
+    { const int rc = pair_fed_open_check(c1, c2, "evs_cache_pair_fed_abort"); if (rc) return rc; }
+    for (evs_cache *c : {c1, c2}) { c->fedc.open = false; c->fedc.pair = false; fed_take_back(c); }
+    return EVS_OK;
+}
+// out8 (host), cumulative: [calls finished, keys listed for C1, for C2, missed positions of fed tables, of those served from a fed
+// block, rows spilled, hit positions served from the spill, 0]
+extern "C" int evs_cache_pair_fed_stats(evs_cache *c1, evs_cache *c2, int64_t *out8, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c1 && c2, "evs_cache_pair_fed_stats: NULL cache");
+    EVS_REQUIRE(out8, "evs_cache_pair_fed_stats: NULL out8");
+    for (evs_cache *c : {c1, c2}) { const int rc = fed_open_refuse(c, "evs_cache_pair_fed_stats"); if (rc) return rc; }
+    unsigned long long h[4] = {0ull, 0ull, 0ull, 0ull};
+    if (c1->pair_fed_cnt) {
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        unsigned long long rows[kFetchReplicas * kFetchRowWords];
+        EVS_HIP_CHECK(hipMemcpyAsync(rows, c1->pair_fed_cnt, sizeof rows, hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int r = 0; r < kFetchReplicas; r++)
+            for (int k = 0; k < 4; k++) h[k] += rows[r * kFetchRowWords + k];
+    }
+    out8[0] = c1->pair_fed_calls; out8[1] = c1->pair_fed_keys1; out8[2] = c1->pair_fed_keys2;
+    out8[3] = (int64_t)h[0]; out8[4] = (int64_t)h[1]; out8[5] = (int64_t)h[2]; out8[6] = (int64_t)h[3]; out8[7] = 0;
     return EVS_OK;
 }
 

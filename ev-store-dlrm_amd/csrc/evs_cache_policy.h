@@ -205,6 +205,11 @@ struct FedSrc {
     unsigned long long *counters;                 // re-point: [0] missed positions of fed tables, [1] of those served from the fed block
     int *err;                                     // re-point: the sticky index-error flag, raised for an index out of range
     const unsigned char *zero_row;                // re-point: what a position is served whose key the scratch table does not hold (never: see there)
+    // a tier of the fed C1 + C2 pair (PairFedArgs below), NULL / 0 for a tier alone: the spill block (a row slot per miss record),
+    // spill_of (an int32 per arena entry: the slot its last victim's row went to) and the replica rows of the pair's totals
+    unsigned char *spill; int *spill_of;
+    unsigned long long *pair_cnt;
+    long long spill_rows, entries;                // slots of the spill block, arena entries of the tier (the re-point's bounds)
 };
 struct FedListArgs {
     const uint4 *miss_rec; const int *list_cnt; int list_cap;   // the probe's lists (either producer: row, table | .. << 8, set, tag + 1)
@@ -310,5 +315,50 @@ struct BagRepoint2Args {
 // the bag probe's grid and walk (block j: positions 256 (j + i grid) + thread, i < iters); the 8 + 8 pair has its way counts
 // compiled in, every other shared-record geometry takes the general form
 void bags_repoint2_launch(const BagRepoint2Args &a, int grid, hipStream_t st);
+
+// Fed backing of the fetch-first pair (evs_cache_pair_fed_begin; the contract: include/evstore_hip.h there): the pair's chain cut
+// in two where the fed chain of a tier alone is cut:
+//   begin    (flush of either tier ->) the pair's probe in fed form (evs_cache.hip: cache_batch_probe2_kernel<true> -- codes, serve
+//            bytes, addresses, both tiers' miss lists, hit totals into the call's own rows; NO way word, NO route-filter word; a
+//            missed position of a fed table gets its tier's zero row) -> fed_list once per tier, each over its own scratch table
+//   finish   fold x 2 -> pair_fed_hits -> the pair's update in fed form, a launch per tier (evs_cache.hip: sa_list_block<FED, SPILL>)
+//            -> sa_repoint2_fed -> consumers -> close bookkeeping
+//   pair_fed_hits     everything the ordinary probe writes that the begin withheld: a way the begin hit (its code names the tier)
+//                     is raised to the sample's agg_hit = the number of its codes that are not 0, the histogram moves into
+//                     part1_1 / part1_2 columns 0 .. T; a miss routed to C1 (serve byte 1) on an odd table is stamped into the
+//                     route filter.  Nothing else writes a way word in that launch.
+//   the spill         The pair keeps ONE arena row per way, so a way the call hit can be the call's victim, and a fed table has no
+//                     table row to serve such a position from.  The update's thread that replaces an OCCUPIED way whose old key
+//                     belongs to a fed table copies the way's arena row into slot `record index` (list * list_cap + i) of the
+//                     tier's spill block -- behind its compare-and-swap, which made the way its own, and in front of the new
+//                     row's stores -- and writes that index at spill_of[entry].  A victim of an addressed table is not spilled:
+//                     its hit positions are served from the table row, as sa_repoint2 serves them.  A way filled from free has
+//                     nothing to spill.
+//   sa_repoint2_fed   per position, in the ways of the tier its serve byte d names:
+//                       code 0, found                       tier d's arena row
+//                       code 0, not found, fed table        fed_d's row through tier d's scratch table (read-only walk; a key the
+//                                                           table does not hold: the zero row stays, the sticky flag is raised)
+//                       code 0, not found, addressed table  the table row the probe wrote stays
+//                       code d, found                       nothing stored
+//                       code d, not found, fed table        spill_d + spill_of_d[entry] * row_bytes_d, entry = (the arena address
+//                                                           the probe wrote - arena_d) / row_bytes_d
+//                       code d, not found, addressed table  tier d's table row
+//                     No stamp and no clearing of spill_of: "code d, not found" means this call's update replaced that way, a way
+//                     changes at most once per update launch (old -> stamped), so exactly ONE thread won the way's
+//                     compare-and-swap and wrote spill_of[entry] -- in this call, in a launch that ended before this one began.
+// counters: r.counters as Repoint2Args has them ([2] counts every "code d, not found" position, spill or table); pair_cnt: replica
+// rows of kFetchRowWords words -- [0] missed positions of fed tables, [1] of those served from a fed block, [2] rows spilled (the
+// update adds it), [3] hit positions served from the spill.
+struct PairFedArgs {
+    Repoint2Args r;
+    FedSrc f1, f2;                         // per tier: the fed block, the scratch table, the zero row, the spill
+    unsigned fed_mask;
+    unsigned long long *pair_cnt;
+    int *part1_1, *part1_2;                // pair_fed_hits: the tiers' replica rows
+    unsigned *route_filter; unsigned route_mask, route_stamp;
+};
+// both: the (B, T) probe's grid and walk, the 8 + 8 pair with its way counts compiled in
+void pair_fed_hits_launch(const PairFedArgs &a, int grid, hipStream_t st);
+void sa_repoint2_fed_launch(const PairFedArgs &a, int grid, hipStream_t st);
 
 }  // namespace evs

@@ -1315,6 +1315,168 @@ __global__ void __launch_bounds__(256) sa_repoint2_kernel(const Repoint2Args arg
         atomicAdd(&args.counters[(blockIdx.x % kFetchReplicas) * kFetchRowWords + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
+// ---- fed backing of the fetch-first pair (evs_cache_pair_fed_begin; the chain and the rule: evs_cache_policy.h at PairFedArgs) ----
+// First launch of the finish: what cache_batch_probe2_kernel writes and the begin's probe withheld.  A position whose code is 1 / 2
+// finds its way again in that tier's ways (the pair has not moved: everything else is refused while the call is open) and raises
+// it to the sample's agg_hit -- the number of the sample's codes that are not 0, which is what the probe's ballot counted --, the
+// histogram moves into the tier's replica rows; a miss (code 0, a serve byte) routed to C1 on an odd table stamps the route filter.
+template <int W>
+__global__ void __launch_bounds__(256) pair_fed_hits_kernel(const PairFedArgs args) {
+    __shared__ int s_d1[64], s_d2[64];   // priority histogram moves per tier (0 .. T, T <= 32; sized by the word's 6-bit field)
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    const Repoint2Args &a = args.r;
+    const int T = a.T;
+    if (threadIdx.x < 64) { s_d1[threadIdx.x] = 0; s_d2[threadIdx.x] = 0; }
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = a.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? a.rows[threadIdx.x] : 0;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < a.B;
+         req += req_stride) {   // block-uniform trip count (the ballot)
+        const bool on = req < a.B && hl < T;
+        const long long p = on ? req * T + hl : 0;
+        const int row_ld = a.requests[p];
+        const int d_ld = a.serve[p], code_ld = a.code[p];
+        const long long row = on ? (long long)row_ld : -1;
+        const bool ok = row >= 0 && row < s_rows[hl];
+        const int code = ok ? code_ld : 0, d = ok ? d_ld : 0;
+        const bool hit = code == 1 || code == 2;
+        const unsigned long long hm = __ballot(hit);
+        const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+        const bool second = hit && code == 2;
+        const SaGeom g = sa_geom_of(a.sa1, a.sa2, second);
+        unsigned es = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(a.sau, s_base[hl] + (hit ? (unsigned)row : 0u)), es, tag1);
+        if (!hit) es = 0u;
+        SaLine line;
+        sa_load<W>(g, es, line);
+        const int way = sa_find<W>(g, line, tag1, w);
+        if (hit && way >= 0 && sa_prio(w) < agg) {
+            const int old = sa_raise(g, sa_ways_ptr(g, es) + way, w, agg);
+            if (old >= 0) { int *sd = second ? s_d2 : s_d1; atomicSub(&sd[old & 63], 1); atomicAdd(&sd[agg & 63], 1); }
+        }
+        if (args.route_filter && ok && code == 0 && d == 1 && (hl & 1)) {
+            const unsigned long long key = ((unsigned long long)(hl + 1) << 32) | (unsigned)row;
+            args.route_filter[mix64(key) & args.route_mask] = args.route_stamp;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= T) {
+        const int i = threadIdx.x;
+        if (s_d1[i]) atomicAdd(&args.part1_1[(blockIdx.x % kPolReplicas) * kPolPartCols + i], s_d1[i]);
+        if (s_d2[i]) atomicAdd(&args.part1_2[(blockIdx.x % kPolReplicas) * kPolPartCols + i], s_d2[i]);
+    }
+}
+
+// sa_repoint2_kernel for a pair with fed tables: the rule per position is written at PairFedArgs.  A missed position of a fed table
+// that found no way -- turned away, or kept by the other tier -- walks its tier's scratch table read-only, as sa_repoint_fed_kernel
+// does; a hit position of a fed table whose way this call's update took is pointed at the spill slot the taker wrote for that arena
+// entry.  Every index that reaches an address is checked against what the call allocated: a bug serves the zero row (which the
+// begin's probe wrote for every missed position of a fed table) and raises the sticky flag; it never stores an address nobody owns.
+template <int W>
+__global__ void __launch_bounds__(256) sa_repoint2_fed_kernel(const PairFedArgs pargs) {
+    __shared__ int s_cnt[6];   // misses re-pointed / left in place / hits whose way the update took / fed misses / from a fed block / from the spill
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    __shared__ const unsigned char *s_tab1[32], *s_tab2[32];
+    const Repoint2Args &args = pargs.r;
+    const int T = args.T;
+    if (threadIdx.x < 6) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.rows[threadIdx.x] : 0;
+        s_tab1[threadIdx.x] = args.backing1[threadIdx.x];
+        s_tab2[threadIdx.x] = args.backing2[threadIdx.x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    int n_in = 0, n_out = 0, n_took = 0, n_fed = 0, n_blk = 0, n_spill = 0;   // this wave's totals, kept on lane 0
+    bool bad = false;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {   // block-uniform trip count (the ballots)
+        const bool on = req < args.B && hl < T;
+        const long long p = on ? req * T + hl : 0;
+        const int row_ld = args.requests[p];
+        const int d_ld = args.serve[p], code_ld = args.code[p];
+        const long long row = on ? (long long)row_ld : -1;
+        const int d = on ? d_ld : 0, code = on ? code_ld : 0;
+        const bool in_range = row >= 0 && row < s_rows[hl];
+        const bool want = (d == 1 || d == 2) && code <= 2 && in_range;
+        bad = bad || (on && !in_range);
+        const bool second = want && d == 2;
+        const SaGeom g = sa_geom_of(args.sa1, args.sa2, second);
+        unsigned es = 0u, tag1 = 0u, w = 0u;
+        sa_split(g, sa_perm(args.sau, s_base[hl] + (want ? (unsigned)row : 0u)), es, tag1);
+        if (!want) es = 0u;
+        SaLine line;
+        sa_load<W>(g, es, line);
+        const int way = sa_find<W>(g, line, tag1, w);
+        const bool hit = code != 0;
+        const bool fedt = ((pargs.fed_mask >> hl) & 1u) != 0u;
+        const bool in = want && !hit && way >= 0, out = want && !hit && way < 0, took = want && hit && way < 0;
+        const long long rb = second ? args.row_bytes2 : args.row_bytes1;
+        unsigned char *const ar = second ? args.arena2 : args.arena1;
+        const unsigned char *const zero = second ? pargs.f2.zero_row : pargs.f1.zero_row;
+        if (in) args.row_ptrs[p] = (long long)(ar + (long long)sa_entry(g, es, (unsigned)way, w) * rb);
+        bool blk = false, spl = false;
+        if (out && fedt) {   // the key's row of tier d's fed block, through tier d's scratch table
+            const unsigned char *const fed = second ? pargs.f2.fed : pargs.f1.fed;
+            const long long stride = second ? pargs.f2.stride : pargs.f1.stride;
+            const unsigned long long *const slot_key = second ? pargs.f2.slot_key : pargs.f1.slot_key;
+            const int *const slot_index = second ? pargs.f2.slot_index : pargs.f1.slot_index;
+            const unsigned slot_mask = second ? pargs.f2.slot_mask : pargs.f1.slot_mask;
+            const unsigned long long key = ((unsigned long long)(hl + 1) << 32) | (unsigned)row;
+            const unsigned char *src = zero;
+            unsigned h = (unsigned)mix64(key) & slot_mask;
+            for (unsigned n = 0; n <= slot_mask; n++, h = (h + 1u) & slot_mask) {
+                const unsigned long long kk = slot_key[h];
+                if (kk == key) { if (fed) { src = fed + (long long)slot_index[h] * stride; blk = true; } break; }
+                if (kk == 0ull) break;
+            }
+            bad = bad || !blk;
+            args.row_ptrs[p] = (long long)src;
+        }
+        if (took && fedt) {   // the row the way held when the begin hit it: the taker's spill slot
+            const unsigned char *const spill = second ? pargs.f2.spill : pargs.f1.spill;
+            const int *const spill_of = second ? pargs.f2.spill_of : pargs.f1.spill_of;
+            const long long spill_rows = second ? pargs.f2.spill_rows : pargs.f1.spill_rows;
+            const long long entries = second ? pargs.f2.entries : pargs.f1.entries;
+            const long long off = args.row_ptrs[p] - (long long)ar;
+            const long long entry = off >= 0 ? off / rb : -1;
+            const unsigned char *src = zero;
+            if (entry >= 0 && entry < entries) {
+                const long long s = spill_of[entry];
+                if (s >= 0 && s < spill_rows) { src = spill + s * rb; spl = true; }
+            }
+            bad = bad || !spl;
+            args.row_ptrs[p] = (long long)src;
+        }
+        if (took && !fedt) args.row_ptrs[p] = (long long)((second ? s_tab2[hl] : s_tab1[hl]) + row * rb);
+        n_in += __popcll(__ballot(in)); n_out += __popcll(__ballot(out)); n_took += __popcll(__ballot(took));
+        n_fed += __popcll(__ballot(want && !hit && fedt)); n_blk += __popcll(__ballot(blk)); n_spill += __popcll(__ballot(spl));
+    }
+    if (bad) atomicOr(args.err, 1);
+    if (lane == 0) {
+        if (n_in) atomicAdd(&s_cnt[0], n_in);
+        if (n_out) atomicAdd(&s_cnt[1], n_out);
+        if (n_took) atomicAdd(&s_cnt[2], n_took);
+        if (n_fed) atomicAdd(&s_cnt[3], n_fed);
+        if (n_blk) atomicAdd(&s_cnt[4], n_blk);
+        if (n_spill) atomicAdd(&s_cnt[5], n_spill);
+    }
+    __syncthreads();
+    const int r = (blockIdx.x % kFetchReplicas) * kFetchRowWords;
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(&args.counters[r + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+    if (threadIdx.x == 3 && s_cnt[3]) atomicAdd(&pargs.pair_cnt[r + 0], (unsigned long long)s_cnt[3]);
+    if (threadIdx.x == 4 && s_cnt[4]) atomicAdd(&pargs.pair_cnt[r + 1], (unsigned long long)s_cnt[4]);
+    if (threadIdx.x == 5 && s_cnt[5]) atomicAdd(&pargs.pair_cnt[r + 3], (unsigned long long)s_cnt[5]);
+}
+
 // ... and of the pair's bag form (the rule: evs_cache_policy.h at BagRepoint2Args): sa_repoint2_kernel over the flat position
 // list, the bag probe's grid and walk.  The probe left (row, table, code, key bit, set, quotient) in prov[p] and the route launch
 // the serving tier in serve[p], so a position costs two loads, sa_place in its tier's view of the record and one line request.
@@ -1535,6 +1697,16 @@ void sa_repoint2_launch(const Repoint2Args &a, int grid, hipStream_t st) {
 void bags_repoint2_launch(const BagRepoint2Args &a, int grid, hipStream_t st) {
     if (a.sa1.ways == 8u && a.sa2.ways == 8u) hipLaunchKernelGGL(bags_repoint2_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(bags_repoint2_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void pair_fed_hits_launch(const PairFedArgs &a, int grid, hipStream_t st) {
+    if (a.r.sa1.ways == 8u && a.r.sa2.ways == 8u) hipLaunchKernelGGL(pair_fed_hits_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(pair_fed_hits_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void sa_repoint2_fed_launch(const PairFedArgs &a, int grid, hipStream_t st) {
+    if (a.r.sa1.ways == 8u && a.r.sa2.ways == 8u) hipLaunchKernelGGL(sa_repoint2_fed_kernel<8>, dim3((unsigned)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(sa_repoint2_fed_kernel<0>, dim3((unsigned)grid), dim3(256), 0, st, a);
 }
 
 template <int CODEC, int UNROLL>

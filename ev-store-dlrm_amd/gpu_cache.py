@@ -859,6 +859,8 @@ def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
     the update in front of the consumers, so either tier's tables may be pinned host tensors; same results as the default
     order (c1.fetch_stats() counts its re-point launch).  No c3 there."""
     B = _check_batch(c1, rows, out, tier)
+    if c3 is None and _fed_pair_with_sources(c1, c2):
+        return _pair_via_sources(c1, c2, rows, threshold, tier, lambda f1, f2: lookup_finish_c1c2(c1, c2, f1, f2, out))
     if out is None:
         out = torch.empty((B, c1.n_tables, c1.dim), dtype=torch.float32, device=c1.device)
     if tier is None:
@@ -872,6 +874,117 @@ def lookup_batch_c1c2(c1, c2, rows, threshold=23, out=None, tier=None, c3=None):
                                                             tier.data_ptr(), int(threshold), st))
     _ran_pair(c1, c2)
     return tier, out
+
+
+# ---- fed backing of the fetch-first pair (include/evstore_hip.h: evs_cache_pair_fed_begin) ----
+def lookup_begin_c1c2(c1, c2, rows, threshold=23, tier=None):
+    """First half of a lookup on a fed pair (both tiers set_fed_backing over the same fed tables, each in its own codec, both
+    'fetch-first'): the pair's probe.  -> (tier, keys1, keys2): tier the (B, n_tables) strict snapshot codes, keys_d an int64
+    device tensor (a view of a buffer c_d owns, valid until its next begin) with every distinct missing key of a fed table that a
+    missed position routed to tier d names, once, as table_1based << 32 | row.  A key routed both ways is in both lists.
+    Synchronises.  `rows` and `tier` must stay alive until the finish; everything else on either cache is refused until
+    lookup_finish[_interact]_c1c2 or lookup_abort_c1c2."""
+    B = _check_batch(c1, rows, None, tier)
+    if tier is None:
+        tier = torch.empty((B, c1.n_tables), dtype=torch.uint8, device=c1.device)
+    kbs = []
+    for c in (c1, c2):
+        kb = getattr(c, "_fed_keys", None)
+        if kb is None or kb.numel() < B * c1.n_tables:
+            kb = c._fed_keys = torch.empty(B * c1.n_tables, dtype=torch.int64, device=c1.device)
+        kbs.append(kb)
+    n1, n2 = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().evs_cache_pair_fed_begin(c1._h, c2._h, B, rows.data_ptr(), tier.data_ptr(), int(threshold), kbs[0].data_ptr(),
+                                                   C.byref(n1), kbs[1].data_ptr(), C.byref(n2),
+                                                   torch.cuda.current_stream(c1.device).cuda_stream))
+    c1._fed_pair_call = (rows, tier, B, int(n1.value), int(n2.value), c2)   # keep alive
+    return tier, kbs[0][:int(n1.value)], kbs[1][:int(n2.value)]
+
+
+def _fed_pair_args(c1, c2, fed1, fed2):
+    call = getattr(c1, "_fed_pair_call", None)
+    if call is None or call[5] is not c2:
+        raise _lib.EvsError(_lib.EVS_ESTATE, "lookup_finish_c1c2: no call is open on this pair (lookup_begin_c1c2)")
+    _, tier, B, n1, n2, _ = call
+    args = []
+    for c, fed, n in ((c1, fed1, n1), (c2, fed2, n2)):
+        rb = c.dim * c.codec // 8
+        if fed is None:
+            args += [0, 0]
+            continue
+        if not (fed.is_cuda and fed.dim() == 2 and fed.shape[0] >= n and fed.shape[1] * fed.element_size() == rb and fed.stride(1) == 1):
+            raise ValueError("fed must be a device tensor of at least %d rows of %d bytes with unit inner stride, got %s %s" %
+                             (n, rb, tuple(fed.shape), fed.dtype))
+        args += [fed.data_ptr(), int(fed.stride(0)) * fed.element_size() if fed.shape[0] > 1 else rb]
+    return B, tier, args
+
+
+def lookup_finish_c1c2(c1, c2, fed1, fed2, out=None):
+    """Second half: fed_d[i] is the row of keys_d[i] in tier d's codec (device tensor (n, row_bytes) uint8, or (n, dim) fp32 for
+    codec 32; None where the list was empty) -> (tier, out (B, n_tables, dim) fp32)."""
+    B, tier, a = _fed_pair_args(c1, c2, fed1, fed2)
+    if out is None:
+        out = torch.empty((B, c1.n_tables, c1.dim), dtype=torch.float32, device=c1.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * c1.n_tables * c1.dim):
+        raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * c1.n_tables * c1.dim))
+    _lib.check(_lib.lib().evs_cache_pair_fed_finish(c1._h, c2._h, a[0], a[1], a[2], a[3], out.data_ptr(),
+                                                    torch.cuda.current_stream(c1.device).cuda_stream))
+    c1._fed_pair_call = None
+    _ran_pair(c1, c2)
+    return tier, out
+
+
+def lookup_finish_interact_c1c2(c1, c2, fed1, fed2, x, itself=False, out=None):
+    """lookup_finish_c1c2 with the fused interaction as the consumer -> (tier, R (B, dim + P))."""
+    B, tier, a = _fed_pair_args(c1, c2, fed1, fed2)
+    F = c1.n_tables + 1
+    P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
+    if out is None:
+        out = torch.empty((B, c1.dim + P), dtype=torch.float32, device=c1.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * (c1.dim + P)):
+        raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * (c1.dim + P)))
+    if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (B, c1.dim) and x.stride(1) == 1):
+        raise ValueError("x must be a (B, %d) fp32 device tensor with unit inner stride" % c1.dim)
+    _lib.check(_lib.lib().evs_cache_pair_fed_finish_interact(
+        c1._h, c2._h, a[0], a[1], a[2], a[3], x.data_ptr(), int(x.stride(0)) if B > 1 else c1.dim, int(bool(itself)), out.data_ptr(),
+        torch.cuda.current_stream(c1.device).cuda_stream))
+    c1._fed_pair_call = None
+    _ran_pair(c1, c2)
+    return tier, out
+
+
+def lookup_abort_c1c2(c1, c2):
+    """Drops the open pair call: nothing was inserted or raised, the batch is not counted, the same begin lists the same keys."""
+    _lib.check(_lib.lib().evs_cache_pair_fed_abort(c1._h, c2._h))
+    c1._fed_pair_call = None
+
+
+def fed_stats_c1c2(c1, c2):
+    """Counters of the fed pair, cumulative: 'calls' (finished), 'keys1' / 'keys2' (listed per tier), 'missed' (missed positions of
+    fed tables), 'from_block' (of those, served from a fed block), 'spilled' (rows the update spilled) and 'from_spill' (hit
+    positions served from the spill).  Synchronises."""
+    s = (C.c_int64 * 8)()
+    _lib.check(_lib.lib().evs_cache_pair_fed_stats(c1._h, c2._h, s, torch.cuda.current_stream(c1.device).cuda_stream))
+    return {"calls": int(s[0]), "keys1": int(s[1]), "keys2": int(s[2]), "missed": int(s[3]), "from_block": int(s[4]),
+            "spilled": int(s[5]), "from_spill": int(s[6])}
+
+
+def _fed_pair_with_sources(c1, c2):
+    return all(getattr(c, "_fed", False) and getattr(c, "_row_source", None) is not None for c in (c1, c2))
+
+
+def _pair_via_sources(c1, c2, rows, threshold, tier, finish):
+    """begin -> the two row sources -> finish; whatever fails in between leaves no call open (GpuCache._via_source's guard)"""
+    tier, k1, k2 = lookup_begin_c1c2(c1, c2, rows, threshold, tier)
+    try:
+        return finish(c1._fetch_fed(k1), c2._fetch_fed(k2))
+    except BaseException:
+        if getattr(c1, "_fed_pair_call", None) is not None:
+            try:
+                lookup_abort_c1c2(c1, c2)
+            except _lib.EvsError:   # (the library had already spent the call)
+                c1._fed_pair_call = None
+        raise
 
 
 def _ran_pair(c1, c2):
@@ -1025,6 +1138,8 @@ def lookup_interact_c1c2(c1, c2, rows, x, threshold=23, itself=False, out=None, 
         tier, rows_fp32 = lookup_batch_c1c2(c1, c2, rows, threshold, out, tier, c3=c3)
         return tier, interact_features(x, list(rows_fp32.unbind(1)), "dot", itself)
     B = _check_batch(c1, rows, None, tier)
+    if c3 is None and _fed_pair_with_sources(c1, c2):
+        return _pair_via_sources(c1, c2, rows, threshold, tier, lambda f1, f2: lookup_finish_interact_c1c2(c1, c2, f1, f2, x, itself))
     F = c1.n_tables + 1
     P = F * (F + 1) // 2 if itself else F * (F - 1) // 2
     R = torch.empty((B, c1.dim + P), dtype=torch.float32, device=c1.device)

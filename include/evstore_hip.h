@@ -934,6 +934,54 @@ EVS_API int evs_cache_fed_finish_bags(evs_cache *c, const void *fed, int64_t fed
                                       int64_t out_table_stride, int64_t out_bag_stride, void *stream);
 EVS_API int evs_cache_fed_finish_bags_interact(evs_cache *c, const void *fed, int64_t fed_stride_bytes, const float *x, int64_t x_stride,
                                                int itself, float *R, void *stream);
+/* Fed backing of the fetch-first C1 + C2 pair: the set-associative pair (evs_cache_lookup_batch_c1c2, "THE FETCH-FIRST PAIR")
+ * over rows the caller supplies, on the (B, T) lookup and its fused interaction.  Both tiers are fed caches over the SAME fed
+ * tables (evs_cache_set_fed_backing on each; a tier's fed rows are in that tier's codec), both at evs_cache_set_miss_order(c, 1).
+ * THE RULE.  A begin + finish is batch n of the pair under the fetch-first pair's contract; nothing else changes.  Given fed rows
+ * equal to the table rows, the tier codes, the bits of out, R, both tiers' evs_cache_batch_dump, evs_cache_batch_stats (with hist)
+ * and evs_cache_fetch_stats(c1) are what evs_cache_lookup_batch_c1c2 / _lookup_interact_c1c2 leave on a fetch-first pair over the
+ * same tables in HBM, on every call whose outcome does not depend on timing.  A served row of a fed table is, byte for byte, a row
+ * the caller fed for that key at that tier's precision: from the arena once installed, from the fed block, or from the spill.
+ * evs_cache_pair_fed_begin(c1, c2, B, rows, tier, high_agghit_threshold, keys1, n_keys1_host, keys2, n_keys2_host, stream) runs
+ *   the pending EvLFU flush of either tier and the pair's probe in a form that writes NO way word and NO route-filter word: the
+ *   tier codes (strict snapshot), the serve bytes, the addresses, the per-tier miss lists, the hit totals into rows of the call's
+ *   own.  Then one fed list per tier: keys_d (device, 8-byte aligned, room for B * T entries) holds every distinct valid key of a
+ *   fed table that at least one missed position routed to tier d names, each once, as table_1based << 32 | row.  A key on an odd
+ *   table that two samples route both ways is in BOTH lists; its C2-routed position is served C2's row in C2's codec, whichever
+ *   tier keeps the key.  The call synchronises the stream and writes both counts.
+ * evs_cache_pair_fed_finish(c1, c2, fed1, fed1_stride_bytes, fed2, fed2_stride_bytes, out, stream) / _finish_interact(..., x,
+ *   x_stride, itself, R, stream): fed_d (device) holds the row of keys_d[i] at fed_d + i * stride, in tier d's codec; alignment and
+ *   stride as evs_cache_fed_finish asks, per tier; fed_d == NULL where list d was empty.  Launches: the raise of the ways the begin
+ *   hit with the histogram moves and the route-filter stamps (all the begin withheld), the pair's update in fed form (a record of a
+ *   fed table reads fed_d through its slot), the re-point, the consumers, the close bookkeeping.
+ *   THE SPILL.  The pair keeps one arena row per way, so a way the call hit can be the call's victim, and a fed table has no table
+ *   row holding "the same bytes".  The update's thread that replaces an occupied way whose old key belongs to a fed table first
+ *   copies the way's arena row into a per-call spill block; the re-point points such a hit position at that copy.  A victim of an
+ *   addressed table is not spilled: its hit positions are served from the table row, as on the addressed pair.  Both kinds are
+ *   counted as victim hits in evs_cache_fetch_stats(c1).
+ *   No address computed from a NULL table base is ever stored: between begin and finish a missed position of a fed table holds its
+ *   tier's zero row, and a position whose key the scratch table does not hold keeps it (the sticky evs_check_index_errors flag is
+ *   raised).  An index out of range: code 0, a zero row, in no list, the sticky flag raised by the finish.
+ * evs_cache_pair_fed_abort(c1, c2) drops the open call: nothing is launched, no stream is touched; ordinals and stamps of both tiers
+ *   are given back; dumps, stats (with hist) and counters are what they were; the same begin lists the same keys.
+ * evs_cache_pair_fed_stats(c1, c2, out8, stream), cumulative: [calls finished, keys listed for C1, for C2, missed positions of fed
+ *   tables, of those served from a fed block, rows spilled, hit positions served from the spill, 0].
+ * THE ENVELOPE, checked at the begin before anything is allocated (the pair stays usable, the message names the policy): the
+ *   fetch-first pair's -- both tiers at order 1, batch policy 2 given or resolved, the shared record, no alt-key tier, no approximate
+ *   threshold --; both tiers fed caches with the same fed mask, else EVS_EINVAL; every codec pair the pair serves; the interact
+ *   finish: d in {16, 32, 36} and T <= 31.  The bag form of the fed pair, the triple and a warm start of a fed pair do not exist.
+ * PROTOCOL.  While a pair call is open, every other call on EITHER cache is EVS_ESTATE (single-tier begin / finish / abort, batched
+ *   calls, stats, dump, row updates, a change of backing).  A finish / abort without an open pair call, or with another partner than
+ *   the begin's, is EVS_ESTATE.  Argument errors of a finish are EVS_EINVAL and leave the call open.  evs_cache_destroy with an open
+ *   call is fine.  evs_cache_lookup_batch_c1c2 and the other pair / triple / bag-pair calls still refuse a fed cache. */
+EVS_API int evs_cache_pair_fed_begin(evs_cache *c1, evs_cache *c2, int64_t B, const int32_t *rows, uint8_t *tier, int high_agghit_threshold,
+                                     uint64_t *keys1, int64_t *n_keys1_host, uint64_t *keys2, int64_t *n_keys2_host, void *stream);
+EVS_API int evs_cache_pair_fed_finish(evs_cache *c1, evs_cache *c2, const void *fed1, int64_t fed1_stride_bytes, const void *fed2,
+                                      int64_t fed2_stride_bytes, float *out, void *stream);
+EVS_API int evs_cache_pair_fed_finish_interact(evs_cache *c1, evs_cache *c2, const void *fed1, int64_t fed1_stride_bytes, const void *fed2,
+                                               int64_t fed2_stride_bytes, const float *x, int64_t x_stride, int itself, float *R, void *stream);
+EVS_API int evs_cache_pair_fed_abort(evs_cache *c1, evs_cache *c2);
+EVS_API int evs_cache_pair_fed_stats(evs_cache *c1, evs_cache *c2, int64_t *out8, void *stream);
 /* The approximate-embedding mode of the batched EvLFU rule (the reference: cache_algo/EvLFU_C1.py:122-125, :142-152 -- a request
  * whose agg_hit reaches approx_emb_thres does not fetch its missing rows; each reuses the vector of the hit before it and is
  * reported as a hit; nothing is inserted for it).  The exact batch-1 engines take it as evs_cache_request's approx_thres; this is

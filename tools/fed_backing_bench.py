@@ -154,6 +154,125 @@ def main_bags(args):
                       "begin_plus_finish_over_a_us": doc["begin_plus_finish_over_a_us"], "out": path}))
 
 
+PAIR_NAMES = ("a_pair_fetch_first_hbm", "b_pair_fetch_first_pinned", "c_fed_pair_device_source")
+
+
+def main_pair(args):
+    """--pair: the fed C1 + C2 pair (lookup_begin_c1c2 / lookup_finish_interact_c1c2) beside the fetch-first pair it is cut from ->
+    profiles/fed_pair_bench.json.  tools/c2_pair_bench.py's Kaggle pair geometry (a u8 C1 and a u4 C2, 2 % of the rows between
+    them, d = 36, B = 16 384) and one Zipf(0.75) stream: --fill batches fill every pair, then --steps batches are timed, the pairs
+    alternating on the same batches in one process.  a: the fetch-first pair over HBM tables, b: over pinned tables, c: the fed
+    pair with a device-resident gather source per tier (one index_select each), split into begin / sources / finish, each ended
+    by a synchronise.  Times are the host clock between two synchronises (wall_us); a and b also by device events (median_us)."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    ln, d, B = bench.KAGGLE_LN, 36, args.batch
+    T = len(ln)
+    ev = bench.make_tables(ln, d)
+    ev8, ev4 = ev.encode(8), ev.encode(4)
+    del ev
+    pin8, pin4 = [t.cpu().pin_memory() for t in ev8.raw], [t.cpu().pin_memory() for t in ev4.raw]
+    budget = int(0.02 * sum(ln))
+    caps = (int(0.48 * budget) * 4, int(0.48 * budget) * 8)
+    base_dev = torch.from_numpy(np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int64)).to(dev)
+    all8, all4 = torch.cat([t.reshape(t.shape[0], -1) for t in ev8.raw]), torch.cat([t.reshape(t.shape[0], -1) for t in ev4.raw])
+
+    def gather(table, keys):
+        return table.index_select(0, base_dev[(keys >> 32) - 1] + (keys & 0xffffffff)) if keys.numel() else None
+
+    tier = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    x = torch.rand((B, d), device=dev)
+    F = T + 1
+    out = torch.empty((B, d + F * (F - 1) // 2), device=dev)
+    rq = [b[1].t().contiguous().to(torch.int32) for b in bench.make_batches(ln, B, args.fill + args.steps, seed=21, device=dev, dist="zipf", alpha=args.alpha)]
+
+    def call(name, pair, r, split=None):
+        c1, c2 = pair
+        if name.startswith("c_"):
+            t0 = time.perf_counter()
+            _, k1, k2 = E.lookup_begin_c1c2(c1, c2, r, tier=tier)       # (synchronises)
+            t1 = time.perf_counter()
+            f1, f2 = gather(all8, k1), gather(all4, k2)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            E.lookup_finish_interact_c1c2(c1, c2, f1, f2, x, out=out)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            if split is not None:
+                split.append((t1 - t0, t2 - t1, t3 - t2, int(k1.numel()), int(k2.numel())))
+        else:
+            E.lookup_interact_c1c2(c1, c2, r, x, tier=tier, fused=True)
+
+    pairs = {}
+    for name in PAIR_NAMES:
+        c1, c2 = E.GpuCache("evlfu", caps[0], T, d, 8, "cpp", dev), E.GpuCache("evlfu", caps[1], T, d, 4, "cpp", dev)
+        for c, hbm, pin in ((c1, ev8, pin8), (c2, ev4, pin4)):
+            c.set_miss_order("fetch-first")
+            if name.startswith("c_"):
+                c.set_fed_backing([None] * T, ln)
+            else:
+                c.set_backing(pin if name.startswith("b_") else hbm)
+        for r in rq[:args.fill]:
+            call(name, (c1, c2), r)
+        pairs[name] = (c1, c2)
+        print("fed_backing_bench: %s filled, C1 %d C2 %d resident" % (name, c1.batch_stats()["size"], c2.batch_stats()["size"]), file=sys.stderr, flush=True)
+    timed = rq[args.fill:]
+    s0 = {n: (p[0].batch_stats(), p[1].batch_stats(), p[0].fetch_stats()) for n, p in pairs.items()}
+    fs0 = E.fed_stats_c1c2(*pairs[PAIR_NAMES[2]])
+    events, wall, split = {n: [] for n in PAIR_NAMES}, {n: [] for n in PAIR_NAMES}, []
+    for r in timed:
+        for n in PAIR_NAMES:
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            call(n, pairs[n], r, split if n.startswith("c_") else None)
+            e1.record()
+            torch.cuda.synchronize()
+            wall[n].append(time.perf_counter() - t0)
+            events[n].append((e0, e1))
+    res = {}
+    for n, (c1, c2) in pairs.items():
+        s1 = (c1.batch_stats(), c2.batch_stats(), c1.fetch_stats())
+        w = np.array(wall[n]) * 1e6
+        res[n] = {"wall_us": round(float(np.median(w)), 2), "wall_p95_us": round(float(np.percentile(w, 95)), 2),
+                  "hit_rate": round(sum(s1[k]["n_hits"] - s0[n][k]["n_hits"] for k in (0, 1)) / (T * B * len(timed)), 4),
+                  "size": (s1[0]["size"], s1[1]["size"]),
+                  "repoint_per_batch": {k: round((s1[2][k] - s0[n][2].get(k, 0)) / len(timed), 2) for k in s1[2] if k != "calls"}}
+        if n.startswith("c_"):
+            sp = np.array(split, np.float64)
+            fs1 = E.fed_stats_c1c2(c1, c2)
+            res[n].update({"begin_us": round(float(np.median(sp[:, 0])) * 1e6, 2), "sources_us": round(float(np.median(sp[:, 1])) * 1e6, 2),
+                           "finish_us": round(float(np.median(sp[:, 2])) * 1e6, 2),
+                           "keys_per_batch": (round(float(sp[:, 3].mean()), 1), round(float(sp[:, 4].mean()), 1)),
+                           "fed_bytes_per_batch": round(float(sp[:, 3].mean()) * d + float(sp[:, 4].mean()) * d / 2),
+                           "fed_stats_delta": {k: fs1[k] - fs0[k] for k in fs1}})
+        else:
+            us = np.array([a.elapsed_time(b) * 1e3 for a, b in events[n]])
+            res[n].update({"median_us": round(float(np.median(us)), 2), "p95_us": round(float(np.percentile(us, 95)), 2)})
+        print("fed_backing_bench: %s %s" % (n, res[n]), file=sys.stderr, flush=True)
+    a, b_, c_ = (res[n] for n in PAIR_NAMES)
+    doc = {"tool": "fed_backing_bench --pair", "device": torch.cuda.get_device_name(0),
+           "shape": {"rows": sum(ln), "capacities": caps, "codecs": (8, 4), "batch": B, "dim": d, "zipf_alpha": args.alpha, "fill_batches": args.fill,
+                     "timed_batches": len(timed), "consumer": "lookup_interact_c1c2 / lookup_finish_interact_c1c2"},
+           "chains": {"a, b": "cache_batch_probe2 -> cache_batch_sa_list2 -> sa_repoint2 -> interaction",
+                      "c": "begin: cache_batch_probe2<fed> -> fed_list x 2 -> synchronise | sources | finish: fold x 2 -> pair_fed_hits -> "
+                           "cache_batch_sa_list_fed_spill x 2 -> sa_repoint2_fed -> interaction"},
+           "timing": "host clock between two synchronises around every call (wall_us; begin / sources / finish each end on a synchronise); a and b also "
+                     "by a pair of device events (median_us); the pairs alternate on the same batches in one process; one run on one box",
+           "configs": res,
+           "begin_plus_finish_over_a_us": round(c_["begin_us"] + c_["finish_us"] - a["wall_us"], 2),
+           "begin_plus_finish_over_a": round((c_["begin_us"] + c_["finish_us"]) / a["wall_us"], 3),
+           "c_over_a": round(c_["wall_us"] / a["wall_us"], 3), "c_over_b": round(c_["wall_us"] / b_["wall_us"], 3),
+           "b_over_a": round(b_["wall_us"] / a["wall_us"], 3)}
+    path = args.out or os.path.join(ROOT, "profiles", "fed_pair_bench.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"tool": doc["tool"], "a_wall_us": a["wall_us"], "c_over_a": doc["c_over_a"], "c_over_b": doc["c_over_b"],
+                      "begin_plus_finish_over_a": doc["begin_plus_finish_over_a"], "out": path}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frac", type=float, default=0.10)
@@ -165,10 +284,14 @@ def main():
     ap.add_argument("--dim", type=int, default=36)
     ap.add_argument("--bags", action="store_true", help="the bag form beside the count-first fetch-first bag chain -> profiles/fed_bags.json")
     ap.add_argument("--max-bag", type=int, default=10, help="--bags: bags of 1 .. this many indices")
-    ap.add_argument("--out", default="", help="default: profiles/fed_backing.json (--bags: profiles/fed_bags.json)")
+    ap.add_argument("--pair", action="store_true", help="the fed C1 + C2 pair beside the fetch-first pair -> profiles/fed_pair_bench.json")
+    ap.add_argument("--fill", type=int, default=180, help="--pair: batches that fill the tiers")
+    ap.add_argument("--out", default="", help="default: profiles/fed_backing.json (--bags: profiles/fed_bags.json, --pair: profiles/fed_pair_bench.json)")
     args = ap.parse_args()
     if args.bags:
         return main_bags(args)
+    if args.pair:
+        return main_pair(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "fed_backing.json")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
