@@ -18,8 +18,55 @@
 //     (library is built with -ffp-contract=off) -> bit-exact with the oracle.
 #include "evs_common.h"
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
 
 namespace evs {
+
+// ---- the dispatch record (evs_gather_kernels_seen, include/evstore_hip.h): one counter per launch site and instantiation that
+// bag_sum_impl can launch, bumped next to the launch.  The tables below ARE the list of instantiations: a launch site names its
+// own template arguments and a static_assert refuses one that has no line here.
+constexpr int kGkCodec[4] = {32, 16, 8, 4};
+constexpr int kGkRowsForm[13][2] = {{4, 1}, {4, 2}, {8, 1}, {8, 2}, {8, 3}, {8, 4}, {9, 1}, {9, 2}, {9, 3}, {9, 4}, {16, 2}, {16, 4}, {16, 7}};   // (LPRD, NJ)
+constexpr int kGkLongForm[5][2] = {{4, 8}, {8, 8}, {9, 9}, {16, 16}, {32, 16}};   // (LPR, K)
+constexpr int kGkFlatLpr[4] = {4, 8, 9, 16};
+constexpr int kGkVecLpr[6] = {4, 8, 9, 16, 32, 0};
+constexpr int kGkRows = 0, kGkLong = kGkRows + 4 * 13 * 2, kGkFlat = kGkLong + 5, kGkVec = kGkFlat + 4 * 2, kGkScalar = kGkVec + 4 * 6 * 2,
+              kGkCount = kGkScalar + 4;
+constexpr int gk_codec(int codec) { return codec == 32 ? 0 : codec == 16 ? 1 : codec == 8 ? 2 : codec == 4 ? 3 : -1; }
+constexpr int gk_find1(const int *a, int n, int v) { for (int i = 0; i < n; i++) if (a[i] == v) return i; return -1; }
+constexpr int gk_find2(const int (*a)[2], int n, int v0, int v1) { for (int i = 0; i < n; i++) if (a[i][0] == v0 && a[i][1] == v1) return i; return -1; }
+constexpr int gk_rows_id(int codec, int lprd, int nj, bool check) {
+    const int c = gk_codec(codec), f = gk_find2(kGkRowsForm, 13, lprd, nj);
+    return (c < 0 || f < 0) ? -1 : kGkRows + (c * 13 + f) * 2 + (check ? 0 : 1);
+}
+constexpr int gk_long_id(int lpr, int k) { const int f = gk_find2(kGkLongForm, 5, lpr, k); return f < 0 ? -1 : kGkLong + f; }
+constexpr int gk_flat_id(int lprd, bool sel) { const int f = gk_find1(kGkFlatLpr, 4, lprd); return f < 0 ? -1 : kGkFlat + f * 2 + (sel ? 0 : 1); }
+constexpr int gk_vec_id(int codec, int lpr_t, bool bag1) {
+    const int c = gk_codec(codec), f = gk_find1(kGkVecLpr, 6, lpr_t);
+    return (c < 0 || f < 0) ? -1 : kGkVec + (c * 6 + f) * 2 + (bag1 ? 0 : 1);
+}
+constexpr int gk_scalar_id(int codec) { return gk_codec(codec) < 0 ? -1 : kGkScalar + gk_codec(codec); }
+static std::atomic<long long> g_gk_seen[kGkCount];
+template <int ID> static inline void gk_count() {
+    static_assert(ID >= 0 && ID < kGkCount, "a gather instantiation without a line in the dispatch record");
+    g_gk_seen[ID].fetch_add(1, std::memory_order_relaxed);
+}
+static void gk_name(int id, char *s, size_t n) {
+    if (id >= kGkScalar) snprintf(s, n, "scalar_c%d", kGkCodec[id - kGkScalar]);
+    else if (id >= kGkVec) {
+        const int k = id - kGkVec;
+        snprintf(s, n, "vec_c%d_lpr%d_%s", kGkCodec[k / 12], kGkVecLpr[(k / 2) % 6], (k & 1) ? "offsets" : "bag1");
+    } else if (id >= kGkFlat) {
+        const int k = id - kGkFlat;
+        snprintf(s, n, "flat_c32_lpr%d_%s", kGkFlatLpr[k / 2], (k & 1) ? "plain" : "select");
+    } else if (id >= kGkLong) snprintf(s, n, "long_c32_lpr%d_k%d", kGkLongForm[id - kGkLong][0], kGkLongForm[id - kGkLong][1]);
+    else {
+        const int k = id - kGkRows;
+        snprintf(s, n, "rows_c%d_lpr%d_nj%d_%s", kGkCodec[k / 26], kGkRowsForm[(k / 2) % 13][0], kGkRowsForm[(k / 2) % 13][1],
+                 (k & 1) ? "declared" : "check");
+    }
+}
 
 struct GatherArgs {
     const void *table[EVS_MAX_TABLES_PER_LAUNCH];
@@ -275,12 +322,15 @@ static void launch_vec(const GatherArgs &a, int lpr, hipStream_t stream, bool ba
     const int64_t cap = (int64_t)kNumCu * gather_blocks_per_cu();  // 8 blocks of 256 threads per CU
     if (blocks > cap) blocks = cap;
     blocks = round_up((int)blocks, kNumXcd);
-    if (bag1)
+    if (bag1) {
         hipLaunchKernelGGL((embedding_bag_sum_kernel<CODEC, LPR_T, UNROLL, true>), dim3((unsigned)blocks), dim3(256), 0,
                            stream, args);
-    else
+        gk_count<gk_vec_id(CODEC, LPR_T, true)>();
+    } else {
         hipLaunchKernelGGL((embedding_bag_sum_kernel<CODEC, LPR_T, UNROLL, false>), dim3((unsigned)blocks), dim3(256),
                            0, stream, args);
+        gk_count<gk_vec_id(CODEC, LPR_T, false)>();
+    }
 }
 
 // ---- one index per bag, fp32, d in {16, 32, 36}: rows in flight in registers (round 3) ----------------------------------
@@ -682,8 +732,9 @@ static bool launch_bag_sum_flat(const GatherArgs &a, bool vec_ok, hipStream_t st
     const int64_t chunks = (a.B + 63) / 64;
     if (chunks * a.T >= (1ll << 31)) return false;
     const dim3 grid((unsigned)(chunks * a.T)), block(256);
-#define EVS_FLAT(L) do { if (sel) hipLaunchKernelGGL((bag_sum_flat_kernel<L, true>), grid, block, 0, stream, a); \
-                         else hipLaunchKernelGGL((bag_sum_flat_kernel<L, false>), grid, block, 0, stream, a); return true; } while (0)
+#define EVS_FLAT(L) do { if (sel) { hipLaunchKernelGGL((bag_sum_flat_kernel<L, true>), grid, block, 0, stream, a); gk_count<gk_flat_id(L, true)>(); } \
+                         else { hipLaunchKernelGGL((bag_sum_flat_kernel<L, false>), grid, block, 0, stream, a); gk_count<gk_flat_id(L, false)>(); } \
+                         return true; } while (0)
     switch (a.d) {
     case 16: EVS_FLAT(4);
     case 32: EVS_FLAT(8);
@@ -797,13 +848,15 @@ static bool launch_bag_sum_long(const GatherArgs &a, bool vec_ok, hipStream_t st
     GatherArgs g = a;
     g.zeros = zero_page();
     const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+#define EVS_LONG(L, K) do { hipLaunchKernelGGL((bag_sum_long_kernel<L, K>), grid, block, 0, stream, g); gk_count<gk_long_id(L, K)>(); } while (0)
     switch (a.d) {
-    case 16: hipLaunchKernelGGL((bag_sum_long_kernel<4, 8>), grid, block, 0, stream, g); break;
-    case 32: hipLaunchKernelGGL((bag_sum_long_kernel<8, 8>), grid, block, 0, stream, g); break;
-    case 36: hipLaunchKernelGGL((bag_sum_long_kernel<9, 9>), grid, block, 0, stream, g); break;
-    case 64: hipLaunchKernelGGL((bag_sum_long_kernel<16, 16>), grid, block, 0, stream, g); break;
-    default: hipLaunchKernelGGL((bag_sum_long_kernel<32, 16>), grid, block, 0, stream, g); break;
+    case 16: EVS_LONG(4, 8); break;
+    case 32: EVS_LONG(8, 8); break;
+    case 36: EVS_LONG(9, 9); break;
+    case 64: EVS_LONG(16, 16); break;
+    default: EVS_LONG(32, 16); break;
     }
+#undef EVS_LONG
     return true;
 }
 
@@ -824,8 +877,8 @@ static bool launch_gather_rows(const GatherArgs &a, bool vec_ok, hipStream_t str
     g.zeros = zp;
 #define EVS_GR(L, N) \
     do { \
-        if (bag1) hipLaunchKernelGGL((gather_rows_kernel<CODEC, L, N, false>), grid, block, 0, stream, g); \
-        else hipLaunchKernelGGL((gather_rows_kernel<CODEC, L, N, true>), grid, block, 0, stream, g); \
+        if (bag1) { hipLaunchKernelGGL((gather_rows_kernel<CODEC, L, N, false>), grid, block, 0, stream, g); gk_count<gk_rows_id(CODEC, L, N, false)>(); } \
+        else { hipLaunchKernelGGL((gather_rows_kernel<CODEC, L, N, true>), grid, block, 0, stream, g); gk_count<gk_rows_id(CODEC, L, N, true)>(); } \
         return true; \
     } while (0)
     if (a.d == 16) { if (nj <= 1) EVS_GR(4, 1); EVS_GR(4, 2); }
@@ -860,6 +913,7 @@ static void launch_codec(const GatherArgs &a, bool vec_ok, hipStream_t stream, b
     if (blocks > cap) blocks = cap;
     blocks = round_up((int)blocks, kNumXcd);
     hipLaunchKernelGGL((embedding_bag_sum_scalar_kernel<CODEC>), dim3((unsigned)blocks), dim3(256), 0, stream, args);
+    gk_count<gk_scalar_id(CODEC)>();
 }
 
 }  // namespace evs
@@ -1048,6 +1102,19 @@ extern "C" int evs_embedding_bag_sum_stacked(int T, int64_t B, int d, int codec,
     }
     return evs_embedding_bag_sum(T, B, d, codec, tables, n_rows, idx, offsets_base ? off : nullptr, nnz, row_weights, out,
                                  out_table_stride, out_bag_stride, stream);
+}
+
+extern "C" int evs_gather_kernels_seen(char *buf, int n) {
+    int len = 0;
+    if (buf && n > 0) buf[0] = 0;
+    for (int id = 0; id < evs::kGkCount; id++) {
+        char name[48], line[80];
+        evs::gk_name(id, name, sizeof name);
+        const int k = snprintf(line, sizeof line, "%s=%lld\n", name, evs::g_gk_seen[id].load(std::memory_order_relaxed));
+        if (buf && len + k < n) memcpy(buf + len, line, (size_t)k + 1);
+        len += k;
+    }
+    return len;
 }
 
 extern "C" int evs_check_index_errors(void *stream) {

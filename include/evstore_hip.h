@@ -50,6 +50,19 @@ EVS_API const char *evs_last_error(void);
  * "NAME=1\n" (the variable was set) or "NAME=0\n" (unset: the default) line per name, in first-read order, written to
  * buf (n bytes, always NUL-terminated when n > 0).  Returns the length of the whole text, which may exceed n - 1. */
 EVS_API int evs_env_switches_seen(char *buf, int n);
+/* Which gather kernels the table-only pooling entry points (evs_embedding_bag_sum and its _sharded / _p2p / _stacked forms)
+ * have launched in this process: one "name=count\n" line per launch site and kernel instantiation that their dispatch can
+ * reach -- every name is listed, a kernel never launched with count 0 -- in a fixed order; buf, n and the return value as for
+ * evs_env_switches_seen.  A count goes up by one per kernel launch (a call over T > EVS_MAX_TABLES_PER_LAUNCH tables: once
+ * per launch).  Names, with c = the row codec (32, 16, 8, 4) and lpr = the lanes per row the kernel was COMPILED for
+ * (d / 4; 0 = read from the arguments at run time):
+ *   rows_c<c>_lpr<l>_nj<n>_check | _declared   rows in registers, whole batches of one-index bags: n load instructions per
+ *                                              sample; check = offsets given and checked per block, declared = offsets NULL
+ *   long_c32_lpr<l>_k<k>                       a lane group per bag, k rows of it in flight (average bag length >= 2)
+ *   flat_c32_lpr<l>_select | _plain            a lane group per lookup, rows through LDS; select = the form for averages above 16
+ *   vec_c<c>_lpr<l>_bag1 | _offsets            the grid-stride kernel: everything else with d % 4 == 0 and d <= 256, weights included
+ *   scalar_c<c>                                one element per lane: any other d, or an output that is not 16-byte aligned */
+EVS_API int evs_gather_kernels_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)

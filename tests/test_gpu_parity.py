@@ -46,6 +46,38 @@ def _dev(a, dtype=None):
     return t.cuda()
 
 
+def _gather_families(E, before):
+    """{kernel family: launches} that the gather's dispatch record (evs_gather_kernels_seen) gained since `before`"""
+    after, out = E._lib.gather_kernels_seen(), {}
+    for k, n in after.items():
+        if n != before[k]:
+            out[k.split("_")[0]] = out.get(k.split("_")[0], 0) + n - before[k]
+    return out
+
+
+def _switch_on(name):
+    return not os.environ.get(name, "").startswith("0")
+
+
+def _multi_hot_family(d, nnz, B):
+    """the family bag_sum_impl picks for ONE launch of unweighted fp32 bags given with offsets (nnz: per table; not a whole batch of
+    one-index bags), under the EVS_GATHER_* switches in force -- tests/test_gpu_switches.py runs these tests under them"""
+    total, bags = int(sum(nnz)), B * len(nnz)
+    if _switch_on("EVS_GATHER_LONG") and d in (16, 32, 36, 64, 128) and total >= int(os.environ.get("EVS_GATHER_LONG_MINAVG", 2)) * bags:
+        return "long"
+    if _switch_on("EVS_GATHER_FLAT") and d in (16, 32, 36, 64) and total <= int(os.environ.get("EVS_GATHER_FLAT_MAXAVG", 128)) * bags:
+        return "flat"
+    return "vec"
+
+
+def _one_index_family(d, T, B, codec, declared):
+    """the same for one launch over a whole batch of one-index bags (offsets = arange, or one index per bag declared)"""
+    most = {16: 2, 32: 4, 36: 4, 64: 7}
+    if _switch_on("EVS_GATHER_RF") and T <= 32 and d in most and -(-T // (64 // (d // 4))) <= most[d]:
+        return "rows"
+    return "vec" if declared or codec != 32 else _multi_hot_family(d, [B] * T, B)
+
+
 def _run_case(E, g, tabs, stacked):
     lS_o, lS_i = split_indices(g)
     vW = split_weights(g)
@@ -127,8 +159,10 @@ def test_codec_tiers_bit_exact(E, orc, codec, d):
     lS_i = [rs.randint(0, n_rows[k], size=lens[k].sum()).astype(np.int64) for k in range(T)]
     lS_o = [np.concatenate([[0], np.cumsum(lens[k])[:-1]]).astype(np.int64) for k in range(T)]
     ev = E.EVTables([torch.from_numpy(r).cuda() for r in raws], d, codec)
+    seen = E._lib.gather_kernels_seen()
     ly = E.apply_emb([_dev(o) for o in lS_o], [_dev(i) for i in lS_i], ev, None, check_indices=True)
     got = torch.stack(ly).cpu().numpy()
+    assert _gather_families(E, seen) == {"vec": 1}   # reduced-precision multi-hot bags: the grid-stride kernel's offsets form
     want = np.stack(orc.apply_emb(lS_o, lS_i, raws, None, codec, d))
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
@@ -733,7 +767,9 @@ def _rows_in_registers_gather_case(E, orc, d, T, B, codec):
     want = np.stack(orc.apply_emb(off, idx, ws))
     o_t, i_t = torch.from_numpy(np.stack(off)).cuda(), torch.from_numpy(np.stack(idx)).cuda()
     for kw in ({}, {"one_index_per_bag": True}):
+        seen = E._lib.gather_kernels_seen()
         got = torch.stack(E.apply_emb(o_t, i_t, ev, None, lazy=False, check_indices=True, **kw)).cpu().numpy()
+        assert _gather_families(E, seen) == {_one_index_family(d, T, B, codec, bool(kw)): 1}, kw
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), kw
     assert np.array_equal(got, np.stack([ws[k][idx[k]] for k in range(T)]))   # bag = 1: exact copies of the rows
     if B >= 8:
@@ -766,11 +802,14 @@ def _rows_in_registers_gather_case(E, orc, d, T, B, codec):
 @pytest.mark.parametrize("d,T,B,max_bag", [(36, 26, 1000 + 3, 10), (16, 8, 128, 10), (32, 5, 65, 40), (64, 3, 700, 6), (36, 2, 64, 300), (36, 40, 50, 5),
                                            (36, 3, 200, 100), (64, 2, 100, 60), (16, 4, 300, 90)])   # (averages above 16: the select form)
 def test_multi_hot_gather_through_lds_vs_oracle(E, orc, d, T, B, max_bag):
-    """Genuinely multi-hot bags in list form (the reference's random-data loader, dlrm_data_pytorch.py:1024-1065) run
-    bag_sum_flat_kernel (round 3: a lane group per LOOKUP, 64 bags of one table per block, rows through LDS, each bag's
-    rows added in index order): bit-exact vs the oracle's sequential EmbeddingBag-sum -- empty bags, bags longer than a
-    tile (112 rows), a batch that is not a whole number of 64-bag chunks, T above the stacked kernels' limit; bad indices
-    (skipped, flagged) and a bad offset (that bag empty, flagged); apply_emb_interact over the same batch = the two calls."""
+    """Genuinely multi-hot bags in list form (the reference's random-data loader, dlrm_data_pytorch.py:1024-1065).  Every case
+    here averages two indices per bag or more, so by default all of them run bag_sum_long_kernel (round 4: a lane group per BAG,
+    K rows of it in flight, a register accumulator in index order) -- asserted below through the dispatch record; the tile
+    kernel this test was written for (bag_sum_flat_kernel, round 3: a lane group per LOOKUP, 64 bags of one table per block, rows
+    through LDS) takes them under EVS_GATHER_LONG=0 (tests/test_gpu_switches.py), and tests/test_gpu_pooling_matrix.py runs both
+    of its forms.  Bit-exact vs the oracle's sequential EmbeddingBag-sum -- empty bags, bags longer than a tile (112 rows), a batch
+    that is not a whole number of 64-bag chunks, T above the stacked kernels' limit; bad indices (skipped, flagged) and a bad
+    offset (that bag empty, flagged); apply_emb_interact over the same batch = the two calls."""
     rs = np.random.RandomState(7 * d + T + B)
     ln = [int(rs.choice([1, 3, 40, 700, 9000])) for _ in range(T)]
     ws = [rs.uniform(-1, 1, size=(n, d)).astype(np.float32) for n in ln]
@@ -783,7 +822,15 @@ def test_multi_hot_gather_through_lds_vs_oracle(E, orc, d, T, B, max_bag):
         off.append(o); idx.append(rs.randint(0, n, size=int(sizes.sum())).astype(np.int64))
     want = np.stack(orc.apply_emb(off, idx, ws))
     lo, li = [torch.from_numpy(o).cuda() for o in off], [torch.from_numpy(i).cuda() for i in idx]
+    seen = E._lib.gather_kernels_seen()
     got = torch.stack(E.apply_emb(lo, li, ev, None, lazy=False, check_indices=True)).cpu().numpy()
+    ran, by_launch = _gather_families(E, seen), {}
+    for k0 in range(0, T, 32):   # (a launch per 32 tables, each with its own average)
+        f = _multi_hot_family(d, [i.size for i in idx[k0:k0 + 32]], B)
+        by_launch[f] = by_launch.get(f, 0) + 1
+    assert ran == by_launch, (ran, by_launch)
+    if not any(k.startswith("EVS_GATHER_") for k in os.environ):
+        assert set(ran) == {"long"}
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     if T + 1 <= 28:
         x = torch.from_numpy(rs.uniform(-1, 1, size=(B, d)).astype(np.float32)).cuda()
