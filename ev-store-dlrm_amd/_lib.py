@@ -64,6 +64,8 @@ _PROTOS = {
     "evs_last_error": (C.c_char_p, []),
     "evs_env_switches_seen": (_int, [C.c_char_p, _int]),
     "evs_gather_kernels_seen": (_int, [C.c_char_p, _int]),
+    "evs_mixed_kernels_seen": (_int, [C.c_char_p, _int]),
+    "evs_interact_rows_by_address": (_int, [_i64, _int, _int, _vp, _i64, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
     "evs_embedding_bag_sum": (_int, [_int, _i64, _int, _int, _pp, _i64p, _pp, _pp, _i64p, _pp, _vp, _i64, _i64, _vp]),
     "evs_embedding_bag_sum_sharded": (_int, [_int, _i64, _int, _int, _pp, _i64p, _i64p, _i64p, _pp, _pp, _i64p, _pp, _vp, _i64, _i64,
                                              _i64, _i64, _vp]),
@@ -247,6 +249,13 @@ def gather_kernels_seen():
     """{name: launches} for every gather kernel instantiation the table-only pooling can launch (evs_gather_kernels_seen)."""
     buf = C.create_string_buffer(lib().evs_gather_kernels_seen(None, 0) + 1)
     lib().evs_gather_kernels_seen(buf, len(buf))
+    return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
+
+
+def mixed_kernels_seen():
+    """{name: launches} for every instantiation of the mixed-precision interaction consumers (evs_mixed_kernels_seen)."""
+    buf = C.create_string_buffer(lib().evs_mixed_kernels_seen(None, 0) + 1)
+    lib().evs_mixed_kernels_seen(buf, len(buf))
     return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
 
 

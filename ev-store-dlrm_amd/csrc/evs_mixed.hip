@@ -15,8 +15,24 @@
 #include "evs_hash.h"
 
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
 
 namespace evs {
+
+// ---- the dispatch record (evs_mixed_kernels_seen, include/evstore_hip.h): one counter per instantiation of the two kernel templates
+// below, bumped next to its launch.  id = family * 6 + (d: 16 / 32 / 36) * 2 + (NT - 1); families: rows, r84, r84 with the probe.
+constexpr int kMkRows = 0, kMkR84 = 6, kMkR84Probe = 12, kMkCount = 18;
+constexpr int mk_id(int family, int CQ, int REM, int NT) { return family + (CQ == 1 ? 0 : REM == 0 ? 1 : 2) * 2 + (NT - 1); }
+static std::atomic<long long> g_mk_seen[kMkCount];
+template <int ID> static inline void mk_count() {
+    static_assert(ID >= 0 && ID < kMkCount, "a mixed-precision interaction instantiation without a line in the dispatch record");
+    g_mk_seen[ID].fetch_add(1, std::memory_order_relaxed);
+}
+static void mk_name(int id, char *s, size_t n) {
+    constexpr int kD[3] = {16, 32, 36};
+    snprintf(s, n, "%s_d%d_nt%d%s", id < kMkR84 ? "rows" : "r84", kD[(id % 6) / 2], (id & 1) + 1, id >= kMkR84Probe ? "_probe" : "");
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -735,12 +751,12 @@ template <int CQ, int REM>
 static void launch_mixed84(const Mixed84Args &a, bool probe, hipStream_t st) {
     const unsigned blocks = (unsigned)((a.m.B + 15) / 16);
     if (probe) {
-        if (a.m.T + 1 > 16) hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 2, true>), dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 1, true>), dim3(blocks), dim3(256), 0, st, a);
+        if (a.m.T + 1 > 16) { mk_count<mk_id(kMkR84Probe, CQ, REM, 2)>(); hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 2, true>), dim3(blocks), dim3(256), 0, st, a); }
+        else { mk_count<mk_id(kMkR84Probe, CQ, REM, 1)>(); hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 1, true>), dim3(blocks), dim3(256), 0, st, a); }
         return;
     }
-    if (a.m.T + 1 > 16) hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 2>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 1>), dim3(blocks), dim3(256), 0, st, a);
+    if (a.m.T + 1 > 16) { mk_count<mk_id(kMkR84, CQ, REM, 2)>(); hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 2>), dim3(blocks), dim3(256), 0, st, a); }
+    else { mk_count<mk_id(kMkR84, CQ, REM, 1)>(); hipLaunchKernelGGL((interact_mixed84_kernel<CQ, REM, 1>), dim3(blocks), dim3(256), 0, st, a); }
 }
 
 // is there a (u8, u4) rows-in-registers kernel for the shape (the two-tier lookup folds its probe into it)
@@ -767,8 +783,9 @@ int probe2_interact_mixed84(long long B, int T, int d, const float *x, long long
     return EVS_OK;
 }
 
-template <auto K>
+template <int CQ, int REM, int NT>
 static void launch_mixed(const MixedArgs &a, hipStream_t st) {
+    constexpr auto K = interact_mixed_rows_kernel<CQ, REM, NT>;
     static int per_cu = 0;
     if (!per_cu) {
         int n = 0;
@@ -778,6 +795,7 @@ static void launch_mixed(const MixedArgs &a, hipStream_t st) {
     long long blocks = (a.B + 3) / 4;
     const long long cap = (long long)kNumCu * per_cu;
     if (blocks > cap) blocks = cap;
+    mk_count<mk_id(kMkRows, CQ, REM, NT)>();
     hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3(256), 0, st, a);
 }
 
@@ -805,9 +823,9 @@ int interact_from_mixed_rows(long long B, int T, int d, const float *x, long lon
         }
     }
     switch (d) {
-    case 16: if (nt2) launch_mixed<interact_mixed_rows_kernel<1, 0, 2>>(a, st); else launch_mixed<interact_mixed_rows_kernel<1, 0, 1>>(a, st); break;
-    case 32: if (nt2) launch_mixed<interact_mixed_rows_kernel<2, 0, 2>>(a, st); else launch_mixed<interact_mixed_rows_kernel<2, 0, 1>>(a, st); break;
-    case 36: if (nt2) launch_mixed<interact_mixed_rows_kernel<2, 1, 2>>(a, st); else launch_mixed<interact_mixed_rows_kernel<2, 1, 1>>(a, st); break;
+    case 16: if (nt2) launch_mixed<1, 0, 2>(a, st); else launch_mixed<1, 0, 1>(a, st); break;
+    case 32: if (nt2) launch_mixed<2, 0, 2>(a, st); else launch_mixed<2, 0, 1>(a, st); break;
+    case 36: if (nt2) launch_mixed<2, 1, 2>(a, st); else launch_mixed<2, 1, 1>(a, st); break;
     default: set_error("interact_from_mixed_rows: no kernel for d=%d", d); return EVS_EINVAL;
     }
     EVS_HIP_CHECK(hipGetLastError());
@@ -815,3 +833,35 @@ int interact_from_mixed_rows(long long B, int T, int d, const float *x, long lon
 }
 
 }  // namespace evs
+
+extern "C" int evs_interact_rows_by_address(int64_t B, int T, int d, const float *x, int64_t x_stride, const int64_t *row_ptrs,
+                                            const unsigned char *row_class, int codec1, int codec2, int itself, int default_class,
+                                            float *R, void *stream) {
+    using namespace evs;
+    auto codec_ok = [](int c) { return c == 32 || c == 16 || c == 8 || c == 4; };
+    EVS_REQUIRE(d == 16 || d == 32 || d == 36, "evs_interact_rows_by_address: no kernel for d=%d (16, 32, 36)", d);
+    EVS_REQUIRE(T >= 1 && T <= 31, "evs_interact_rows_by_address: T=%d (1 .. 31)", T);
+    EVS_REQUIRE(codec_ok(codec1) && codec_ok(codec2), "evs_interact_rows_by_address: codec %d / %d (32, 16, 8, 4)", codec1, codec2);
+    EVS_REQUIRE(B >= 0 && B < (1ll << 31), "evs_interact_rows_by_address: B=%lld", (long long)B);
+    EVS_REQUIRE(default_class == 1 || default_class == 2, "evs_interact_rows_by_address: default_class %d (1 or 2)", default_class);
+    if (B == 0) return EVS_OK;
+    EVS_REQUIRE(x && R && row_ptrs, "evs_interact_rows_by_address: NULL argument");
+    EVS_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(R) % 16 == 0 && x_stride >= d && x_stride % 4 == 0,
+                "evs_interact_rows_by_address: x and R must be 16-byte aligned, x_stride a multiple of 4 and >= d");
+    static_assert(sizeof(long long) == sizeof(int64_t), "row addresses are 64-bit");
+    return interact_from_mixed_rows((long long)B, T, d, x, (long long)x_stride, reinterpret_cast<const long long *>(row_ptrs), row_class, codec1,
+                                    codec2, itself, R, reinterpret_cast<hipStream_t>(stream), default_class);
+}
+
+extern "C" int evs_mixed_kernels_seen(char *buf, int n) {
+    int len = 0;
+    if (buf && n > 0) buf[0] = 0;
+    for (int id = 0; id < evs::kMkCount; id++) {
+        char name[48], line[80];
+        evs::mk_name(id, name, sizeof name);
+        const int k = snprintf(line, sizeof line, "%s=%lld\n", name, evs::g_mk_seen[id].load(std::memory_order_relaxed));
+        if (buf && len + k < n) memcpy(buf + len, line, (size_t)k + 1);
+        len += k;
+    }
+    return len;
+}

@@ -63,6 +63,14 @@ EVS_API int evs_env_switches_seen(char *buf, int n);
  *   vec_c<c>_lpr<l>_bag1 | _offsets            the grid-stride kernel: everything else with d % 4 == 0 and d <= 256, weights included
  *   scalar_c<c>                                one element per lane: any other d, or an output that is not 16-byte aligned */
 EVS_API int evs_gather_kernels_seen(char *buf, int n);
+/* The same record for the mixed-precision interaction consumers (csrc/evs_mixed.hip), which evs_interact_rows_by_address and the
+ * two-tier lookups with interaction (evs_cache_lookup_interact_c1c2 and its bag / fed forms) launch: one "name=count\n" line per
+ * kernel instantiation, all 18 always listed, in a fixed order; buf, n and the return value as for evs_env_switches_seen.
+ * Names, with d = 16 / 32 / 36 and nt = the 16-row tiles of the features (1: T + 1 <= 16, 2: T + 1 <= 32):
+ *   rows_d<d>_nt<n>          one sample per wave through an fp32 image in LDS: any codec pair
+ *   r84_d<d>_nt<n>           rows in registers, codec pair (8, 4), T + 1 <= 28, addresses and classes given
+ *   r84_d<d>_nt<n>_probe     the same with the two-tier probe folded into its head (the (8, 4) tier pair's lookup) */
+EVS_API int evs_mixed_kernels_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)
@@ -328,6 +336,28 @@ EVS_API int evs_emb_interact_mlp1_stacked(int64_t B, int T, int d, const void *c
                                           const float *x, int64_t x_stride, const int64_t *indices_base,
                                           int64_t indices_row_stride, int itself, const float *w1_padded, int kp,
                                           const float *b1, int n1, int relu, float *Z1, float *R, void *stream);
+
+/* The interaction over x and T rows given BY ADDRESS, each in one of two precisions: what the two-tier lookups with interaction
+ * run over the rows their probe finds (csrc/evs_mixed.hip), as an entry point of its own.
+ *   R[b] = [ x[b] | Z[b][i][j] for i in 0..T for j in 0..i-1(+itself) ],  Z = M M^T,  M = (x[b]; row (b, 0); ...; row (b, T - 1))
+ * x: device, sample b at x + b * x_stride (floats), 16-byte aligned, x_stride a multiple of 4 and >= d.
+ * row_ptrs: device (B, T) int64 row-major: element (b, k) is the DEVICE ADDRESS of the row feature k + 1 of sample b takes.
+ * row_class: device (B, T) uint8, same layout: 1 = the row is in codec1, 2 = in codec2, 0 = no row.  NULL: every row is of class
+ * default_class (1 or 2).  Address 0 or class 0 -- either alone -- means a row of zeros: nothing is read for it.  The classes are device
+ * data the host cannot check: a value other than 0, 1 or 2 is undefined (the row is then decoded by one of the two codecs, which one
+ * depends on the kernel).
+ * A row is d elements, row-major: 4 d bytes (codec 32, fp32), 2 d (16), d (8), d / 2 (4: two codes per byte, high nibble first).
+ * Alignment the kernels assume: every row address is a 16-byte aligned base plus a multiple of the row size of its codec -- what
+ * the rows of a cache arena or of a backing table have.  (For d = 36 that makes a u4 row 2-byte and a u8 row 4-byte aligned.)
+ * The kernels read no byte outside a row they are given.
+ * R: device (B, d + P) row-major, 16-byte aligned, P = F (F - 1) / 2 (itself = 0) or F (F + 1) / 2 with F = T + 1; as evs_interact_dot.
+ * Checked on the host (EVS_EINVAL, nothing launched): d in {16, 32, 36}; 1 <= T <= 31; both codecs in {32, 16, 8, 4}; default_class
+ * 1 or 2; 0 <= B < 2^31; x, R, row_ptrs not NULL and aligned as above.  B == 0 is success and touches nothing.
+ * Which kernel runs is the library's choice (evs_mixed_kernels_seen tells): rows in registers for the pair (8, 4) with T <= 27, one
+ * sample per wave through LDS otherwise. */
+EVS_API int evs_interact_rows_by_address(int64_t B, int T, int d, const float *x, int64_t x_stride, const int64_t *row_ptrs,
+                                         const unsigned char *row_class, int codec1, int codec2, int itself, int default_class,
+                                         float *R, void *stream);
 
 /* "cat" interaction (dlrm_s_pytorch.py:506-508): R[b] = [x[b] | ly_0[b] | ...], (B, F*d). */
 EVS_API int evs_interact_cat(int64_t B, int F, int d, const float *const *feats,
