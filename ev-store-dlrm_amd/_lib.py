@@ -65,6 +65,7 @@ _PROTOS = {
     "evs_env_switches_seen": (_int, [C.c_char_p, _int]),
     "evs_gather_kernels_seen": (_int, [C.c_char_p, _int]),
     "evs_mixed_kernels_seen": (_int, [C.c_char_p, _int]),
+    "evs_mlp1_kernels_seen": (_int, [C.c_char_p, _int]),
     "evs_interact_rows_by_address": (_int, [_i64, _int, _int, _vp, _i64, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
     "evs_embedding_bag_sum": (_int, [_int, _i64, _int, _int, _pp, _i64p, _pp, _pp, _i64p, _pp, _vp, _i64, _i64, _vp]),
     "evs_embedding_bag_sum_sharded": (_int, [_int, _i64, _int, _int, _pp, _i64p, _i64p, _i64p, _pp, _pp, _i64p, _pp, _vp, _i64, _i64,
@@ -256,6 +257,13 @@ def mixed_kernels_seen():
     """{name: launches} for every instantiation of the mixed-precision interaction consumers (evs_mixed_kernels_seen)."""
     buf = C.create_string_buffer(lib().evs_mixed_kernels_seen(None, 0) + 1)
     lib().evs_mixed_kernels_seen(buf, len(buf))
+    return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
+
+
+def mlp1_kernels_seen():
+    """{name: launches} for the six instantiations of the fused first top-MLP layer (evs_mlp1_kernels_seen)."""
+    buf = C.create_string_buffer(lib().evs_mlp1_kernels_seen(None, 0) + 1)
+    lib().evs_mlp1_kernels_seen(buf, len(buf))
     return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
 
 

@@ -29,6 +29,7 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include "evs_fused_rf_body.h"
 
 namespace evs {
@@ -101,18 +102,26 @@ static int64_t rf_max_batch() {
     return rf_max_batch_env() >= 0 ? rf_max_batch_env() : 16ll * kNumCu * EVS_RF_LB;
 }
 
+// the dispatch record of the MLP form (evs_mlp1_kernels_seen, include/evstore_hip.h): one counter per instantiation, bumped next to
+// its launch.  id = (d: 16 / 32 / 36) * 2 + (NT - 1)
+constexpr int kMlp1Count = 6;
+static std::atomic<long long> g_mlp1_seen[kMlp1Count];
+
 bool launch_rf_mlp(const FusedArgs &a, hipStream_t st) {
     if (a.F > kTileMaxF || a.bag1 != 1 || a.kp > kMlpRowStride - 4 || (a.kp & 15) || a.kp < a.d + a.P) return false;
     const bool nt2 = a.F > 16;
     switch (a.d) {
     case 16:
         if (nt2) launch_rf_grid<emb_interact_rf_kernel<1, 0, 2, 4, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<1, 0, 1, 4, true>>(a, st);
+        g_mlp1_seen[0 + nt2].fetch_add(1, std::memory_order_relaxed);
         return true;
     case 32:
         if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 0, 2, 4, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 0, 1, 4, true>>(a, st);
+        g_mlp1_seen[2 + nt2].fetch_add(1, std::memory_order_relaxed);
         return true;
     case 36:
         if (nt2) launch_rf_grid<emb_interact_rf_kernel<2, 1, 2, 4, true>>(a, st); else launch_rf_grid<emb_interact_rf_kernel<2, 1, 1, 4, true>>(a, st);
+        g_mlp1_seen[4 + nt2].fetch_add(1, std::memory_order_relaxed);
         return true;
     default:
         return false;
@@ -562,6 +571,19 @@ __global__ void __launch_bounds__(256, (CQ >= 4 ? 2 : EVS_RF_LB)) emb_interact_r
 }
 
 }  // namespace evs
+
+extern "C" int evs_mlp1_kernels_seen(char *buf, int n) {
+    constexpr int kD[3] = {16, 32, 36};
+    int len = 0;
+    if (buf && n > 0) buf[0] = 0;
+    for (int id = 0; id < evs::kMlp1Count; id++) {
+        char line[64];
+        const int k = snprintf(line, sizeof line, "mlp1_d%d_nt%d=%lld\n", kD[id / 2], (id & 1) + 1, evs::g_mlp1_seen[id].load(std::memory_order_relaxed));
+        if (buf && len + k < n) memcpy(buf + len, line, (size_t)k + 1);
+        len += k;
+    }
+    return len;
+}
 
 struct evs_rf_server {
     evs::FusedArgs tmpl{};

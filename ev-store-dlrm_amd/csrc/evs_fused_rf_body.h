@@ -916,7 +916,10 @@ __device__ __forceinline__ void rf_body(const FusedArgs &args, const FusedArgs *
         for (int nt = wave_in_block; nt < n_tiles; nt += 4) {
             const int n = 16 * nt + r16;
             const float *wrow = args.w1p + (size_t)n * kp + q * kq;       // B: output n, k-slot q (rows padded to 16 * n_tiles)
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            // four accumulators, one per element of a 16-byte piece: each is an fma chain of kp / 4 terms, added at the end.  One chain
+            // over all kp terms carries a running sum four times as large over four times as many steps; on same-sign data its median
+            // error is 2.0 - 3.2 u sum |R||W| from kp = 160 on, the four chains' is below 1 (tests/test_gpu_mlp1_matrix.py)
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
             // software pipeline: the operand pieces of step group g + 1 (kPf steps of 4 MFMAs) are requested before the
             // MFMAs of group g issue -- W1 comes from L2 (~500 cycles), a load-use loop runs at 4 MFMAs per round trip
             // (measured at B = 16 384, n1 = 512: 229 -> 137 us; two tiles per wave sharing the A pieces: 195 us, dropped)
@@ -944,19 +947,20 @@ __device__ __forceinline__ void rf_body(const FusedArgs &args, const FusedArgs *
 #pragma unroll
                 for (int p = 0; p < kPf; p++) {
                     if (g + p < nj) {
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].x, bc[p][0], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].y, bc[p][1], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].z, bc[p][2], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].w, bc[p][3], acc, 0, 0, 0);
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].x, bc[p][0], acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].y, bc[p][1], acc1, 0, 0, 0);
+                        acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].z, bc[p][2], acc2, 0, 0, 0);
+                        acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[p].w, bc[p][3], acc3, 0, 0, 0);
                     }
                 }
             }
+            const f32x4 acc = (acc0 + acc1) + (acc2 + acc3);
             const float bias = n < n1 ? args.b1[n] : 0.f;
 #pragma unroll
             for (int v = 0; v < 4; v++) {   // lane holds Z1[sample 4q + v][output n]
                 const int m = 4 * q + v;
                 float z = acc[v] + bias;
-                if (args.relu) z = z > 0.f ? z : 0.f;
+                if (args.relu) z = z <= 0.f ? 0.f : z;   // NaN stays NaN, as torch.relu keeps it (z > 0 ? z : 0 would hide it)
                 if (m < blk_n && n < n1) args.z1[(blk_first + m) * (int64_t)n1 + n] = z;
             }
         }

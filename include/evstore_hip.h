@@ -71,6 +71,11 @@ EVS_API int evs_gather_kernels_seen(char *buf, int n);
  *   r84_d<d>_nt<n>           rows in registers, codec pair (8, 4), T + 1 <= 28, addresses and classes given
  *   r84_d<d>_nt<n>_probe     the same with the two-tier probe folded into its head (the (8, 4) tier pair's lookup) */
 EVS_API int evs_mixed_kernels_seen(char *buf, int n);
+/* The same record for the fused gather + interaction + first top-MLP layer (evs_emb_interact_mlp1_stacked): one "name=count\n" line
+ * per kernel instantiation, all six always listed, in a fixed order (d = 16, 32, 36; nt = 1 then 2 within each); buf, n and the
+ * return value as for evs_env_switches_seen.  A count goes up by one per kernel launch; a refused call and B == 0 launch nothing.
+ *   mlp1_d<d>_nt<n>          d = 16 / 32 / 36, nt = the 16-row tiles of the features (1: T + 1 <= 16, 2: T + 1 <= 28) */
+EVS_API int evs_mlp1_kernels_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)
