@@ -129,6 +129,9 @@ _PROTOS = {
     "evs_cache_fed_finish_interact": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
     "evs_cache_fed_abort": (_int, [_vp]),
     "evs_cache_fed_stats": (_int, [_vp, _i64p, _vp]),
+    "evs_cache_set_fed_depth": (_int, [_vp, _int]),
+    "evs_cache_fed_open_calls": (_int, [_vp]),
+    "evs_cache_fed_ahead_stats": (_int, [_vp, _i64p, _vp]),
     "evs_cache_fed_begin_bags": (_int, [_vp, _i64, _pp, _pp, _i64p, _vp, _vp, _i64p, _vp]),
     "evs_cache_fed_finish_bags": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "evs_cache_fed_finish_bags_interact": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp]),

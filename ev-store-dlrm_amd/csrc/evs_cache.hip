@@ -2875,9 +2875,13 @@ template <> struct SaNative<NoTail> { using type = int; };
 // the way's arena row into slot `rec` (the record's own index) of fs->spill and writes rec at fs->spill_of[entry] -- behind its
 // compare-and-swap (the way is this thread's alone: a way changes at most once per launch, so nobody else writes that arena row or
 // that spill_of word in this launch) and in front of the new row's stores.  One more dependent load, paid by this form alone.
-template <int PIECES, typename U, typename TAIL = NoTail, int W = 0, bool FED = false, bool SPILL = false>
+// HOLD (other fed calls are open on the cache; evs_cache_policy.h at FedHold): the set's hold bytes of the other open calls are
+// loaded next to the line, a held way is no candidate, and a copy of the key that an earlier call installed (its stamp is not this
+// batch's) is counted.
+template <int PIECES, typename U, typename TAIL = NoTail, int W = 0, bool FED = false, bool SPILL = false, bool HOLD = false>
 __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsigned char *table, int t, unsigned row, int agg, unsigned set, unsigned tag1, int *s_delta, int *s_stat,
-                                              const unsigned char *fsrc = nullptr, const FedSrc *fs = nullptr, long long rec = 0, int *s_spilled = nullptr) {
+                                              const unsigned char *fsrc = nullptr, const FedSrc *fs = nullptr, long long rec = 0, int *s_spilled = nullptr,
+                                              const FedHold *fh = nullptr) {
     constexpr int NW = W > 0 ? W : kSaMaxWays;   // ways the scans below walk (W = 0: any geometry, masked by args.sa.ways)
     const unsigned long long key = ((unsigned long long)(t + 1) << 32) | row;
     // two tiers: the other tier took this key in this very batch (only an odd table index can be routed both ways by two
@@ -2891,6 +2895,10 @@ __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsig
     // the CAS); through an address-space-1 pointer they are global_load.
     SaLine line;
     sa_load<W>(args.sa, set, line);
+    unsigned held = 0u;
+    if constexpr (HOLD) {
+        for (int k = 0; k < fh->n_others; k++) held |= fh->others[k][set];
+    }
     __builtin_amdgcn_sched_barrier(0);
     const unsigned char *srow = (FED && fsrc) ? fsrc : table + (long long)row * args.row_bytes;
     using NU = typename SaNative<U>::type;
@@ -2938,10 +2946,13 @@ __device__ __forceinline__ void sa_insert_one(const BatchArgs &args, const unsig
             const bool is_dup = on && (w[j] & g.tag_mask) == tag1;
             dup = is_dup ? j : dup; dw = is_dup ? w[j] : dw;
             const int pj = w[j] == 0u ? -1 : sa_prio(w[j]);
-            const bool cand = on && (w[j] == 0u || sa_stamp(g, w[j]) != cur) && pj < bp;
+            const bool cand = on && (w[j] == 0u || sa_stamp(g, w[j]) != cur) && !(HOLD && ((held >> j) & 1u)) && pj < bp;   // (a free way is never held)
             best = cand ? j : best; bp = cand ? pj : bp; bw = cand ? w[j] : bw;
         }
         if (dup >= 0) {   // another copy of the key got here first: its priority is the maximum over the copies
+            if constexpr (HOLD) {
+                if (sa_stamp(g, dw) != cur) atomicAdd(&fh->counters[1], 1ull);
+            }
             if (sa_prio(dw) < agg) {   // (a CAS, not a maximum: see sa_raise)
                 const int old = sa_raise(g, &tags[dup], dw, agg);
                 if (old >= 0) { atomicSub(&s_delta[old], 1); atomicAdd(&s_delta[agg], 1); }
@@ -3048,8 +3059,8 @@ __global__ void __launch_bounds__(256) cache_batch_sampled_list_kernel(const Bat
 // the set-associative policy's update: the same lists, sa_insert_one per record.  The list's length, the lane's first
 // record and the table base addresses (into LDS: a per-lane index into the kernel arguments is a memory access) are
 // asked for together -- three dependent round trips per record: those, {set line, source row}, the CAS.
-template <int PIECES, typename U, typename TAIL, bool FED = false, bool SPILL = false>
-__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs = nullptr);
+template <int PIECES, typename U, typename TAIL, bool FED = false, bool SPILL = false, bool HOLD = false>
+__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs = nullptr, const FedHold *fh = nullptr);
 template <int PIECES, typename U, typename TAIL = NoTail>
 __global__ void __launch_bounds__(256) cache_batch_sa_list_kernel(const BatchArgs args) { sa_list_block<PIECES, U, TAIL>(args, (int)blockIdx.x); }
 // both tiers of a two- / three-tier lookup in one launch: blocks [0, g1) take C1's lists, [g1, 2 g1) C2's (the route filter
@@ -3066,8 +3077,13 @@ __global__ void __launch_bounds__(256) cache_batch_sa_list_fed_kernel(const Batc
 // ... and of a tier of the fed pair: the same, and an occupied way's old row is spilled first (sa_insert_one, SPILL)
 template <int PIECES, typename U, typename TAIL = NoTail>
 __global__ void __launch_bounds__(256) cache_batch_sa_list_fed_spill_kernel(const BatchArgs args, const FedSrc fs) { sa_list_block<PIECES, U, TAIL, true, true>(args, (int)blockIdx.x, &fs); }
-template <int PIECES, typename U, typename TAIL, bool FED, bool SPILL>
-__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs) {
+// ... and of a fed cache while other calls are open on it: the ways they hold are left alone (sa_insert_one, HOLD)
+template <int PIECES, typename U, typename TAIL = NoTail>
+__global__ void __launch_bounds__(256) cache_batch_sa_list_fed_hold_kernel(const BatchArgs args, const FedSrc fs, const FedHold fh) {
+    sa_list_block<PIECES, U, TAIL, true, false, true>(args, (int)blockIdx.x, &fs, &fh);
+}
+template <int PIECES, typename U, typename TAIL, bool FED, bool SPILL, bool HOLD>
+__device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, const FedSrc *fs, const FedHold *fh) {
     __shared__ int s_delta[kMaxBuckets];
     __shared__ int s_stat[3];
     __shared__ int s_spilled;
@@ -3091,8 +3107,8 @@ __device__ __forceinline__ void sa_list_block(const BatchArgs &args, int bid, co
             if constexpr (FED) {
                 const int slot = fs->rec_slot[(long long)bid * args.list_cap + i];
                 const unsigned char *fsrc = slot >= 0 ? fs->fed + (long long)fs->slot_index[slot] * fs->stride : nullptr;
-                sa_insert_one<PIECES, U, TAIL, W, true, SPILL>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat, fsrc, fs,
-                                                               (long long)bid * args.list_cap + i, &s_spilled);
+                sa_insert_one<PIECES, U, TAIL, W, true, SPILL, HOLD>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat, fsrc, fs,
+                                                                     (long long)bid * args.list_cap + i, &s_spilled, fh);
             } else
             sa_insert_one<PIECES, U, TAIL, W>(args, s_table[t & 31], t, r.x, (int)((r.y >> 8) & 0xffu), r.z, r.w, s_delta, s_stat);
         }
@@ -3579,8 +3595,19 @@ struct evs_cache {
     unsigned long long *fed_cnt = nullptr;
     int *fed_part1 = nullptr;   // the replica rows an open call's probe adds into (behind fed_cnt; zero between calls): fed_part_fold_kernel
     long long fed_calls = 0, fed_keys = 0;
+    // what a (B, T) call owns from its begin to its end: the scratch of the list kernel, its replica rows, its miss lists and its
+    // pointer table.  Call slot 0 -- a call that begins alone -- is the members above and the per-batch slab; slots 1 .. kFedMaxDepth
+    // -- a call that begins behind another (evs_cache_set_fed_depth) -- are one slab each, grown by the begin that takes the slot
+    // (fed_ahead_scratch)
+    struct FedScratch {
+        unsigned long long *slot_key = nullptr; int *slot_index = nullptr, *rec_slot = nullptr, *n = nullptr;
+        int *part1 = nullptr;
+        long long *row_ptrs = nullptr; uint4 *miss_rec = nullptr; int *list_cnt = nullptr;
+    };
     struct FedOpen {
         bool open = false;
+        int slot = 0; FedScratch sc;            // a (B, T) call: its call slot and the scratch there
+        unsigned char *hold = nullptr;          // ... begun while another call was open: its hold map (evs_cache_policy.h at FedHold)
         evs::BatchArgs a; evs::PolicyArgs pa;
         int64_t B = 0; const int32_t *rows = nullptr; uint8_t *hit = nullptr;
         long long n_keys = 0;
@@ -3596,6 +3623,18 @@ struct evs_cache {
         evs_cache *partner = nullptr;
         uint8_t *tier = nullptr; int threshold = 0;
     } fedc;
+    // More than one (B, T) call open (evs_cache_set_fed_depth; the contract: include/evstore_hip.h there): fedc is the OLDEST open
+    // call -- what every refusal looks at --, fed_ahead the calls begun behind it, oldest first.  Per slot >= 1 (index slot - 1) the scratch slab
+    // and what it has room for, and a hold map of one byte per set; slabs of the per-batch buffers that a begin outgrew while a
+    // call still used them (freed by the next begin that finds no call open); [0] hold bits set, [1] records found installed
+    int fed_depth = 1;
+    bool fed_begin_behind = false;
+    std::vector<FedOpen> fed_ahead;
+    struct FedSlab { void *slab = nullptr; long long max_pos = 0, max_rec = 0, max_lists = 0; FedScratch sc; } fed_slab[evs::kFedMaxDepth];
+    unsigned char *fed_hold[evs::kFedMaxDepth] = {nullptr, nullptr, nullptr, nullptr}; size_t fed_hold_bytes[evs::kFedMaxDepth] = {0, 0, 0, 0};
+    std::vector<void *> fed_retired;
+    unsigned long long *fed_ahead_cnt = nullptr;
+    long long fed_ahead_begins = 0;
     long long fed_max_rec = 0;      // the records rec_slot has room for (the two forms round a call's lists differently)
     // a tier of the fed pair: the spill block (a row slot per miss record of the largest call) and spill_of (an int32 per arena
     // entry), evs_cache_policy.h at PairFedArgs; C1 keeps the pair's totals: replica rows on the device, calls and keys here
@@ -3750,6 +3789,12 @@ extern "C" int evs_cache_destroy(evs_cache *c) {
     void *ptrs[] = {c->slab_create, c->slab_batch, c->slab_perbatch, c->estamp, c->new_keys, c->slot_stage, c->evicted_keys, c->vict_keys, c->vict_cnt, c->route_filter, c->sa_arena, c->arena_create, c->slab_bags, c->slab_bags2, c->bag_pool, c->fetch_cnt, c->approx_cnt, c->slab_fed, c->fed_cnt, c->fed_spill, c->fed_spill_of, c->pair_fed_cnt};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    for (int k = 0; k < evs::kFedMaxDepth; k++) {
+        if (c->fed_slab[k].slab) (void)hipFree(c->fed_slab[k].slab);
+        if (c->fed_hold[k]) (void)hipFree(c->fed_hold[k]);
+    }
+    for (void *p : c->fed_retired) (void)hipFree(p);
+    if (c->fed_ahead_cnt) (void)hipFree(c->fed_ahead_cnt);
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
     if (c->new_keys_host) (void)hipHostFree(c->new_keys_host);
     if (c->staging) (void)hipHostFree(c->staging);
@@ -3978,8 +4023,9 @@ extern "C" int evs_cache_set_bag_count(evs_cache *c, int when) {
 static int serve_pause(evs_cache *c);
 static int exact_launched(evs_cache *c, hipStream_t st);
 // a begin without its finish (evs_cache_fed_begin): everything that would read or move the state the open call stands on is refused
+// (fed_begin_behind: a begin behind open (B, T) calls is walking the checks every batched call walks -- fed_begin_ahead)
 static int fed_open_refuse(evs_cache *c, const char *who) {
-    if (!c || !c->fedc.open) return EVS_OK;
+    if (!c || !c->fedc.open || c->fed_begin_behind) return EVS_OK;
     if (c->fedc.pair) {
         evs::set_error("%s: a fed pair call is open on this %s cache (evs_cache_pair_fed_begin without evs_cache_pair_fed_finish / evs_cache_pair_fed_abort)", who,
                        policy_name(c->host.policy));
@@ -4606,7 +4652,8 @@ static int batch_prepare(evs_cache *c, int64_t B, const int32_t *rows, hipStream
             set_error("%s: allocating the buffers of a %lld-request batch failed", who, (long long)B);
             return EVS_ENOMEM;
         }
-        if (c->slab_perbatch) {
+        if (c->slab_perbatch && c->fedc.open) c->fed_retired.push_back(c->slab_perbatch);   // (an open fed call works on it: freed once none is open)
+        else if (c->slab_perbatch) {
             EVS_HIP_CHECK(hipStreamSynchronize(st));
             (void)hipFree(c->slab_perbatch);
         }
@@ -4793,6 +4840,13 @@ static void launch_sa_update_fed(const evs::BatchArgs &a, const evs::FedSrc &fs,
     with_row_shape(a.row_bytes, [&](auto s) {
         using S = decltype(s);
         hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs);
+    });
+}
+// ... while other fed calls are open on the cache (the hold form)
+static void launch_sa_update_fed_hold(const evs::BatchArgs &a, const evs::FedSrc &fs, const evs::FedHold &fh, hipStream_t st) {
+    with_row_shape(a.row_bytes, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((evs::cache_batch_sa_list_fed_hold_kernel<S::PIECES, typename S::U, typename S::TAIL>), dim3((unsigned)a.g1), dim3(sampled_list_threads(a)), 0, st, a, fs, fh);
     });
 }
 
@@ -5057,11 +5111,13 @@ static evs::PolicyArgs policy_args(evs_cache *c, int64_t B, const int32_t *reque
 // A tier's step into a new batch, in front of the batch's probe.  EvLFU: the next batch stamp, handed back, and the flush the close
 // of an earlier batch asked for (the tier's, not the call's: it stands if a fed call is dropped).  LRU / LFU: the layout of the way
 // words and the batch number n = 1, 2, ... modulo 2^S into pa; 0 is handed back.
-static int tier_next_batch(evs_cache *c, evs::PolicyArgs &pa, hipStream_t st) {
+// hold_flush (a fed begin made while another call is open): the flush zeroes way words an open call may have hit, so the request
+// stays standing -- the host flag is left set -- for the next begin that finds no call open.
+static int tier_next_batch(evs_cache *c, evs::PolicyArgs &pa, hipStream_t st, bool hold_flush = false) {
     using namespace evs;
     if (c->host.policy == kEvLFU) {
         const int stamp = next_batch_stamp(c);
-        sampled_flush_if_wanted(c, st);
+        if (!hold_flush) sampled_flush_if_wanted(c, st);
         return stamp;
     }
     pa.lay = pol_layout(c->sa, c->host.policy == kLFU);
@@ -5838,27 +5894,37 @@ static int fed_open_scratch(evs_cache *c, long long n_pos, long long n_rec, hipS
 }
 // a begin that refuses behind the point where the call was counted, and evs_cache_fed_abort: the call's ordinal and stamp go back
 // (a flush the begin ran stands: it is due before the next call, as ever)
-static void fed_take_back(evs_cache *c) {
-    c->batch_calls--; c->stamp_counter = c->fedc.stamp_counter0;
+static void fed_take_back(evs_cache *c, long long stamp_counter0) {
+    c->batch_calls--; c->stamp_counter = stamp_counter0;
     if (c->last_flush_call > c->batch_calls) c->last_flush_call = c->batch_calls;
 }
+static void fed_take_back(evs_cache *c) { fed_take_back(c, c->fedc.stamp_counter0); }
+// call slot 0: the scratch fed_open_scratch and batch_prepare have just set up
+static evs_cache::FedScratch fed_scratch0(evs_cache *c) {
+    evs_cache::FedScratch sc;
+    sc.slot_key = c->fed_slot_key; sc.slot_index = c->fed_slot_index; sc.rec_slot = c->fed_rec_slot; sc.n = c->fed_n; sc.part1 = c->fed_part1;
+    sc.row_ptrs = c->row_ptrs; sc.miss_rec = c->miss_rec; sc.list_cnt = c->list_cnt;
+    return sc;
+}
+// a (B, T) call of a tier alone works on the scratch its frame names (the bag form and the pair: slot 0's, as the cache holds it)
+static bool fed_frame_owns_scratch(const evs_cache::FedOpen &o) { return !o.bags && !o.pair; }
 // The end of both begins: the distinct missing keys of the fed tables out of the probe's `grid` miss lists into keys (grid 0: a call
 // without a position lists nothing), their number to the host, and -- the stream synchronised -- the call written down as open.
 // bag_grid: the bag form's grid, which its finish launches over again.
-static int fed_list_keys(evs_cache *c, const uint4 *rec, const int *cnt, int rec_cap, uint64_t *keys, int grid, hipStream_t st, const char *who,
-                         bool bags, int64_t B, const int32_t *rows, uint8_t *hit, int64_t *n_keys_host) {
+// o: the call's frame (c->fedc, or the frame of a call begun behind an open one); sc: its scratch.
+static int fed_list_keys(evs_cache *c, evs_cache::FedOpen &o, const evs_cache::FedScratch &sc, const uint4 *rec, const int *cnt, int rec_cap, uint64_t *keys, int grid,
+                         hipStream_t st, const char *who, bool bags, int64_t B, const int32_t *rows, uint8_t *hit, int64_t *n_keys_host) {
     using namespace evs;
-    evs_cache::FedOpen &o = c->fedc;
     if (grid) {
         FedListArgs la{};
         la.miss_rec = rec; la.list_cnt = cnt; la.list_cap = rec_cap;
-        la.slot_key = c->fed_slot_key; la.slot_index = c->fed_slot_index; la.rec_slot = c->fed_rec_slot;
+        la.slot_key = sc.slot_key; la.slot_index = sc.slot_index; la.rec_slot = sc.rec_slot;
         la.slot_mask = o.slot_mask; la.fed_mask = c->fed_mask;
-        la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = c->fed_n;
+        la.keys = reinterpret_cast<unsigned long long *>(keys); la.n_keys = sc.n;
         fed_list_launch(la, grid, st);
     }
     int n = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, c->fed_n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&n, sc.n, sizeof n, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) {
         (void)hipGetLastError(); set_error("%s: the probe or the list launch failed", who); return EVS_EHIP;
     }
@@ -5869,12 +5935,104 @@ static int fed_list_keys(evs_cache *c, const uint4 *rec, const int *cnt, int rec
 static evs::FedSrc fed_src(evs_cache *c, const void *fed, int64_t stride) {
     evs::FedSrc f{};
     f.fed = reinterpret_cast<const unsigned char *>(fed); f.stride = stride;
-    f.rec_slot = c->fed_rec_slot; f.slot_index = c->fed_slot_index; f.slot_key = c->fed_slot_key;
+    const evs_cache::FedScratch sc = fed_frame_owns_scratch(c->fedc) ? c->fedc.sc : fed_scratch0(c);
+    f.rec_slot = sc.rec_slot; f.slot_index = sc.slot_index; f.slot_key = sc.slot_key;
     f.slot_mask = c->fedc.slot_mask; f.fed_mask = c->fed_mask; f.counters = c->fed_cnt; f.err = evs::index_error_flag();
     // (the zero row of the cache's codec, where a row fits it: 4 KiB of fp32, 1 KiB of codes)
     if (c->host.row_bytes <= (c->host.codec == 32 ? 4096 : 1024))
         f.zero_row = reinterpret_cast<const unsigned char *>(c->host.codec == 32 ? evs::zero_page() : evs::zero_code_page(c->host.codec));
     return f;
+}
+
+// ---- more than one (B, T) call open (evs_cache_set_fed_depth; the contract: include/evstore_hip.h there) ----
+// The scratch of call slot k >= 1, everything fed_open_scratch and the per-batch slab give slot 0, as one slab grown with the largest
+// call the slot has taken (nobody works on a free slot's slab); then the call's share of the slot table, the list length and the
+// call's replica rows cleared on st.
+static int fed_ahead_scratch(evs_cache *c, int k, long long n_pos, long long n_rec, long long n_lists, hipStream_t st, const char *who, unsigned *slot_mask) {
+    using namespace evs;
+    auto slots_of = [](long long np) { long long s = 64; while (s < 2 * np) s <<= 1; return s; };
+    evs_cache::FedSlab &fsl = c->fed_slab[k - 1];
+    if (n_pos > fsl.max_pos || n_rec > fsl.max_rec || n_lists > fsl.max_lists) {
+        const long long np = std::max(n_pos, fsl.max_pos), nr = std::max(n_rec, fsl.max_rec), nl = std::max(n_lists, fsl.max_lists), slots = slots_of(np);
+        evs_cache::FedScratch sc;
+        void *slab = nullptr;
+        SlabPlan sp;
+        sp.add(&sc.slot_key, slots * 8); sp.add(&sc.slot_index, slots * 4); sp.add(&sc.rec_slot, nr * 4); sp.add(&sc.n, 4);
+        sp.add(&sc.part1, (long long)kReplicas * kPartCols * (long long)sizeof(int));
+        sp.add(&sc.row_ptrs, np * 8); sp.add(&sc.miss_rec, nr * 16); sp.add(&sc.list_cnt, nl * 4);
+        if (!sp.carve(&slab)) { set_error("%s: allocating the scratch of call slot %d for a call of %lld positions failed", who, k, np); return EVS_ENOMEM; }
+        if (fsl.slab) { EVS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(fsl.slab); }
+        fsl.slab = slab; fsl.sc = sc; fsl.max_pos = np; fsl.max_rec = nr; fsl.max_lists = nl;
+    }
+    const long long slots = slots_of(n_pos);
+    *slot_mask = (unsigned)(slots - 1);
+    if (hipMemsetAsync(fsl.sc.slot_key, 0, (size_t)slots * 8, st) != hipSuccess || hipMemsetAsync(fsl.sc.n, 0, 4, st) != hipSuccess ||
+        hipMemsetAsync(fsl.sc.part1, 0, (size_t)kReplicas * kPartCols * sizeof(int), st) != hipSuccess) {
+        (void)hipGetLastError(); set_error("%s: clearing the scratch of call slot %d failed", who, k); return EVS_EHIP;
+    }
+    return EVS_OK;
+}
+// A begin behind open (B, T) calls.  The frame is built beside the open ones and joins them when the list is on the host.  What differs
+// from a begin alone: a call slot of its own (1 .. kFedMaxDepth: slot 0 belongs to a call that began alone), no flush (tier_next_batch),
+// and the probe's hold form -- the older calls' updates run between this probe and this call's finish, and the ways it hits must still
+// be there.  (A call that began alone needs no map: it is the oldest until it ends, and no update runs in front of its finish.)
+static int fed_begin_ahead(evs_cache *c, int64_t B, const int32_t *rows, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream, const char *who) {
+    using namespace evs;
+    const int n_open = 1 + (int)c->fed_ahead.size();
+    if (n_open >= c->fed_depth) {
+        set_error("%s: %d fed calls are open on this %s cache, the depth evs_cache_set_fed_depth gave it: finish the oldest (evs_cache_fed_finish / "
+                  "_fed_finish_interact) or drop the newest (evs_cache_fed_abort)", who, n_open, policy_name(c->host.policy));
+        return EVS_ESTATE;
+    }
+    struct Behind {   // the checks below are those of every batched call, which refuse a cache with an open call: not this begin
+        evs_cache *c;
+        explicit Behind(evs_cache *c_) : c(c_) { c->fed_begin_behind = true; }
+        ~Behind() { c->fed_begin_behind = false; }
+    } behind(c);
+    { const int rc = fed_call_check(c, who); if (rc) return rc; }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned busy = c->fedc.slot ? 1u << c->fedc.slot : 0u;
+    for (const evs_cache::FedOpen &f : c->fed_ahead) busy |= 1u << f.slot;
+    int k = 1;
+    while ((busy >> k) & 1u) k++;   // (at most kFedMaxDepth - 1 calls are open: one of the slots 1 .. kFedMaxDepth is free)
+    evs_cache::FedOpen o;
+    o.stamp_counter0 = c->stamp_counter;
+    o.slot = k;
+    BatchArgs &a = o.a;
+    { const int rc = batch_prepare(c, B, rows, st, a, who); if (rc) return rc; }
+    auto fail = [&](int rc) { fed_take_back(c, o.stamp_counter0); return rc; };
+    const int T = c->host.n_tables;
+    a.list_cap = (int)list_cap(B, a.g1, T);
+    { const int rc = fetch_first_state(c, st, who); if (rc) return fail(rc); }
+    { const int rc = ensure_counters(&c->fed_ahead_cnt, 2 * sizeof(unsigned long long), st, who, "fed-depth"); if (rc) return fail(rc); }
+    { const int rc = fed_ahead_scratch(c, k, B * T, (long long)a.g1 * a.list_cap, a.g1, st, who, &o.slot_mask); if (rc) return fail(rc); }
+    o.sc = c->fed_slab[k - 1].sc;
+    a.out = nullptr; a.hit = hit; a.row_ptrs = o.sc.row_ptrs; a.miss_rec = o.sc.miss_rec; a.list_cnt = o.sc.list_cnt;
+    // the hold map: one byte per set (in whole words: the probe's atomicOr takes the aligned word), zero in front of the probe
+    const size_t hold_bytes = ((size_t)c->sa.nset + 3u) & ~(size_t)3u;
+    if (c->fed_hold[k - 1] && c->fed_hold_bytes[k - 1] != hold_bytes) {   // (the set records were made anew: the slot is free, nobody reads its map)
+        if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); set_error("%s: the stream failed", who); return fail(EVS_EHIP); }
+        (void)hipFree(c->fed_hold[k - 1]); c->fed_hold[k - 1] = nullptr;
+    }
+    if (!c->fed_hold[k - 1]) {
+        if (hipMalloc(reinterpret_cast<void **>(&c->fed_hold[k - 1]), hold_bytes) != hipSuccess) {
+            (void)hipGetLastError(); c->fed_hold[k - 1] = nullptr;
+            set_error("%s: allocating the hold map of call slot %d failed", who, k); return fail(EVS_ENOMEM);
+        }
+        c->fed_hold_bytes[k - 1] = hold_bytes;
+    }
+    o.hold = c->fed_hold[k - 1];
+    if (hipMemsetAsync(o.hold, 0, hold_bytes, st) != hipSuccess) { (void)hipGetLastError(); set_error("%s: clearing the hold map failed", who); return fail(EVS_EHIP); }
+    PolicyArgs &pa = o.pa;
+    pa = policy_args(c, B, rows, hit, o.sc.row_ptrs, o.sc.miss_rec, o.sc.list_cnt, a.list_cap, o.sc.part1);
+    a.stamp = tier_next_batch(c, pa, st, true);
+    FedHold fh{};
+    fh.mine = o.hold; fh.counters = c->fed_ahead_cnt;
+    fed_probe_hold_launch(pa, fh, c->host.policy == kEvLFU, a.g1, st);
+    { const int rc = fed_list_keys(c, o, o.sc, o.sc.miss_rec, o.sc.list_cnt, a.list_cap, keys, a.g1, st, who, false, B, rows, hit, n_keys_host); if (rc) return fail(rc); }
+    c->fed_ahead.push_back(o);
+    c->fed_ahead_begins++;
+    return EVS_OK;
 }
 
 extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream) {
@@ -5884,11 +6042,19 @@ extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows,
     EVS_REQUIRE(rows && hit && keys && n_keys_host, "%s: NULL argument", who);
     EVS_REQUIRE(B > 0, "%s: B = %lld", who, (long long)B);
     EVS_REQUIRE(reinterpret_cast<uintptr_t>(keys) % 8 == 0, "%s: keys must be 8-byte aligned", who);
+    // (a second begin: at depth 1, and behind a bag call or a pair call at any depth, the refusal of ever; else up to the depth)
+    if (c->fedc.open && c->fed_depth > 1 && fed_frame_owns_scratch(c->fedc)) return fed_begin_ahead(c, B, rows, hit, keys, n_keys_host, stream, who);
     { const int rc = fed_open_refuse(c, who); if (rc) return rc; }
     { const int rc = fed_call_check(c, who); if (rc) return rc; }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!c->fed_retired.empty()) {   // (per-batch slabs a begin outgrew under an open call: nobody works on them any more)
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        for (void *p : c->fed_retired) (void)hipFree(p);
+        c->fed_retired.clear();
+    }
     evs_cache::FedOpen &o = c->fedc;
     o.stamp_counter0 = c->stamp_counter;
+    o.slot = 0; o.hold = nullptr;
     BatchArgs &a = o.a;
     { const int rc = batch_prepare(c, B, rows, st, a, who); if (rc) return rc; }
     // (from here on a refusal takes the call's ordinal back: batch_prepare has counted it)
@@ -5905,7 +6071,8 @@ extern "C" int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows,
     pa = policy_args(c, B, rows, hit, c->row_ptrs, c->miss_rec, c->list_cnt, a.list_cap, c->fed_part1);
     a.stamp = tier_next_batch(c, pa, st);
     fed_probe_launch(pa, c->host.policy == kEvLFU, a.g1, st);
-    { const int rc = fed_list_keys(c, c->miss_rec, c->list_cnt, a.list_cap, keys, a.g1, st, who, false, B, rows, hit, n_keys_host); if (rc) return fail(rc); }
+    o.sc = fed_scratch0(c);
+    { const int rc = fed_list_keys(c, o, o.sc, c->miss_rec, c->list_cnt, a.list_cap, keys, a.g1, st, who, false, B, rows, hit, n_keys_host); if (rc) return fail(rc); }
     return EVS_OK;
 }
 
@@ -5938,7 +6105,7 @@ static evs::FedSrc fed_finish_enter(evs_cache *c, const void *fed, int64_t strid
     const evs::FedSrc fs = fed_src(c, fed, fed ? stride : 0);
     c->fedc.open = false;
     c->fetch_calls++;
-    hipLaunchKernelGGL(evs::fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, c->fed_part1);
+    hipLaunchKernelGGL(evs::fed_part_fold_kernel, dim3(1), dim3(256), 0, st, c->part1, fed_frame_owns_scratch(c->fedc) ? c->fedc.sc.part1 : c->fed_part1);
     return fs;
 }
 static int fed_finish_done(evs_cache *c, int64_t B, hipStream_t st) {
@@ -5947,8 +6114,12 @@ static int fed_finish_done(evs_cache *c, int64_t B, hipStream_t st) {
     return rc;
 }
 
-static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
-                           const char *who) {
+// The finish of the OLDEST open call (c->fedc), on that call's own stamp, records and pointer table.  With other calls open behind it
+// the update runs in its hold form over their maps (evs_cache_policy.h at FedHold) -- and so does the update of a call that BEGAN
+// behind another and finishes alone: there is no map to pass, but its records may name keys an earlier call installed, which that
+// form counts.  A call that was alone from its begin to its finish takes the launch of ever.
+static int fed_finish_oldest(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
+                             const char *who) {
     using namespace evs;
     evs_cache::FedOpen &o = c->fedc;
     { const int rc = fed_finish_check(c, false, fed, stride, who); if (rc) return rc; }
@@ -5965,13 +6136,37 @@ static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float 
         ha.part1 = c->part1;
         fed_hits_launch(ha, c->host.policy == kEvLFU, a.g1, st);
     }
-    if (c->host.policy != kEvLFU) policy_insert_fed_launch(o.pa, fs, a.g1, sampled_list_threads(a), st);
-    else launch_sa_update_fed(a, fs, st);
-    RepointArgs ra = repoint_args(c, o.hit, c->row_ptrs, o.B);
+    if (c->fed_ahead.empty() && !o.hold) {
+        if (c->host.policy != kEvLFU) policy_insert_fed_launch(o.pa, fs, a.g1, sampled_list_threads(a), st);
+        else launch_sa_update_fed(a, fs, st);
+    } else {
+        FedHold fh{};
+        for (const evs_cache::FedOpen &f : c->fed_ahead) fh.others[fh.n_others++] = f.hold;
+        fh.counters = c->fed_ahead_cnt;
+        if (c->host.policy != kEvLFU) policy_insert_fed_hold_launch(o.pa, fs, fh, a.g1, sampled_list_threads(a), st);
+        else launch_sa_update_fed_hold(a, fs, fh, st);
+    }
+    RepointArgs ra = repoint_args(c, o.hit, o.sc.row_ptrs, o.B);
     ra.requests = o.rows; ra.n_pos = o.B * c->host.n_tables;
     sa_repoint_fed_launch(ra, fs, a.g1, st);
-    { const int rc = batch_consumers(c, nullptr, o.B, out, x, x_stride, itself, R, st); if (rc) return rc; }   // (a consumer that refuses: the batch is not counted)
+    {   // the consumers read the cache's pointer table: this call's, while they are launched
+        long long *const tier_ptrs = c->row_ptrs;
+        c->row_ptrs = o.sc.row_ptrs;
+        const int rc = batch_consumers(c, nullptr, o.B, out, x, x_stride, itself, R, st);
+        c->row_ptrs = tier_ptrs;
+        if (rc) return rc;   // (a consumer that refuses: the batch is not counted)
+    }
     return fed_finish_done(c, o.B, st);
+}
+// ... and, the call spent, the next oldest open call takes its place
+static int fed_finish_impl(evs_cache *c, const void *fed, int64_t stride, float *out, const float *x, int64_t x_stride, int itself, float *R, void *stream,
+                           const char *who) {
+    const int rc = fed_finish_oldest(c, fed, stride, out, x, x_stride, itself, R, stream, who);
+    if (!c->fedc.open && !c->fed_ahead.empty()) {
+        c->fedc = c->fed_ahead.front();
+        c->fed_ahead.erase(c->fed_ahead.begin());
+    }
+    return rc;
 }
 extern "C" int evs_cache_fed_finish(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *out, void *stream) {
     using namespace evs;
@@ -5992,8 +6187,41 @@ extern "C" int evs_cache_fed_abort(evs_cache *c) {
     EVS_REQUIRE(c, "evs_cache_fed_abort: NULL cache");
     if (!c->fedc.open) { set_error("evs_cache_fed_abort: no fed call is open on this %s cache (evs_cache_fed_begin)", policy_name(c->host.policy)); return EVS_ESTATE; }
     { const int rc = c->fedc.pair ? fed_open_refuse(c, "evs_cache_fed_abort") : EVS_OK; if (rc) return rc; }
+    if (!c->fed_ahead.empty()) {   // the NEWEST open call: its ordinal and stamp are the last ones given; its holds lapse with its frame
+        const long long stamp_counter0 = c->fed_ahead.back().stamp_counter0;
+        c->fed_ahead.pop_back();
+        fed_take_back(c, stamp_counter0);
+        return EVS_OK;
+    }
     c->fedc.open = false;
     fed_take_back(c);
+    return EVS_OK;
+}
+extern "C" int evs_cache_set_fed_depth(evs_cache *c, int depth) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_set_fed_depth: NULL cache");
+    EVS_REQUIRE(depth >= 1 && depth <= kFedMaxDepth, "evs_cache_set_fed_depth: depth %d (1 .. %d calls open at a time)", depth, kFedMaxDepth);
+    { const int rc = fed_open_refuse(c, "evs_cache_set_fed_depth"); if (rc) return rc; }
+    c->fed_depth = depth;
+    return EVS_OK;
+}
+extern "C" int evs_cache_fed_open_calls(evs_cache *c) {
+    if (!c) return -1;
+    return c->fedc.open ? 1 + (int)c->fed_ahead.size() : 0;
+}
+// out4 (host): [begins made with another call open, hold bits set, miss records found installed by an earlier call, 0]
+extern "C" int evs_cache_fed_ahead_stats(evs_cache *c, int64_t *out4, void *stream) {
+    using namespace evs;
+    EVS_REQUIRE(c, "evs_cache_fed_ahead_stats: NULL cache");
+    EVS_REQUIRE(out4, "evs_cache_fed_ahead_stats: NULL out4");
+    if (c->fedc.open && c->fedc.pair) return fed_open_refuse(c, "evs_cache_fed_ahead_stats");
+    unsigned long long h[2] = {0ull, 0ull};
+    if (c->fed_ahead_cnt) {
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        EVS_HIP_CHECK(hipMemcpyAsync(h, c->fed_ahead_cnt, sizeof h, hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    out4[0] = c->fed_ahead_begins; out4[1] = (int64_t)h[0]; out4[2] = (int64_t)h[1]; out4[3] = 0;
     return EVS_OK;
 }
 // out4 (host): [calls finished, keys listed, missed positions of fed tables, positions served straight from a fed block]
@@ -6587,7 +6815,7 @@ extern "C" int evs_cache_fed_begin_bags(evs_cache *c, int64_t B, const int64_t *
         bags_count_launch(a, st);   // (column 39 into the call's rows; sample_cnt is zero again behind it)
         if (grid) bags_fed_list_launch(a, (int)grid, st);
     }
-    const int rc = fed_list_keys(c, c->bag_rec, c->bag_list_cnt, a.p.list_cap, keys, (int)grid, st, who, true, B, nullptr, a.p.hit, n_keys_host);
+    const int rc = fed_list_keys(c, o, fed_scratch0(c), c->bag_rec, c->bag_list_cnt, a.p.list_cap, keys, (int)grid, st, who, true, B, nullptr, a.p.hit, n_keys_host);
     if (rc) fed_take_back(c);
     return rc;
 }

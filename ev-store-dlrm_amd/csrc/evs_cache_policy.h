@@ -229,6 +229,28 @@ void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, un
 // sa_repoint_launch's (B, T) form for a cache with fed tables
 void sa_repoint_fed_launch(const RepointArgs &a, const FedSrc &f, int grid, hipStream_t st);
 
+// Several (B, T) calls of a fed cache open at once (evs_cache_set_fed_depth; the contract: include/evstore_hip.h there).  A call
+// that begins while another is open probes a tier the older calls' updates will still move, so every way it flags 1 is HELD until
+// it ends: one byte per set in a map of the call's own (bit j = way j; zeroed in front of the probe), set by the probe's hold
+// form, read by the hold form of every update that runs while the call is open.  A held way is no candidate there; a set without
+// a candidate turns the key away ("left in place": the position is served from the fed block).  No way word is written for a
+// hold, so dropping the call is still free: the host stops passing its map.
+//   probe, hold form   fed_probe plus, per position flagged 1, the bit: a plain load of the aligned 32-bit word that contains the
+//                      set's byte first, an atomicOr only where the bit is still clear (hot keys would queue on one word)
+//   update, hold form  the set's hold bytes of the other open calls (up to kFedMaxDepth - 1) are loaded next to the set's line;
+//                      the duplicate branch ("another copy got there first") counts a copy whose stamp is not this call's: the
+//                      key was missed by this call's probe and installed by a call that finished in between
+// counters: [0] hold bits set (one add per probe block), [1] miss records found installed by an earlier call.
+constexpr int kFedMaxDepth = 4;
+struct FedHold {
+    unsigned char *mine;                            // probe: this call's map
+    const unsigned char *others[kFedMaxDepth - 1];  // update: the maps of the other open calls ...
+    int n_others;                                   // ... and their number
+    unsigned long long *counters;
+};
+void fed_probe_hold_launch(const PolicyArgs &a, const FedHold &h, bool evlfu, int grid, hipStream_t st);
+void policy_insert_fed_hold_launch(const PolicyArgs &a, const FedSrc &f, const FedHold &h, int grid, unsigned threads, hipStream_t st);
+
 // Ragged bags over fed backing (evs_cache_fed_begin_bags; the contract: include/evstore_hip.h there): the count-first fetch-first
 // bag chain cut in two where the fed chain above is cut:
 //   begin    (flush ->) bags_fed_probe -> (EvLFU: bags_count, its column 39 into the call's own replica rows -> bags_fed_list) ->

@@ -190,6 +190,77 @@ __global__ void __launch_bounds__(256) fed_probe_kernel(const PolicyArgs args) {
     if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
 }
 
+// The hold form of that probe (a call that begins while another is open; evs_cache_policy.h at FedHold): the same kernel, line for
+// line -- kept as a kernel of its own so that fed_probe_kernel compiles to what it was --, and every way a position is flagged 1 for
+// gets its bit in the call's hold map: the word is read first, the atomicOr goes out only where the bit is still clear, and the lane
+// whose atomicOr found it clear counts it.
+template <bool EVLFU>
+__global__ void __launch_bounds__(256) fed_probe_hold_kernel(const PolicyArgs args, const FedHold fh) {
+    __shared__ int s_sum[2];   // hits / all-hit requests of this block
+    __shared__ int s_list_n;
+    __shared__ unsigned s_base[32];
+    __shared__ long long s_rows[32];
+    __shared__ const unsigned char *s_table[32];
+    __shared__ int s_held;
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_list_n = 0;
+    if (threadIdx.x == 0) s_held = 0;
+    const int T = args.T;
+    if (threadIdx.x < 32) {
+        s_base[threadIdx.x] = args.sau.row_base[threadIdx.x];
+        s_rows[threadIdx.x] = (int)threadIdx.x < T ? args.backing_rows[threadIdx.x] : 0;
+        s_table[threadIdx.x] = args.backing[threadIdx.x];
+    }
+    __syncthreads();
+    const SaGeom &g = args.sa;
+    const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
+    const long long req_stride = (long long)gridDim.x * 8;
+    for (long long req = (long long)blockIdx.x * 8 + (threadIdx.x >> 6) * 2 + half; req - half - (threadIdx.x >> 6) * 2 < args.B;
+         req += req_stride) {
+        const bool req_on = req < args.B;
+        const bool key_on = req_on && hl < T;
+        const int row = key_on ? args.requests[req * T + hl] : -1;
+        const bool ok = key_on && row >= 0 && row < s_rows[hl];
+        PolKey key;
+        const bool is_hit = policy_probe_key<false>(g, args.sau, args.lay, args.cur, ok, s_base[hl] + (ok ? (unsigned)row : 0u), key);
+        const unsigned long long hm = __ballot(is_hit);
+        const int agg = __popc((unsigned)(half ? (hm >> 32) : hm));
+        if (key_on) {
+            const long long at = req * T + hl;
+            args.hit[at] = is_hit ? 1 : 0;
+            const unsigned char *src = nullptr;
+            if (is_hit) src = args.arena + (long long)sa_entry(g, key.set, (unsigned)key.way, key.w) * args.row_bytes;
+            else if (ok) src = s_table[hl] + (long long)row * args.row_bytes;   // (a fed table: NULL-based, rewritten by sa_repoint_fed_kernel)
+            args.row_ptrs[at] = (long long)src;
+        }
+        if (is_hit) {   // the hold
+            unsigned *word = reinterpret_cast<unsigned *>(fh.mine) + (key.set >> 2);
+            const unsigned bit = 1u << ((key.set & 3u) * 8u + (unsigned)key.way);
+            if (!(__atomic_load_n(word, __ATOMIC_RELAXED) & bit) && !(atomicOr(word, bit) & bit)) atomicAdd(&s_held, 1);
+        }
+        {   // the half-wave's misses, packed, behind the block's earlier ones
+            const bool is_miss = ok && key.way < 0;
+            const unsigned long long mm = __ballot(is_miss);
+            const unsigned mh = (unsigned)(half ? (mm >> 32) : mm);
+            int base = 0;
+            if (hl == 0 && mh) base = atomicAdd(&s_list_n, __popc(mh));
+            base = __shfl(base, half * 32, 64);
+            if (is_miss) {
+                const int at = base + __popc(mh & ((1u << hl) - 1u));
+                if (at < args.list_cap)
+                    args.miss_rec[(long long)blockIdx.x * args.list_cap + at] =
+                        make_uint4((unsigned)row, (unsigned)hl | (EVLFU ? (unsigned)agg << 8 : 0u), key.set, key.tag1);
+            }
+        }
+        if (req_on && hl == 0) { atomicAdd(&s_sum[0], agg); if (agg == T) atomicAdd(&s_sum[1], 1); }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_sum[threadIdx.x])
+        atomicAdd(&args.part1[(blockIdx.x % kPolReplicas) * kPolPartCols + 38 + threadIdx.x], s_sum[threadIdx.x]);
+    if (threadIdx.x == 0) args.list_cnt[blockIdx.x] = s_list_n < args.list_cap ? s_list_n : args.list_cap;
+    if (threadIdx.x == 0 && s_held) atomicAdd(&fh.counters[0], (unsigned long long)s_held);
+}
+
 // ... and, first launch of the finish, what that probe left undone: every position the begin flagged 1 finds its way again (the tier
 // has not moved: everything else is refused while the call is open) and is touched (LRU / LFU: policy_probe_key's plain store) or
 // raised to its request's agg_hit = the number of its flags that are 1 (EvLFU: sa_raise, the histogram moves into part1 columns
@@ -1541,15 +1612,21 @@ template <> struct Native<NoTail> { using type = int; };
 // then the CAS, then the row stores nobody waits for.  PIECES x U (+ TAIL) = row_bytes; PIECES = 0: any row size, copied
 // after the claim.
 // FED: fsrc, when not NULL, is the key's row in the caller's fed block and is read instead of the table row.
-template <int PIECES, typename U, typename TAIL, bool FED = false>
+// HOLD (evs_cache_policy.h at FedHold): the ways the other open calls hold are no candidates, and a copy of the key that another
+// call installed (its stamp is not this batch's) is counted.
+template <int PIECES, typename U, typename TAIL, bool FED = false, bool HOLD = false>
 __device__ __forceinline__ void policy_insert_one(const PolicyArgs &args, const unsigned char *table, unsigned row, unsigned set, unsigned tag1,
-                                                  int *s_stat, const unsigned char *fsrc = nullptr) {
+                                                  int *s_stat, const unsigned char *fsrc = nullptr, const FedHold *fh = nullptr) {
     const SaGeom &g = args.sa;
     const PolLayout &L = args.lay;
     const unsigned cur = args.cur;
     unsigned *tags = sa_ways_ptr(g, set);
     SaLine line;
     sa_load<8>(g, set, line);
+    unsigned held = 0u;
+    if constexpr (HOLD) {
+        for (int k = 0; k < fh->n_others; k++) held |= fh->others[k][set];
+    }
     __builtin_amdgcn_sched_barrier(0);
     const unsigned char *srow = (FED && fsrc) ? fsrc : table + (long long)row * args.row_bytes;
     using NU = typename Native<U>::type;
@@ -1580,17 +1657,23 @@ __device__ __forceinline__ void policy_insert_one(const PolicyArgs &args, const 
         // LRU the largest circular age, LFU the lowest counter and then the largest age; equal keys: the lowest index
         int best = -1;
         bool dup = false;
-        unsigned bk = 0u, bw = 0u;
+        unsigned bk = 0u, bw = 0u, dw = 0u;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            dup = dup || (w[j] & L.tag_mask) == tag1;
+            const bool is_dup = (w[j] & L.tag_mask) == tag1;
+            dup = dup || is_dup;
+            if constexpr (HOLD) dw = is_dup ? w[j] : dw;
             const unsigned age = (cur - pol_last(L, w[j])) & smask;
             const unsigned score = L.lfu ? (((kPolCntMax - pol_cnt(w[j])) << sbits) | age) : age;   // (< 2^31: 6 + S <= 31 bits under LFU)
-            const unsigned k = w[j] == 0u ? 0xffffffffu : (age != 0u ? score : 0u);                 // 0: not eligible (eligible ways have age >= 1)
+            const bool on = age != 0u && !(HOLD && ((held >> j) & 1u));                             // (a free way is never held)
+            const unsigned k = w[j] == 0u ? 0xffffffffu : (on ? score : 0u);                        // 0: not eligible (eligible ways have age >= 1)
             const bool cand = k > bk;
             best = cand ? j : best; bk = cand ? k : bk; bw = cand ? w[j] : bw;
         }
-        if (dup || best < 0) return;   // another copy of the key got there first / every way belongs to this batch: turned away
+        if constexpr (HOLD) {
+            if (dup && pol_last(L, dw) != cur) atomicAdd(&fh->counters[1], 1ull);
+        }
+        if (dup || best < 0) return;   // another copy of the key got there first / every way belongs to this batch (or is held): turned away
         const unsigned prev = atomicCAS(&tags[best], bw, pol_word(L, tag1, cur, 1u, pol_sel(L, bw) ^ 1u));
         if (prev == bw) { way = best; old_word = bw; break; }
 #pragma unroll
@@ -1660,9 +1743,40 @@ __global__ void __launch_bounds__(256) policy_insert_fed_kernel(const PolicyArgs
     }
 }
 
+// ... while other calls are open on the cache: their held ways are left alone (evs_cache_policy.h at FedHold).  policy_insert_fed_kernel
+// line for line but for the HOLD flag and fh -- a change to either is a change to both.  (One body under both kernels was tried: it
+// moves the device code of every policy_insert_fed_kernel instantiation, and of fed_probe_kernel likewise, which this unit does
+// not allow a new form to do.)
 template <int PIECES, typename U, typename TAIL = NoTail>
-void insert_launch_t(const PolicyArgs &a, const FedSrc *f, int grid, unsigned threads, hipStream_t st) {
-    if (f) hipLaunchKernelGGL((policy_insert_fed_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a, *f);
+__global__ void __launch_bounds__(256) policy_insert_fed_hold_kernel(const PolicyArgs args, const FedSrc fs, const FedHold fh) {
+    __shared__ int s_stat[2];
+    __shared__ const unsigned char *s_table[32];
+    if (threadIdx.x < 2) s_stat[threadIdx.x] = 0;
+    if (threadIdx.x < 32) s_table[threadIdx.x] = args.backing[threadIdx.x];
+    const uint4 *rec = args.miss_rec + (long long)blockIdx.x * args.list_cap;
+    const int *rec_slot = fs.rec_slot + (long long)blockIdx.x * args.list_cap;
+    const int nw = (int)blockDim.x >> 6;
+    const int i0 = ((int)threadIdx.x & 63) * nw + ((int)threadIdx.x >> 6);
+    const int n = args.list_cnt[blockIdx.x];
+    __syncthreads();
+    for (int i = i0; i < n; i += 64 * nw) {
+        const uint4 r = rec[i];
+        const int slot = rec_slot[i];
+        const unsigned char *fsrc = slot >= 0 ? fs.fed + (long long)fs.slot_index[slot] * fs.stride : nullptr;
+        policy_insert_one<PIECES, U, TAIL, true, true>(args, s_table[r.y & 31u], r.x, r.z, r.w, s_stat, fsrc, &fh);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int *p = args.part2 + (blockIdx.x % kPolReplicas) * kPolPartCols;
+        if (s_stat[0]) { atomicAdd(&p[0], s_stat[0]); atomicAdd(&p[33], s_stat[0]); }
+        if (s_stat[1]) atomicAdd(&p[34], s_stat[1]);
+    }
+}
+
+template <int PIECES, typename U, typename TAIL = NoTail>
+void insert_launch_t(const PolicyArgs &a, const FedSrc *f, const FedHold *h, int grid, unsigned threads, hipStream_t st) {
+    if (f && h) hipLaunchKernelGGL((policy_insert_fed_hold_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a, *f, *h);
+    else if (f) hipLaunchKernelGGL((policy_insert_fed_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a, *f);
     else hipLaunchKernelGGL((policy_insert_kernel<PIECES, U, TAIL>), dim3((unsigned)grid), dim3(threads), 0, st, a);
 }
 
@@ -1788,27 +1902,35 @@ bool bags_pool2_launch(const BagPairArgs &a, int codec1, int codec2, hipStream_t
 }
 
 // compiled per row size like the EvLFU update (row_bytes = PIECES pieces of 16 / 8 bytes + a tail); f: the fed form
-static void policy_insert_dispatch(const PolicyArgs &a, const FedSrc *f, int grid, unsigned threads, hipStream_t st) {
+static void policy_insert_dispatch(const PolicyArgs &a, const FedSrc *f, const FedHold *h, int grid, unsigned threads, hipStream_t st) {
     switch (a.row_bytes) {
-    case 144: insert_launch_t<9, float4>(a, f, grid, threads, st); break;     // d = 36 fp32
-    case 256: insert_launch_t<16, float4>(a, f, grid, threads, st); break;    // d = 64 fp32
-    case 128: insert_launch_t<8, float4>(a, f, grid, threads, st); break;     // d = 32 fp32, d = 64 u16
-    case 64: insert_launch_t<4, float4>(a, f, grid, threads, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
-    case 32: insert_launch_t<2, float4>(a, f, grid, threads, st); break;
-    case 16: insert_launch_t<1, float4>(a, f, grid, threads, st); break;
-    case 72: insert_launch_t<4, float4, uint2>(a, f, grid, threads, st); break;            // d = 36 u16: 4 x 16 + 8
-    case 36: insert_launch_t<2, float4, unsigned>(a, f, grid, threads, st); break;         // d = 36 u8: 2 x 16 + 4
-    case 18: insert_launch_t<1, float4, unsigned short>(a, f, grid, threads, st); break;   // d = 36 u4: 16 + 2
-    case 8: insert_launch_t<1, uint2>(a, f, grid, threads, st); break;
-    default: insert_launch_t<0, float4>(a, f, grid, threads, st); break;
+    case 144: insert_launch_t<9, float4>(a, f, h, grid, threads, st); break;     // d = 36 fp32
+    case 256: insert_launch_t<16, float4>(a, f, h, grid, threads, st); break;    // d = 64 fp32
+    case 128: insert_launch_t<8, float4>(a, f, h, grid, threads, st); break;     // d = 32 fp32, d = 64 u16
+    case 64: insert_launch_t<4, float4>(a, f, h, grid, threads, st); break;      // d = 16 fp32, d = 32 u16, d = 64 u8
+    case 32: insert_launch_t<2, float4>(a, f, h, grid, threads, st); break;
+    case 16: insert_launch_t<1, float4>(a, f, h, grid, threads, st); break;
+    case 72: insert_launch_t<4, float4, uint2>(a, f, h, grid, threads, st); break;            // d = 36 u16: 4 x 16 + 8
+    case 36: insert_launch_t<2, float4, unsigned>(a, f, h, grid, threads, st); break;         // d = 36 u8: 2 x 16 + 4
+    case 18: insert_launch_t<1, float4, unsigned short>(a, f, h, grid, threads, st); break;   // d = 36 u4: 16 + 2
+    case 8: insert_launch_t<1, uint2>(a, f, h, grid, threads, st); break;
+    default: insert_launch_t<0, float4>(a, f, h, grid, threads, st); break;
     }
 }
-void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, nullptr, grid, threads, st); }
-void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, &f, grid, threads, st); }
+void policy_insert_launch(const PolicyArgs &a, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, nullptr, nullptr, grid, threads, st); }
+void policy_insert_fed_launch(const PolicyArgs &a, const FedSrc &f, int grid, unsigned threads, hipStream_t st) { policy_insert_dispatch(a, &f, nullptr, grid, threads, st); }
+void policy_insert_fed_hold_launch(const PolicyArgs &a, const FedSrc &f, const FedHold &h, int grid, unsigned threads, hipStream_t st) {
+    policy_insert_dispatch(a, &f, &h, grid, threads, st);
+}
 
 void fed_probe_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st) {
     if (evlfu) hipLaunchKernelGGL(fed_probe_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(fed_probe_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+}
+
+void fed_probe_hold_launch(const PolicyArgs &a, const FedHold &h, bool evlfu, int grid, hipStream_t st) {
+    if (evlfu) hipLaunchKernelGGL(fed_probe_hold_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, a, h);
+    else hipLaunchKernelGGL(fed_probe_hold_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, a, h);
 }
 
 void fed_hits_launch(const PolicyArgs &a, bool evlfu, int grid, hipStream_t st) {

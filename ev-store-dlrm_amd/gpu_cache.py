@@ -4,6 +4,7 @@ Reference policies: cache_algo/EvLFU_C1.py, LRU.py, LFU.py; C++/Cython EvLFU var
 only in three constants (see include/evstore_hip.h).  All state (hash table, priority lists,
 row arena) lives in HBM; this class only owns device buffers and marshals pointers.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -343,32 +344,131 @@ class GpuCache:
         n = int(keys.numel())
         if n == 0:
             return None
+        return self._into_fed_block(self._row_source(keys.cpu().numpy().view(np.uint64)), n)
+
+    def _into_fed_block(self, got, n, which=0):
+        """what the row source answered for n keys, copied into device block `which` of this object (lookup_stream: one per open call)"""
+        import numpy as np
         rb = self.dim * self.codec // 8
-        got = self._row_source(keys.cpu().numpy().view(np.uint64))
         got = got if isinstance(got, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(got))
         if got.dtype != torch.uint8:
             got = got.contiguous().view(torch.uint8)
         if got.numel() != n * rb:
             raise _lib.EvsError(_lib.EVS_EINVAL, "the row source returned %d bytes for %d keys of %d-byte rows" % (got.numel(), n, rb))
-        blk = getattr(self, "_fed_block", None)
+        name = "_fed_block" if which == 0 else "_fed_block%d" % which
+        blk = getattr(self, name, None)
         if blk is None or blk.shape[0] < n:
-            blk = self._fed_block = torch.empty((max(n, 256), rb), dtype=torch.uint8, device=self.device)
+            blk = torch.empty((max(n, 256), rb), dtype=torch.uint8, device=self.device)
+            setattr(self, name, blk)
         blk[:n].copy_(got.reshape(n, rb), non_blocking=False)
         return blk[:n]
 
     def _via_source(self, rows, hit, finish, begin=None):
-        """begin -> the row source -> finish; whatever fails in between leaves no call open.  begin: the bag form's (rows and
-        hit are then unused)"""
+        """begin -> the row source -> finish; whatever fails in between leaves no call open -- at depth > 1 that includes calls
+        the caller opened by hand with lookup_begin before this one: every open call is dropped, newest first.  begin: the bag
+        form's (rows and hit are then unused)"""
         hit, keys = begin() if begin is not None else self.lookup_begin(rows, hit)
         try:
             return hit, finish(self._fetch_fed(keys))
         except BaseException:
-            if self._fed_call is not None:
-                try:
-                    self.lookup_abort()
-                except _lib.EvsError:   # (the library had already spent the call)
-                    self._fed_call = None
+            self._abort_open_calls()
             raise
+
+    def _open_calls(self):
+        """the open calls, oldest first: (rows, hit, B, listed keys, the key buffer) -- kept alive until the call ends"""
+        q = getattr(self, "_fed_call", None)
+        if q is None:
+            q = self._fed_call = collections.deque()
+        return q
+
+    def _abort_open_calls(self):
+        """drops every open call, newest first (a call the library had already spent is only forgotten)"""
+        q = self._open_calls()
+        while q:
+            try:
+                self.lookup_abort()
+            except _lib.EvsError:
+                q.clear()
+
+    def set_fed_depth(self, n):
+        """How many (B, n_tables) calls may be open at once on a fed cache, 1 (the default) .. 4: lookup_begin is accepted while
+        fewer are open, lookup_finish[_interact] end the OLDEST open call, lookup_abort drops the NEWEST (include/evstore_hip.h:
+        evs_cache_set_fed_depth).  Not while a call is open.  lookup_stream is the driver that keeps the calls open."""
+        _lib.check(_lib.lib().evs_cache_set_fed_depth(self._h, int(n)))
+        self._fed_depth = int(n)
+        return self
+
+    def fed_open_calls(self):
+        return int(_lib.lib().evs_cache_fed_open_calls(self._h))
+
+    def fed_ahead_stats(self):
+        """Counters of the calls that overlapped, cumulative: 'ahead_begins' (begins made with another call open), 'hold_bits'
+        (ways such a begin held) and 'found_installed' (miss records whose key an earlier call had installed by the finish:
+        keys fetched twice).  Synchronises."""
+        s = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().evs_cache_fed_ahead_stats(self._h, s, torch.cuda.current_stream(self.device).cuda_stream))
+        return {"ahead_begins": int(s[0]), "hold_bits": int(s[1]), "found_installed": int(s[2])}
+
+    def lookup_stream(self, batches, x=None, itself=False, depth=None):
+        """The pipelined driver of a fed cache with a row source (set_row_source): a generator over `batches` -- items `rows` or
+        `(rows, x)` -- that yields (hit, out) per item, in order: lookup_batch's out for an item without x, lookup_interact's for
+        one with (the argument x: the dense features of every item that carries none).  Up to `depth` calls (default: the
+        depth set_fed_depth gave; another value is set first) are open at a time: each begin hands its keys to a pool of `depth`
+        threads that run the source -- host work only --, the main thread copies each answer into that call's own device block
+        and finishes the calls oldest first; when no call can begin it waits for the oldest fetch.  Whatever fails -- the source,
+        a finish, the consumer closing the generator -- every open call is dropped, newest first, before it propagates (calls
+        the caller had opened by hand before the stream included).  At depth 1 this is a loop over lookup_batch / lookup_interact.
+        An 'evlfu' cache's flush waits for a begin that finds no call open: in steady state the pipe never drains, so a flush
+        request stands until the stream ends -- end the stream now and then (a stream per epoch, say) where the tier fills its
+        top priority."""
+        import numpy as np
+        from concurrent.futures import ThreadPoolExecutor
+        if getattr(self, "_row_source", None) is None or not getattr(self, "_fed", False):
+            raise _lib.EvsError(_lib.EVS_ESTATE, "lookup_stream: a fed cache with a row source (set_fed_backing, set_row_source)")
+        depth = int(getattr(self, "_fed_depth", 1) if depth is None else depth)
+        if depth != getattr(self, "_fed_depth", 1):
+            self.set_fed_depth(depth)
+
+        def split(item):
+            rows, xi = item if isinstance(item, (tuple, list)) else (item, None)
+            return rows, (x if xi is None else xi)
+
+        if depth == 1:
+            for item in batches:
+                rows, xi = split(item)
+                finish = (lambda fed: self.lookup_finish(fed)) if xi is None else (lambda fed: self.lookup_finish_interact(fed, xi, itself))
+                yield self._via_source(rows, None, finish)
+            return
+        pool = ThreadPoolExecutor(max_workers=depth)
+        fetches = collections.deque()          # per open call, oldest first: (the source's future or None, keys listed, hit, x, block)
+        it, more, seq = iter(batches), True, 0
+        try:
+            while True:
+                while more and len(fetches) < depth:
+                    item = next(it, None)
+                    if item is None:
+                        more = False
+                        break
+                    rows, xi = split(item)
+                    hit, keys = self.lookup_begin(rows)
+                    n = int(keys.numel())
+                    fut = pool.submit(self._row_source, keys.cpu().numpy().view(np.uint64)) if n else None
+                    fetches.append((fut, n, hit, xi, seq % depth))
+                    seq += 1
+                if not fetches:
+                    break
+                fut, n, hit, xi, which = fetches.popleft()
+                fed = self._into_fed_block(fut.result(), n, which) if fut is not None else None
+                out = self.lookup_finish(fed) if xi is None else self.lookup_finish_interact(fed, xi, itself)
+                yield hit, out
+        except BaseException:
+            self._abort_open_calls()
+            raise
+        finally:
+            for f in fetches:
+                if f[0] is not None:
+                    f[0].cancel()
+            pool.shutdown(wait=True)
 
     def lookup_begin(self, rows, hit=None):
         """First half of a lookup on a fed cache: the probe.  -> (hit, keys): hit the (B, n_tables) strict snapshot flags, keys
@@ -378,19 +478,28 @@ class GpuCache:
         B = _check_batch(self, rows, None, hit)
         if hit is None:
             hit = torch.empty((B, self.n_tables), dtype=torch.uint8, device=self.device)
-        kb = getattr(self, "_fed_keys", None)
-        if kb is None or kb.numel() < B * self.n_tables:
-            kb = self._fed_keys = torch.empty(B * self.n_tables, dtype=torch.int64, device=self.device)
+        if getattr(self, "_fed_depth", 1) > 1:
+            # every open call keeps a key buffer of its own: the view stays valid until that call ends
+            busy = {id(call[4]) for call in self._open_calls()}
+            bufs = self.__dict__.setdefault("_fed_key_bufs", [])
+            kb = next((b for b in bufs if id(b) not in busy and b.numel() >= B * self.n_tables), None)
+            if kb is None:
+                kb = torch.empty(B * self.n_tables, dtype=torch.int64, device=self.device)
+                bufs[:] = [b for b in bufs if id(b) in busy] + [kb]
+        else:
+            kb = getattr(self, "_fed_keys", None)
+            if kb is None or kb.numel() < B * self.n_tables:
+                kb = self._fed_keys = torch.empty(B * self.n_tables, dtype=torch.int64, device=self.device)
         n = C.c_int64()
         _lib.check(_lib.lib().evs_cache_fed_begin(self._h, B, rows.data_ptr(), hit.data_ptr(), kb.data_ptr(), C.byref(n),
                                                   torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = (rows, hit, B, int(n.value))   # keep alive
+        self._open_calls().append((rows, hit, B, int(n.value), kb))   # keep alive
         return hit, kb[:int(n.value)]
 
     def _fed_args(self, fed):
-        if getattr(self, "_fed_call", None) is None:
+        if not self._open_calls():
             raise _lib.EvsError(_lib.EVS_ESTATE, "lookup_finish: no call is open on this cache (lookup_begin)")
-        _, _, B, n = self._fed_call
+        _, _, B, n = self._open_calls()[0][:4]   # (the oldest open call: the one a finish ends)
         rb = self.dim * self.codec // 8
         if fed is None:
             return B, 0, 0
@@ -410,7 +519,7 @@ class GpuCache:
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * self.n_tables * self.dim):
             raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (B * self.n_tables * self.dim))
         _lib.check(_lib.lib().evs_cache_fed_finish(self._h, ptr, stride, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = None
+        self._open_calls().popleft()
         return out
 
     def lookup_finish_interact(self, fed, x, itself=False, out=None):
@@ -427,13 +536,13 @@ class GpuCache:
         _lib.check(_lib.lib().evs_cache_fed_finish_interact(
             self._h, ptr, stride, x.data_ptr(), int(x.stride(0)) if B > 1 else self.dim, int(bool(itself)), out.data_ptr(),
             torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = None
+        self._open_calls().popleft()
         return out
 
     def lookup_abort(self):
         """Drops the open call: nothing was inserted, the batch is not counted, the same begin lists the same keys."""
         _lib.check(_lib.lib().evs_cache_fed_abort(self._h))
-        self._fed_call = None
+        self._open_calls().pop()
 
     def fed_stats(self):
         """Counters of the fed form, cumulative: 'calls' (finished), 'keys' (listed), 'missed' (missed positions of fed
@@ -574,7 +683,7 @@ class GpuCache:
         n = C.c_int64()
         _lib.check(_lib.lib().evs_cache_fed_begin_bags(self._h, B, idx_c, off_c, nnz_c, flat.data_ptr(), kb.data_ptr(), C.byref(n),
                                                        torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = ((keep, hits, "bags"), flat, B, int(n.value))   # keep alive
+        self._open_calls().append(((keep, hits, "bags"), flat, B, int(n.value), kb))   # keep alive
         return hits, kb[:int(n.value)]
 
     def lookup_bags_finish(self, fed, out=None):
@@ -588,7 +697,7 @@ class GpuCache:
             raise ValueError("out must be a contiguous (%d, %d, %d) fp32 device tensor" % (T, B, d))
         _lib.check(_lib.lib().evs_cache_fed_finish_bags(self._h, ptr, stride, out.data_ptr(), B * d, d,
                                                         torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = None
+        self._open_calls().popleft()
         return list(out.unbind(0))
 
     def lookup_bags_finish_interact(self, fed, x, itself=False, out=None):
@@ -605,7 +714,7 @@ class GpuCache:
         _lib.check(_lib.lib().evs_cache_fed_finish_bags_interact(
             self._h, ptr, stride, x.data_ptr(), int(x.stride(0)) if B > 1 else self.dim, int(bool(itself)), out.data_ptr(),
             torch.cuda.current_stream(self.device).cuda_stream))
-        self._fed_call = None
+        self._open_calls().popleft()
         return out
 
     def lookup_bags(self, lS_o, lS_i, out=None):

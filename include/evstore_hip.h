@@ -930,7 +930,43 @@ EVS_API int evs_cache_fetch_stats(evs_cache *c, int64_t *out4, void *stream);
  * any other batched call, stats, dump, export, load, row update or change of backing while a call is open.  evs_cache_destroy
  * with an open call is fine.  Argument errors are EVS_EINVAL and leave an open call open: NULL arguments, B < 1, fed == NULL with
  * a non-empty list, a misaligned fed or stride, a stride below the row size.  A consumer that refuses behind the update ends the
- * call as it ends evs_cache_lookup_batch: the batch is not counted. */
+ * call as it ends evs_cache_lookup_batch: the batch is not counted.
+ *
+ * SEVERAL CALLS OPEN AT ONCE.  A store with latency L behind the begin / finish pair costs L + G per batch (G: the GPU time of a
+ * begin and a finish) while one call may be open; with D calls open and their fetches in flight together it approaches
+ * max(G, (L + G) / D).  The tier alone takes that in its (B, T) form, under all three policies and all four codecs.
+ * evs_cache_set_fed_depth(c, depth): depth 1 .. 4 calls open at a time, 1 the default.  EVS_EINVAL for a NULL cache or a depth
+ *   outside 1 .. 4, EVS_ESTATE while a call is open; allowed at any other time.  It allocates nothing: the scratch of a call slot is
+ *   grown by the begin that takes it.  At depth 1 every entry point behaves as written above, the EVS_ESTATE of a second begin and
+ *   its wording included.
+ * evs_cache_fed_open_calls(c): the number of open calls, 0 .. depth; -1 for a NULL cache.
+ * evs_cache_fed_begin with fewer than `depth` calls open is accepted.  It probes the tier AS IT STANDS: every finished call is
+ *   applied, no open call's touch, raise or insert is.  Its flags are strict snapshot flags of that state, its list is the list
+ *   written above, its ordinal and stamp are the next ones, and every way it hit is HELD until the call ends: no other call's
+ *   update takes a held way (an update that finds no other way in the set turns its key away -- "left in place", served from that
+ *   call's fed block).  A hold is WRITTEN only by a begin made while another call is open: a call that begins alone is the oldest
+ *   call until it ends, no other call's update runs in front of its finish, so nothing could take its ways and it sets no bit
+ *   (evs_cache_fed_ahead_stats counts no hold bit for it).  With `depth` calls open already: EVS_ESTATE, naming the depth.  Only (B, T) calls overlap:
+ *   evs_cache_fed_begin_bags and evs_cache_pair_fed_begin while any call is open, and any begin while a bag call or a pair call is
+ *   open, are EVS_ESTATE as ever.
+ * evs_cache_fed_finish / _fed_finish_interact end the OLDEST open call: the steps written above -- fold, touch / raise of the ways
+ *   its begin hit, update, re-point, consumers, close -- on that call's own stamp, records and pointer table; fed holds the rows of
+ *   THAT call's list.  Two things differ, and only while another call is open: the ways the other open calls hold are no
+ *   victims, and a pending EvLFU flush is not run by a begin (the request stands; the next begin that finds no call open runs
+ *   it, as evs_cache_batch_stats does).  A key two open calls both missed is in both lists; the older call installs it, the newer
+ *   call's record finds it resident ("another copy got there first": EvLFU folds the priority, LRU / LFU leave the way as it is)
+ *   and its positions are served the arena row.
+ * evs_cache_fed_abort drops the NEWEST open call, as written above: nothing is launched, its ordinal and stamp are given back, its
+ *   holds lapse.  To drop an older call, abort down to it.
+ * THE ROW RULE, restated: a served row of a fed table is, byte for byte, a row the caller fed for that key in this call or in a
+ *   call that was open together with it.  A caller whose store changes under open calls gets either version.
+ * EQUIVALENCE: a call that is alone between its begin and its finish runs exactly as at depth 1, whatever depth is set.
+ * ORDERING: all calls of a cache go on one stream, or are ordered by the caller, as for every other call on a cache.
+ * REFUSALS: everything refused while one call is open stays refused while any is: evs_cache_batch_stats, the dump, export and
+ *   load, row updates, a change of backing, every other batched call.
+ * evs_cache_fed_ahead_stats(c, out4, stream): cumulative [begins made with another call open, hold bits set, miss records whose key
+ *   an earlier call had installed by the time of the finish -- keys fetched twice, the price of the stale snapshot --, 0].
+ *   Synchronises the stream; refuses as evs_cache_fed_stats does. */
 EVS_API int evs_cache_set_fed_backing(evs_cache *c, const void *const *tables, const int64_t *n_rows);
 EVS_API int evs_cache_fed_begin(evs_cache *c, int64_t B, const int32_t *rows, uint8_t *hit, uint64_t *keys, int64_t *n_keys_host, void *stream);
 EVS_API int evs_cache_fed_finish(evs_cache *c, const void *fed, int64_t fed_stride_bytes, float *out, void *stream);
@@ -938,6 +974,9 @@ EVS_API int evs_cache_fed_finish_interact(evs_cache *c, const void *fed, int64_t
                                           float *R, void *stream);
 EVS_API int evs_cache_fed_abort(evs_cache *c);
 EVS_API int evs_cache_fed_stats(evs_cache *c, int64_t *out4, void *stream);
+EVS_API int evs_cache_set_fed_depth(evs_cache *c, int depth);
+EVS_API int evs_cache_fed_open_calls(evs_cache *c);
+EVS_API int evs_cache_fed_ahead_stats(evs_cache *c, int64_t *out4, void *stream);
 /* RAGGED BAGS OVER FED BACKING: the begin / finish form of evs_cache_lookup_bags / _lookup_bags_interact on a fed cache -- the
  * count-first fetch-first bag chain cut in two where the bus fetch sits.  evs_cache_fed_abort and evs_cache_fed_stats serve
  * both forms.

@@ -273,8 +273,140 @@ def main_pair(args):
                       "begin_plus_finish_over_a": doc["begin_plus_finish_over_a"], "out": path}))
 
 
+AHEAD_DEPTHS, AHEAD_LATENCIES_US = (1, 2, 4), (0, 200, 1000)
+
+
+def main_ahead(args):
+    """--ahead D: case d (fed, a host source) through GpuCache.lookup_stream with up to D calls open -> profiles/fed_ahead.json.
+    The source is the numpy gather of case d plus a sleep of L microseconds -- the store's latency --, run by lookup_stream's worker
+    threads; the main thread copies each answer to the device and finishes the calls oldest first.  Per depth in {1, 2, 4} (and D)
+    one cache is warmed through the stream at L = 0; then, per L in {0, 200, 1000} (and --source-latency-us), --steps batches are
+    timed as ONE stream between two synchronises: per_call_us = wall / batches.  Depth 1 at the largest L is timed three times: the
+    spread the gain is held against.  begin_us / finish_us at depth 1 and 2 (L = 0) come from a hand-driven loop -- begin k + 1,
+    finish k -- whose finish ends on a synchronise (the begin synchronises by itself): the cost of the hold stores and hold loads.
+    Per depth the hit rate and the three fed_ahead_stats words per call, over the timed batches of all latencies together.  Only case d
+    runs here: a device source is GPU work, which the driver's worker threads do not do.  The depth-1 comparison with the parent
+    commit is NOT made by this tool: --baseline takes the case-c wall_us of three plain runs of this tool on each commit (same box,
+    same session, alternating) from a file and records them beside the parent's spread."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    d, B = args.dim, args.batch
+    ln, ev, pinned, scale = pinned_tables(bench.KAGGLE_LN, d, args.scale, dev)
+    T = len(ln)
+    cap = int(args.frac * sum(ln))
+    base_np = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int64)
+    all_host = np.concatenate([p.numpy() for p in pinned])
+    del ev
+    depths = sorted(set(AHEAD_DEPTHS) | {args.ahead})
+    lats = sorted(set(AHEAD_LATENCIES_US) | {args.source_latency_us})
+    n_warm = args.max_warm
+    n_b = n_warm + args.steps
+    rows = [b[1].t().contiguous().to(torch.int32) for b in bench.make_batches(ln, B, n_b, seed=3, device=dev, dist="zipf", alpha=args.alpha)]
+    x = torch.rand((B, d), device=dev)
+    timed = rows[n_warm:]
+
+    def source(lat_us):
+        def fn(keys):                                       # keys: uint64 numpy, on a worker thread: host work only
+            k = keys.astype(np.int64)
+            got = all_host[base_np[(k >> 32) - 1] + (k & 0xffffffff)]
+            if lat_us:
+                time.sleep(lat_us * 1e-6)
+            return got
+        return fn
+
+    def stream_us(c, depth, lat_us):
+        c.set_row_source(source(lat_us))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in c.lookup_stream(((r, x) for r in timed), depth=depth):
+            pass
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / len(timed)
+
+    def halves_us(c, depth):
+        """begin and finish of a hand-driven loop at `depth` (1 or 2), L = 0: medians over the timed batches"""
+        fn = source(0)
+        tb, tf, open_calls = [], [], []
+
+        def begin(r):
+            t0 = time.perf_counter()
+            _, keys = c.lookup_begin(r)                     # (synchronises)
+            tb.append(time.perf_counter() - t0)
+            open_calls.append(torch.from_numpy(fn(keys.cpu().numpy().view(np.uint64))).to(dev) if keys.numel() else None)
+
+        def finish():
+            fed = open_calls.pop(0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c.lookup_finish_interact(fed, x)
+            torch.cuda.synchronize()
+            tf.append(time.perf_counter() - t0)
+
+        for r in timed:
+            begin(r)
+            if len(open_calls) == depth:
+                finish()
+        while open_calls:
+            finish()
+        return round(float(np.median(tb)) * 1e6, 2), round(float(np.median(tf)) * 1e6, 2)
+
+    res = {}
+    for depth in depths:
+        c = E.GpuCache("evlfu", cap, T, d, 32, "python", dev).set_miss_order("fetch-first")
+        c.set_fed_backing([None] * T, ln).set_fed_depth(depth)
+        c.set_row_source(source(0))
+        for _ in c.lookup_stream(((r, x) for r in rows[:n_warm]), depth=depth):
+            pass
+        print("fed_backing_bench: depth %d warm, size %d of %d" % (depth, c.batch_stats()["size"], cap), file=sys.stderr, flush=True)
+        s0, a0 = c.batch_stats(), c.fed_ahead_stats()
+        per = {str(lat): round(stream_us(c, depth, lat), 2) for lat in lats}
+        s1, a1 = c.batch_stats(), c.fed_ahead_stats()
+        n_calls = len(lats) * len(timed)
+        res[str(depth)] = {"per_call_us": per, "hit_rate": round((s1["n_hits"] - s0["n_hits"]) / (T * B * n_calls), 4),
+                           "fed_ahead_stats_per_call": {k: round((a1[k] - a0[k]) / n_calls, 2) for k in a1}, "flushes": s1["n_flush"] - s0["n_flush"]}
+        if depth == 1:
+            res["1"]["repeats_at_%d_us" % lats[-1]] = [per[str(lats[-1])]] + [round(stream_us(c, 1, lats[-1]), 2) for _ in range(2)]
+        if depth in (1, 2):
+            res[str(depth)]["begin_us"], res[str(depth)]["finish_us"] = halves_us(c, depth)
+        print("fed_backing_bench: depth %d %s" % (depth, res[str(depth)]), file=sys.stderr, flush=True)
+        del c
+    rep = res["1"]["repeats_at_%d_us" % lats[-1]]
+    G = res["1"]["begin_us"] + res["1"]["finish_us"]
+    L = float(lats[-1])
+    doc = {"tool": "fed_backing_bench --ahead", "device": torch.cuda.get_device_name(0),
+           "shape": {"rows": sum(ln), "table_scale": scale, "capacity": cap, "frac": args.frac, "batch": B, "dim": d, "zipf_alpha": args.alpha,
+                     "warm_batches": n_warm, "timed_batches": len(timed), "policy": "evlfu", "consumer": "lookup_finish_interact",
+                     "source": "numpy gather from host tables + sleep(L), on lookup_stream's worker threads"},
+           "timing": "per_call_us: one lookup_stream over the timed batches between two synchronises, wall / batches; begin_us / finish_us: medians of "
+                     "a hand-driven loop (begin k + 1, finish k) at L = 0, the finish between two synchronises; one run on one box",
+           "depths": res,
+           "depth_1_spread_us": round(max(rep) - min(rep), 2),
+           "gain_at_%d_us" % lats[-1]: {str(D): round(res[str(D)]["per_call_us"][str(lats[-1])] / res["1"]["per_call_us"][str(lats[-1])], 3) for D in depths if D > 1},
+           "model_at_%d_us" % lats[-1]: {str(D): round(max(G, (L + G) / D) / (L + G), 3) for D in depths if D > 1},
+           "G_us": round(G, 2),
+           "hold_cost_us": {"begin": round(res["2"]["begin_us"] - res["1"]["begin_us"], 2), "finish": round(res["2"]["finish_us"] - res["1"]["finish_us"], 2)}}
+    if args.baseline:   # case c of this tool on the parent commit and on this one, three runs each in one session (wall_us per call)
+        with open(args.baseline) as f:
+            base = json.load(f)
+        par, new = base["parent_c_wall_us"], base["this_c_wall_us"]
+        spread = round(max(par) - min(par), 2)
+        doc["depth_1_regression"] = {"case": "c_fed_device_source, wall_us per call, runs alternating in one session on one box",
+                                     "parent_c_wall_us": par, "this_c_wall_us": new, "parent_spread_us": spread,
+                                     "bound_us": round(max(par) + spread, 2), "within_bound": bool(max(new) <= max(par) + spread)}
+    path = args.out or os.path.join(ROOT, "profiles", "fed_ahead.json")
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"tool": doc["tool"], "per_call_us": {D: res[D]["per_call_us"] for D in res}, "depth_1_spread_us": doc["depth_1_spread_us"],
+                      "hold_cost_us": doc["hold_cost_us"], "out": path}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ahead", type=int, default=0, help="case d through lookup_stream with up to this many calls open (1 .. 4) -> profiles/fed_ahead.json")
+    ap.add_argument("--source-latency-us", type=int, default=0, help="--ahead: a store latency measured beside 0, 200 and 1000 us")
+    ap.add_argument("--baseline", default="", help="--ahead: a JSON file {parent_c_wall_us: [..], this_c_wall_us: [..]} of case c timed on the parent commit "
+                                                   "and on this one, recorded into the output beside the parent's spread")
     ap.add_argument("--frac", type=float, default=0.10)
     ap.add_argument("--batch", type=int, default=16384)
     ap.add_argument("--alpha", type=float, default=0.75)
@@ -286,8 +418,11 @@ def main():
     ap.add_argument("--max-bag", type=int, default=10, help="--bags: bags of 1 .. this many indices")
     ap.add_argument("--pair", action="store_true", help="the fed C1 + C2 pair beside the fetch-first pair -> profiles/fed_pair_bench.json")
     ap.add_argument("--fill", type=int, default=180, help="--pair: batches that fill the tiers")
-    ap.add_argument("--out", default="", help="default: profiles/fed_backing.json (--bags: profiles/fed_bags.json, --pair: profiles/fed_pair_bench.json)")
+    ap.add_argument("--out", default="", help="default: profiles/fed_backing.json (--bags: profiles/fed_bags.json, --pair: profiles/fed_pair_bench.json, "
+                                              "--ahead: profiles/fed_ahead.json)")
     args = ap.parse_args()
+    if args.ahead:
+        return main_ahead(args)
     if args.bags:
         return main_bags(args)
     if args.pair:
