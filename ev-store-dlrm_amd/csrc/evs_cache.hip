@@ -7637,6 +7637,14 @@ static int cache_rows_impl(evs_cache *c, int64_t n, const int32_t *keys, const f
     // behind that event and re-records it, so the server start keeps waiting for both
     if (c->exact_pending && c->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->exact_done, 0));
     if (c->tsrv && c->tsrv->exact_pending && c->tsrv->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->tsrv->exact_done, 0));
+    if (refresh && c->ft) {
+        // a registered table is a pinned copy of its file: the rows the caller wrote reach it here, in stream order
+        // (the work ahead on the stream may still read the old rows, so the host waits for it before it copies)
+        std::vector<int32_t> hk((size_t)n * 2);
+        EVS_HIP_CHECK(hipMemcpyAsync(hk.data(), keys, hk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        EVS_HIP_CHECK(hipStreamSynchronize(st));
+        filetier_reload_rows(c->ft, n, hk.data());
+    }
     if (n_resident) EVS_HIP_CHECK(hipMemsetAsync(n_resident, 0, sizeof(int64_t), st));
     if (refresh) launch_row_refresh(a, st);
     else launch_row_update(c->host.codec, a, st);

@@ -223,5 +223,6 @@ int filetier_tables(const evs_filetier *ft);
 long long filetier_row_bytes(const evs_filetier *ft);
 long long filetier_rows(const evs_filetier *ft, int k);
 const void *filetier_dev(const evs_filetier *ft, int k);
+void filetier_reload_rows(evs_filetier *ft, int64_t n, const int32_t *keys_host);
 
 }  // namespace evs

@@ -1,9 +1,12 @@
 // File-backed miss tier: the reference's mmap miss path (emb_storage/mmap_file_read.py:32-40: ev-table-N.bin mapped
 // read-only, row r at byte row_bytes * r; C++ reader pool mixed_precs_caching/evlfu_8.cpp:191-250) for the GPU cache.
 //
-// Every table file is mmap'ed (PROT_READ, MAP_SHARED).  Tables are then REGISTERED with the GPU (hipHostRegister,
-// mapped: the kernels read their rows over the bus, zero-copy, exactly like the PINNED tier) smallest first while the
-// running total fits `pinned_budget_bytes` -- registering pins the pages in RAM.  Tables that do not fit stay plain
+// Every table file is mmap'ed (PROT_READ, MAP_SHARED).  Tables are then REGISTERED with the GPU smallest first while the
+// running total fits `pinned_budget_bytes`: the table is loaded into pinned, device-mapped host memory (hipHostMalloc)
+// and the kernels read its rows from there over the bus, zero-copy, exactly like the PINNED tier.  (Pinning the file
+// mapping itself in place, hipHostRegister, is not available on every machine -- a virtual machine's GPU refuses
+// it --, so the registered table is a pinned COPY: rows of the file written later reach it through
+// evs::filetier_reload_rows, which evs_cache_refresh_rows calls.)  Tables that do not fit stay plain
 // mappings backed by the page cache / the disk: their missing rows are STAGED -- the batched lookup hands the host the
 // de-duplicated list of new keys, a pool of reader threads copies those rows out of the mappings into a pinned staging
 // buffer, and the fill kernel takes them from there (evs_cache.hip: cache_batch_impl, file mode).
@@ -98,7 +101,8 @@ struct evs_filetier {
     std::vector<int> fd;
     std::vector<void *> map;            // host mapping
     std::vector<long long> bytes, rows;
-    std::vector<void *> dev;            // device-visible address of a registered table, else nullptr
+    std::vector<void *> pin;            // a registered table's pinned copy (hipHostMalloc), else nullptr
+    std::vector<void *> dev;            // ... and its device-visible address
     std::vector<char> registered;
     long long pinned_bytes = 0;
     int n_threads = 8;
@@ -136,7 +140,7 @@ extern "C" int evs_filetier_close(evs_filetier *ft) {
     delete ft->pool;
     ft->pool = nullptr;
     for (int k = 0; k < ft->n_tables; k++) {
-        if (ft->registered[k] && ft->map[k]) (void)hipHostUnregister(ft->map[k]);
+        if (ft->pin[k]) (void)hipHostFree(ft->pin[k]);
         if (ft->map[k] && ft->bytes[k] > 0) munmap(ft->map[k], (size_t)ft->bytes[k]);
         if (ft->fd[k] >= 0) close(ft->fd[k]);
     }
@@ -151,7 +155,8 @@ extern "C" int evs_filetier_open(evs_filetier **out, int n_tables, const char *c
     evs_filetier *ft = new evs_filetier();
     ft->n_tables = n_tables; ft->row_bytes = row_bytes;
     ft->fd.assign(n_tables, -1); ft->map.assign(n_tables, nullptr); ft->bytes.assign(n_tables, 0);
-    ft->rows.assign(n_tables, 0); ft->dev.assign(n_tables, nullptr); ft->registered.assign(n_tables, 0);
+    ft->rows.assign(n_tables, 0); ft->pin.assign(n_tables, nullptr); ft->dev.assign(n_tables, nullptr);
+    ft->registered.assign(n_tables, 0);
     for (int k = 0; k < n_tables; k++) {
         const int fd = open(paths[k], O_RDONLY);
         if (fd < 0) { set_error("evs_filetier_open: cannot open %s", paths[k]); evs_filetier_close(ft); return EVS_EIO; }
@@ -176,10 +181,12 @@ extern "C" int evs_filetier_open(evs_filetier **out, int n_tables, const char *c
     std::sort(order.begin(), order.end(), [&](int a, int b) { return ft->bytes[a] != ft->bytes[b] ? ft->bytes[a] < ft->bytes[b] : a < b; });
     for (int k : order) {
         if (ft->bytes[k] == 0 || ft->pinned_bytes + ft->bytes[k] > pinned_budget_bytes) continue;
-        if (hipHostRegister(ft->map[k], (size_t)ft->bytes[k], hipHostRegisterMapped) != hipSuccess) { (void)hipGetLastError(); continue; }
+        void *h = nullptr;
+        if (hipHostMalloc(&h, (size_t)ft->bytes[k], hipHostMallocMapped) != hipSuccess || !h) { (void)hipGetLastError(); continue; }
         void *d = nullptr;
-        if (hipHostGetDevicePointer(&d, ft->map[k], 0) != hipSuccess || !d) { (void)hipGetLastError(); (void)hipHostUnregister(ft->map[k]); continue; }
-        ft->dev[k] = d; ft->registered[k] = 1; ft->pinned_bytes += ft->bytes[k];
+        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) { (void)hipGetLastError(); (void)hipHostFree(h); continue; }
+        memcpy(h, ft->map[k], (size_t)ft->bytes[k]);
+        ft->pin[k] = h; ft->dev[k] = d; ft->registered[k] = 1; ft->pinned_bytes += ft->bytes[k];
     }
     const unsigned hc = std::thread::hardware_concurrency();
     // readers incl. the calling thread (EVS_FILETIER_THREADS overrides).  Measured on the Kaggle workload, every table staged
@@ -236,4 +243,15 @@ int filetier_tables(const evs_filetier *ft) { return ft->n_tables; }
 long long filetier_row_bytes(const evs_filetier *ft) { return ft->row_bytes; }
 long long filetier_rows(const evs_filetier *ft, int k) { return ft->rows[k]; }
 const void *filetier_dev(const evs_filetier *ft, int k) { return ft->dev[k]; }
+// keys (n, 2) int32 HOST memory, (table index 0-based, row): the rows of registered tables are copied again from the
+// file mappings into the pinned copies the kernels read (the caller wrote the files); other keys are left alone
+void filetier_reload_rows(evs_filetier *ft, int64_t n, const int32_t *keys) {
+    const long long rb = ft->row_bytes;
+    for (int64_t i = 0; i < n; i++) {
+        const int t = keys[2 * i];
+        const long long r = keys[2 * i + 1];
+        if (t < 0 || t >= ft->n_tables || !ft->pin[t] || r < 0 || r >= ft->rows[t]) continue;
+        memcpy(static_cast<char *>(ft->pin[t]) + r * rb, static_cast<const char *>(ft->map[t]) + r * rb, (size_t)rb);
+    }
+}
 }  // namespace evs

@@ -1218,8 +1218,9 @@ EVS_API int evs_cache_pair_load_plan(int64_t cap1, int64_t cap2, int n_tables, c
                                      int64_t *out8);
 /* File-backed miss tier: the reference's mmap miss path (emb_storage/mmap_file_read.py:32-40,
  * reader pool mixed_precs_caching/evlfu_8.cpp:191-250) under the GPU cache.  evs_filetier_open maps every
- * ev-table-N.bin read-only (row r at byte row_bytes * r) and REGISTERS tables with the GPU (hipHostRegister, mapped:
- * kernels read them over the bus, zero-copy) smallest first while their total fits pinned_budget_bytes; the others stay
+ * ev-table-N.bin read-only (row r at byte row_bytes * r) and REGISTERS tables with the GPU (loaded into pinned, mapped
+ * host memory, hipHostMalloc: kernels read them over the bus, zero-copy; rows of the file written afterwards reach the
+ * pinned copy with evs_cache_refresh_rows) smallest first while their total fits pinned_budget_bytes; the others stay
  * plain mappings ("staged"): the batched lookup lists the batch's de-duplicated new keys, a pool of host threads copies
  * those rows out of the mappings into a pinned staging buffer and the fill kernel takes them from there -- every missing
  * row is read from the file once per batch.  evs_cache_set_file_backing replaces evs_cache_set_backing; with staged

@@ -622,3 +622,44 @@ def test_refresh_rows_over_pinned_host_tables(E, orc):
     out = out.cpu().numpy()
     for k in range(T):
         assert np.array_equal(out[:, k, :].view(np.uint32), tabs[k].numpy()[rq[:, k]].view(np.uint32))
+
+
+def test_refresh_rows_over_registered_file_tables(E, tmp_path):
+    """rows of a FileTier's registered tables written INTO THE FILES, then refresh_rows: resident keys and misses alike are
+    served the new rows (a cache smaller than the key set: both kinds occur), rows that were not written stay, and the
+    policy state does not move"""
+    rs = np.random.RandomState(11)
+    nr = 96
+    tabs = [rs.uniform(-1, 1, size=(nr, D)).astype(np.float32) for _ in range(T)]
+    paths = []
+    for k, w in enumerate(tabs):
+        p = tmp_path / ("ev-table-%d.bin" % (k + 1))
+        w.tofile(p)
+        paths.append(str(p))
+    ft = E.FileTier(paths, 4 * D, 1 << 30)
+    assert all(ft.registered) and ft.pinned_bytes == T * nr * D * 4
+    c = E.GpuCache("evlfu", 40 * T, T, D, 32)
+    c.set_file_backing(ft)
+    rq = np.stack([rs.permutation(nr) for _ in range(T)], 1).astype(np.int32)   # every row of every table once
+    c.lookup_batch(_dev(rq[:64]))
+    dump0, stats0 = c.batch_dump(), c.batch_stats()
+    resident = {(int(t) - 1, int(rw)) for _, t, rw in dump0}
+    keys = np.array([(k, r) for k in range(T) for r in range(0, nr, 2)], np.int64)     # the even rows, resident or not
+    n_res = sum(1 for k, r in keys if (int(k), int(r)) in resident)
+    assert 0 < n_res < len(keys)
+    torch.cuda.synchronize()
+    for k in range(T):
+        tabs[k][0::2] = _values(rs, nr // 2, D, neg_zero=True)
+        m = np.memmap(paths[k], np.float32, "r+", shape=(nr, D))
+        m[0::2] = tabs[k][0::2]
+        m.flush()
+        del m
+    assert c.refresh_rows(keys, count=True) == n_res
+    assert {tuple(v) for v in c.batch_dump().tolist()} == {tuple(v) for v in dump0.tolist()} and c.batch_stats() == stats0
+    for s in (0, 48):
+        hit, out = c.lookup_batch(_dev(rq[s:s + 48]))
+        out = out.cpu().numpy()
+        for k in range(T):
+            assert np.array_equal(out[:, k, :].view(np.uint32), tabs[k][rq[s:s + 48, k]].view(np.uint32)), (s, k)
+    del c
+    ft.close()
