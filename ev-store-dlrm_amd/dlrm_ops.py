@@ -899,6 +899,40 @@ def apply_emb_interact(x, lS_o, lS_i, emb_l, v_W_l=None, arch_interaction_itself
     return R
 
 
+def apply_emb_interact_bags(x, lS_o, lS_i, emb_l, arch_interaction_itself=False, check_indices=False, out=None):
+    """R = interact_features(x, apply_emb(lS_o, lS_i, emb_l)) for MULTI-HOT bags in ONE kernel (csrc/evs_fused_bags.hip:
+    include/evstore_hip.h, evs_emb_interact_bags): lane groups take lookups, a sample's rows are pooled in LDS in index order
+    (the bits of apply_emb) and go to the matrix cores without the (T, B, d) block in between.  lS_o / lS_i: lists of T int64
+    device tensors (B or B + 1 offsets per table); fp32 tables, unweighted, d in {16, 32, 36, 64}, T <= 27 -- anything else
+    raises the library's error (there is no other path behind this call).  -> R (B, d + P)."""
+    ev = _as_evtables(emb_l)
+    T, d = len(ev), ev.d
+    F = T + 1
+    B = int(x.shape[0])
+    if ev.codec != 32:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "apply_emb_interact_bags: fp32 tables only (codec %d)" % ev.codec)
+    assert x.is_cuda and x.dtype == torch.float32 and x.shape == (B, d) and x.stride(1) == 1
+    assert not torch.is_tensor(lS_i) and not torch.is_tensor(lS_o) and len(lS_i) == T and len(lS_o) == T
+    P = F * (F + 1) // 2 if arch_interaction_itself else F * (F - 1) // 2
+    R = out if out is not None else torch.empty((B, d + P), dtype=torch.float32, device=ev.device)
+    assert R.shape == (B, d + P) and R.is_contiguous() and R.dtype == torch.float32
+    for i, o in zip(lS_i, lS_o):
+        assert i.dtype == torch.int64 and o.dtype == torch.int64 and i.is_cuda and o.is_cuda
+        assert (i.numel() == 0 or i.stride(0) == 1) and (o.numel() == 0 or o.stride(0) == 1)
+    # (an empty index tensor's data_ptr() is NULL: with nnz == 0 the C entry takes that as a table of empty bags)
+    idx_c = (C.c_void_p * T)(*[i.data_ptr() or None for i in lS_i])
+    off_c = (C.c_void_p * T)(*[o.data_ptr() or None for o in lS_o])
+    nnz_c = (C.c_int64 * T)(*[int(i.numel()) for i in lS_i])
+    len_c = (C.c_int64 * T)(*[int(o.numel()) for o in lS_o])
+    stream = _stream_ptr(ev.device)
+    L = _lib.lib()
+    _lib.check(L.evs_emb_interact_bags(B, T, d, ev._tables_c, ev._n_rows_c, x.data_ptr(), int(x.stride(0)) if B > 1 else d,
+                                       idx_c, nnz_c, off_c, len_c, int(bool(arch_interaction_itself)), R.data_ptr(), stream))
+    if check_indices:
+        _lib.check(L.evs_check_index_errors(stream))
+    return R
+
+
 def apply_emb_interact_multi(xs, lS_os, lS_is, emb_l, arch_interaction_itself=False, outs=None, one_index_per_bag=False):
     """K independent batches -- lists of K x (B,d), lS_o (T,B) (or None with one_index_per_bag), lS_i (T,B) -- in ONE call:
     [apply_emb_interact(xs[k], lS_os[k], lS_is[k], emb_l) for k in range(K)], bit for bit, as ONE launch per 8 batches for

@@ -76,6 +76,11 @@ EVS_API int evs_mixed_kernels_seen(char *buf, int n);
  * return value as for evs_env_switches_seen.  A count goes up by one per kernel launch; a refused call and B == 0 launch nothing.
  *   mlp1_d<d>_nt<n>          d = 16 / 32 / 36, nt = the 16-row tiles of the features (1: T + 1 <= 16, 2: T + 1 <= 28) */
 EVS_API int evs_mlp1_kernels_seen(char *buf, int n);
+/* The same record for the fused multi-hot pooling + interaction (evs_emb_interact_bags): eight lines, always listed, in a fixed
+ * order (d = 16, 32, 36, 64; nt = 1 then 2 within each).  A count goes up by one per kernel launch; a refused call and B == 0
+ * launch nothing.
+ *   bagsf_d<d>_nt<n>         d = 16 / 32 / 36 / 64, nt = the 16-row tiles of the features (1: T + 1 <= 16, 2: T + 1 <= 28) */
+EVS_API int evs_bags_fused_kernels_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)
@@ -276,6 +281,23 @@ EVS_API int evs_fused_dim_supported(int d);
 
 EVS_API int evs_emb_interact_dot(int64_t B, int F, int d, int codec, const evs_feature *feats,
                                  int itself, float *R, void *stream);
+
+/* Multi-hot bags pooled and interacted in ONE launch (csrc/evs_fused_bags.hip): R = interact_features(x, apply_emb(lS_o, lS_i))
+ * for fp32 tables with ragged bags, unweighted sum pooling, without the (T, B, d) intermediate of the pooling-then-interaction
+ * pair.  d in {16, 32, 36, 64}, 1 <= T <= 27 (F = T + 1).  tables / n_rows / indices / nnz / offsets / offsets_len are HOST arrays
+ * of T entries; indices[k] (nnz[k] int64) and offsets[k] (offsets_len[k] = B or B + 1 int64: bag b of table k is
+ * [offsets[k][b], offsets[k][b + 1]), the last bag ends at offsets[k][B] where B + 1 entries are given, else at nnz[k]) are device
+ * arrays; x (B, d) with x_stride floats between samples; R (B, d + P) contiguous, P = F (F - 1) / 2, or F (F + 1) / 2 with itself.
+ * Pooled sums are sequential fp32 adds in index order from +0.0f (the bits of evs_embedding_bag_sum).  A bag that is not a valid
+ * [start, end) inside [0, nnz[k]] counts as empty, an index outside [0, n_rows[k]) as a zero row; both raise the sticky flag
+ * evs_check_index_errors reports.  nnz[k] == 0 with indices[k] == NULL is a table of empty bags.  Everything is validated before
+ * the device is touched: a shape without a kernel, a NULL offsets array, a misaligned table or x, sizes >= 2^31 return
+ * EVS_EINVAL and launch nothing; B == 0 succeeds and touches nothing. */
+EVS_API int evs_emb_interact_bags(int64_t B, int T, int d, const void *const *tables, const int64_t *n_rows,
+                                  const float *x, int64_t x_stride, const int64_t *const *indices, const int64_t *nnz,
+                                  const int64_t *const *offsets, const int64_t *offsets_len, int itself, float *R, void *stream);
+/* Rows per stage the kernel of evs_emb_interact_bags walks a sample's lookups in (0: no kernel for this d). */
+EVS_API int evs_bags_fused_stage_rows(int d);
 
 /* Stacked-layout form (Criteo collate: indices and offsets are (T,B) int64 tensors, see
  * evs_embedding_bag_sum_stacked): feature 0 = x (B,d) with row stride x_stride floats,
