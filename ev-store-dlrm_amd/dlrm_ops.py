@@ -649,6 +649,42 @@ def apply_emb(lS_o, lS_i, emb_l, v_W_l=None, out=None, check_indices=False, lazy
     return ly
 
 
+def apply_emb_long(lS_o, lS_i, emb_l, out=None, check_indices=False):
+    """apply_emb for ENCODED tables (codec 16 / 8 / 4) and multi-hot bags through the long-bag kernel of csrc/evs_gather_longq.hip
+    (include/evstore_hip.h, evs_embedding_bag_sum_long): K rows of a bag in flight per lane as raw code words, decoded after
+    they arrive, the bits of apply_emb.  lS_o / lS_i: the (T, B) int64 tensors or the lists of T 1-D int64 tensors apply_emb
+    takes; unweighted, d in {16, 32, 36, 64, 128}.  -> a list of T (B, d) fp32 views of one (T, B, d) buffer, or of `out` = the
+    (B, T + 1, d) interaction tile (slot 0 is left alone).  An explicit call (DESIGN 3.1 has the measured comparison with
+    apply_emb's own route); fp32 tables and whatever else the C entry has no kernel for raise the library's error."""
+    ev = _as_evtables(emb_l)
+    T, d = len(ev), ev.d
+    if ev.codec == 32:
+        raise _lib.EvsError(_lib.EVS_EINVAL, "apply_emb_long: encoded tables only (codec 32)")
+    li = [lS_i[k] for k in range(T)]
+    lo = [lS_o[k] for k in range(T)]
+    for t in li + lo:
+        assert t.dtype == torch.int64 and t.is_cuda and t.dim() == 1 and (t.numel() == 0 or t.stride(0) == 1)
+    B = int(lo[0].shape[0])
+    if out is None:
+        buf = torch.empty((T, B, d), dtype=torch.float32, device=ev.device)
+        out_ptr, tstride, bstride = buf.data_ptr(), B * d, d
+        ly = list(buf.unbind(0))
+    else:  # (B, F, d) tile: table k -> out[:, k+1, :]
+        assert out.shape == (B, T + 1, d) and out.is_contiguous() and out.dtype == torch.float32
+        out_ptr, tstride, bstride = out.data_ptr() + 4 * d, d, (T + 1) * d
+        ly = list(out.unbind(1)[1:])
+    # (an empty index tensor's data_ptr() is NULL: with nnz == 0 the C entry takes that as a table of empty bags)
+    idx_c = (C.c_void_p * T)(*[t.data_ptr() or None for t in li])
+    off_c = (C.c_void_p * T)(*[t.data_ptr() or None for t in lo])
+    nnz_c = (C.c_int64 * T)(*[int(t.numel()) for t in li])
+    stream = _stream_ptr(ev.device)
+    L = _lib.lib()
+    _lib.check(L.evs_embedding_bag_sum_long(T, B, d, ev.codec, ev._tables_c, ev._n_rows_c, idx_c, off_c, nnz_c, out_ptr, tstride, bstride, stream))
+    if check_indices:
+        _lib.check(L.evs_check_index_errors(stream))
+    return ly
+
+
 def interact_features(x, ly, arch_interaction_op="dot", arch_interaction_itself=False):
     """Drop-in for DLRM_Net.interact_features (dlrm_s_pytorch.py:483-516).
 

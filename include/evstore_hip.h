@@ -81,6 +81,12 @@ EVS_API int evs_mlp1_kernels_seen(char *buf, int n);
  * launch nothing.
  *   bagsf_d<d>_nt<n>         d = 16 / 32 / 36 / 64, nt = the 16-row tiles of the features (1: T + 1 <= 16, 2: T + 1 <= 28) */
 EVS_API int evs_bags_fused_kernels_seen(char *buf, int n);
+/* The same record for the long-bag pooling of encoded tables (evs_embedding_bag_sum_long): fifteen lines, always listed, in a
+ * fixed order (c = 16, 8, 4; lpr = 4, 8, 9, 16, 32 within each).  A count goes up by one per kernel launch (a call over
+ * T > EVS_MAX_TABLES_PER_LAUNCH tables: once per launch); a refused call, T == 0 and B == 0 launch nothing.
+ * evs_gather_kernels_seen does not count these launches.
+ *   longq_c<c>_lpr<l>        c = the row codec, l = d / 4 */
+EVS_API int evs_long_q_kernels_seen(char *buf, int n);
 
 /* ---------------------------------------------------------------------------
  * a1: DLRM_Net.apply_emb  (dlrm_s_pytorch.py:407-461)
@@ -114,6 +120,25 @@ EVS_API int evs_embedding_bag_sum(int T, int64_t B, int d, int codec,
                           const int64_t *nnz, const float *const *row_weights,
                           float *out, int64_t out_table_stride, int64_t out_bag_stride,
                           void *stream);
+
+/* The same sums for ENCODED tables and multi-hot bags by a kernel of their own (csrc/evs_gather_longq.hip): codec 16, 8 or 4,
+ * d in {16, 32, 36, 64, 128}, unweighted, offsets[k] given for every table.  The d / 4 lanes that hold a pooled row own its bag;
+ * K = evs_long_q_chunk(codec, d) rows of the bag are in flight per lane as raw code words and are decoded after they arrive;
+ * the sums are the same sequential fp32 adds in index order from +0.0f (bit-exact with evs_embedding_bag_sum and the oracle).
+ * Arguments and the output layout as above.  A bag that is not a valid [start, end) inside [0, nnz[k]] counts as empty, an
+ * index outside [0, n_rows[k]) contributes nothing; both raise the sticky flag evs_check_index_errors reports.  An explicit
+ * call: evs_embedding_bag_sum keeps its own dispatch.  Everything is validated before the device is touched -- fp32 tables
+ * (codec 32) or another codec, a d without a kernel, offsets[k] == NULL, B, nnz[k] or n_rows[k] >= 2^31, out or a table not
+ * 16-byte aligned, strides that are not multiples of 4, a NULL table with rows, NULL indices with nnz[k] > 0 return EVS_EINVAL
+ * and launch nothing; T == 0 or B == 0 succeeds and touches nothing.  Any T: EVS_MAX_TABLES_PER_LAUNCH tables per launch. */
+EVS_API int evs_embedding_bag_sum_long(int T, int64_t B, int d, int codec,
+                          const void *const *tables, const int64_t *n_rows,
+                          const int64_t *const *indices, const int64_t *const *offsets,
+                          const int64_t *nnz, float *out, int64_t out_table_stride, int64_t out_bag_stride,
+                          void *stream);
+/* Rows of a bag in flight per lane (the K of the instantiation) in the kernel of evs_embedding_bag_sum_long for (codec, d);
+ * 0: there is no such kernel. */
+EVS_API int evs_long_q_chunk(int codec, int d);
 
 /* The pool step of the table-sharded forward (dlrm_s_pytorch.py:543-570 distributed_forward: every rank pools ITS
  * tables for the FULL batch, then one all-to-all): evs_embedding_bag_sum with two extensions.
