@@ -27,6 +27,7 @@
 #include "evs_cache_policy.h"
 #include "evs_cache_warm.h"
 #include "evs_exact_warm.h"
+#include "evs_mailbox.h"
 #include <type_traits>
 
 #include <chrono>
@@ -272,37 +273,14 @@ __device__ int evlfu_set(const CacheState &cs, const CacheArrays &a, Hot &h, uns
     return e;
 }
 
-// The same kernel as a SERVER (round 5; evs_cache_serve_*): it stays resident and takes one request at a time from a
-// mailbox in pinned host memory -- the reference's operating point is batch 1 (cache_algo/EvLFU_C1.py:97-166,
-// dlrm_s_pytorch_C1.py:227-275), where a launch and a synchronise per request cost twice what the request does.
-//   request line  (host -> device, 128 bytes): four 32-byte sectors of seven row ids and a guard word (words 7, 15, 23, 31 =
-//                 the sequence number) -- the host writes the ids, then the four guards; the device reads the line as one
-//                 32-lane load (bus reads of 32 or 64 bytes that may be taken at different times) and accepts it when ALL
-//                 guards hold the number it waits for: every sector was then read after its guard, hence after its ids,
-//                 was written -- whatever the granularity the fabric delivers the line in;
-//   control line  (host -> device): word 0 = stop;
-//   answer line   (device -> host): the T hit flags in bytes 0..63, `done` (the sequence number served) in word 16, `alive`
-//                 in word 17 -- flags first, a system-scope fence, then `done`.
-// The rows go to slot (sequence % n_slots) of a ring in HBM: the caller gets DEVICE rows with no launch, copy or synchronise.
-// An idle server leaves by itself after idle_ticks of the 100 MHz wall clock (a device-wide synchronise elsewhere in the
-// process waits no longer than that); the host starts it again with the next request.
-#ifndef EVS_X_SERVE_FENCE
-#define EVS_X_SERVE_FENCE 0
-#endif
+// The same kernel as a SERVER (evs_cache_serve_*): it stays resident and takes one request at a time from a mailbox in
+// pinned host memory; the protocol, ServeArgs and the mbox_* steps are evs_mailbox.h's.
 #ifdef EVS_X_EXACT_TIMING   // developer build: where a request's time goes (100 MHz ticks per stage, summed over a launch)
 static __device__ long long g_exact_ticks[8];
 #define EVS_TICK(k) do { const long long now_ = (long long)wall_clock64(); if (lane == 0) tick_acc[k] += now_ - tick_t; tick_t = now_; } while (0)
 #else
 #define EVS_TICK(k) do { } while (0)
 #endif
-struct ServeArgs {
-    volatile unsigned *req;     // request line (device address of the mapped host block)
-    volatile unsigned *ctl;     // control line
-    volatile unsigned *ans;     // answer line
-    float *ring; int n_slots;
-    long long idle_ticks;
-};
-// One wavefront, requests strictly in order.
 // The exact kernels are ONE wavefront (launched with 64 threads): what its lanes hand each other through LDS, and what lane 0
 // writes to the entry arrays for the lanes of the next request to read, is ordered by the wave's own in-order issue -- a
 // wavefront-scope fence (no cache action, no wait) and a scheduling barrier say so to the compiler.  __syncthreads() here was a
@@ -357,50 +335,13 @@ __device__ __forceinline__ void cache_exact_body(const CacheArgs &args, const Se
 #ifdef EVS_X_EXACT_TIMING
     long long tick_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tick_t = (long long)wall_clock64();
 #endif
-    if constexpr (SERVE) {
-        serve_seq = __hip_atomic_load(const_cast<unsigned *>(sv.ans) + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // alive
-    }
+    if constexpr (SERVE) serve_seq = mbox_enter(sv, lane);
     for (long long rq = 0; SERVE || rq < args.B; rq++) {
         int row;
         float *out;
         unsigned char *hitp;
         if constexpr (SERVE) {
-            // ---- wait for the next request: the whole line in one load (lane = word), both guards = the number awaited ----
-            const unsigned want = (serve_seq + 1u) & 0x7fffffffu;
-            const long long t0 = (long long)wall_clock64();
-            unsigned word = 0u;
-            bool leave = false;
-            for (;;) {
-                // ONE load per poll (round 6: the control word was a second dependent load, and the request waited out both):
-                // lanes 0..31 the request line, lane 32 the control word in the line behind it
-                word = __hip_atomic_load(const_cast<unsigned *>(sv.req) + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                // words 7, 15, 23, 31: one guard per 32-byte sector (bit 31 of a guard: the ids are given by ADDRESS, below)
-                if ((__ballot((word & 0x7fffffffu) == want) & 0x80808080ull) == 0x80808080ull) break;
-                const unsigned stop = (unsigned)__builtin_amdgcn_readlane((int)word, 32);
-                if (stop != 0u || (long long)wall_clock64() - t0 > sv.idle_ticks) { leave = true; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (leave) break;
-            // id of table t: word t + t / 7 (seven ids, then the sector's guard) ...
-            const int src_lane = lane + lane / 7;
-            row = __shfl((int)word, src_lane & 31);
-            // ... or, round 6 (evs_cache_serve_request_dev: the reference's loop has the ids on the DEVICE -- dlrm_wrap moved lS_i
-            // there -- and fetching them back costs the plug-in a copy and a synchronise per request): words 0..2 = the address of
-            // table 0's first index and the elements between two tables' rows; one agent-scope load per lane
-            if (((unsigned)rl((int)word, 7) >> 31) != 0u) {
-                const unsigned long long pa = ((unsigned long long)(unsigned)rl((int)word, 1) << 32) | (unsigned)rl((int)word, 0);
-                const long long stride = (long long)(unsigned)rl((int)word, 2);
-                const long long *ip = reinterpret_cast<const long long *>((uintptr_t)pa) + (long long)(lane < T ? lane : 0) * stride;
-                row = (int)__hip_atomic_load(ip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // ... and, round 6 (evs_cache_serve_request_to), where the rows go: a DEVICE address of the caller's (words 3, 4 beside
-            // an id address; words 29, 30 -- the ids of tables 26, 27 -- beside ids when T <= 26), 0 = this request's ring slot
-            unsigned long long out_a = 0ull;
-            if (((unsigned)rl((int)word, 7) >> 31) != 0u) out_a = ((unsigned long long)(unsigned)rl((int)word, 4) << 32) | (unsigned)rl((int)word, 3);
-            else if (T <= 26) out_a = ((unsigned long long)(unsigned)rl((int)word, 30) << 32) | (unsigned)rl((int)word, 29);
-            if (lane >= T) row = 0;
-            out = out_a ? reinterpret_cast<float *>((uintptr_t)out_a) : sv.ring + (long long)(want % (unsigned)sv.n_slots) * T * d;
+            if (!mbox_next(sv, lane, T, d, serve_seq, row, out)) break;
             hitp = nullptr;   // (flags go to the answer line, below)
         } else {
             row = lane < T ? args.requests[rq * T + lane] : 0;   // the only read of the ids (they may live in host memory)
@@ -871,22 +812,7 @@ __device__ __forceinline__ void cache_exact_body(const CacheArgs &args, const Se
             // arena (below) -- that is this server's own bookkeeping, in program order in front of its next request, and it
             // now runs while the answer travels ----
             served++;
-            serve_seq = (serve_seq + 1u) & 0x7fffffffu;
-            if (lane < T) const_cast<volatile unsigned char *>(reinterpret_cast<volatile unsigned char *>(sv.ans))[lane] = my_flag;
-            // (round 6: the ring rows were written THROUGH, agent scope; what is left to do before the sequence number goes out is to
-            //  wait for those stores and the flags -- a system-scope fence here was an L2 write-back per request)
-#if EVS_X_SERVE_FENCE == 1      // developer A/B: the round-5 form, a system-scope fence
-            __threadfence_system();
-#elif EVS_X_SERVE_FENCE == 2    // agent-scope fence
-            __threadfence();
-#else
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-#endif
-#if EVS_X_SERVE_FENCE == 0
-            if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 16, serve_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (behind the wait above; a release here would be the write-back again)
-#else
-            if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 16, serve_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
+            serve_seq = mbox_answer(sv, lane, T, my_flag, serve_seq);
         }
         {   // every new entry's row, table -> arena
             // the entry may already have been evicted again by a later key of this request (only if this request evicted at all):
@@ -945,10 +871,7 @@ __device__ __forceinline__ void cache_exact_body(const CacheArgs &args, const Se
         gs->n_perfect_hits = cs.n_perfect_hits + n_perfect_hits;
     }
     for (int b = lane; b < kMaxBuckets; b += 64) { gs->head[b] = h.head[b]; gs->tail[b] = h.tail[b]; gs->len[b] = h.len[b]; }
-    if constexpr (SERVE) {   // the state is back in HBM: only now may the host start another server (or anything else) on it
-        __threadfence_system();
-        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if constexpr (SERVE) mbox_leave(sv, lane);   // (the state is back in HBM)
 }
 __global__ void __launch_bounds__(64) cache_exact_kernel(const CacheArgs args) { cache_exact_body<false>(args, ServeArgs{}); }
 __global__ void __launch_bounds__(64) cache_serve_kernel(const CacheArgs args, const ServeArgs sv) { cache_exact_body<true>(args, sv); }
@@ -1335,42 +1258,13 @@ __device__ __forceinline__ void cache_c1c2_body(const C1C2Args &args, const Serv
     long long n_perfect_req = 0, n_hits = 0;
     unsigned serve_seq = 0;            // SERVE: the last sequence number served
     long long served = 0;
-    if constexpr (SERVE) {
-        serve_seq = __hip_atomic_load(const_cast<unsigned *>(sv.ans) + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // alive
-    }
+    if constexpr (SERVE) serve_seq = mbox_enter(sv, lane);
 
     for (long long rq = 0; SERVE || rq < args.B; rq++) {
         int row;
         float *out;
         if constexpr (SERVE) {
-            // ---- wait for the next request: the line and the control word in one 64-lane load (cache_exact_body's) ----
-            const unsigned want = (serve_seq + 1u) & 0x7fffffffu;
-            const long long t0 = (long long)wall_clock64();
-            unsigned word = 0u;
-            bool leave = false;
-            for (;;) {
-                word = __hip_atomic_load(const_cast<unsigned *>(sv.req) + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if ((__ballot((word & 0x7fffffffu) == want) & 0x80808080ull) == 0x80808080ull) break;
-                const unsigned stop = (unsigned)__builtin_amdgcn_readlane((int)word, 32);
-                if (stop != 0u || (long long)wall_clock64() - t0 > sv.idle_ticks) { leave = true; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (leave) break;
-            const int src_lane = lane + lane / 7;   // id of table t: word t + t / 7
-            row = __shfl((int)word, src_lane & 31);
-            const bool by_addr = ((unsigned)rl((int)word, 7) >> 31) != 0u;
-            if (by_addr) {                          // words 0..2: the address of table 0's id and the elements between two tables' ids
-                const unsigned long long pa = ((unsigned long long)(unsigned)rl((int)word, 1) << 32) | (unsigned)rl((int)word, 0);
-                const long long stride = (long long)(unsigned)rl((int)word, 2);
-                const long long *ip = reinterpret_cast<const long long *>((uintptr_t)pa) + (long long)(lane < T ? lane : 0) * stride;
-                row = (int)__hip_atomic_load(ip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            unsigned long long out_a = 0ull;        // where the rows go: an address of the caller's, 0 = this request's ring slot
-            if (by_addr) out_a = ((unsigned long long)(unsigned)rl((int)word, 4) << 32) | (unsigned)rl((int)word, 3);
-            else if (T <= 26) out_a = ((unsigned long long)(unsigned)rl((int)word, 30) << 32) | (unsigned)rl((int)word, 29);
-            if (lane >= T) row = 0;
-            out = out_a ? reinterpret_cast<float *>((uintptr_t)out_a) : sv.ring + (long long)(want % (unsigned)sv.n_slots) * T * d;
+            if (!mbox_next(sv, lane, T, d, serve_seq, row, out)) break;
         } else {
             row = lane < T ? args.requests[rq * T + lane] : 0;
             out = args.out + rq * (long long)T * d;
@@ -1576,10 +1470,7 @@ __device__ __forceinline__ void cache_c1c2_body(const C1C2Args &args, const Serv
             // ---- the answer: the T tier codes, then -- behind a wait for the rows (written through) and the codes -- the
             // sequence number the host polls for; BEFORE both tiers' arena fills, which run while it travels ----
             served++;
-            serve_seq = (serve_seq + 1u) & 0x7fffffffu;
-            if (lane < T) const_cast<volatile unsigned char *>(reinterpret_cast<volatile unsigned char *>(sv.ans))[lane] = code;
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-            if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 16, serve_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            serve_seq = mbox_answer(sv, lane, T, code, serve_seq);
         }
         // ---- every new entry's row, table -> arena ----
         if ((f1 >= 0 || f2 >= 0) && fkey != key) s_fdst[fill_rank] = nullptr;
@@ -1599,10 +1490,7 @@ __device__ __forceinline__ void cache_c1c2_body(const C1C2Args &args, const Serv
         args.t1.st->n_perfect_hits = cs1.n_perfect_hits + n_perfect_req;
         args.t1.st->n_hits = cs1.n_hits + n_hits;
     }
-    if constexpr (SERVE) {   // the state is back in HBM: only now may the host start another server (or anything else) on it
-        __threadfence_system();
-        if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(sv.ans) + 17, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if constexpr (SERVE) mbox_leave(sv, lane);   // (the state is back in HBM)
 }
 __global__ void __launch_bounds__(64) cache_c1c2_kernel(const C1C2Args args) { cache_c1c2_body<false>(args, ServeArgs{}); }
 __global__ void __launch_bounds__(64) cache_c1c2_serve_kernel(const C1C2Args args, const ServeArgs sv) { cache_c1c2_body<true>(args, sv); }
@@ -3552,25 +3440,10 @@ struct evs_cache {
     struct SaShared { unsigned *tags = nullptr; size_t bytes = 0; int refs = 0; } *sa_mem = nullptr;
     unsigned char *sa_arena = nullptr;   // two-copy arena of a dual geometry (a.arena points here then)
     unsigned char *arena_create = nullptr;   // the one-row-per-entry arena evs_cache_create made (freed when sa_arena replaces it)
-    // the exact policy as a resident server (evs_cache_serve_*): a mailbox in mapped host memory, its own stream
-    unsigned *mbox = nullptr, *mbox_dev = nullptr;   // 3 lines of 128 bytes: request, control, answer
-    // (Round 6 tried the request + control lines in DEVICE memory, written by the host through the large-BAR aperture:
-    //  tools/mailbox_probe.hip's bare echo makes a round trip in 1.8 us against 2.4, the server's p50 did not move -- 14.3-14.9
-    //  against 14.4-14.8 us over four runs each --, so the lines stay where an ordinary store reaches them.)
-    volatile unsigned *req_host = nullptr;           // the host's view of the request + control lines
-    unsigned *req_dev = nullptr;                     // the device's
-    hipStream_t serve_stream = nullptr;
+    // the exact policy as a resident server (evs_cache_serve_*): the mailbox, its stream, the ring (evs_mailbox.h)
+    evs::ServeHost srv;
     bool serving = false;
-    unsigned serve_seq = 0;
-    float *serve_ring = nullptr; int serve_slots = 0, serve_thres = -1;
-    long long serve_idle_ticks = 0;
-    // ordering of the server against everything else that touches the exact state or reads the ring:
-    //   exact_done: recorded behind every exact-path launch on the CALLER's stream; a server started afterwards waits for it
-    //               on its own stream (two kernels must never mutate the lists / the map / the free stack at once);
-    //   slot_done[s]: recorded by evs_cache_serve_consumed on the stream that READS ring slot s; the request that is about
-    //               to hand slot s out again waits for it on the host (the server overwrites the slot in host order).
-    hipEvent_t exact_done = nullptr; bool exact_pending = false;
-    std::vector<hipEvent_t> slot_done; std::vector<char> slot_busy;
+    int serve_thres = -1;
     // order of update and consumers on the set-associative batched path (evs_cache_set_miss_order): 0 "consume first", 1 "fetch
     // first" (probe -> update -> sa_repoint -> consumers: every missing row is read once, by the update); the counters the
     // repoint kernel adds into (device, 2 words, allocated at the first fetch-first call) and the calls that ran the chain
@@ -3650,14 +3523,8 @@ struct evs_tier_server {
     evs_cache *c1 = nullptr, *c2 = nullptr;
     evs_aprx *c3 = nullptr;
     int threshold = 23, n_tables = 0;
-    unsigned *mbox = nullptr, *mbox_dev = nullptr;   // 3 lines of 128 bytes: request, control, answer
-    hipStream_t stream = nullptr;
+    evs::ServeHost srv;
     bool serving = false, dead = false;              // dead: a member was destroyed
-    unsigned seq = 0;
-    float *ring = nullptr; int slots = 0;
-    long long idle_ticks = 0;
-    hipEvent_t exact_done = nullptr; bool exact_pending = false;   // (as evs_cache's)
-    std::vector<hipEvent_t> slot_done; std::vector<char> slot_busy;
 };
 static int tiers_pause(evs_tier_server *s);
 static int tiers_launched(evs_tier_server *s, hipStream_t st);
@@ -3798,14 +3665,7 @@ extern "C" int evs_cache_destroy(evs_cache *c) {
     if (c->host_tomb) (void)hipHostFree(c->host_tomb);
     if (c->new_keys_host) (void)hipHostFree(c->new_keys_host);
     if (c->staging) (void)hipHostFree(c->staging);
-    if (c->mbox) {
-        c->req_host[32] = 1u;   // stop
-        __atomic_thread_fence(__ATOMIC_SEQ_CST);
-        if (c->serve_stream) { (void)hipStreamSynchronize(c->serve_stream); (void)hipStreamDestroy(c->serve_stream); }
-        (void)hipHostFree(c->mbox);
-    }
-    if (c->exact_done) (void)hipEventDestroy(c->exact_done);
-    for (hipEvent_t e : c->slot_done) if (e) (void)hipEventDestroy(e);
+    c->srv.close();
     sa_release(c);
     delete c;
     return EVS_OK;
@@ -4139,43 +3999,25 @@ extern "C" int evs_cache_request(evs_cache *c, int64_t B, const int32_t *rows, f
 }
 
 // ---- the exact policy as a resident server (cache_serve_kernel) ------------------------------------------------------------
-static void serve_launch(evs_cache *c) {
+static void serve_launch(evs_cache *c, const evs::ServeArgs &sv, hipStream_t st) {
     using namespace evs;
     CacheArgs args;
     args.st = c->st; args.a = c->a;
     for (int k = 0; k < kMaxTables; k++) { args.backing[k] = c->backing[k]; args.backing_rows[k] = c->backing_rows[k]; }
     args.requests = nullptr; args.out = nullptr; args.hit = nullptr; args.B = 0; args.approx_thres = c->serve_thres;
-    ServeArgs sv;
-    sv.req = c->req_dev; sv.ctl = c->req_dev + 32; sv.ans = c->mbox_dev + 64;
-    sv.ring = c->serve_ring; sv.n_slots = c->serve_slots; sv.idle_ticks = c->serve_idle_ticks;
-    // an exact-path launch of the caller's (evs_cache_request, evs_cache_request_c1c2[c3]) may still be running on ITS stream:
-    // the server starts behind it
-    if (c->exact_pending) { (void)hipStreamWaitEvent(c->serve_stream, c->exact_done, 0); c->exact_pending = false; }
     c->exact_touched = true;
-    hipLaunchKernelGGL(cache_serve_kernel, dim3(1), dim3(64), 0, c->serve_stream, args, sv);
+    hipLaunchKernelGGL(cache_serve_kernel, dim3(1), dim3(64), 0, st, args, sv);
 }
-// behind every exact-path launch: where a server started later has to wait (only caches that have a server pay the record)
+// behind every exact-path launch (evs_cache_request, evs_cache_request_c1c2[c3]): a server started later waits for it
 static int exact_launched(evs_cache *c, hipStream_t st) {
     if (c->tsrv) { const int trc = tiers_launched(c->tsrv, st); if (trc) return trc; }
-    if (!c->serve_stream) return EVS_OK;
-    if (!c->exact_done) EVS_HIP_CHECK(hipEventCreateWithFlags(&c->exact_done, hipEventDisableTiming));
-    EVS_HIP_CHECK(hipEventRecord(c->exact_done, st));
-    c->exact_pending = true;
-    return EVS_OK;
+    return c->srv.launched(st);
 }
 // anything else that reads or writes the exact state first sends the server home (it writes the state back on its way out);
 // the next evs_cache_serve_request starts it again
 static int serve_pause(evs_cache *c) {
     if (c && c->tsrv) { const int trc = tiers_pause(c->tsrv); if (trc) return trc; }
-    if (!c || !c->mbox || !c->serve_stream) return EVS_OK;
-    if (hipStreamQuery(c->serve_stream) == hipSuccess) return EVS_OK;   // nothing running
-    (void)hipGetLastError();
-    c->req_host[32] = 1u;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    const hipError_t e = hipStreamSynchronize(c->serve_stream);
-    c->req_host[32] = 0u;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    return e == hipSuccess ? EVS_OK : EVS_EHIP;
+    return c ? c->srv.pause("evs_cache_serve") : EVS_OK;
 }
 extern "C" int evs_cache_serve_start(evs_cache *c, int approx_thres, float *ring, int n_slots, int64_t idle_us) {
     using namespace evs;
@@ -4186,30 +4028,14 @@ extern "C" int evs_cache_serve_start(evs_cache *c, int approx_thres, float *ring
     if (c->staged_mask) { set_error("evs_cache_serve_start: a file-backed tier with staged tables serves batched lookups only"); return EVS_ESTATE; }
     if (c->used == 2) { set_error("evs_cache_serve_start: this cache is used through the batched path"); return EVS_ESTATE; }
     if (c->tsrv) { set_error("evs_cache_serve_start: this cache belongs to a tier server (evs_tiers_serve_start)"); return EVS_ESTATE; }
-    EVS_REQUIRE(c->host.n_tables <= 28, "evs_cache_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
+    EVS_REQUIRE(c->host.n_tables <= MailboxLayout::kMaxTables, "evs_cache_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
     c->used = 1;
-    if (!c->mbox) {
-        EVS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&c->mbox), 3 * 128, hipHostMallocMapped));
-        memset(c->mbox, 0, 3 * 128);
-        EVS_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->mbox_dev), c->mbox, 0));
-        c->req_host = c->mbox; c->req_dev = c->mbox_dev;
-        // a stream of the highest priority: streams share a handful of hardware queues, round-robin per priority level, and a
-        // queue runs its commands in order -- a copy or a kernel of the caller's that lands on the queue of the resident server
-        // waits until the server goes home idle (measured through the plug-in loop: 299 us per request instead of 104 once a
-        // process had made a few more streams).  Nothing else of this library uses the level.
-        int prio_lo = 0, prio_hi = 0;
-        EVS_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        EVS_HIP_CHECK(hipStreamCreateWithPriority(&c->serve_stream, hipStreamNonBlocking, prio_hi));
-        c->serve_seq = 0;
-    } else {
-        const int rc = serve_pause(c);
-        if (rc) return rc;
+    {   // (this entry point reports a failed allocation of the mailbox as EVS_EHIP)
+        const int rc = c->srv.is_open() ? serve_pause(c) : c->srv.open("evs_cache_serve_start");
+        if (rc) return rc == EVS_ENOMEM ? EVS_EHIP : rc;
     }
-    for (size_t k = 0; k < c->slot_busy.size(); k++)      // (a new ring: whoever still reads the old one finishes first)
-        if (c->slot_busy[k]) { (void)hipEventSynchronize(c->slot_done[k]); c->slot_busy[k] = 0; }
-    c->slot_done.resize((size_t)n_slots, nullptr); c->slot_busy.assign((size_t)n_slots, 0);
-    c->serve_ring = ring; c->serve_slots = n_slots; c->serve_thres = approx_thres;
-    c->serve_idle_ticks = idle_us * 100;   // wall_clock64(): 100 MHz
+    c->srv.rearm(ring, n_slots, idle_us);
+    c->serve_thres = approx_thres;
     c->serving = true;
     EVS_HIP_CHECK(hipDeviceSynchronize());   // (the ring and the tables' contents are in place before the server's first read)
     return EVS_OK;
@@ -4231,7 +4057,7 @@ extern "C" int evs_cache_serve_request_to(evs_cache *c, const int32_t *rows, con
     using namespace evs;
     EVS_REQUIRE(c && out_dev && hit && ((rows != nullptr) != (ids_dev != nullptr)) && ids_stride >= 0 && ids_stride < (1ll << 32),
                 "evs_cache_serve_request_to: bad argument");
-    EVS_REQUIRE(c->host.n_tables <= 26, "evs_cache_serve_request_to: at most 26 tables (the line's last two id words carry the address)");
+    EVS_REQUIRE(c->host.n_tables <= MailboxLayout::kMaxTablesTo, "evs_cache_serve_request_to: at most 26 tables (the line's last two id words carry the address)");
     int slot = 0;
     return serve_request_impl(c, rows, ids_dev, ids_stride, out_dev, hit, &slot);
 }
@@ -4246,70 +4072,16 @@ extern "C" int evs_cache_serve_request_dev(evs_cache *c, const int64_t *ids_dev,
 static int serve_request_impl(evs_cache *c, const int32_t *rows, const int64_t *ids_dev, int64_t ids_stride, float *out_dev, uint8_t *hit, int *slot_out) {
     using namespace evs;
     if (!c->serving) { set_error("evs_cache_serve_request: call evs_cache_serve_start first"); return EVS_ESTATE; }
-    volatile unsigned *req = c->req_host, *ans = c->mbox + 64;
-    const int T = c->host.n_tables;
-    const unsigned want = (c->serve_seq + 1u) & 0x7fffffffu;
-    // the ring slot this request's rows go to: whoever still READS it (evs_cache_serve_consumed) finishes first
-    const int slot = (int)(want % (unsigned)c->serve_slots);
-    if (!out_dev && c->slot_busy[(size_t)slot]) {
-        EVS_HIP_CHECK(hipEventSynchronize(c->slot_done[(size_t)slot]));
-        c->slot_busy[(size_t)slot] = 0;
-    }
-    c->serve_seq = want;
-    const unsigned long long oa = (unsigned long long)reinterpret_cast<uintptr_t>(out_dev);
-    // seven ids and a guard per 32-byte sector: whatever granularity the bus delivers the line in, ids are accepted only from
-    // a sector whose guard (written after them) holds the number awaited
-    unsigned guard = want;
-    if (rows) {
-        for (int t = 0; t < T; t++) req[t + t / 7] = (unsigned)rows[t];
-        if (T <= 26) { req[29] = (unsigned)oa; req[30] = (unsigned)(oa >> 32); }   // (the id words of tables 26, 27: where the rows go, 0 = the ring)
-    } else {   // by address: words 0..2 (3, 4: where the rows go), and bit 31 of the guards says so
-        const unsigned long long pa = (unsigned long long)reinterpret_cast<uintptr_t>(ids_dev);
-        req[0] = (unsigned)pa; req[1] = (unsigned)(pa >> 32); req[2] = (unsigned)ids_stride;
-        req[3] = (unsigned)oa; req[4] = (unsigned)(oa >> 32);
-        guard |= 0x80000000u;
-    }
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    req[7] = guard; req[15] = guard; req[23] = guard; req[31] = guard;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    long long spins = 0;
-    // a request that fails leaves host and device agreeing on the sequence number: the one the device last ANSWERED
-    auto fail = [&](int rc) { c->serve_seq = ans[16]; return rc; };
-    while (ans[16] != want) {
-        if ((spins & 63) == 0 && ans[17] == 0u) {   // no server (never started, went home idle, or was paused): start one
-            const hipError_t q = hipStreamQuery(c->serve_stream);
-            if (q == hipSuccess) {
-                serve_launch(c);
-                if (hipGetLastError() != hipSuccess) { set_error("evs_cache_serve_request: the server could not be started"); return fail(EVS_EHIP); }
-            }
-            else if (q != hipErrorNotReady) { (void)hipGetLastError(); return fail(EVS_EHIP); }
-            else (void)hipGetLastError();
-        }
-        if (++spins > (1ll << 31)) {
-            // send a server that may still be there home (it re-reads the answer line's number when it starts again), then agree
-            (void)serve_pause(c);
-            set_error("evs_cache_serve_request: the server did not answer");
-            return fail(EVS_EHIP);
-        }
-        __builtin_ia32_pause();
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    const volatile unsigned char *fl = reinterpret_cast<const volatile unsigned char *>(ans);
-    for (int t = 0; t < T; t++) hit[t] = fl[t];
-    *slot_out = out_dev ? -1 : slot;
-    return EVS_OK;
+    return c->srv.request("evs_cache_serve_request", c->host.n_tables, rows, ids_dev, ids_stride, out_dev, hit, slot_out,
+                          [c](const ServeArgs &sv, hipStream_t st) { serve_launch(c, sv, st); });
 }
 // The caller has ENQUEUED its reads of ring slot `slot` (a copy, a kernel) on `stream`: the slot is handed out again only
 // after they have finished.  Without this call the contract is stream order, not host order: the rows of a slot are valid
 // until n_slots - 1 more requests have been POSTED, whatever the caller's stream has executed by then.
 extern "C" int evs_cache_serve_consumed(evs_cache *c, int slot, void *stream) {
     using namespace evs;
-    EVS_REQUIRE(c && c->serving && slot >= 0 && slot < c->serve_slots, "evs_cache_serve_consumed: bad argument");
-    hipEvent_t &e = c->slot_done[(size_t)slot];
-    if (!e) EVS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    EVS_HIP_CHECK(hipEventRecord(e, reinterpret_cast<hipStream_t>(stream)));
-    c->slot_busy[(size_t)slot] = 1;
-    return EVS_OK;
+    EVS_REQUIRE(c && c->serving && slot >= 0 && slot < c->srv.mb.slots, "evs_cache_serve_consumed: bad argument");
+    return c->srv.consumed(slot, reinterpret_cast<hipStream_t>(stream));
 }
 #ifdef EVS_X_EXACT_TIMING
 extern "C" __attribute__((visibility("default"))) int evs_x_exact_ticks(long long *out8, int reset) {
@@ -7635,8 +7407,8 @@ static int cache_rows_impl(evs_cache *c, int64_t n, const int32_t *keys, const f
     if (!a.err) return EVS_EHIP;
     // an exact-path launch may be pending on ANOTHER stream, with a server start waiting for its event: this launch goes
     // behind that event and re-records it, so the server start keeps waiting for both
-    if (c->exact_pending && c->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->exact_done, 0));
-    if (c->tsrv && c->tsrv->exact_pending && c->tsrv->exact_done) EVS_HIP_CHECK(hipStreamWaitEvent(st, c->tsrv->exact_done, 0));
+    { const int wrc = c->srv.wait_exact(st); if (wrc) return wrc; }
+    if (c->tsrv) { const int wrc = c->tsrv->srv.wait_exact(st); if (wrc) return wrc; }
     if (refresh && c->ft) {
         // a registered table is a pinned copy of its file: the rows the caller wrote reach it here, in stream order
         // (the work ahead on the stream may still read the old rows, so the host waits for it before it copies)
@@ -7783,39 +7555,16 @@ static void tiers_args(evs_cache *c1, evs_cache *c2, evs_aprx *c3, int threshold
     if (c3) args.c3 = c3->x; else { args.c3 = AprxArrays{}; args.c3.st = nullptr; }
     args.requests = nullptr; args.out = nullptr; args.tier_out = nullptr; args.B = 0; args.threshold = threshold;
 }
-static void tiers_launch(evs_tier_server *s) {
+static void tiers_launch(evs_tier_server *s, const evs::ServeArgs &sv, hipStream_t st) {
     using namespace evs;
     C1C2Args args;
     tiers_args(s->c1, s->c2, s->c3, s->threshold, args);
-    ServeArgs sv;
-    sv.req = s->mbox_dev; sv.ctl = s->mbox_dev + 32; sv.ans = s->mbox_dev + 64;
-    sv.ring = s->ring; sv.n_slots = s->slots; sv.idle_ticks = s->idle_ticks;
-    // a launch-per-call request on the members may still be running on the caller's stream: the server starts behind it
-    if (s->exact_pending) { (void)hipStreamWaitEvent(s->stream, s->exact_done, 0); s->exact_pending = false; }
     s->c1->exact_touched = s->c2->exact_touched = true;
-    hipLaunchKernelGGL(cache_c1c2_serve_kernel, dim3(1), dim3(64), 0, s->stream, args, sv);
+    hipLaunchKernelGGL(cache_c1c2_serve_kernel, dim3(1), dim3(64), 0, st, args, sv);
 }
-static int tiers_launched(evs_tier_server *s, hipStream_t st) {
-    if (!s || s->dead || !s->stream) return EVS_OK;
-    if (!s->exact_done) EVS_HIP_CHECK(hipEventCreateWithFlags(&s->exact_done, hipEventDisableTiming));
-    EVS_HIP_CHECK(hipEventRecord(s->exact_done, st));
-    s->exact_pending = true;
-    return EVS_OK;
-}
+static int tiers_launched(evs_tier_server *s, hipStream_t st) { return (s && !s->dead) ? s->srv.launched(st) : EVS_OK; }
 // send the server home (it writes h1, h2, s3 and the counters back on its way out); the next request starts it again
-static int tiers_pause(evs_tier_server *s) {
-    if (!s || !s->mbox || !s->stream) return EVS_OK;
-    if (hipStreamQuery(s->stream) == hipSuccess) return EVS_OK;   // nothing running
-    (void)hipGetLastError();
-    volatile unsigned *req = s->mbox;
-    req[32] = 1u;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    const hipError_t e = hipStreamSynchronize(s->stream);
-    req[32] = 0u;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    if (e != hipSuccess) { evs::set_error("the tier server's stream failed: %s", hipGetErrorString(e)); return EVS_EHIP; }
-    return EVS_OK;
-}
+static int tiers_pause(evs_tier_server *s) { return s ? s->srv.pause("evs_tiers_serve") : EVS_OK; }
 static void tiers_detach(evs_tier_server *s) {
     if (s->c1) s->c1->tsrv = nullptr;
     if (s->c2) s->c2->tsrv = nullptr;
@@ -7835,7 +7584,7 @@ extern "C" int evs_tiers_serve_start(evs_tier_server **out, evs_cache *c1, evs_c
     EVS_REQUIRE(c1 != c2, "evs_tiers_serve_start: C1 and C2 are the same cache");
     EVS_REQUIRE(c1->host.policy == kEvLFU && c2->host.policy == kEvLFU, "evs_tiers_serve_start: both tiers must be EvLFU");
     EVS_REQUIRE(c1->host.n_tables == c2->host.n_tables && c1->host.dim == c2->host.dim, "evs_tiers_serve_start: the tiers disagree on n_tables/dim");
-    EVS_REQUIRE(c1->host.n_tables <= 28, "evs_tiers_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
+    EVS_REQUIRE(c1->host.n_tables <= MailboxLayout::kMaxTables, "evs_tiers_serve_start: at most 28 tables (the request line holds 4 x 7 ids)");
     EVS_REQUIRE(!c3 || c3->n_tables == c1->host.n_tables, "evs_tiers_serve_start: alt-key tier has a different n_tables");
     if (!c1->has_backing || !c2->has_backing) { set_error("evs_tiers_serve_start: set the backing tables of both tiers first"); return EVS_ESTATE; }
     for (evs_cache *c : {c1, c2}) {
@@ -7850,22 +7599,10 @@ extern "C" int evs_tiers_serve_start(evs_tier_server **out, evs_cache *c1, evs_c
     if (c1->tsrv || c2->tsrv || (c3 && c3->tsrv)) { set_error("evs_tiers_serve_start: a tier already belongs to a tier server"); return EVS_ESTATE; }
     { const int p1 = serve_pause(c1), p2 = serve_pause(c2); if (p1 || p2) return EVS_EHIP; }   // (a stopped single-tier server inside its idle window)
     evs_tier_server *s = new evs_tier_server();
-    auto fail = [&](int rc) {
-        if (s->stream) (void)hipStreamDestroy(s->stream);
-        if (s->mbox) (void)hipHostFree(s->mbox);
-        delete s;
-        return rc;
-    };
-    if (hipHostMalloc(reinterpret_cast<void **>(&s->mbox), 3 * 128, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: no mailbox"); return fail(EVS_ENOMEM); }
-    memset(s->mbox, 0, 3 * 128);
-    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&s->mbox_dev), s->mbox, 0) != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: the mailbox is not device-accessible"); return fail(EVS_EHIP); }
-    int prio_lo = 0, prio_hi = 0;   // (the highest priority, non-blocking: see evs_cache_serve_start)
-    if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess || hipStreamCreateWithPriority(&s->stream, hipStreamNonBlocking, prio_hi) != hipSuccess) {
-        (void)hipGetLastError(); set_error("evs_tiers_serve_start: no stream"); return fail(EVS_EHIP);
-    }
+    auto fail = [&](int rc) { s->srv.close(); delete s; return rc; };
+    { const int rc = s->srv.open("evs_tiers_serve_start"); if (rc) return fail(rc); }
     s->c1 = c1; s->c2 = c2; s->c3 = c3; s->threshold = high_agghit_threshold; s->n_tables = c1->host.n_tables;
-    s->ring = ring; s->slots = n_slots; s->idle_ticks = idle_us * 100;   // wall_clock64(): 100 MHz
-    s->slot_done.assign((size_t)n_slots, nullptr); s->slot_busy.assign((size_t)n_slots, 0);
+    s->srv.rearm(ring, n_slots, idle_us);
     if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); set_error("evs_tiers_serve_start: hipDeviceSynchronize failed"); return fail(EVS_EHIP); }   // (ring, tables and earlier requests in place)
     c1->used = c2->used = 1; c1->tsrv = c2->tsrv = s;
     if (c3) { c3->used = 1; c3->tsrv = s; }
@@ -7878,53 +7615,8 @@ static int tiers_request_impl(evs_tier_server *s, const int32_t *rows, const int
     using namespace evs;
     if (s->dead) { set_error("evs_tiers_serve_request: a member of this tier server was destroyed"); return EVS_ESTATE; }
     if (!s->serving) { set_error("evs_tiers_serve_request: the server was stopped"); return EVS_ESTATE; }
-    volatile unsigned *req = s->mbox, *ans = s->mbox + 64;
-    const int T = s->n_tables;
-    const unsigned want = (s->seq + 1u) & 0x7fffffffu;
-    const int slot = (int)(want % (unsigned)s->slots);
-    if (!out_dev && s->slot_busy[(size_t)slot]) {   // whoever still READS the slot (evs_tiers_serve_consumed) finishes first
-        EVS_HIP_CHECK(hipEventSynchronize(s->slot_done[(size_t)slot]));
-        s->slot_busy[(size_t)slot] = 0;
-    }
-    s->seq = want;
-    const unsigned long long oa = (unsigned long long)reinterpret_cast<uintptr_t>(out_dev);
-    unsigned guard = want;   // the line is the single-tier server's (serve_request_impl): seven ids and a guard per 32-byte sector
-    if (rows) {
-        for (int t = 0; t < T; t++) req[t + t / 7] = (unsigned)rows[t];
-        if (T <= 26) { req[29] = (unsigned)oa; req[30] = (unsigned)(oa >> 32); }
-    } else {
-        const unsigned long long pa = (unsigned long long)reinterpret_cast<uintptr_t>(ids_dev);
-        req[0] = (unsigned)pa; req[1] = (unsigned)(pa >> 32); req[2] = (unsigned)ids_stride;
-        req[3] = (unsigned)oa; req[4] = (unsigned)(oa >> 32);
-        guard |= 0x80000000u;
-    }
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    req[7] = guard; req[15] = guard; req[23] = guard; req[31] = guard;
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    long long spins = 0;
-    auto fail = [&](int rc) { s->seq = ans[16]; return rc; };   // host and device agree on the number last ANSWERED
-    while (ans[16] != want) {
-        if ((spins & 63) == 0 && ans[17] == 0u) {   // no server (never started, went home idle, or was paused): start one
-            const hipError_t q = hipStreamQuery(s->stream);
-            if (q == hipSuccess) {
-                tiers_launch(s);
-                if (hipGetLastError() != hipSuccess) { set_error("evs_tiers_serve_request: the server could not be started"); return fail(EVS_EHIP); }
-            }
-            else if (q != hipErrorNotReady) { (void)hipGetLastError(); set_error("evs_tiers_serve_request: the server's stream failed"); return fail(EVS_EHIP); }
-            else (void)hipGetLastError();
-        }
-        if (++spins > (1ll << 31)) {
-            (void)tiers_pause(s);
-            set_error("evs_tiers_serve_request: the server did not answer");
-            return fail(EVS_EHIP);
-        }
-        __builtin_ia32_pause();
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    const volatile unsigned char *fl = reinterpret_cast<const volatile unsigned char *>(ans);
-    for (int t = 0; t < T; t++) tier[t] = fl[t];
-    *slot_out = out_dev ? -1 : slot;
-    return EVS_OK;
+    return s->srv.request("evs_tiers_serve_request", s->n_tables, rows, ids_dev, ids_stride, out_dev, tier, slot_out,
+                          [s](const ServeArgs &sv, hipStream_t st) { tiers_launch(s, sv, st); });
 }
 extern "C" int evs_tiers_serve_request(evs_tier_server *s, const int32_t *rows, uint8_t *tier, int *slot_out) {
     using namespace evs;
@@ -7935,18 +7627,14 @@ extern "C" int evs_tiers_serve_request_to(evs_tier_server *s, const int32_t *row
     using namespace evs;
     EVS_REQUIRE(s && out_dev && tier && ((rows != nullptr) != (ids_dev != nullptr)) && ids_stride >= 0 && ids_stride < (1ll << 32),
                 "evs_tiers_serve_request_to: bad argument");
-    EVS_REQUIRE(s->n_tables <= 26, "evs_tiers_serve_request_to: at most 26 tables (the line's last two id words carry the address)");
+    EVS_REQUIRE(s->n_tables <= MailboxLayout::kMaxTablesTo, "evs_tiers_serve_request_to: at most 26 tables (the line's last two id words carry the address)");
     int slot = 0;
     return tiers_request_impl(s, rows, ids_dev, ids_stride, out_dev, tier, &slot);
 }
 extern "C" int evs_tiers_serve_consumed(evs_tier_server *s, int slot, void *stream) {
     using namespace evs;
-    EVS_REQUIRE(s && s->serving && slot >= 0 && slot < s->slots, "evs_tiers_serve_consumed: bad argument");
-    hipEvent_t &e = s->slot_done[(size_t)slot];
-    if (!e) EVS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    EVS_HIP_CHECK(hipEventRecord(e, reinterpret_cast<hipStream_t>(stream)));
-    s->slot_busy[(size_t)slot] = 1;
-    return EVS_OK;
+    EVS_REQUIRE(s && s->serving && slot >= 0 && slot < s->srv.mb.slots, "evs_tiers_serve_consumed: bad argument");
+    return s->srv.consumed(slot, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int evs_tiers_serve_stop(evs_tier_server *s) {
     using namespace evs;
@@ -7959,10 +7647,7 @@ extern "C" int evs_tiers_serve_destroy(evs_tier_server *s) {
     if (!s) return EVS_OK;
     (void)tiers_pause(s);
     tiers_detach(s);
-    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
-    if (s->mbox) (void)hipHostFree(s->mbox);
-    if (s->exact_done) (void)hipEventDestroy(s->exact_done);
-    for (hipEvent_t e : s->slot_done) if (e) (void)hipEventDestroy(e);
+    s->srv.close();
     delete s;
     return EVS_OK;
 }

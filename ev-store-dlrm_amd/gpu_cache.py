@@ -144,6 +144,34 @@ def _warn_hw_queues():
                       "evstore_dlrm_amd.configure_runtime() before the first GPU call, or export GPU_MAX_HW_QUEUES=8" % n)
 
 
+# ---- what the two resident servers (GpuCache.serve_*, TierServer) share on the Python side ----
+def _serve_buffers(n_slots, n_tables, dim, device):
+    """-> (ring, one view per ring slot, staging ids, staging flags, the slot of the last request)"""
+    import numpy as np
+    ring = torch.empty((n_slots, n_tables, dim), dtype=torch.float32, device=device)
+    views = [ring[k] for k in range(n_slots)]   # (a tensor index per request is 2 us of a 15 us request)
+    return ring, views, np.zeros(n_tables, np.int32), np.zeros(n_tables, np.uint8), C.c_int(0)
+
+
+def _serve_request_to(fn, h, n_tables, dim, rows, flags, row_ids, out):
+    """fn: evs_cache_serve_request_to / evs_tiers_serve_request_to; ids from the host (through `rows`) or by device address"""
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_tables * dim):
+        raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (n_tables * dim))
+    if torch.is_tensor(row_ids) and row_ids.is_cuda:
+        if row_ids.dtype != torch.int64 or row_ids.shape[0] != n_tables:
+            raise ValueError("device ids: a (T, ...) int64 tensor")
+        _lib.check(fn(h, None, row_ids.data_ptr(), int(row_ids.stride(0)), out.data_ptr(), flags.ctypes.data))
+    else:
+        rows[:] = row_ids
+        _lib.check(fn(h, rows.ctypes.data, None, 0, out.data_ptr(), flags.ctypes.data))
+    return flags
+
+
+def _serve_consumed(fn, h, slot, device, stream):
+    st = torch.cuda.current_stream(device) if stream is None else stream
+    _lib.check(fn(h, int(slot), st.cuda_stream))
+
+
 class GpuCache:
     def __init__(self, policy, capacity, n_tables=26, dim=36, codec=32, variant="python", device="cuda"):
         self.policy, self.capacity, self.n_tables, self.dim, self.codec = policy, int(capacity), n_tables, dim, codec
@@ -225,13 +253,8 @@ class GpuCache:
         """Arm the mailbox server: batch-1 requests then cost two cache-line hand-overs over the bus instead of a launch and a
         synchronise each.  The rows of request i land in self.serve_ring[slot] on the DEVICE."""
         import ctypes as C
-        import numpy as np
         _warn_hw_queues()
-        self.serve_ring = torch.empty((n_slots, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
-        self._srv_views = [self.serve_ring[k] for k in range(n_slots)]   # (a tensor index per request is 2 us of a 15 us request)
-        self._srv_rows = np.zeros(self.n_tables, np.int32)
-        self._srv_hit = np.zeros(self.n_tables, np.uint8)
-        self._srv_slot = C.c_int(0)
+        self.serve_ring, self._srv_views, self._srv_rows, self._srv_hit, self._srv_slot = _serve_buffers(n_slots, self.n_tables, self.dim, self.device)
         self._srv_call = (_lib.lib().evs_cache_serve_request, self._h, self._srv_rows.ctypes.data, self._srv_hit.ctypes.data, C.byref(self._srv_slot))
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().evs_cache_serve_start(self._h, int(approx_thres), self.serve_ring.data_ptr(), int(n_slots), int(idle_us)))
@@ -254,22 +277,11 @@ class GpuCache:
         """the same request with the rows written by the server into `out` (a contiguous (T, dim) fp32 DEVICE tensor of the
         caller's, not in use by pending work) instead of a ring slot; row_ids: n_tables ints on the host, or a (T, ...) int64
         device tensor whose element 0 of each row is the id (the reference's lS_i on the GPU).  -> hit flags (numpy uint8 view)"""
-        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.n_tables * self.dim):
-            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (self.n_tables * self.dim))
-        L = _lib.lib()
-        if torch.is_tensor(row_ids) and row_ids.is_cuda:
-            if row_ids.dtype != torch.int64 or row_ids.shape[0] != self.n_tables:
-                raise ValueError("device ids: a (T, ...) int64 tensor")
-            _lib.check(L.evs_cache_serve_request_to(self._h, None, row_ids.data_ptr(), int(row_ids.stride(0)), out.data_ptr(), self._srv_hit.ctypes.data))
-        else:
-            self._srv_rows[:] = row_ids
-            _lib.check(L.evs_cache_serve_request_to(self._h, self._srv_rows.ctypes.data, None, 0, out.data_ptr(), self._srv_hit.ctypes.data))
-        return self._srv_hit
+        return _serve_request_to(_lib.lib().evs_cache_serve_request_to, self._h, self.n_tables, self.dim, self._srv_rows, self._srv_hit, row_ids, out)
 
     def serve_consumed(self, slot=None, stream=None):
         """the reads of ring slot `slot` (default: the last request's) have been enqueued on `stream` (default: the current one)"""
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        _lib.check(_lib.lib().evs_cache_serve_consumed(self._h, int(self._srv_slot.value if slot is None else slot), st.cuda_stream))
+        _serve_consumed(_lib.lib().evs_cache_serve_consumed, self._h, self._srv_slot.value if slot is None else slot, self.device, stream)
 
     def set_inline_update(self, on=True):
         """the set-associative tier's policy update inside the probe + interaction launch (the default where it applies; hit
@@ -1353,15 +1365,10 @@ class TierServer:
     (stats, dump, request, ...) sends the server home first and the next request starts it again."""
 
     def __init__(self, c1, c2, c3=None, threshold=23, n_slots=4, idle_us=200):
-        import numpy as np
         _warn_hw_queues()
         self.c1, self.c2, self.c3 = c1, c2, c3
         self.n_tables, self.dim, self.device = c1.n_tables, c1.dim, c1.device
-        self.ring = torch.empty((n_slots, self.n_tables, self.dim), dtype=torch.float32, device=self.device)
-        self._views = [self.ring[k] for k in range(n_slots)]   # (a tensor index per request is 2 us)
-        self._rows = np.zeros(self.n_tables, np.int32)
-        self._tier = np.zeros(self.n_tables, np.uint8)
-        self._slot = C.c_int(0)
+        self.ring, self._views, self._rows, self._tier, self._slot = _serve_buffers(n_slots, self.n_tables, self.dim, self.device)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().evs_tiers_serve_start(C.byref(h), c1._h, c2._h, c3._h if c3 is not None else None, int(threshold),
@@ -1383,22 +1390,11 @@ class TierServer:
         """the same request with the rows written into `out` (a contiguous (T, dim) fp32 DEVICE tensor, not in use by pending
         work); row_ids: n_tables ints on the host, or a (T, ...) int64 device tensor whose element 0 of each row is the id.
         -> tier codes (numpy uint8 view)"""
-        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.n_tables * self.dim):
-            raise ValueError("out must be a contiguous fp32 device tensor of %d elements" % (self.n_tables * self.dim))
-        L = _lib.lib()
-        if torch.is_tensor(row_ids) and row_ids.is_cuda:
-            if row_ids.dtype != torch.int64 or row_ids.shape[0] != self.n_tables:
-                raise ValueError("device ids: a (T, ...) int64 tensor")
-            _lib.check(L.evs_tiers_serve_request_to(self._h, None, row_ids.data_ptr(), int(row_ids.stride(0)), out.data_ptr(), self._tier.ctypes.data))
-        else:
-            self._rows[:] = row_ids
-            _lib.check(L.evs_tiers_serve_request_to(self._h, self._rows.ctypes.data, None, 0, out.data_ptr(), self._tier.ctypes.data))
-        return self._tier
+        return _serve_request_to(_lib.lib().evs_tiers_serve_request_to, self._h, self.n_tables, self.dim, self._rows, self._tier, row_ids, out)
 
     def consumed(self, slot=None, stream=None):
         """the reads of ring slot `slot` (default: the last request's) have been enqueued on `stream` (default: the current one)"""
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
-        _lib.check(_lib.lib().evs_tiers_serve_consumed(self._h, int(self._slot.value if slot is None else slot), st.cuda_stream))
+        _serve_consumed(_lib.lib().evs_tiers_serve_consumed, self._h, self._slot.value if slot is None else slot, self.device, stream)
 
     def stop(self):
         """send the server home for good (the members' state is back in HBM); later requests raise"""
