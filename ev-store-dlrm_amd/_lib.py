@@ -70,6 +70,9 @@ _PROTOS = {
     "evs_bags_fused_stage_rows": (_int, [_int]),
     "evs_long_q_kernels_seen": (_int, [C.c_char_p, _int]),
     "evs_long_q_chunk": (_int, [_int, _int]),
+    "evs_wide_kernels_seen": (_int, [C.c_char_p, _int]),
+    "evs_interact_dot_wide": (_int, [_i64, _int, _int, _pp, _i64p, _int, _vp, _vp]),
+    "evs_emb_interact_wide_stacked": (_int, [_i64, _int, _int, _pp, _i64p, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
     "evs_embedding_bag_sum_long": (_int, [_int, _i64, _int, _int, _pp, _i64p, _pp, _pp, _i64p, _vp, _i64, _i64, _vp]),
     "evs_emb_interact_bags": (_int, [_i64, _int, _int, _pp, _i64p, _vp, _i64, _pp, _i64p, _pp, _i64p, _int, _vp, _vp]),
     "evs_interact_rows_by_address": (_int, [_i64, _int, _int, _vp, _i64, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
@@ -287,6 +290,13 @@ def long_q_kernels_seen():
     """{name: launches} for the fifteen instantiations of the encoded long-bag kernel (evs_long_q_kernels_seen)."""
     buf = C.create_string_buffer(lib().evs_long_q_kernels_seen(None, 0) + 1)
     lib().evs_long_q_kernels_seen(buf, len(buf))
+    return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
+
+
+def wide_kernels_seen():
+    """{name: launches} for the wide interaction kernel, dense and gather form of its sixteen instantiations (evs_wide_kernels_seen)."""
+    buf = C.create_string_buffer(lib().evs_wide_kernels_seen(None, 0) + 1)
+    lib().evs_wide_kernels_seen(buf, len(buf))
     return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
 
 

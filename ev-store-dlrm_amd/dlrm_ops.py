@@ -728,7 +728,9 @@ def interact_features(x, ly, arch_interaction_op="dot", arch_interaction_itself=
         # still the list apply_emb built?  (first and last element where they were put)
         if ly[0].data_ptr() == base and ly[-1].data_ptr() == base + 4 * tstride * (T - 1):
             pooled = meta
-    X = _ext.ext() if arch_interaction_op == "dot" else None
+    # past 32 features the extension refuses: the wide kernel's shapes go through the C entry below, with or without it
+    wide = arch_interaction_op == "dot" and wide_supported(len(ly) + 1, d)
+    X = _ext.ext() if arch_interaction_op == "dot" and not wide else None
     if X is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2:
         if pooled is not None:
             return X.interact_dot_pooled(x, pooled[0], pooled[1], pooled[2], pooled[5], bool(arch_interaction_itself))
@@ -741,26 +743,31 @@ def interact_features(x, ly, arch_interaction_op="dot", arch_interaction_itself=
         fast = _feat_cache.get(key)
         if fast is None:
             F = T + 1
-            fast = ((C.c_void_p * F)(key[0], *[base + 4 * tstride * k for k in range(T)]),
-                    (C.c_int64 * F)(key[1], *([bstride if B > 1 else d] * T)), F)
+            row = bstride if B > 1 else d
+            fast = ((C.c_void_p * F)(key[0], *[base + 4 * tstride * k for k in range(T)]), (C.c_int64 * F)(key[1], *([row] * T)), F,
+                    key[0] % 16 == 0 and key[1] % 4 == 0 and base % 16 == 0 and tstride % 4 == 0 and row % 4 == 0)
             if len(_feat_cache) > 256:
                 _feat_cache.clear()
             _feat_cache[key] = fast
     if fast is not None:
-        ptrs, strides, F = fast
+        ptrs, strides, F, aligned = fast
     else:
         feats = [x] + list(ly)
         F = len(feats)
         for f in feats:
             assert f.is_cuda and f.dtype == torch.float32 and f.shape == (B, d) and (d == 1 or f.stride(1) == 1)
-        ptrs = (C.c_void_p * F)(*[f.data_ptr() for f in feats])
-        strides = (C.c_int64 * F)(*[int(f.stride(0)) if B > 1 else d for f in feats])
+        at = [f.data_ptr() for f in feats]
+        rows = [int(f.stride(0)) if B > 1 else d for f in feats]
+        ptrs = (C.c_void_p * F)(*at)
+        strides = (C.c_int64 * F)(*rows)
+        aligned = wide and all(p % 16 == 0 for p in at) and all(s % 4 == 0 for s in rows)   # every row on a 16-byte boundary
     L = _lib.lib()
     if arch_interaction_op == "dot":
         P = F * (F + 1) // 2 if arch_interaction_itself else F * (F - 1) // 2
         R = torch.empty((B, d + P), dtype=torch.float32, device=dev)
-        rc = L.evs_interact_dot(B, F, d, ptrs, strides, int(bool(arch_interaction_itself)),
-                                R.data_ptr(), _stream_ptr(dev))
+        # (a feature the wide kernel cannot address -- not 16-byte aligned -- keeps evs_interact_dot's generic kernel)
+        dot = L.evs_interact_dot_wide if wide and aligned else L.evs_interact_dot
+        rc = dot(B, F, d, ptrs, strides, int(bool(arch_interaction_itself)), R.data_ptr(), _stream_ptr(dev))
     else:
         R = torch.empty((B, F * d), dtype=torch.float32, device=dev)
         rc = L.evs_interact_cat(B, F, d, ptrs, strides, R.data_ptr(), _stream_ptr(dev))
@@ -771,6 +778,13 @@ def interact_features(x, ly, arch_interaction_op="dot", arch_interaction_itself=
 def fused_supported(F, d):
     """Shapes the fused gather+interaction kernel is built for (csrc/evs_fused.hip)."""
     return F <= 32 and d in (16, 32, 36, 48, 64, 128)
+
+
+def wide_supported(F, d):
+    """Shapes past fused_supported's 32 features that the wide interaction kernel is built for (csrc/evs_fused_wide.hip): x plus
+    32 to 127 tables, fp32.  interact_features runs its dense form, apply_emb_interact its gather form (stacked one-index bags of
+    fp32 tables) or apply_emb followed by the dense form (everything else)."""
+    return 32 < F <= 128 and d in (16, 32, 36, 64)
 
 
 class InteractServer:
@@ -876,6 +890,29 @@ def apply_emb_interact(x, lS_o, lS_i, emb_l, v_W_l=None, arch_interaction_itself
     B = int(x.shape[0])
     dev = ev.device
     assert x.is_cuda and x.dtype == torch.float32 and x.shape == (B, d) and x.stride(1) == 1
+    if wide_supported(F, d):
+        # rows from the tables to the matrix cores in one launch: stacked one-index bags of fp32 tables, unweighted
+        if ev.codec == 32 and (v_W_l is None or all(w is None for w in v_W_l)) and torch.is_tensor(lS_i) and \
+                (one_index_per_bag or lS_o is None) and lS_i.is_cuda and lS_i.dtype == torch.int64 and tuple(lS_i.shape) == (T, B) and \
+                lS_i.stride(1) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0:
+            P = F * (F + 1) // 2 if arch_interaction_itself else F * (F - 1) // 2
+            R = out if out is not None else torch.empty((B, d + P), dtype=torch.float32, device=dev)
+            assert R.shape == (B, d + P) and R.is_contiguous() and R.dtype == torch.float32
+            L = _lib.lib()
+            stream = _stream_ptr(dev)
+            _lib.check(L.evs_emb_interact_wide_stacked(B, T, d, ev._tables_c, ev._n_rows_c, x.data_ptr(), int(x.stride(0)) if B > 1 else d,
+                                                       lS_i.data_ptr(), lS_i.stride(0), int(bool(arch_interaction_itself)), R.data_ptr(), stream))
+            if check_indices:
+                _lib.check(L.evs_check_index_errors(stream))
+            return R
+        # everything else two-launch: apply_emb takes any T, then the dense form (out= then costs a copy of R:
+        # interact_features allocates its result)
+        if lS_o is None:
+            raise ValueError("apply_emb_interact: F = %d > 32 without offsets takes a stacked (T, B) int64 lS_i on the device, fp32 "
+                             "tables, no weights and 16-byte aligned x rows; pass lS_o for anything else" % F)
+        R =interact_features(x, apply_emb(lS_o, lS_i, ev, v_W_l, check_indices=check_indices, one_index_per_bag=one_index_per_bag),
+                              "dot", arch_interaction_itself)
+        return R if out is None else out.copy_(R)
     if not fused_supported(F, d):
         return interact_features(x, apply_emb(lS_o, lS_i, ev, v_W_l), "dot", arch_interaction_itself)
     if torch.is_tensor(lS_i) and (torch.is_tensor(lS_o) or lS_o is None) and (v_W_l is None or all(w is None for w in v_W_l)):

@@ -337,6 +337,34 @@ EVS_API int evs_emb_interact_dot_stacked(int64_t B, int T, int d, int codec,
                                  const int64_t *offsets_base, int64_t offsets_row_stride,
                                  const float *const *row_weights, int itself, float *R, void *stream);
 
+/* Wide models (csrc/evs_fused_wide.hip): the interaction for EVS_MAX_FEATURES < F <= EVS_MAX_WIDE_FEATURES on the matrix cores,
+ * d in {16, 32, 36, 64}, fp32.  A block owns 16 samples, a wave holds the ceil(F / 16) row-tiles of one sample in registers,
+ * every 16 x 16 tile of T T^T is a chain of d / 4 v_mfma_f32_16x16x4_f32 between two register sets, and R leaves in bands of 16
+ * rows of the packed triangle through LDS.  Output as evs_interact_dot; R 16-byte aligned.
+ *   evs_interact_dot_wide          dense form: feats / feat_strides as evs_interact_dot takes them, every feats[f] 16-byte
+ *                                  aligned, every stride a multiple of 4 floats.
+ *   evs_emb_interact_wide_stacked  gather form: F = T + 1; feature 0 = x (B, d) with row stride x_stride floats, feature k + 1 =
+ *                                  row indices[k * idx_stride + b] of the fp32 table tables[k] (n_rows[k] rows of d floats,
+ *                                  16-byte aligned) -- ONE index per bag, the stacked (T, B) int64 tensor of the Criteo collate.
+ *                                  The (T, B, d) block is never written.  An index outside [0, n_rows[k]) contributes a zero row
+ *                                  and raises the sticky flag evs_check_index_errors reports.
+ * Everything is validated before the device is touched: F outside 33 .. 128, a d without a kernel, a NULL argument, feature or
+ * table, a pointer that is not 16-byte aligned, a stride that is not a multiple of 4, B or n_rows[k] >= 2^31 return EVS_EINVAL
+ * and launch nothing; B == 0 succeeds and touches nothing.  evs_interact_dot keeps its own dispatch. */
+#define EVS_MAX_WIDE_FEATURES 128
+EVS_API int evs_interact_dot_wide(int64_t B, int F, int d, const float *const *feats, const int64_t *feat_strides, int itself,
+                                  float *R, void *stream);
+EVS_API int evs_emb_interact_wide_stacked(int64_t B, int T, int d, const void *const *tables, const int64_t *n_rows,
+                                          const float *x, int64_t x_stride, const int64_t *indices, int64_t idx_stride,
+                                          int itself, float *R, void *stream);
+/* The dispatch record of the two entries above, in the form of evs_long_q_kernels_seen: 32 lines, always listed, in a fixed order
+ * (dense then gather; d = 16, 32, 36, 64 within each; nt = 3, 4, 6, 8 within each d).  The two forms of one (d, nt) share a
+ * kernel instantiation and are counted apart.  A count goes up by one per kernel launch; a refused call and B == 0 launch
+ * nothing.
+ *   wide_dense_d<d>_nt<n> | wide_gather_d<d>_nt<n>   nt = the 16-row tiles the kernel was compiled for: 3 (F <= 48), 4 (F <= 64),
+ *                                                    6 (F <= 96), 8 (F <= 128) */
+EVS_API int evs_wide_kernels_seen(char *buf, int n);
+
 /* K independent batches of B samples in one call (a serving loop's queue): x, indices_base, offsets_base (NULL = one
  * index per bag for every batch) and R are HOST arrays of K device pointers, every batch with the same shape and strides.
  * fp32 tables with d in {16, 32, 36} and T <= 27: ONE launch per 8 batches -- a batch's last blocks drain under the
