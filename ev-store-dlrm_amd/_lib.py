@@ -73,6 +73,8 @@ _PROTOS = {
     "evs_wide_kernels_seen": (_int, [C.c_char_p, _int]),
     "evs_interact_dot_wide": (_int, [_i64, _int, _int, _pp, _i64p, _int, _vp, _vp]),
     "evs_emb_interact_wide_stacked": (_int, [_i64, _int, _int, _pp, _i64p, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "evs_emb_interact_wide_q_stacked": (_int, [_i64, _int, _int, _int, _pp, _i64p, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "evs_wide_q_kernels_seen": (_int, [C.c_char_p, _int]),
     "evs_embedding_bag_sum_long": (_int, [_int, _i64, _int, _int, _pp, _i64p, _pp, _pp, _i64p, _vp, _i64, _i64, _vp]),
     "evs_emb_interact_bags": (_int, [_i64, _int, _int, _pp, _i64p, _vp, _i64, _pp, _i64p, _pp, _i64p, _int, _vp, _vp]),
     "evs_interact_rows_by_address": (_int, [_i64, _int, _int, _vp, _i64, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
@@ -297,6 +299,13 @@ def wide_kernels_seen():
     """{name: launches} for the wide interaction kernel, dense and gather form of its sixteen instantiations (evs_wide_kernels_seen)."""
     buf = C.create_string_buffer(lib().evs_wide_kernels_seen(None, 0) + 1)
     lib().evs_wide_kernels_seen(buf, len(buf))
+    return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
+
+
+def wide_q_kernels_seen():
+    """{name: launches} for the 48 instantiations of the wide kernel over encoded tables (evs_wide_q_kernels_seen)."""
+    buf = C.create_string_buffer(lib().evs_wide_q_kernels_seen(None, 0) + 1)
+    lib().evs_wide_q_kernels_seen(buf, len(buf))
     return {k: int(v) for k, v in (ln.split("=") for ln in buf.value.decode().splitlines())}
 
 

@@ -67,6 +67,16 @@ __device__ __forceinline__ float dec_u16_main(unsigned v) {
     const float w = (float)((int)v - 32500);
     return __fmaf_rn(w, 2e-05f, __fmul_rn(w, 5.052425e-13f));
 }
+// two u16 codes of the main range (<= 65 000) -> two floats: the same value and the same three roundings as dec_u16_main
+// -- (float)v - 32 500.0f is exact, like the integer subtraction there -- written on float pairs so that the subtraction,
+// the product and the fma are one packed instruction each (v_pk_add/mul/fma_f32)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 dec_u16_main2(unsigned w) {
+    f32x2 f = {(float)(w & 0xffffu), (float)(w >> 16)};
+    f = f - 32500.0f;
+    const f32x2 lo = f * 5.052425e-13f;
+    return __builtin_elementwise_fma(f, (f32x2){2e-05f, 2e-05f}, lo);
+}
 __device__ __forceinline__ float dec_u16(unsigned v) {
     if (v > 65000u) {
         float diff = __fdiv_rn((float)(int)(v - 65000u), 100.0f);

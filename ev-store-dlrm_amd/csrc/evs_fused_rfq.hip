@@ -104,18 +104,8 @@ __device__ __forceinline__ void store_raw(unsigned long long p, const unsigned (
     }
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-// two u16 codes of the main range (<= 65 000) -> two floats: the same value and the same three roundings as dec_u16_main
-// (evs_common.h) -- (float)v - 32 500.0f is exact, like the integer subtraction there -- written on float pairs so that
-// the subtraction, the product and the fma are one packed instruction each (v_pk_add/mul/fma_f32)
-__device__ __forceinline__ f32x2 dec_u16_main2(unsigned w) {
-    f32x2 f = {(float)(w & 0xffffu), (float)(w >> 16)};
-    f = f - 32500.0f;
-    const f32x2 lo = f * 5.052425e-13f;
-    return __builtin_elementwise_fma(f, (f32x2){2e-05f, 2e-05f}, lo);
-}
 // one chunk (4 elements).  FAST (u16 only): the caller has checked that no lane of the wave holds a tail code (> 65 000)
 template <int CODEC, bool FAST>
 __device__ __forceinline__ float4 dec_chunk_q(unsigned w0, unsigned w1, const float *lut) {

@@ -22,32 +22,11 @@
 //     device-side descriptor, no allocation or synchronisation per call.  Both forms run the same instantiation -- they differ
 //     in how a lane forms its row address (a block-uniform branch).
 // Templates: d in {16, 32, 36, 64} x NT in {3, 4, 6, 8} (F <= 48 / 64 / 96 / 128): register arrays statically indexed.
-#include "evs_common.h"
+#include "evs_fused_wide.h"
 #include <string.h>
 #include <atomic>
 
 namespace evs {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) f32x4 global_f32x4;
-
-struct WideArgs {
-    const char *base[EVS_MAX_WIDE_FEATURES];   // dense: feature f.  gather: x, then table f - 1
-    int64_t aux[EVS_MAX_WIDE_FEATURES];        // dense: row stride in BYTES.  gather: x's stride in bytes, then the rows of table f - 1
-    const int64_t *idx;                        // gather: the (T, B) indices; NULL = dense form
-    int64_t idx_stride;
-    float *R;
-    const char *zeros;                         // zero_page()
-    int *err;
-    int B, F, itself, out_row;                 // out_row = d + P
-};
-
-constexpr int kWideD[4] = {16, 32, 36, 64};
-constexpr int kWideNt[4] = {3, 4, 6, 8};
-constexpr int wide_d_id(int d) { return d == 16 ? 0 : d == 32 ? 1 : d == 36 ? 2 : d == 64 ? 3 : -1; }
-constexpr int wide_nt_id(int F) { return F <= 48 ? 0 : F <= 64 ? 1 : F <= 96 ? 2 : 3; }
-// pairs in front of row i of the packed triangle
-__device__ __forceinline__ int wide_tri(int i, int itself) { return (i * (i - 1 + 2 * itself)) >> 1; }
 
 template <int D, int NT>
 __global__ void __launch_bounds__(256) interact_wide_kernel(const WideArgs args) {
@@ -245,16 +224,6 @@ static int launch_wide(WideArgs &a, int d, hipStream_t st) {
     g_wide_seen[(a.idx ? 16 : 0) + wide_d_id(d) * 4 + wide_nt_id(a.F)].fetch_add(1, std::memory_order_relaxed);
     return EVS_OK;
 }
-
-// what both entries refuse alike, before a device is touched
-static int wide_shape_ok(const char *who, int64_t B, int F, int d) {
-    EVS_REQUIRE(B >= 0, "%s: bad shape B=%lld", who, (long long)B);
-    EVS_REQUIRE(F > EVS_MAX_FEATURES && F <= EVS_MAX_WIDE_FEATURES, "%s: F=%d features (the wide kernel takes %d to %d)", who, F,
-                EVS_MAX_FEATURES + 1, EVS_MAX_WIDE_FEATURES);
-    EVS_REQUIRE(wide_d_id(d) >= 0, "%s: no kernel for d=%d (16, 32, 36, 64)", who, d);
-    return EVS_OK;
-}
-static inline bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace evs
 

@@ -781,9 +781,10 @@ def fused_supported(F, d):
 
 
 def wide_supported(F, d):
-    """Shapes past fused_supported's 32 features that the wide interaction kernel is built for (csrc/evs_fused_wide.hip): x plus
-    32 to 127 tables, fp32.  interact_features runs its dense form, apply_emb_interact its gather form (stacked one-index bags of
-    fp32 tables) or apply_emb followed by the dense form (everything else)."""
+    """Shapes past fused_supported's 32 features that the wide interaction kernels are built for: x plus 32 to 127 tables.
+    interact_features runs the dense form (csrc/evs_fused_wide.hip, fp32), apply_emb_interact the gather form for stacked one-index
+    bags -- of fp32 tables in the same unit, of 16- / 8- / 4-bit tables in csrc/evs_fused_wide_q.hip -- or apply_emb followed by
+    the dense form (everything else)."""
     return 32 < F <= 128 and d in (16, 32, 36, 64)
 
 
@@ -891,8 +892,9 @@ def apply_emb_interact(x, lS_o, lS_i, emb_l, v_W_l=None, arch_interaction_itself
     dev = ev.device
     assert x.is_cuda and x.dtype == torch.float32 and x.shape == (B, d) and x.stride(1) == 1
     if wide_supported(F, d):
-        # rows from the tables to the matrix cores in one launch: stacked one-index bags of fp32 tables, unweighted
-        if ev.codec == 32 and (v_W_l is None or all(w is None for w in v_W_l)) and torch.is_tensor(lS_i) and \
+        # rows from the tables to the matrix cores in one launch: stacked one-index bags, unweighted; fp32 rows as they are,
+        # encoded rows (16 / 8 / 4 bits) as raw codes that the kernel decodes in registers
+        if (v_W_l is None or all(w is None for w in v_W_l)) and torch.is_tensor(lS_i) and \
                 (one_index_per_bag or lS_o is None) and lS_i.is_cuda and lS_i.dtype == torch.int64 and tuple(lS_i.shape) == (T, B) and \
                 lS_i.stride(1) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0:
             P = F * (F + 1) // 2 if arch_interaction_itself else F * (F - 1) // 2
@@ -900,16 +902,21 @@ def apply_emb_interact(x, lS_o, lS_i, emb_l, v_W_l=None, arch_interaction_itself
             assert R.shape == (B, d + P) and R.is_contiguous() and R.dtype == torch.float32
             L = _lib.lib()
             stream = _stream_ptr(dev)
-            _lib.check(L.evs_emb_interact_wide_stacked(B, T, d, ev._tables_c, ev._n_rows_c, x.data_ptr(), int(x.stride(0)) if B > 1 else d,
-                                                       lS_i.data_ptr(), lS_i.stride(0), int(bool(arch_interaction_itself)), R.data_ptr(), stream))
+            xs = int(x.stride(0)) if B > 1 else d
+            if ev.codec == 32:
+                _lib.check(L.evs_emb_interact_wide_stacked(B, T, d, ev._tables_c, ev._n_rows_c, x.data_ptr(), xs, lS_i.data_ptr(),
+                                                           lS_i.stride(0), int(bool(arch_interaction_itself)), R.data_ptr(), stream))
+            else:
+                _lib.check(L.evs_emb_interact_wide_q_stacked(B, T, d, ev.codec, ev._tables_c, ev._n_rows_c, x.data_ptr(), xs, lS_i.data_ptr(),
+                                                             lS_i.stride(0), int(bool(arch_interaction_itself)), R.data_ptr(), stream))
             if check_indices:
                 _lib.check(L.evs_check_index_errors(stream))
             return R
         # everything else two-launch: apply_emb takes any T, then the dense form (out= then costs a copy of R:
         # interact_features allocates its result)
         if lS_o is None:
-            raise ValueError("apply_emb_interact: F = %d > 32 without offsets takes a stacked (T, B) int64 lS_i on the device, fp32 "
-                             "tables, no weights and 16-byte aligned x rows; pass lS_o for anything else" % F)
+            raise ValueError("apply_emb_interact: F = %d > 32 without offsets takes a stacked (T, B) int64 lS_i on the device, "
+                             "no weights and 16-byte aligned x rows; pass lS_o for anything else" % F)
         R =interact_features(x, apply_emb(lS_o, lS_i, ev, v_W_l, check_indices=check_indices, one_index_per_bag=one_index_per_bag),
                               "dot", arch_interaction_itself)
         return R if out is None else out.copy_(R)

@@ -365,6 +365,21 @@ EVS_API int evs_emb_interact_wide_stacked(int64_t B, int T, int d, const void *c
  *                                                    6 (F <= 96), 8 (F <= 128) */
 EVS_API int evs_wide_kernels_seen(char *buf, int n);
 
+/* The gather form over ENCODED tables (csrc/evs_fused_wide_q.hip): as evs_emb_interact_wide_stacked, with tables[k] holding
+ * n_rows[k] rows of d codes of `codec` bits (16, 8 or 4: d * codec / 8 bytes per row, rows packed, the table 16-byte aligned).  A
+ * row travels as raw codes and is decoded once, in registers, with the decoders of evs_emb_bag_sum (bit-exact with the
+ * reference's); x stays fp32 and reaches R bit for bit; the dot products are the same fp32 MFMA chains over the decoded values.
+ * Nothing outside a table's rows is read.  An out-of-range index contributes a row of exact zeros and raises the sticky flag.
+ * The same refusals, in the same order and wording, as evs_emb_interact_wide_stacked; a codec outside {16, 8, 4} returns
+ * EVS_EINVAL (codec 32: the message names evs_emb_interact_wide_stacked).  B == 0 succeeds and touches nothing. */
+EVS_API int evs_emb_interact_wide_q_stacked(int64_t B, int T, int d, int codec, const void *const *tables, const int64_t *n_rows,
+                                            const float *x, int64_t x_stride, const int64_t *indices, int64_t idx_stride,
+                                            int itself, float *R, void *stream);
+/* Its dispatch record, in the form of evs_wide_kernels_seen: 48 lines, always listed, in a fixed order (codec = 16, 8, 4; d = 16,
+ * 32, 36, 64 within each; nt = 3, 4, 6, 8 within each d); a count goes up by one per kernel launch.
+ *   wideq_c<codec>_d<d>_nt<n> */
+EVS_API int evs_wide_q_kernels_seen(char *buf, int n);
+
 /* K independent batches of B samples in one call (a serving loop's queue): x, indices_base, offsets_base (NULL = one
  * index per bag for every batch) and R are HOST arrays of K device pointers, every batch with the same shape and strides.
  * fp32 tables with d in {16, 32, 36} and T <= 27: ONE launch per 8 batches -- a batch's last blocks drain under the

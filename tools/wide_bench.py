@@ -8,6 +8,7 @@ Bytes moved (what the algorithm has to move, from the shapes) over time stand be
 device-to-device copy of 1 GiB, read + written bytes over its time.  Writes profiles/wide.json (--out).
 
     python tools/wide_bench.py [--reps 2000] [--generic-reps 60] [--out profiles/wide.json]
+    python tools/wide_bench.py --codec 16,8,4 [--reps 500]      the encoded kernel (measure_encoded), writes profiles/wide_q.json
 
 The two wide routes take tens to hundreds of microseconds a call, so they are timed --reps times each (a good second of device
 time per shape); the generic route takes milliseconds and joins every (reps / generic-reps)-th round.
@@ -57,13 +58,83 @@ def generic(x, ly):
     return R
 
 
+def encoded_tables(codec, T, d, gen):
+    """T tables of ROWS random rows of `codec`-bit codes (u16 up to 65 000: the main range of trained tables; u4 never nibble 15)"""
+    if codec == 16:
+        v = torch.randint(0, 65001, (T, ROWS, d), device="cuda", generator=gen, dtype=torch.int32)
+        raw = torch.stack((v & 255, v >> 8), -1).to(torch.uint8)   # little-endian ushorts
+    elif codec == 8:
+        raw = torch.randint(0, 256, (T, ROWS, d), device="cuda", generator=gen).to(torch.uint8)
+    else:
+        nib = torch.randint(0, 15, (T, ROWS, d), device="cuda", generator=gen)
+        raw = (nib[..., 0::2] * 16 + nib[..., 1::2]).to(torch.uint8)
+    return E.EVTables(list(raw.reshape(T, ROWS, -1).unbind(0)), d, codec)
+
+
+def measure_encoded(a, codecs, out, copy_gbs, ev0, ev1):
+    """--codec: the wide kernel over encoded tables (csrc/evs_fused_wide_q.hip), three routes per codec and shape, rotating:
+        one_launch    apply_emb_interact(..., one_index_per_bag=True) over the encoded tables
+        two_launch    the same call with lS_o given and nothing declared: apply_emb decodes the (T, B, d) block, the dense form reads it
+        fp32_gather   the gather form over fp32 tables of the same shape, the yardstick"""
+    for codec in codecs:
+        for F, d in SHAPES:
+            T, P = F - 1, F * (F - 1) // 2
+            gen = torch.Generator(device="cuda").manual_seed(100 * F + d + codec)
+            evq = encoded_tables(codec, T, d, gen)
+            ev32 = E.EVTables.from_fp32(list((torch.rand((T, ROWS, d), device="cuda") * 2 - 1).unbind(0)))
+            data = [(torch.randn((B, d), device="cuda", generator=gen), torch.randint(0, ROWS, (T, B), device="cuda", generator=gen))
+                    for _ in range(a.batches)]
+            lS_o = torch.arange(B, device="cuda").repeat(T, 1)
+            calls = {"one_launch": lambda x, i: E.apply_emb_interact(x, None, i, evq, one_index_per_bag=True),
+                     "two_launch": lambda x, i: E.apply_emb_interact(x, lS_o, i, evq),
+                     "fp32_gather": lambda x, i: E.apply_emb_interact(x, None, i, ev32, one_index_per_bag=True)}
+            route, same = {}, True
+            for x, i in data:   # warm-up of every batch and route; the routes from the records; do the two encoded routes agree bit for bit
+                R = {}
+                for k, f in calls.items():
+                    q0, w0 = E._lib.wide_q_kernels_seen(), E._lib.wide_kernels_seen()
+                    R[k] = f(x, i)
+                    route[k] = {"wide_q": went_up(q0, E._lib.wide_q_kernels_seen()), "wide": went_up(w0, E._lib.wide_kernels_seen())}
+                assert len(route["one_launch"]["wide_q"]) == 1 and not route["one_launch"]["wide"], route
+                assert not route["two_launch"]["wide_q"] and list(route["two_launch"]["wide"])[0].startswith("wide_dense"), route
+                assert list(route["fp32_gather"]["wide"])[0].startswith("wide_gather"), route
+                same = same and torch.equal(R["one_launch"].view(torch.int32), R["two_launch"].view(torch.int32))
+            torch.cuda.synchronize()
+            ms = {k: [] for k in calls}
+            order = list(calls)
+            for r in range(a.reps):
+                x, i = data[r % len(data)]
+                for k in order[r % 3:] + order[:r % 3]:
+                    ms[k].append(timed(lambda: calls[k](x, i), ev0, ev1))
+            # what each route has to move: rows, indices and x in, R out; two launches write the fp32 (T, B, d) block and read it back
+            rest = B * (T * 8 + d * 4 + (d + P) * 4)
+            nbytes = {"one_launch": rest + B * T * d * codec // 8, "two_launch": rest + B * T * d * codec // 8 + 2 * T * B * d * 4,
+                      "fp32_gather": rest + B * T * d * 4}
+            rec = {"codec": codec, "T": T, "d": d, "route": route, "routes_bit_equal": same}
+            for k, v in ms.items():
+                s = stats_us(v)
+                gbs = nbytes[k] / s["median"] / 1e3
+                rec[k] = {"us": s, "algorithmic_bytes": nbytes[k], "GB_per_s": round(gbs, 1), "of_copy_rate": round(gbs / copy_gbs, 3)}
+            rec["one_over_two_launch"] = round(rec["one_launch"]["us"]["median"] / rec["two_launch"]["us"]["median"], 4)
+            rec["one_launch_over_fp32_gather"] = round(rec["one_launch"]["us"]["median"] / rec["fp32_gather"]["us"]["median"], 4)
+            out["shapes"]["u%d_F%d_d%d" % (codec, F, d)] = rec
+            print("u%d_F%d_d%d" % (codec, F, d), json.dumps(rec), flush=True)
+            del evq, ev32, data
+            torch.cuda.empty_cache()
+
+
 def main():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=2000)
     ap.add_argument("--generic-reps", type=int, default=60)
     ap.add_argument("--batches", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wide.json"))
+    ap.add_argument("--codec", default=None, help="16, 8, 4 or a comma list: measure the encoded kernel instead (profiles/wide_q.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    codecs = [int(c) for c in a.codec.split(",")] if a.codec else []
+    assert all(c in (16, 8, 4) for c in codecs), "--codec takes 16, 8, 4"
+    a.out = a.out or os.path.join(root, "profiles", "wide_q.json" if codecs else "wide.json")
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     torch.manual_seed(0)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -77,7 +148,9 @@ def main():
     out = {"library": os.path.basename(E._lib.LIB_PATH), "reps": a.reps, "generic_reps": a.generic_reps, "B": B, "rows_per_table": ROWS,
            "copy_calibration": {"bytes": 2 << 30, "median_ms": round(copy_ms, 4), "GB_per_s": round(copy_gbs, 1)}, "shapes": {}}
     print("copy calibration", json.dumps(out["copy_calibration"]), flush=True)
-    for F, d in SHAPES:
+    if codecs:
+        measure_encoded(a, codecs, out, copy_gbs, ev0, ev1)
+    for F, d in SHAPES if not codecs else []:
         T, P = F - 1, F * (F - 1) // 2
         ev = E.EVTables.from_fp32(list((torch.rand((T, ROWS, d), device="cuda") * 2 - 1).unbind(0)))
         gen = torch.Generator(device="cuda").manual_seed(100 * F + d)
